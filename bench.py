@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- QPNet hot-path benchmark on MI355X (contract: see the task prompt / DESIGN.md §6).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode decode|train] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode decode|train] [--batch B] [--dump-outputs DIR] [--full]
 
 One "step" is one pass of the hot path over one batch of synthetic WORLD-shaped input:
   decode: QPNet.batch_fast_generate(mode="argmax") of B 10-second utterances @22.05 kHz
@@ -9,6 +9,9 @@ One "step" is one pass of the hot path over one batch of synthetic WORLD-shaped 
   train : one optimisation step (forward + CE + backward + Adam) on one chunk of RF+20000 samples.
 Rank 0 prints ONE JSON line.  Multi-GPU: one process per GPU (torch.distributed / RCCL); decode
 runs independent replicas (no collective, "replicas only"), training all-reduces gradients.
+A plain run sets up, warms up, times the K steps and prints the headline; --full adds what takes runs of its own (per-launch
+profile and roofline of the training step, the runner / drop-in loops, CPU baselines, sampling mode, the other decode batches,
+F0 factors and the default geometry).  --dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -108,6 +111,15 @@ def measured_pmc():
     return None
 
 
+def dump_outputs(d, arrays):
+    """DIR/<name>.npy (float32) of what the last timed step handed its caller: two builds run with the same arguments get the same inputs."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def decode_weight_bytes_per_sample(cfg):
     """172 B of per-sample inputs/outputs + 4 B x the parameters touched per sample
     (all but the one-hot table, of which two columns are looked up)."""
@@ -173,10 +185,16 @@ def run_decode(args, rank, local, world):
     barrier(world)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        outs = step()
         kms.append(m.last_decode_kernel_ms)
     barrier(world)
     dt = max_over_ranks(time.perf_counter() - t0, world, dev)
+    if args.dump_outputs and rank == 0:
+        # the generated class ids of every utterance, in the order batch_fast_generate returned them (-1 past a shorter row's end)
+        samples = np.full((len(outs), max(len(o) for o in outs)), -1, dtype=np.float32)
+        for i, o in enumerate(outs):
+            samples[i, :len(o)] = o
+        dump_outputs(args.dump_outputs, {"samples": samples})
     total_samples = sum(ns) * args.steps * world
     value = total_samples / dt
     k_ms = float(np.mean(kms))
@@ -220,13 +238,13 @@ def run_decode(args, rank, local, world):
                      "kernel": kernel, "kernel_ms": k_ms, "note": note},
     }
     out["plan"] = getattr(m, "last_decode_plan", "")
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         # the reference decode script's default mode (softmax + draw, qpnet_decode.py:312-314): one untimed-in-`value` launch
         torch.cuda.synchronize(); t1 = time.perf_counter()
         m.batch_fast_generate(xb, hb, list(ns), bd, mode="sampling")
         torch.cuda.synchronize()
         out["sampling_mode"] = {"value": sum(ns) / (time.perf_counter() - t1), "unit": "samples/s", "kernel_ms": m.last_decode_kernel_ms}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline_decode(cfg, flat, F)
     return out
 
@@ -399,7 +417,7 @@ def run_train(args, rank, local, world):
     from qpnet_amd import synth, harness, _lib
     from qpnet_amd.config import PAPER
     from qpnet_amd.qpnet import QPNet
-    from qpnet_amd.train import FusedTrainer
+    from qpnet_amd.train import FusedTrainer, ensure_flat
     dev = torch.device("cuda", local)
     cfg = PAPER
     flat = synth.make_weights(cfg, 13)
@@ -409,7 +427,6 @@ def run_train(args, rank, local, world):
     tr = FusedTrainer(m, lr=1e-4, world_size=2 if (world == 1 and os.environ.get("QPN_EXCHANGE_ALWAYS")) else world)
     if world > 1:
         from qpnet_amd import parallel
-        from qpnet_amd.train import ensure_flat
         parallel.broadcast_parameters(ensure_flat(m, dev))          # every rank starts from rank 0's parameters
     # utterance-sharded synthetic chunks: rank r consumes chunks r, r+world, ...
     nchunks = 4
@@ -431,6 +448,16 @@ def run_train(args, rank, local, world):
     # before the pause: the power state after the idle period, not the library's state).  The trainer is therefore stepped until the device has been
     # busy for QPN_BENCH_INIT_MS (default 40 ms) before the contract's warm-up starts: `--steps 20 --warmup 5` then measures the steady rate a run is in
     # from its first 30 ms on, not the ramp.  config.init reports what was run.
+    # The backward adds with float atomics: a step's gradient carries rounding noise from run to run, which Adam (g / sqrt(v)) grows over the steps
+    # that follow.  The LAST timed step therefore starts from the initial weights and a fresh Adam state (three copies enqueued on the step's stream,
+    # a few microseconds once per run): what it computes is the same in every run up to rounding, whatever ran before it (--dump-outputs).
+    flat0 = ensure_flat(m, dev).clone()
+
+    def reset():
+        m._flat.copy_(flat0)
+        if tr.m is not None:
+            tr.m.zero_(); tr.v.zero_()
+        tr.step_count = 0
     init_ms = float(os.environ.get("QPN_BENCH_INIT_MS", "40"))
     n_init = 0
     if init_ms > 0:
@@ -443,9 +470,34 @@ def run_train(args, rank, local, world):
     barrier(world)
     t0 = time.perf_counter()
     for i in range(args.steps):
+        if i == args.steps - 1:
+            reset()
         step(i)
     barrier(world)
     dt = max_over_ranks(time.perf_counter() - t0, world, dev)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step has after it: the updated weights (the module's parameters are views of the flat buffer) and the step's
+        # gradient (the fused step does not write logits)
+        dump_outputs(args.dump_outputs, {"params": m._flat, "grad": tr.g[:m._flat.numel()]})
+    x0, h0, t0_, d0, b0 = host_batches[0]
+    BL = int(b0[0]); maxd = int(np.ceil(d0).max())
+    N1 = cfg.receptive_field(maxd) + BL - 1
+    hoist = os.environ.get("QPN_AUX_HOIST", "1") != "0"
+    value = args.steps * world / dt
+    out = {
+        "metric": "train steps/sec (batch-1 chunk-steps of RF+20000 samples, aggregate over GPUs)",
+        "value": value, "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "config[1]: paper-size SI-QPNet (C=64,S=256,4F+4A) training step, forward+CE+backward+Adam on one chunk "
+                               "of %d samples (RF %d + batch_length %d), batch 1 per GPU" % (x0.shape[1], N1 + 1 - BL, BL),
+                   "global_batch": world, "parallelism": "dp%d (utterance-sharded chunks, one flat-gradient all-reduce per step)" % world,
+                   "backend": BACKEND, "world_size": (dist.get_world_size() if dist.is_initialized() else 1),
+                   "aux_1x1": "frame rate (hoisted: K = 128 + one 4-deep step)" if hoist else "sample rate (K = 176)",
+                   "init": {"steps": n_init, "busy_ms": init_ms, "why": "handle initialisation + the device's ramp out of its idle power state, before the W warm-up steps (MEASUREMENTS R6.1)"}},
+    }
+    if not args.full:
+        return out
     # per-kernel-group device time of more (untimed) steps: serial (every launch alone on one stream) and as the timed loop runs them (two streams)
     L_, hd = m._native(dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
@@ -460,15 +512,11 @@ def run_train(args, rank, local, world):
         return [v / nprof for v in buf]
     ms = profile(L_.qpn_train_profile_begin)
     ms_ov = profile(L_.qpn_train_profile_begin_overlapped) if world == 1 else ms
-    x0, h0, t0_, d0, b0 = host_batches[0]
-    BL = int(b0[0]); maxd = int(np.ceil(d0).max())
-    N1 = cfg.receptive_field(maxd) + BL - 1
     starts, s_ = [], 0
     for dil in cfg.dilationsF:
         s_ += dil; starts.append(s_)
     for dil in cfg.dilationsA:
         s_ += dil * maxd; starts.append(s_)
-    hoist = os.environ.get("QPN_AUX_HOIST", "1") != "0"
     fl_algo, fl = train_flops(cfg, N1, BL, starts, hoist)
     knames = pg_kernel_names(hoist)
     if os.environ.get("QPN_POST_FUSE", "1") != "0":
@@ -496,49 +544,36 @@ def run_train(args, rank, local, world):
     low_ov = min((k_ for k_ in overlapped if k_["gflop"] > 0 and k_["us"] >= 50.0), key=lambda k_: k_["frac"], default=dom)
     wg_ms = sum(ms[i] for i in PG_WGRAD); wg_fl = sum(fl[i] for i in PG_WGRAD)
     total_flops, total_algo = sum(fl), sum(fl_algo)
-    value = args.steps * world / dt
-    out = {
-        "metric": "train steps/sec (batch-1 chunk-steps of RF+20000 samples, aggregate over GPUs)",
-        "value": value, "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "config[1]: paper-size SI-QPNet (C=64,S=256,4F+4A) training step, forward+CE+backward+Adam on one chunk "
-                               "of %d samples (RF %d + batch_length %d), batch 1 per GPU" % (x0.shape[1], N1 + 1 - BL, BL),
-                   "global_batch": world, "parallelism": "dp%d (utterance-sharded chunks, one flat-gradient all-reduce per step)" % world,
-                   "backend": BACKEND, "world_size": (dist.get_world_size() if dist.is_initialized() else 1),
-                   "aux_1x1": "frame rate (hoisted: K = 128 + one 4-deep step)" if hoist else "sample rate (K = 176)",
-                   "init": {"steps": n_init, "busy_ms": init_ms, "why": "handle initialisation + the device's ramp out of its idle power state, before the W warm-up steps (MEASUREMENTS R6.1)"}},
-        "roofline": {"bound": "mfma", "achieved": dom["tflops"], "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": dom["tflops"] / F32_MFMA_PEAK_TFLOPS,
-                     "traffic": dom["hbm_bytes"],
-                     "traffic_source": "%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, per kernel and launch; commit %s)"
-                                       % (tr_meas.get("_file"), tr_meas.get("commit", "?")),
-                     "step_traffic": tr_meas.get("train", {}).get("hbm_bytes_per_step_all_kernels"),
-                     "kernel": dom["name"], "kernel_ms": dom["us"] / 1e3, "flops_per_launch": dom["gflop"] * 1e9,
-                     # every heavy kernel of the step, longest first: us from HIP events around the launch (one stream), gflop = EXECUTED FLOPs,
-                     # mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES fraction from the committed PMC pass (profiles/), hbm_bytes per launch likewise
-                     "kernels": kernels[:8],
-                     # the same launches timed INSIDE the two-stream step (qpn_train_profile_begin_overlapped): roofline.kernel / achieved / frac are the longest of THESE;
-                     # the committed rocprofv3 pass of the same two-stream command is profiles/r06_train2_kernel_stats.csv
-                     "overlapped": overlapped[:8],
-                     "kernel_alone": {"name": kernels[0]["name"], "us": kernels[0]["us"], "frac": kernels[0]["frac"]},
-                     # the kernel (of those >= 50 us) furthest below the matrix-core roofline, alone and inside the step
-                     "lowest": {"name": low["name"], "us": low["us"], "frac": low["frac"], "mfma_busy": low["mfma_busy"]},
-                     "lowest_overlapped": {"name": low_ov["name"], "us": low_ov["us"], "frac": low_ov["frac"]},
-                     "wgrad_group": {"launches": 5, "ms": round(wg_ms, 4), "tflops": round(wg_fl / (wg_ms * 1e-3) / 1e12, 1) if wg_ms > 0 else None,
-                                     "frac": round(wg_fl / (wg_ms * 1e-3) / 1e12 / F32_MFMA_PEAK_TFLOPS, 3) if wg_ms > 0 else None},
-                     "step_tflops": total_flops / (sum(ms) * 1e-3) / 1e12, "step_device_ms": sum(ms),
-                     # the whole step against the same peak: executed FLOPs of every group / the timed loop's ms_per_step
-                     "step_flops": total_flops, "step_flops_algorithmic": total_algo, "step_achieved": total_flops / (dt / args.steps) / 1e12,
-                     "step_frac": total_flops / (dt / args.steps) / 1e12 / F32_MFMA_PEAK_TFLOPS,
-                     "step_frac_algorithmic": total_algo / (dt / args.steps) / 1e12 / F32_MFMA_PEAK_TFLOPS,
-                     "groups_ms": dict(zip(PG_NAMES, [round(v, 4) for v in ms])),
-                     "groups_ms_overlapped": dict(zip(PG_NAMES, [round(v, 4) for v in ms_ov])),
-                     "note": "roofline.kernel = the single longest kernel of the step AS THE TIMED LOOP RUNS IT (two streams: the skip / post-net weight gradients, the early slab "
-                             "reduction, the aux-gradient tail and dWr on a side stream next to the stack backward and dW1); achieved = its EXECUTED FLOPs / its device time "
-                             "from HIP events around the launch on the stream it runs on (roofline.overlapped); roofline.kernels = the same launches alone on one stream.  "
-                             "step_frac counts executed FLOPs over the timed loop's ms_per_step; step_frac_algorithmic credits the reference's sample-rate aux 1x1 (SURVEY 8d) instead."},
-    }
+    out["roofline"] = {"bound": "mfma", "achieved": dom["tflops"], "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                       "frac": dom["tflops"] / F32_MFMA_PEAK_TFLOPS,
+                       "traffic": dom["hbm_bytes"],
+                       "traffic_source": "%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, per kernel and launch; commit %s)"
+                                         % (tr_meas.get("_file"), tr_meas.get("commit", "?")),
+                       "step_traffic": tr_meas.get("train", {}).get("hbm_bytes_per_step_all_kernels"),
+                       "kernel": dom["name"], "kernel_ms": dom["us"] / 1e3, "flops_per_launch": dom["gflop"] * 1e9,
+                       # every heavy kernel of the step, longest first: us from HIP events around the launch (one stream), gflop = EXECUTED FLOPs,
+                       # mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES fraction from the committed PMC pass (profiles/), hbm_bytes per launch likewise
+                       "kernels": kernels[:8],
+                       # the same launches timed INSIDE the two-stream step (qpn_train_profile_begin_overlapped): roofline.kernel / achieved / frac are the longest of THESE;
+                       # the committed rocprofv3 pass of the same two-stream command is profiles/r06_train2_kernel_stats.csv
+                       "overlapped": overlapped[:8],
+                       "kernel_alone": {"name": kernels[0]["name"], "us": kernels[0]["us"], "frac": kernels[0]["frac"]},
+                       # the kernel (of those >= 50 us) furthest below the matrix-core roofline, alone and inside the step
+                       "lowest": {"name": low["name"], "us": low["us"], "frac": low["frac"], "mfma_busy": low["mfma_busy"]},
+                       "lowest_overlapped": {"name": low_ov["name"], "us": low_ov["us"], "frac": low_ov["frac"]},
+                       "wgrad_group": {"launches": 5, "ms": round(wg_ms, 4), "tflops": round(wg_fl / (wg_ms * 1e-3) / 1e12, 1) if wg_ms > 0 else None,
+                                       "frac": round(wg_fl / (wg_ms * 1e-3) / 1e12 / F32_MFMA_PEAK_TFLOPS, 3) if wg_ms > 0 else None},
+                       "step_tflops": total_flops / (sum(ms) * 1e-3) / 1e12, "step_device_ms": sum(ms),
+                       # the whole step against the same peak: executed FLOPs of every group / the timed loop's ms_per_step
+                       "step_flops": total_flops, "step_flops_algorithmic": total_algo, "step_achieved": total_flops / (dt / args.steps) / 1e12,
+                       "step_frac": total_flops / (dt / args.steps) / 1e12 / F32_MFMA_PEAK_TFLOPS,
+                       "step_frac_algorithmic": total_algo / (dt / args.steps) / 1e12 / F32_MFMA_PEAK_TFLOPS,
+                       "groups_ms": dict(zip(PG_NAMES, [round(v, 4) for v in ms])),
+                       "groups_ms_overlapped": dict(zip(PG_NAMES, [round(v, 4) for v in ms_ov])),
+                       "note": "roofline.kernel = the single longest kernel of the step AS THE TIMED LOOP RUNS IT (two streams: the skip / post-net weight gradients, the early slab "
+                               "reduction, the aux-gradient tail and dWr on a side stream next to the stack backward and dW1); achieved = its EXECUTED FLOPs / its device time "
+                               "from HIP events around the launch on the stream it runs on (roofline.overlapped); roofline.kernels = the same launches alone on one stream.  "
+                               "step_frac counts executed FLOPs over the timed loop's ms_per_step; step_frac_algorithmic credits the reference's sample-rate aux 1x1 (SURVEY 8d) instead."}
     if world == 1 and not args.no_cpu:
         # the drop-in path north_star describes: the reference's own loop on this module (weights keep training; timing only)
         # the loop `python -m qpnet_amd.run_train` runs: generator + pinned staging + prefetch thread + step(want_loss="lagged"): every step's loss
@@ -672,6 +707,11 @@ def main():
     ap.add_argument("--frames", type=int, default=2005, help="frames per utterance (2005 -> 10 s @22.05 kHz)")
     ap.add_argument("--f0-factor", dest="f0_factor", type=float, default=1.0, help="F0 scaling of the decode workload (BASELINE config[4]: 0.5 / 1.5)")
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: train roofline profile, runner / drop-in loops, CPU baselines, sampling mode, "
+                         "and with --mode all the decode batches, F0 factors and the default geometry")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 3 if args.mode == "decode" else 200
@@ -685,10 +725,10 @@ def main():
         out = run_decode(args, rank, local, world)
     else:
         out = run_train(args, rank, local, world)
-        if args.mode == "all" and world == 1:
+        if args.full and args.mode == "all" and world == 1:
             # the other half of BASELINE.json's metric: AR decode samples/sec/GPU (same JSON line)
             import copy
-            a2 = copy.copy(args); a2.steps, a2.warmup = 2, 1
+            a2 = copy.copy(args); a2.steps, a2.warmup, a2.dump_outputs = 2, 1, None
             out["decode"] = run_decode(a2, rank, local, world)
             a3 = copy.copy(a2); a3.batch, a3.no_cpu = 1, True
             d1 = run_decode(a3, rank, local, world)

@@ -1,97 +1,80 @@
-"""Build-container proof that the REFERENCE's own task scripts bind the drop-in module.
+"""The reference's own task scripts bind the drop-in module.
 
-runQP.py puts src/utils:src/nets on PYTHONPATH and the scripts do `from qpnet import ...`
-(/root/reference/src/bin/qpnet_train.py:35-37, qpnet_decode.py:32-34).  With qpnet_amd/dropin in FRONT of src/nets the names they bind
-must be this repo's, and everything they do with them on the host -- construct from the argparse namespace, .apply(initialize), read the
-receptive fields, wrap in DataParallel, write a checkpoint (qpnet_train.py:400-423,463-465,338-353) -- must work on the drop-in class.
-Construction / state only: no kernel runs on the CPU, the library has no CPU path.
-
-Skipped where /root/reference does not exist (the GPU box); nothing of the reference is copied or shipped -- it is imported in a child
-process of this test, here, as SURVEY.md section 8c established is possible."""
+runQP.py puts src/utils:src/nets on PYTHONPATH and the scripts do `from qpnet import ...` (qpnet_train.py:35-37, qpnet_decode.py:32-34).
+With qpnet_amd/dropin in FRONT of src/nets the names they bind must be this repo's, and everything they do with them on the host --
+construct from the argparse namespace, .apply(initialize), read the receptive fields, wrap in DataParallel, write and resume a checkpoint
+(qpnet_train.py:400-423,463-465,338-353,481-499) -- must work on the drop-in class and match what the reference class does.
+What the reference does is recorded in tests/golden/dropin.json (tests/golden/make_dropin_golden.py imports the scripts to write it).
+Construction / state only: no kernel runs on the CPU, the library has no CPU path."""
+import copy
+import importlib
+import json
 import os
-import subprocess
 import sys
 
+import numpy as np
 import pytest
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/src"
+DROPIN = os.path.join(ROOT, "qpnet_amd", "dropin")
 
-_CHILD = r"""
-import importlib.util, os, sys, tempfile, types, warnings
-warnings.filterwarnings("ignore")
-ROOT, REF = sys.argv[1], sys.argv[2]
-for name in ("h5py", "torchvision"):                       # absent from this image; the scripts only import them
+
+@pytest.fixture
+def dropin(monkeypatch):
+    """`import qpnet` with the drop-in directory first on the path, as the scripts' PYTHONPATH has it"""
+    monkeypatch.syspath_prepend(DROPIN)
+    saved = sys.modules.pop("qpnet", None)
     try:
-        __import__(name)
-    except ImportError:
-        sys.modules[name] = types.ModuleType(name)
-tv = sys.modules["torchvision"]
-if not hasattr(tv, "transforms"):
-    tv.transforms = types.ModuleType("torchvision.transforms"); sys.modules["torchvision.transforms"] = tv.transforms
-# the PYTHONPATH runQP.py builds (src/utils:src/nets, runQP.py:81-82) with the drop-in directory in front of it
-sys.path[:0] = [os.path.join(ROOT, "qpnet_amd", "dropin"), os.path.join(REF, "utils"), os.path.join(REF, "nets"), os.path.join(REF, "bin")]
-import torch
-import qpnet_train as rt
-import qpnet_decode as rd
-import qpnet_amd.qpnet as mine
-assert sys.modules["qpnet"].__file__.startswith(os.path.join(ROOT, "qpnet_amd", "dropin")), sys.modules["qpnet"].__file__
-assert rt.QPNet is mine.QPNet and rd.QPNet is mine.QPNet
-assert rt.initialize is mine.initialize and rt.encode_mu_law is mine.encode_mu_law
-assert rd.decode_mu_law is mine.decode_mu_law and rd.encode_mu_law is mine.encode_mu_law
+        yield importlib.import_module("qpnet")
+    finally:
+        sys.modules.pop("qpnet", None)
+        if saved is not None:
+            sys.modules["qpnet"] = saved
 
-# the network exactly as qpnet_train.py:400-414 builds it from its argparse namespace (defaults of runQP's 'default' model, param_model.py:58-64)
-args = types.SimpleNamespace(n_quantize=256, n_aux=39, n_resch=512, n_skipch=256, dilationF_depth=4, dilationF_repeat=3,
-                             dilationA_depth=4, dilationA_repeat=1, kernel_size=2, upsampling_factor=110, n_gpus=2, batch_size=1,
-                             lr=1e-4, weight_decay=0.0)
-model = rt.QPNet(n_quantize=args.n_quantize, n_aux=args.n_aux, n_resch=args.n_resch, n_skipch=args.n_skipch,
-                 dilationF_depth=args.dilationF_depth, dilationF_repeat=args.dilationF_repeat,
-                 dilationA_depth=args.dilationA_depth, dilationA_repeat=args.dilationA_repeat,
-                 kernel_size=args.kernel_size, upsampling_factor=args.upsampling_factor)
-model.apply(rt.initialize)
-model.train()
-assert float(model.upsampling.conv.weight.min()) == 1.0 and float(model.causal.conv.bias.abs().max()) == 0.0     # initialize reached the holders
-# the reference class, under another module name, as the yardstick for names / shapes / receptive fields
-spec = importlib.util.spec_from_file_location("ref_qpnet_module", os.path.join(REF, "nets", "qpnet.py"))
-refmod = importlib.util.module_from_spec(spec); spec.loader.exec_module(refmod)
-ref = refmod.QPNet(**{k: v for k, v in vars(args).items() if k not in ("n_gpus", "batch_size", "lr", "weight_decay")})
-for a in ("receptiveCausal_field", "receptiveF_field", "receptiveA_field", "n_quantize", "n_aux", "upsampling_factor"):
-    assert getattr(model, a) == getattr(ref, a), a
-assert list(model.dilationsF) == list(ref.dilationsF) and list(model.dilationsA) == list(ref.dilationsA)
-sd, rsd = model.state_dict(), ref.state_dict()
-assert list(sd.keys()) == list(rsd.keys())
-assert all(tuple(sd[k].shape) == tuple(rsd[k].shape) for k in sd)
-# setups for multi GPUs (qpnet_train.py:416-423)
-dp = torch.nn.DataParallel(model, range(args.n_gpus))
-dp.receptiveF_field = dp.module.receptiveF_field
-dp.receptiveA_field = dp.module.receptiveA_field
-dp.receptiveCausal_field = dp.module.receptiveCausal_field
-assert (dp.receptiveCausal_field, dp.receptiveF_field, dp.receptiveA_field) == (1, 45, 15)
-# optimizer and checkpoint (qpnet_train.py:426-429,338-353), and the resume path's load (qpnet_train.py:481-499) in both directions
-optimizer = torch.optim.Adam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
-with tempfile.TemporaryDirectory() as td:
-    rt._save_checkpoint(td, model, optimizer, 7)
-    ck = torch.load(td + "/checkpoint-7.pkl", map_location="cpu")
-    assert ck["iterations"] == 7 and list(ck["model"].keys()) == list(rsd.keys())
-    ref.load_state_dict(ck["model"])                       # a checkpoint written through the drop-in loads into the reference class ...
-    model.load_state_dict(ref.state_dict())                # ... and back
+
+def test_reference_scripts_bind_the_dropin_module(dropin, golden_dir, tmp_path):
+    import qpnet_amd.qpnet as mine
+    from qpnet_amd import loaders
+    g = json.load(open(os.path.join(golden_dir, "dropin.json")))
+    assert dropin.__file__.startswith(DROPIN), dropin.__file__
+    for script, names in g["imports"].items():
+        for n in names:
+            assert getattr(dropin, n) is getattr(mine, n), (script, n)
+    # the network as qpnet_train.py builds it from its argparse namespace
+    model = dropin.QPNet(**g["kwargs"])
+    model.apply(dropin.initialize)
+    model.train()
+    assert float(model.upsampling.conv.weight.min()) == 1.0 and float(model.causal.conv.bias.abs().max()) == 0.0     # initialize reached the holders
+    for a, v in g["attributes"].items():
+        assert getattr(model, a) == v, a
+    assert list(model.dilationsF) == g["dilationsF"] and list(model.dilationsA) == g["dilationsA"]
+    sd = model.state_dict()
+    assert [[k, list(v.shape)] for k, v in sd.items()] == g["state_dict"]
+    assert [[k, list(p.shape)] for k, p in model.named_parameters()] == g["parameters"]     # Adam's state is indexed in this order
+    # setups for multi GPUs (qpnet_train.py:416-423), over the devices this machine has (none: a plain wrapper; DataParallel moves the module to the first)
+    dp = torch.nn.DataParallel(copy.deepcopy(model), list(range(torch.cuda.device_count())))
+    dp.receptiveF_field = dp.module.receptiveF_field
+    dp.receptiveA_field = dp.module.receptiveA_field
+    dp.receptiveCausal_field = dp.module.receptiveCausal_field
+    assert (dp.receptiveCausal_field, dp.receptiveF_field, dp.receptiveA_field) == (1, 45, 15)
+    # a checkpoint laid out as the reference trainer writes it, and the resume path's load in both directions
+    optimizer = torch.optim.Adam(model.parameters(), lr=1e-4)
+    path = loaders.save_checkpoint(str(tmp_path), model, optimizer, g["checkpoint"]["iterations"])
+    ck = torch.load(path, map_location="cpu", weights_only=False)
+    assert sorted(os.listdir(tmp_path)) == g["checkpoint"]["files"]
+    assert sorted(ck.keys()) == g["checkpoint"]["keys"] and ck["iterations"] == g["checkpoint"]["iterations"]
+    assert list(ck["model"].keys()) == g["checkpoint"]["model_keys"]
+    assert sorted(ck["optimizer"].keys()) == g["checkpoint"]["optimizer_keys"]
+    assert [len(pg["params"]) for pg in ck["optimizer"]["param_groups"]] == g["checkpoint"]["optimizer_params"]
+    # a state dict with the reference class's names and shapes loads strictly into the drop-in class, and the decode script's construction takes it
+    ref_sd = {k: torch.full(s, 0.5) for k, s in g["state_dict"]}
+    model.load_state_dict(ref_sd)
+    m2 = dropin.QPNet(**g["kwargs"])
+    m2.load_state_dict(ck["model"]); m2.eval()
+    assert all(torch.equal(v, model.state_dict()[k]) for k, v in ref_sd.items())
     optimizer.load_state_dict(ck["optimizer"])
-# the decode script's model construction (qpnet_decode.py:276-288) and mu-law round trip on the drop-in's functions
-m2 = rd.QPNet(**{k: v for k, v in vars(args).items() if k not in ("n_gpus", "batch_size", "lr", "weight_decay")})
-m2.load_state_dict(ck["model"]); m2.eval()
-import numpy as np
-x = np.linspace(-1, 1, 101)
-assert np.array_equal(rd.encode_mu_law(x, 256), refmod.encode_mu_law(x, 256))
-assert np.array_equal(rd.decode_mu_law(np.arange(256), 256), refmod.decode_mu_law(np.arange(256), 256))
-print("DROPIN-BINDS-OK")
-"""
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference checkout (build container only)")
-def test_reference_scripts_bind_the_dropin_module(tmp_path):
-    script = tmp_path / "child.py"
-    script.write_text(_CHILD)
-    env = dict(os.environ)
-    env.pop("PYTHONPATH", None)
-    r = subprocess.run([sys.executable, str(script), ROOT, REF], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "DROPIN-BINDS-OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    # mu-law round trip on the drop-in's functions against the reference's tables
+    x = np.asarray(g["mu_law"]["x"])
+    assert np.array_equal(dropin.encode_mu_law(x, 256), np.asarray(g["mu_law"]["encoded"]))
+    assert np.array_equal(dropin.decode_mu_law(np.arange(256), 256), np.asarray(g["mu_law"]["decoded"]))

@@ -6,8 +6,8 @@ OUT=gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 export QPN_TRAIN_SERIAL=1
-TRAIN="python3 bench.py --mode train --steps 20 --warmup 3 --no-cpu"
-PMCT="python3 bench.py --mode train --steps 2 --warmup 1 --no-cpu"
+TRAIN="python3 bench.py --mode train --steps 20 --warmup 3 --no-cpu --full"
+PMCT="python3 bench.py --mode train --steps 2 --warmup 1 --no-cpu --full"
 DEC="python3 bench.py --mode decode --batch 20 --frames 2005 --steps 1 --warmup 0 --no-cpu"     # the BASELINE workload: 20 x 10 s
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/train_stats -o train -- $TRAIN > $OUT/train_stats.log 2>&1; echo "train stats rc=$?"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/decode_stats -o decode -- $DEC > $OUT/decode_stats.log 2>&1; echo "decode stats rc=$?"

@@ -73,7 +73,7 @@ if f:
         agg[norm(r.get("Kernel_Name") or "")][r["Counter_Name"]] += float(r["Counter_Value"])
     with open(os.path.join(dst, "%s_train_wait_pmc.txt" % tag), "w") as o:
         o.write("rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_VALU\n")
-        o.write("  -- python3 bench.py --mode train --steps 2 --warmup 1 --no-cpu   (QPN_TRAIN_SERIAL=1); fractions of SQ_WAVE_CYCLES summed over a kernel's dispatches\n")
+        o.write("  -- python3 bench.py --mode train --steps 2 --warmup 1 --no-cpu --full   (QPN_TRAIN_SERIAL=1); fractions of SQ_WAVE_CYCLES summed over a kernel's dispatches\n")
         o.write("%-44s %10s %8s %8s %8s %8s %8s %8s %8s\n" % ("kernel", "wave_cyc", "wait", "waitinst", "active", "wlds", "alds", "avmem", "avalu"))
         for k, v in sorted(agg.items(), key=lambda kv: -kv[1]["SQ_WAVE_CYCLES"])[:16]:
             w = v["SQ_WAVE_CYCLES"] or 1

@@ -1,6 +1,6 @@
 # dev: where one overlapped training step spends its wall time -- from a rocprofv3 --kernel-trace csv of `bench.py --mode train`:
-#   rocprofv3 --kernel-trace --output-format csv -d gpurun_out/tl -o tl -- python3 bench.py --mode train --steps 12 --warmup 3 --no-cpu
-#   python3 tools/step_timeline.py gpurun_out/tl
+#   rocprofv3 --kernel-trace --output-format csv -d trace/tl -o tl -- python3 bench.py --mode train --steps 12 --warmup 3 --no-cpu --full
+#   python3 tools/step_timeline.py trace/tl
 # prints, for the median of the last steps, every kernel's start offset from the step's first kernel, its duration, queue, and the idle gaps of the main queue
 import csv, glob, sys, re, statistics
 root = sys.argv[1]
