@@ -108,6 +108,24 @@ int qpn_decode_enqueue(qpn_handle* h, int B, int n_x, int64_t F, int64_t Td,
                        const int64_t* d_teacher, int64_t* d_out, float* d_logits, void* stream);
 int qpn_decode_finish(qpn_handle* h, void* stream);
 
+/* Live output: read finished samples while the decode kernel runs.
+ * Arm (every >= 1) or disarm (every == 0) live output for the decode calls enqueued on this handle from now on.  An armed
+ * call is the same launch plan with the same results; in addition the kernel mirrors every sample it picks into host memory
+ * owned by the handle and publishes, per row, how many are final there: after every `every` samples of the row and after
+ * its last one.  Not offered together with teacher forcing or the logits output (an armed enqueue with d_teacher or
+ * d_logits returns QPN_EINVAL), and an armed enqueue must not be captured into a HIP graph (it writes the counters from
+ * the host).  QPN_ESTATE while a decode is in flight. */
+int qpn_decode_live(qpn_handle* h, int every);
+
+/* Non-blocking.  For the decode in flight: h_done[B] = samples of each row (input order) that are final in the mirror;
+ * *h_samples / *row_stride = the mirror (int32 sample ids, row b at *h_samples + b * *row_stride; host memory owned by the
+ * handle, valid until the next enqueue); *running = 0 once everything the enqueue put on the stream has completed.  The
+ * counts never decrease during a call, also not while qpn_decode_finish re-runs a launch that gave up (the re-run produces
+ * the same samples bit for bit, so what has been read stays valid).  A launch that gave up leaves *running == 0 with rows
+ * short of their n_samples: qpn_decode_finish completes them in d_out.  QPN_ESTATE with no decode in flight or live output
+ * not armed for it, QPN_EINVAL for null arguments. */
+int qpn_decode_poll(qpn_handle* h, int64_t* h_done, const int32_t** h_samples, int64_t* row_stride, int* running);
+
 /* Device time (ms) of the persistent decode kernel of the last finished qpn_decode call,
  * measured with HIP events on the launch stream (bench.py roofline). */
 float qpn_last_decode_kernel_ms(qpn_handle* h);

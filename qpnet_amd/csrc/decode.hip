@@ -252,7 +252,7 @@ __device__ __forceinline__ void run_slot(const Ctx& c, int slot, int64_t t, floa
             if (p.mode == QPN_MODE_SAMPLING) bi = sample_wave(p.o_lg, Q, p.seed, (unsigned)u.row, (unsigned)i, lane);
             next = bi;
             if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
-            if (lane == 0) u.out[i] = bi;
+            if (lane == 0) { u.out[i] = bi; live_put(p, u, (int)i, bi); }
         } else next = u.known[t + 1];
         const int cur = smi[p.o_samp + 1];
         if (t + 2 < c.Ttot) causal_rows(p, u, cur, next, t + 1, lane);     // layer-0 input of the next step
@@ -553,7 +553,7 @@ __device__ __forceinline__ void fast_steps(const DecodeParams& p, const FastPara
                 if (p.mode == QPN_MODE_SAMPLING) bi = sample_wave(p.o_lg, Q, p.seed, (unsigned)u.row, (unsigned)i, lane);
                 next = bi;
                 if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
-                if (lane == 0) u.out[i] = bi;
+                if (lane == 0) { u.out[i] = bi; live_put(p, u, (int)i, bi); }
             } else next = u.known[t + 1];
             const int cur = smi[p.o_samp + 1];
             if (t + 2 < Ttot) causal_rows(p, u, cur, next, t + 1, lane);
@@ -891,6 +891,7 @@ extern "C" int qpn_create(const qpn_config* cfg, qpn_handle** out) {
     h->d_xch = nullptr; h->xch_cap = 0; h->single_cu_ok = true;
     h->d_utts = nullptr; h->utts_cap = 0; h->ev0 = h->ev1 = nullptr; h->last_ms = 0; h->pending = false; h->device = -1; h->train = nullptr;
     h->n_cus = 0; h->pipe_rows = 0; h->h_utts_pinned = nullptr; h->h_utts_cap = 0; h->dec_side = nullptr; h->dec_fork = h->dec_join = nullptr;
+    h->live_every = 0; h->live_call = false; h->h_live = h->d_live = nullptr; h->live_cap = 0; h->h_live_done = h->d_live_done = nullptr; h->live_done_cap = 0; h->live_stride = 0;
     {   // the environment is read HERE, once per handle: no decode or training call looks at it again
         DecodeKnobs& k = h->dk;
         k.generic = getenv("QPN_DECODE_GENERIC") != nullptr;
@@ -939,6 +940,8 @@ extern "C" void qpn_destroy(qpn_handle* h) {
         if (h->ev0) (void)hipEventDestroy(h->ev0);
         if (h->ev1) (void)hipEventDestroy(h->ev1);
         if (h->h_utts_pinned) (void)hipHostFree(h->h_utts_pinned);
+        if (h->h_live) (void)hipHostFree(h->h_live);
+        if (h->h_live_done) (void)hipHostFree(h->h_live_done);
         if (h->dec_side) (void)hipStreamDestroy(h->dec_side);
         if (h->dec_fork) (void)hipEventDestroy(h->dec_fork);
         if (h->dec_join) (void)hipEventDestroy(h->dec_join);
@@ -995,6 +998,20 @@ static int grow(T** p, size_t* cap, size_t need) {
     *p = nullptr; *cap = 0;
     hipError_t e = hipMalloc(p, need * sizeof(T));
     if (e != hipSuccess) { qpn_set_error("hipMalloc(%zu bytes) failed: %s", need * sizeof(T), hipGetErrorString(e)); return QPN_ENOMEM; }
+    *cap = need;
+    return QPN_OK;
+}
+
+// host-coherent pinned buffer of >= need elements (grow only) and the address the device uses for it
+template <class T>
+static int grow_coherent(T** hp, T** dp, size_t* cap, size_t need) {
+    if (need <= *cap) return QPN_OK;
+    if (*hp) (void)hipHostFree(*hp);
+    *hp = nullptr; *dp = nullptr; *cap = 0;
+    hipError_t e = hipHostMalloc((void**)hp, need * sizeof(T), hipHostMallocCoherent);
+    if (e != hipSuccess) { *hp = nullptr; qpn_set_error("hipHostMalloc(%zu bytes, coherent) failed: %s", need * sizeof(T), hipGetErrorString(e)); return QPN_ENOMEM; }
+    e = hipHostGetDevicePointer((void**)dp, *hp, 0);
+    if (e != hipSuccess) { (void)hipHostFree(*hp); *hp = nullptr; *dp = nullptr; qpn_set_error("hipHostGetDevicePointer failed: %s", hipGetErrorString(e)); return QPN_ENODEV; }
     *cap = need;
     return QPN_OK;
 }
@@ -1113,6 +1130,15 @@ static int decode_enqueue_impl(qpn_handle* h, int B, int n_x, int64_t F, int64_t
         QPN_HIP(hipHostMalloc((void**)&h->h_utts_pinned, (size_t)B * sizeof(UttDesc), hipHostMallocDefault));
         h->h_utts_cap = (size_t)B;
     }
+    if (h->live_call) {
+        // live output: the mirror and the counts grow like the descriptors; the counts are zeroed from the host (no kernel of this handle is
+        // running: one decode in flight, and the re-run of qpn_decode_finish comes after a stream synchronisation)
+        rc = grow_coherent(&h->h_live, &h->d_live, &h->live_cap, (size_t)B * (size_t)std::max<int64_t>(max_n, 1)); if (rc) return rc;
+        rc = grow_coherent(&h->h_live_done, &h->d_live_done, &h->live_done_cap, (size_t)B); if (rc) return rc;
+        for (int b = 0; b < B; ++b) __atomic_store_n(&h->h_live_done[b], 0LL, __ATOMIC_RELEASE);
+        h->live_stride = max_n;
+        p.live = h->d_live; p.live_done = h->d_live_done; p.live_every = h->live_every;
+    }
     UttDesc* utts = h->h_utts_pinned;      // pinned and owned by the handle (one decode in flight per handle): no host synchronisation here
     for (int k = 0; k < B; ++k) {
         const int b = order[k];
@@ -1204,8 +1230,40 @@ extern "C" int qpn_decode_enqueue(qpn_handle* h, int B, int n_x, int64_t F, int6
     c.B = B; c.n_x = n_x; c.F = F; c.Td = Td; c.d_x = d_x; c.d_h = d_h; c.d_dfac = d_dfac; c.d_is_f32 = d_is_f32;
     c.n_samples.assign(h_n_samples, h_n_samples + B); c.maxd = maxd; c.mode = mode; c.seed = seed;
     c.d_teacher = d_teacher; c.d_out = d_out; c.d_logits = d_logits; c.multi_wg = 0; c.coopG = 0;
+    h->live_call = h->live_every > 0;
+    if (h->live_call) {
+        if (d_teacher || d_logits) { h->live_call = false; qpn_set_error("live output is not offered together with teacher forcing or the logits output"); return QPN_EINVAL; }
+        h->live_seen.assign((size_t)B, 0);
+    }
     return decode_enqueue_impl(h, B, n_x, F, Td, d_x, d_h, d_dfac, d_is_f32, c.n_samples.data(), maxd, mode, seed, d_teacher, d_out, d_logits,
                                (hipStream_t)stream_, false, 0);
+}
+
+extern "C" int qpn_decode_live(qpn_handle* h, int every) {
+    int rc = need_device(h); if (rc) return rc;
+    if (every < 0) { qpn_set_error("every must be >= 1 (arm) or 0 (disarm)"); return QPN_EINVAL; }
+    if (h->pending) { qpn_set_error("a decode is in flight: call qpn_decode_finish first"); return QPN_ESTATE; }
+    h->live_every = every;
+    return QPN_OK;
+}
+
+extern "C" int qpn_decode_poll(qpn_handle* h, int64_t* h_done, const int32_t** h_samples, int64_t* row_stride, int* running) {
+    int rc = need_device(h); if (rc) return rc;
+    if (!h_done || !h_samples || !row_stride || !running) { qpn_set_error("null argument"); return QPN_EINVAL; }
+    if (!h->pending) { qpn_set_error("no decode in flight"); return QPN_ESTATE; }
+    if (!h->live_call) { qpn_set_error("the decode in flight was enqueued without live output (qpn_decode_live)"); return QPN_ESTATE; }
+    // the event first: once it has completed, the counts read below are the launch's last ones
+    const hipError_t q = hipEventQuery(h->ev1);
+    if (q != hipSuccess && q != hipErrorNotReady) { qpn_set_error("hipEventQuery failed: %s", hipGetErrorString(q)); return QPN_ENODEV; }
+    if (q == hipErrorNotReady) (void)hipGetLastError();      // (not an error: do not leave it for the next launch check to find)
+    *running = q == hipErrorNotReady ? 1 : 0;
+    for (int b = 0; b < h->call.B; ++b) {
+        const int64_t v = (int64_t)__atomic_load_n(&h->h_live_done[b], __ATOMIC_ACQUIRE);
+        if (v > h->live_seen[b]) h->live_seen[b] = v;
+        h_done[b] = h->live_seen[b];
+    }
+    *h_samples = h->h_live; *row_stride = h->live_stride;
+    return QPN_OK;
 }
 
 extern "C" const char* qpn_last_decode_plan(qpn_handle* h) { return h ? h->plan.c_str() : ""; }

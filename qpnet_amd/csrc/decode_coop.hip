@@ -256,7 +256,7 @@ __global__ __launch_bounds__(COOP_NT) void k_decode_coop(DecodeParams p, FastPar
                 if (p.mode == QPN_MODE_SAMPLING) bi = sample_wave(o_lg, Q, p.seed, (unsigned)u.row, (unsigned)i, lane);
                 next = bi;
                 if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
-                if (lane == 0 && gidx == 0) u.out[i] = bi;
+                if (lane == 0 && gidx == 0) { u.out[i] = bi; live_put(p, u, i, bi, c.abort); }
             } else next = u.known[t + 1];
             if (lane == 0) {
                 smi[o_samp] = smi[o_samp + 1]; smi[o_samp + 1] = next;

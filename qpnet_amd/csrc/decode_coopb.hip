@@ -332,7 +332,7 @@ __global__ __launch_bounds__(CBB_NT) void k_decode_coopb(const DecodeParams p, c
                 if (p.mode == QPN_MODE_SAMPLING) bi = sample_wave(o_lg + k * Q, Q, p.seed, (unsigned)u.row, (unsigned)i, lane);
                 next = bi;
                 if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
-                if (lane == 0 && w == 0) u.out[i] = bi;
+                if (lane == 0 && w == 0) { u.out[i] = bi; live_put(p, u, i, bi, c.abort); }
             } else next = u.known[t + 1];
             if (lane == 0) { smi[o_samp + 2 * k] = smi[o_samp + 2 * k + 1]; smi[o_samp + 2 * k + 1] = next; }
         }

@@ -230,6 +230,26 @@ __device__ __forceinline__ UttView make_view(const DecodeParams& p, const UttDes
     return u;
 }
 
+// Live output: the lane that has just stored sample i of its row (bi) mirrors it into host memory and, every live_every samples and after the
+// row's last one, publishes the row's count.  The mirror stores are system-scope (write-through) and the count is a system-scope release
+// store, which waits for them: a host that reads the count with an acquire load finds every sample below it in the mirror.  Rows of one
+// launch, of several launches and of one group all publish under their own row index, so the plan does not matter.  Not armed (live ==
+// nullptr, a kernel argument): one wave-uniform branch.
+// gave_up: the abort flag of a multi-workgroup launch.  A wait that ran out raises it and lets its step finish on whatever it holds, so the
+// pick of that step may be wrong; nothing is published once the flag is seen up.  The host then finds the launch ended short of the row's
+// length, and the re-run (qpn_decode_finish) produces the rest.  Where the wait that ran out is the picking workgroup's own, the flag is up
+// before the pick in program order.  Where it is a peer's or an upstream role's, this rests on timing, not on the memory model: the flag store
+// and the later stores that carry the step's values on are relaxed stores to different addresses, and the flag store leads them by the rest
+// of that stage's work and every hand-off between there and the pick (microseconds).
+__device__ __forceinline__ void live_put(const DecodeParams& p, const UttView& u, int i, int bi, const int* gave_up = nullptr) {
+    if (!p.live) return;
+    __hip_atomic_store(p.live + (u.out - p.out) + i, bi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if ((unsigned)(i + 1) % (unsigned)p.live_every == 0u || i + 1 == u.n_samples) {
+        if (gave_up && __hip_atomic_load(gave_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+        __hip_atomic_store(p.live_done + u.row, (long long)(i + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 // pitch-dependent tap distance of ring `r` at (padded) time t  (qpnet.py:613-624)
 // `widx` != 0: warm-up step over the known prefix -- the reference takes those taps from _dilated_index (qpnet.py:416,
 // 592-611: rint(-d*dil + idx), idx = position from the end of the prefix), not from _generate_dilated_index

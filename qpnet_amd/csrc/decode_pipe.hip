@@ -571,7 +571,7 @@ __device__ __forceinline__ void post2_pick_role(const DecodeParams& p, const Fas
                 u64* nx = X + PX_NX;
                 pst(nx + 65 + lane, tag, sm[o_tab + next * C + lane]);
                 pst(nx + 1 + lane, tag, sm[o_tab + (Q + next) * C + lane]);
-                if (lane == 0) { pst(nx, tag, __int_as_float(next)); u.out[i] = bi; }
+                if (lane == 0) { pst(nx, tag, __int_as_float(next)); u.out[i] = bi; live_put(p, u, i, bi, pp.abort); }
                 if (u.logits) for (int k = lane; k < Q; k += 64) u.logits[(size_t)i * Q + k] = sm[vb + o_lg + k];
             }
         }

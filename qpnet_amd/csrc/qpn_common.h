@@ -122,4 +122,8 @@ struct DecodeParams {
     const int* bias_src;    // [n_bias] flat indices of the biases mirrored in LDS
     unsigned long long seed;
     RingDesc rings[QPN_MAX_LAYERS];
+    // live output (qpn_decode_live), all null / 0 when it is not armed.  Host-coherent pinned memory that the host reads WHILE the launch runs:
+    int32_t* live;          // mirror of `out` ([B][max_n], the element offsets of UttDesc.out)
+    long long* live_done;   // [B], indexed by UttDesc.row: samples of that row that are final in the mirror
+    int live_every;         // a row publishes its count after every live_every samples, and after its last one
 };

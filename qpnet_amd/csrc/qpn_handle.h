@@ -48,6 +48,14 @@ struct qpn_handle {
     // pinned staging of the utterance descriptors (enqueue does not synchronise) + the side stream of a hybrid launch
     UttDesc* h_utts_pinned; size_t h_utts_cap;
     hipStream_t dec_side; hipEvent_t dec_fork, dec_join;
+    // live output (qpn_decode_live / qpn_decode_poll): host-coherent pinned memory the running kernel writes and the host reads
+    int live_every;                  // 0: not armed
+    bool live_call;                  // the decode in flight was enqueued armed
+    int32_t* h_live; int32_t* d_live; size_t live_cap;                 // mirror of d_out, [B][max_n] (host address / the device's address of it)
+    long long* h_live_done; long long* d_live_done; size_t live_done_cap;   // [B] published counts
+    int64_t live_stride;             // max_n of the call in flight
+    std::vector<int64_t> live_seen;  // per-row high-water mark of what qpn_decode_poll has reported.  The counts restart only while qpn_decode_finish re-runs a launch that gave up,
+                                     // and a handle is not thread-safe: only a caller that polls from a second thread under its own lock around finish could ever see the restart
     struct DecodeCall {              // arguments of the decode in flight: qpn_decode_finish re-runs it on the one-CU kernel when a
         int B, n_x; int64_t F, Td;   // multi-workgroup launch gave up (peers not co-resident: masked / shared GPU)
         const int64_t* d_x; const float* d_h; const void* d_dfac; int d_is_f32;

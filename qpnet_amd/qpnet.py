@@ -74,6 +74,20 @@ class _FrameUpsampler(nn.Module):
         self.conv = nn.ConvTranspose2d(1, 1, kernel_size=(1, factor), stride=(1, factor))
 
 
+def live_pieces(delivered, done):
+    """The step between two polls of a live decode: `delivered[b]` samples of row b have been handed on, `done[b]` are
+    reported final.  -> [(row, start, stop), ...] for the rows with something new, in row order, and `delivered` is advanced
+    in place.  A report below what has been delivered (a re-run starts its counts at zero) brings nothing and takes nothing
+    back: the row's next piece starts where the last one ended, once the report has caught up."""
+    pieces = []
+    for b, d in enumerate(done):
+        d = int(d)
+        if d > delivered[b]:
+            pieces.append((b, delivered[b], d))
+            delivered[b] = d
+    return pieces
+
+
 class QPNet(nn.Module):
     """Quasi-Periodic WaveNet vocoder; drop-in for the reference class (qpnet.py:160)."""
 
@@ -127,6 +141,7 @@ class QPNet(nn.Module):
         self.sampling_seed = None          # set to an int to pin the sampling-mode random stream
         self._n_generate_calls = 0
         self.last_sampling_seed = None
+        self._live_first_piece_s, self._live_mirror_pieces = None, 0      # generate_live (diagnostics): enqueue return -> first piece, pieces of the last call that were read from the mirror while the call was in flight
 
     # ------------------------------------------------------------------ native handle
     def _native(self, device):
@@ -207,6 +222,33 @@ class QPNet(nn.Module):
         the reference does), dilated_factors (B,T): numpy float64 when extra_memory is False,
         float tensor otherwise.  Returns the list of int64 ndarrays in completion order
         (ascending length, ties in input order)."""
+        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory)
+        L, hd, dev, B, ns, max_n, out, stream = a["L"], a["hd"], a["dev"], a["B"], a["ns"], a["max_n"], a["out"], a["stream"]
+        t_start = a["t_start"]
+        with torch.cuda.device(dev):
+            _lib.check(L.qpn_decode(*a["call"]))
+            self.last_decode_kernel_ms = float(L.qpn_last_decode_kernel_ms(hd))
+            self.last_decode_plan = L.qpn_last_decode_plan(hd).decode("utf-8", "replace")
+        out_np = out.cpu().numpy()
+        if intervals is not None and intervals > 0 and max_n > 0:
+            # progress lines of the reference loop (qpnet.py:519-524).  The whole call is one persistent launch, so they are
+            # written once it has returned, with the measured mean time per sample (the estimate the reference prints is
+            # the same quantity taken over the last `intervals` samples)
+            per = (time.time() - t_start) / max_n
+            for i in range(intervals, max_n + 1, intervals):
+                logging.info("%d/%d estimated time = %.3f sec (%.3f sec / sample)" % (i, max_n, (max_n - i) * per, per))
+        # completion order + in-place consumption of n_samples_list (reference qpnet.py:527-557)
+        order = sorted(range(B), key=lambda i: ns[i])
+        result = [out_np[i, :ns[i]].copy() for i in order]
+        keep = ns[order[-1]]
+        del n_samples_list[:]
+        n_samples_list.append(keep)
+        return result
+
+    def _decode_args(self, x, h, n_samples_list, dilated_factors, mode, extra_memory):
+        """What batch_fast_generate and generate_live do before the library call: mode check, maxd, dtype and device moves, the
+        output buffer, the sampling seed, binding the weights.  -> dict; "call" is the argument tuple of qpn_decode / qpn_decode_enqueue, the rest
+        keeps the tensors behind its pointers alive."""
         if mode not in ("sampling", "argmax"):
             logging.error("mode should be sampling or argmax")
             sys.exit(1)
@@ -239,30 +281,91 @@ class QPNet(nn.Module):
         seed = self.sampling_seed if self.sampling_seed is not None else (torch.initial_seed() + self._n_generate_calls) % (1 << 64)
         self._n_generate_calls += 1
         self.last_sampling_seed = seed
-        t_start = time.time()
+        t_start = time.time()           # (the clock of batch_fast_generate's progress lines starts here, in front of the weight binding)
+        arr = (C.c_int64 * B)(*ns)
+        call = (hd, B, xd.shape[1], hd_.shape[2], d_dev.shape[1], xd.data_ptr(), hd_.data_ptr(), d_dev.data_ptr(), d_is_f32,
+                arr, maxd, 1 if mode == "sampling" else 0, seed, None, out.data_ptr(), None, stream)
         with torch.cuda.device(dev):
-            self._bind_decode_weights(L, hd, dev, stream)
-            arr = (C.c_int64 * B)(*ns)
-            _lib.check(L.qpn_decode(hd, B, xd.shape[1], hd_.shape[2], d_dev.shape[1],
-                                    xd.data_ptr(), hd_.data_ptr(), d_dev.data_ptr(), d_is_f32,
-                                    arr, maxd, 1 if mode == "sampling" else 0, seed, None, out.data_ptr(), None, stream))
-            self.last_decode_kernel_ms = float(L.qpn_last_decode_kernel_ms(hd))
-            self.last_decode_plan = L.qpn_last_decode_plan(hd).decode("utf-8", "replace")
-        out_np = out.cpu().numpy()
-        if intervals is not None and intervals > 0 and max_n > 0:
-            # progress lines of the reference loop (qpnet.py:519-524).  The whole call is one persistent launch, so they are
-            # written once it has returned, with the measured mean time per sample (the estimate the reference prints is
-            # the same quantity taken over the last `intervals` samples)
-            per = (time.time() - t_start) / max_n
-            for i in range(intervals, max_n + 1, intervals):
-                logging.info("%d/%d estimated time = %.3f sec (%.3f sec / sample)" % (i, max_n, (max_n - i) * per, per))
-        # completion order + in-place consumption of n_samples_list (reference qpnet.py:527-557)
-        order = sorted(range(B), key=lambda i: ns[i])
-        result = [out_np[i, :ns[i]].copy() for i in order]
-        keep = ns[order[-1]]
-        del n_samples_list[:]
-        n_samples_list.append(keep)
-        return result
+            flat = self._bind_decode_weights(L, hd, dev, stream)
+        return dict(L=L, hd=hd, dev=dev, B=B, ns=ns, max_n=max_n, out=out, stream=stream, call=call, t_start=t_start, keep=(xd, hd_, d_dev, arr, flat))
+
+    # ------------------------------------------------------------------ live decode output
+    def generate_live(self, x, h, n_samples_list, dilated_factors, intervals=None, mode="sampling",
+                      extra_memory=False, every=256, poll_s=0.001):
+        """batch_fast_generate as a generator that hands samples over while the decode kernel runs: yields (row, start, samples)
+        -- row = index in the input order, samples = a fresh int64 ndarray holding that row's samples [start, start + len) --
+        as soon as a poll of the library (qpn_decode_poll) shows new finished samples of a row.  A row's pieces are contiguous
+        and in order; concatenated they are what batch_fast_generate returns for that row.  The kernel publishes a row's
+        progress every `every` samples and at its end.  After the last piece the call is finished and raises what
+        batch_fast_generate raises (a QpnError for a dilated factor outside the rings, ...).  Same arguments and seed rule as
+        batch_fast_generate, except that n_samples_list is not consumed.  Polling happens in the caller's thread (no background
+        thread), with time.sleep(poll_s) between polls that brought nothing; with `intervals` the reference's progress line
+        (qpnet.py:519-524) is written as the longest row passes each multiple.  Closing or dropping the generator early finishes
+        the call (the kernel runs to its end: there is no cancel) and leaves the model usable."""
+        if int(every) < 1:
+            raise ValueError("every must be >= 1")
+        self._native(x.device)          # (CPU tensors are refused here, at the call, not at the first next())
+        return self._live_pieces(x, h, list(n_samples_list), dilated_factors, intervals, mode, extra_memory, int(every), float(poll_s))
+
+    def _live_pieces(self, x, h, n_samples_list, dilated_factors, intervals, mode, extra_memory, every, poll_s):
+        import ctypes as C
+        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory)
+        L, hd, dev, B, ns, max_n, out, stream = a["L"], a["hd"], a["dev"], a["B"], a["ns"], a["max_n"], a["out"], a["stream"]
+        done = (C.c_int64 * B)()
+        mirror, stride, running = C.POINTER(C.c_int32)(), C.c_int64(), C.c_int()
+        delivered = [0] * B
+        longest = max(range(B), key=lambda b: ns[b])
+        next_line, t_line = (intervals if intervals is not None and intervals > 0 else 0), time.time()
+        in_flight = False
+
+        def progress(b, stop):          # the reference's progress line, as the longest row passes each multiple of `intervals`
+            nonlocal next_line, t_line
+            while next_line and b == longest and next_line <= stop:
+                now = time.time()
+                per = (now - t_line) / intervals
+                logging.info("%d/%d estimated time = %.3f sec (%.3f sec / sample)" % (next_line, max_n, (max_n - next_line) * per, per))
+                t_line = now
+                next_line += intervals
+
+        try:
+            with torch.cuda.device(dev):
+                _lib.check(L.qpn_decode_live(hd, every))
+                _lib.check(L.qpn_decode_enqueue(*a["call"]))
+                in_flight = True
+                t_enqueued = time.time()
+                self._live_first_piece_s, self._live_mirror_pieces = None, 0      # (diagnostics: tools/live_decode.py)
+                self.last_decode_plan = L.qpn_last_decode_plan(hd).decode("utf-8", "replace")
+            while any(delivered[b] < ns[b] for b in range(B)):
+                with torch.cuda.device(dev):
+                    _lib.check(L.qpn_decode_poll(hd, done, C.byref(mirror), C.byref(stride), C.byref(running)))
+                pieces = live_pieces(delivered, [min(int(done[b]), ns[b]) for b in range(B)])
+                if pieces:
+                    rows = np.ctypeslib.as_array(mirror, shape=(B, max(int(stride.value), 1)))
+                for b, start, stop in pieces:
+                    progress(b, stop)
+                    if self._live_first_piece_s is None:
+                        self._live_first_piece_s = time.time() - t_enqueued
+                    self._live_mirror_pieces += 1
+                    yield b, start, rows[b, start:stop].astype(np.int64)
+                if not pieces:
+                    if not running.value:
+                        break           # the launch gave up short of the end: finish re-runs it, the rest comes from its output
+                    time.sleep(poll_s)
+            with torch.cuda.device(dev):
+                in_flight = False
+                _lib.check(L.qpn_decode_finish(hd, stream))
+                self.last_decode_kernel_ms = float(L.qpn_last_decode_kernel_ms(hd))
+                self.last_decode_plan = L.qpn_last_decode_plan(hd).decode("utf-8", "replace")
+            if any(delivered[b] < ns[b] for b in range(B)):
+                out_np = out.cpu().numpy()
+                for b, start, stop in live_pieces(delivered, ns):
+                    progress(b, stop)
+                    yield b, start, out_np[b, start:stop].copy()
+        finally:
+            with torch.cuda.device(dev):
+                if in_flight:
+                    L.qpn_decode_finish(hd, stream)      # (abandoned, or an error on the way: what it reports has nobody to go to)
+                L.qpn_decode_live(hd, 0)
 
     # test/diagnostic helper (not part of the reference surface): teacher-forced streaming logits
     def _stream_logits(self, x, h, dilated_factors, teacher, n_samples):
