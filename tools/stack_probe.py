@@ -1,6 +1,6 @@
 """dev: device time of the two stack launches ALONE (serial per-launch profile, qpn_train_profile_begin) on the bench chunk, for the launch plan the environment selects
-(QPN_STACK_WAVE[_FWD|_BWD], QPN_STACK_WAVES, QPN_STACK_WGS[_BWD], QPN_LIB=<a -DSW_EXP variant>), plus the queues' counters.
-    python tools/stackw_probe.py [label]"""
+(QPN_STACK_QUEUE[_BWD], QPN_STACK_WGS[_BWD], QPN_LIB=<a build variant>), plus the queues' counters.
+    python tools/stack_probe.py [label]"""
 import ctypes as C, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
