@@ -6,7 +6,7 @@ data (seeds, small inputs, expected outputs) and are what travels to the GPU box
 Inputs are regenerated from seeds by qpnet_amd.synth (np.random.RandomState: frozen streams),
 so fixtures store only what cannot be regenerated: the reference's outputs.
 
-    python tests/golden/make_golden.py [--only decode|decode2|decode_d|forward|train|kat|default|deep]
+    python tests/golden/make_golden.py [--only decode|decode2|decode_d|forward|train|kat|kat_ties|default|deep]
 """
 import argparse
 import os
@@ -71,6 +71,41 @@ def gen_kat():
     out["didx_long_train_f32_3"] = m._dilated_index(torch.from_numpy(dl), 8, 1)[:, 0].numpy()
     np.savez_compressed(os.path.join(HERE, "kat.npz"), **out)
     print("kat.npz written")
+
+
+def kat_ties_input():
+    """pitch factors on the 1/16 grid over 1.0 ... 62.0 (float64; exact in float32 too): d * dilation hits exact .5 and exact integers at every adaptive
+    dilation 1, 2, 4, 8.  Row 0: the whole grid, with a run of the unvoiced value 1.0 and a run of integers; row 1: the half grid n + 0.5 (a tie at
+    dilation 1 wherever it stands) with a run of 1.0 and the two ends of the range."""
+    rs = np.random.RandomState(17)
+    d = rs.randint(16, 62 * 16 + 1, size=(2, 400)) / 16.0
+    d[1] = np.minimum(np.floor(d[1]), 61.0) + 0.5
+    d[0, 40:80] = 1.0
+    d[0, 200:260] = rs.randint(1, 63, size=60)
+    d[1, 300:330] = 1.0
+    d[1, 0], d[1, -1] = 62.0, 1.0
+    return d
+
+
+def gen_kat_ties():
+    """the reference's own index tensors where its rounding rule (torch.round / np.round: half to even) differs from roundf's (half away from zero)"""
+    m = ref.QPNet(**TINY.kwargs())
+    d64 = kat_ties_input()
+    d32 = d64.astype(np.float32)
+    assert np.array_equal(d32.astype(np.float64), d64) and d64.min() == 1.0 and d64.max() == 62.0
+    out = {"d64": d64}
+    for k in range(4):
+        dil = 2 ** k
+        out["train_f32_%d" % k] = m._dilated_index(torch.from_numpy(d32), dil, 1)[:, 0].numpy()
+        out["train_f64_%d" % k] = m._dilated_index(d64, dil, 1, tensor=False)[:, 0]
+        out["gen_f32_%d" % k] = m._generate_dilated_index(torch.from_numpy(d32), dil, 1)[:, 0].numpy()
+        out["gen_f64_%d" % k] = m._generate_dilated_index(d64, dil, 1, tensor=False)[:, 0]
+        p = d64 * dil
+        half_away = -np.floor(p + 0.5)                   # what roundf(-p) gives
+        print("dilation %d: %d exact .5 products, %d exact integers; roundf would change %d of %d generation taps"
+              % (dil, int((p - np.floor(p) == 0.5).sum()), int((p == np.floor(p)).sum()), int((half_away != out["gen_f64_%d" % k]).sum()), p.size))
+    np.savez_compressed(os.path.join(HERE, "kat_ties.npz"), **out)
+    print("kat_ties.npz written")
 
 
 
@@ -182,9 +217,9 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
     a = ap.parse_args()
-    todo = [a.only] if a.only else ["kat", "decode", "decode2", "decode_d", "forward", "train", "default", "deep"]
+    todo = [a.only] if a.only else ["kat", "kat_ties", "decode", "decode2", "decode_d", "forward", "train", "default", "deep"]
     for t in todo:
-        {"kat": gen_kat, "decode": gen_decode, "decode2": gen_decode2, "forward": gen_forward, "train": gen_train,
+        {"kat": gen_kat, "kat_ties": gen_kat_ties, "decode": gen_decode, "decode2": gen_decode2, "forward": gen_forward, "train": gen_train,
          "decode_d": lambda: gen_decode(DECODE_CASES_D, "decode_d.npz"),
          "default": lambda: (gen_forward(FORWARD_CASES_D, "forward_d.npz"), gen_train(TRAIN_CASES_D, "train_d.npz", 2000)),
          "deep": lambda: (gen_forward(FORWARD_CASES_DEEP, "forward_deep.npz"), gen_train(TRAIN_CASES_DEEP, "train_deep.npz", 22500),

@@ -342,6 +342,78 @@ def test_dilated_index_exports_vs_reference_kat(tag, cuda, golden_dir):
         np.testing.assert_array_equal(o.cpu().numpy(), g["didx_long_train_f32_3"])
 
 
+def _tie_factors(cfg, utts):
+    """a ragged decode batch whose pitch factors lie on the 1/16 grid and walk through all its residues (util.snap_to_grid; the zero padding stays zero):
+    d * dilation is an exact .5 or an exact integer at a good part of the steps of every adaptive ring, and row 0 carries a run of the unvoiced value 1.0"""
+    bx, bh, bd, ns = util.decode_batch(cfg, utts)
+    bd = util.snap_to_grid(bd, walk=+1)
+    bd[0, 150:260] = 1.0
+    for dil in (1, 2, 4, 8):
+        p = bd[bd > 0] * dil
+        assert (p - np.floor(p) == 0.5).sum() >= 40, dil
+    assert np.array_equal(bd.astype(np.float32).astype(np.float64), bd)
+    return bx, bh, bd, ns
+
+
+_TIE_KERNELS = {   # name: (geometry kwargs or None for PAPER, environment, what last_decode_plan must say)
+    "pipe": (None, {}, "pipe rows=2"),
+    "one-cu": (None, {"QPN_DECODE_PIPE": "0"}, "one-cu rows=2"),
+    "interpreter": (dict(n_resch=128, n_skipch=128, dilationF_depth=2, dilationF_repeat=1, dilationA_depth=2, dilationA_repeat=1), {}, ""),
+    "coop": (None, {"QPN_DECODE_COOP": "4"}, "coop G=4"),
+    "coopb": (dict(n_resch=256, n_skipch=256, dilationF_depth=2, dilationF_repeat=1, dilationA_depth=2, dilationA_repeat=2), {"QPN_DECODE_COOP": "32"}, "coopb G=32 "),
+}
+
+
+@pytest.mark.parametrize("kernel", list(_TIE_KERNELS))
+def test_decode_on_tie_pitch_factors_vs_oracle(kernel, cuda, oracle, monkeypatch):
+    """Pitch factors on the 1/16 grid: the tap distance round(d * dilation) meets exact ties, which the reference rounds to even (torch.round / np.round,
+    qpnet.py:617-622; the oracle is pinned there by tests/golden/kat_ties.npz) and roundf would round away from zero.  Every decode kernel, both factor
+    types (float64 numpy, float32 tensor with extra_memory: two rounding code paths in decode_dev.h), greedy and sampling, B = 2 ragged: bit-exact."""
+    import torch
+    from qpnet_amd.config import PAPER, QPNetConfig
+    geo, env, plan = _TIE_KERNELS[kernel]
+    monkeypatch.delenv("QPN_DECODE_COOPB", raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    cfg = PAPER if geo is None else QPNetConfig(**geo)
+    flat = synth.make_weights(cfg, 29)
+    m = util.build_model(cfg, flat, cuda)
+    bx, bh, bd, ns = _tie_factors(cfg, [(61, 4, 1.0), (62, 3, 0.5)])
+    xb, hb = torch.from_numpy(bx).to(cuda), torch.from_numpy(bh).to(cuda)
+    for extra in (False, True):
+        for mode in ("argmax", "sampling"):
+            m.sampling_seed = 5
+            d_arg = torch.from_numpy(bd).float().to(cuda) if extra else bd
+            outs = m.batch_fast_generate(xb, hb, list(ns), d_arg, mode=mode, extra_memory=extra)
+            assert plan in m.last_decode_plan, m.last_decode_plan
+            o_outs = oracle.batch_fast_generate(cfg, flat, bx, bh, list(ns), bd.astype(np.float32) if extra else bd, mode=mode, seed=5)
+            assert [len(a) for a in outs] == sorted(ns)
+            for i, (a, b) in enumerate(zip(outs, o_outs)):
+                np.testing.assert_array_equal(a, b, err_msg="%s, %s d, %s: stream %d" % (kernel, "float32" if extra else "float64", mode, i))
+
+
+def test_dilated_index_exports_at_ties_vs_reference_kat(cuda, golden_dir):
+    """the same three exports on tests/golden/kat_ties.npz: pitch factors on the 1/16 grid, i.e. exact .5 and integer products at every adaptive dilation
+    and runs of the unvoiced value 1.0 -- the reference rounds half to even (torch.round / np.round), roundf would change 197 of the 800 dilation-1 taps"""
+    import torch
+    from qpnet_amd import _lib
+    L = _lib.lib()
+    g = np.load(golden_dir + "/kat_ties.npz")
+    d64 = g["d64"]
+    d32 = d64.astype(np.float32)
+    B, n = d32.shape
+    t32 = torch.from_numpy(d32).to(cuda); t64 = torch.from_numpy(d64).to(cuda)
+    for k in range(4):
+        o = torch.empty((B, n), dtype=torch.int64, device=cuda)
+        _lib.check(L.qpn_dilated_index_train(t32.data_ptr(), B, n, 2 ** k, o.data_ptr(), None))
+        np.testing.assert_array_equal(o.cpu().numpy(), g["train_f32_%d" % k], err_msg="train, dilation %d" % 2 ** k)
+        _lib.check(L.qpn_dilated_index_gen_f32(t32.data_ptr(), B * n, 2 ** k, o.data_ptr(), None))
+        np.testing.assert_array_equal(o.cpu().numpy(), g["gen_f32_%d" % k], err_msg="gen_f32, dilation %d" % 2 ** k)
+        o32 = torch.empty((B, n), dtype=torch.int32, device=cuda)
+        _lib.check(L.qpn_dilated_index_gen_f64(t64.data_ptr(), B * n, 2 ** k, o32.data_ptr(), None))
+        np.testing.assert_array_equal(o32.cpu().numpy(), g["gen_f64_%d" % k], err_msg="gen_f64, dilation %d" % 2 ** k)
+
+
 # ---------------------------------------------------------------- several cooperating workgroups per utterance (decode_coop.hip)
 @pytest.mark.parametrize("case", DECODE_CASES, ids=[c[0] for c in DECODE_CASES])
 def test_cooperative_decode_matches_reference_streams(case, cuda, golden_dir, monkeypatch):

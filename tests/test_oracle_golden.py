@@ -41,6 +41,27 @@ def test_dilated_index_long(oracle, golden_dir):
     np.testing.assert_array_equal(oracle.dilated_index_train(g["didx_long_d32"], 8), g["didx_long_train_f32_3"])
 
 
+def test_dilated_index_at_ties_kat(oracle, golden_dir):
+    """tests/golden/kat_ties.npz: pitch factors on the 1/16 grid (exact .5 and integer products d * dilation at every adaptive dilation, runs of the
+    unvoiced value 1.0 and of integers) -- where the reference's round-half-to-even (torch.round / np.round, qpnet.py:600-622) and roundf part.  Both
+    oracles reproduce the reference's four index functions there, so they can serve as the yardstick of the GPU tests on such inputs."""
+    from oracle import train_oracle as TO
+    g = np.load(golden_dir + "/kat_ties.npz")
+    d64 = g["d64"]
+    d32 = d64.astype(np.float32)
+    assert np.array_equal(d32.astype(np.float64), d64)
+    for k in range(4):
+        p = d64 * 2 ** k
+        assert (p - np.floor(p) == 0.5).sum() >= 30 and (p == np.floor(p)).sum() >= 100      # ties and integers at every dilation
+        assert (-np.floor(p + 0.5) != g["gen_f64_%d" % k]).sum() >= 15                        # ... which round-half-away-from-zero gets wrong
+        np.testing.assert_array_equal(oracle.dilated_index_train(d32, 2 ** k), g["train_f32_%d" % k])
+        np.testing.assert_array_equal(oracle.dilated_index_train(d64, 2 ** k), g["train_f64_%d" % k])
+        np.testing.assert_array_equal(oracle.dilated_index_gen(d32, 2 ** k), g["gen_f32_%d" % k])
+        np.testing.assert_array_equal(oracle.dilated_index_gen(d64, 2 ** k), g["gen_f64_%d" % k])
+        for b in range(d32.shape[0]):
+            np.testing.assert_array_equal(TO.dilated_index(d32[b], 2 ** k), g["train_f32_%d" % k][b])
+
+
 @pytest.mark.parametrize("case", DECODE_CASES, ids=[c[0] for c in DECODE_CASES])
 def test_oracle_decode_equals_reference_streams(case, oracle, golden_dir):
     """bit-exact mu-law indices for greedy decode, incl. B>1 completion order, f0 x0.5 / x1.5,

@@ -30,14 +30,40 @@ def run_giveup_child(which, env_name):
     assert r.returncode == 0 and "GIVEUP_CHILD_OK " + which in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
-def assert_grads_match_oracle(TO, cfg, flat, caches, dl, grad, a_scale=2e-5, a_rel=1e-4, kink_eps=4e-6, max_units=6):
+def distinct_rows_batch(cfg, batch_length, seed, max_length, batch_size, f0_lo=60.0):
+    """A training batch whose rows DIFFER in everything a row owns, the way consecutive chunks of loaders.train_generator(batch_size=B) do: synth.train_inputs
+    draws every row's features (another pitch contour, so another d, and another h) and waveform from streams of that row's own.  With the pitch floor
+    pinned in every row's buffer the rows share the chunk geometry (receptive field, batch_length) without sharing ceil(max d) of the chunk itself.
+    Returns x, h, t, d, blength like synth.train_inputs, checked to differ row by row."""
+    x, h, t, d, b = synth.train_inputs(cfg, batch_length, seed, max_length, f0_lo=f0_lo, batch_size=batch_size, pin_f0_floor=True)
+    for r in range(batch_size):
+        for s in range(r):
+            assert not np.array_equal(x[r], x[s]) and not np.array_equal(h[r], h[s]) and not np.array_equal(d[r], d[s])
+    return x, h, t, d, b
+
+
+def snap_to_grid(d, step=1.0 / 16, walk=0):
+    """Pitch factors snapped to a multiple of `step` (a power of two: exact in float32 and float64).  On the 1/16 grid d * dilation is a multiple of 1/16,
+    1/8, 1/4, 1/2 at the adaptive dilations 1, 2, 4, 8: exact .5 products -- where round-half-to-even (torch.round / np.round, the reference's rule) and
+    round-half-away-from-zero (roundf) part -- and exact integers occur at every one of them.
+    walk = +1 / -1: the factors are constant over a frame (110 samples), so a snapped frame meets a tie at dilation 1 only if its one value happens to end
+    in .5; (n mod 16) * step is added to (subtracted from) sample n, which walks every frame through all sixteen residues.  Zeros (padding) stay zero."""
+    d = np.asarray(d)
+    g = np.round(d.astype(np.float64) / step) * step
+    if walk:
+        g = g + walk * step * (np.arange(d.shape[-1]) % 16)
+    return np.where(d > 0, g, 0.0).astype(d.dtype)
+
+
+def assert_grads_match_oracle(TO, cfg, flat, caches, dl, grad, a_scale=2e-5, a_rel=1e-4, kink_eps=4e-6, max_units=6, og=None):
     """Per-tensor comparison of a flat gradient with the numpy oracle's hand-derived backward: |g - ref| <= a_scale * max|ref (all tensors)| +
     a_rel * max|ref (this tensor)|.
 
     ReLU kinks: where a post-net pre-activation of the oracle's forward lies within fp32 reassociation error of zero (|s0| or |y0| < kink_eps;
     the logits of two correct fp32 implementations differ by ~1e-6), which side of the kink a unit falls on is decided by summation order, not
     by the algorithm -- and the side changes that row's gradient by a whole, small, term.  For those units (at most `max_units`) either side is
-    accepted: the gradient must match the oracle's backward for ONE assignment of sides.  Returns the oracle gradient that matched."""
+    accepted: the gradient must match the oracle's backward for ONE assignment of sides.  Returns the oracle gradient that matched.
+    og: the oracle's backward for these caches and dl if the caller has it already (it is computed once per input and shared)."""
     import itertools
     import numpy as np
     offs, _ = cfg.param_offsets()
@@ -53,7 +79,8 @@ def assert_grads_match_oracle(TO, cfg, flat, caches, dl, grad, a_scale=2e-5, a_r
                 bad = ("%s: err %.3e > bound %.3e" % (k, e, bound), e / bound)
         return bad
 
-    og = TO.backward(cfg, flat, caches, dl)
+    if og is None:
+        og = TO.backward(cfg, flat, caches, dl)
     bad = worst(og)
     if bad is None:
         return og
