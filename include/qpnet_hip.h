@@ -221,6 +221,24 @@ int qpn_adam_step_ex(qpn_handle* h, float* d_flat, const float* d_grad, float* d
                      int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                      const float* d_grad_denominator, void* stream);
 
+/* Gradient-norm clipping inside the optimiser step (no reference counterpart in the trainer itself; the reference-side loop a user writes is
+ * `torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)` followed by `Adam.step()`, and this is exactly that pair):
+ *   total = sqrt(sum_i g_i^2) over the first n floats of d_grad (/ d_grad_denominator[0] when given: the norm of the AVERAGED gradient), accumulated in fp64 in
+ *           a fixed order without atomics -- the same bits from run to run and on every data-parallel rank;
+ *   coef  = min(1, max_grad_norm / (total + 1e-6)), computed in fp64 and rounded once to fp32;
+ *   g_i  <- (g_i / denominator) * coef, before the weight-decay term; the rest of the update is qpn_adam_step_ex's.  d_grad itself is not modified.
+ * max_grad_norm <= 0: exactly qpn_adam_step_ex (qpn_adam_step and qpn_adam_step_ex are this call with 0).  One extra kernel launch per step, no copy, no host wait.
+ * A non-finite total (an inf or NaN in the gradient) is reported like the other device-side status bits: the update is skipped (weights, both moments and the
+ * applied-update count stay), bit 16 of the sticky status word is set, and the next status report returns QPN_ERANGE ("non-finite gradient norm"). */
+int qpn_adam_step_clip(qpn_handle* h, float* d_flat, const float* d_grad, float* d_m, float* d_v, int64_t n,
+                       int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       const float* d_grad_denominator, float max_grad_norm, void* stream);
+/* The norm (`total` above) of the LATEST Adam launch on this handle; *h_valid = 0 when that launch did not clip or there was none.  Drains `stream`. */
+int qpn_train_grad_norm(qpn_handle* h, double* h_norm, int* h_valid, void* stream);
+/* The same without a wait of its own, for a lagged loop: the norm of the step whose loss the last qpn_train_loss_collect returned (behind a clipping launch
+ * qpn_train_loss_enqueue takes the norm out in the loss's copy).  *h_valid = 0 when that step did not clip or no loss was returned. */
+int qpn_train_grad_norm_lagged(qpn_handle* h, double* h_norm, int* h_valid);
+
 /* Adam updates APPLIED on this handle so far, counted on the device: a k_adam launch that finds the sticky status word set -- or, behind a data-parallel
  * exchange, a peer rank's flag in the trailer (d_grad_denominator[1] > 0) -- applies nothing (every rank skips a step ANY rank flagged; the others report
  * "a peer rank flagged ..." with QPN_ERANGE).  Drains `stream`.  A caller that keeps the bias correction's step number on the host (the reference:
@@ -238,6 +256,15 @@ int qpn_train_step(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, in
                    float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
                    int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                    int loss_mode, double* h_loss, int* h_valid, void* stream);
+
+/* qpn_train_step with qpn_adam_step_clip as its optimiser step (max_grad_norm <= 0: exactly qpn_train_step, which is this call with 0 and NULL).  *h_grad_norm
+ * (may be NULL) is delivered with *h_loss: loss_mode 1 -- the previous step's norm, valid exactly when *h_valid is set (it comes out of the same pinned slot; after the
+ * last step qpn_train_loss_collect(newest = 1) + qpn_train_grad_norm_lagged fetch the pair); 2 -- this step's; 0 -- none.  The norm launch counts towards QPN_PG_ADAM. */
+int qpn_train_step_clip(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
+                        const int64_t* d_x, const float* d_h, const float* d_dfac, const int64_t* d_targets, int64_t tgt_stride,
+                        float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
+                        int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                        int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm, void* stream);
 
 /* Per-launch-group device timings of the training calls issued between begin and end (HIP events on `stream`; used by bench.py for
  * the roofline).  h_ms[QPN_PG_*] receives milliseconds.  While a profile is being taken a step runs on ONE stream, and every heavy

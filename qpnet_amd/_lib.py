@@ -55,6 +55,12 @@ SYMBOLS = [
     ("qpn_adam_step_ex", _i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]),
     ("qpn_train_step", _i, [_vp, _vp, _i, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
                             _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _i, C.POINTER(C.c_double), C.POINTER(C.c_int), _vp]),
+    ("qpn_adam_step_clip", _i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp, C.c_float, _vp]),
+    ("qpn_train_grad_norm", _i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int), _vp]),
+    ("qpn_train_grad_norm_lagged", _i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    ("qpn_train_step_clip", _i, [_vp, _vp, _i, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
+                                 _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _i, C.POINTER(C.c_double), C.POINTER(C.c_int),
+                                 C.c_float, C.POINTER(C.c_double), _vp]),
     ("qpn_train_applied_updates", _i, [_vp, C.POINTER(C.c_int64), _vp]),
     ("qpn_train_stack_stats", _i, [_vp, C.POINTER(C.c_uint), _i, _vp]),
     ("qpn_train_early_bucket", _i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp]),
@@ -89,8 +95,15 @@ def lib():
     return _lib
 
 
+# status errors (QPN_ERANGE / QPN_ENODEV: what the device-side status word raises) seen by check() so far: an optimizer that counts its steps on the host
+# (train.FlatAdam with clipping on) looks at this to learn that a step of its own may have been skipped on the device
+STATUS_ERRORS = [0]
+
+
 def check(rc):
     if rc != 0:
+        if rc in (-4, -2):
+            STATUS_ERRORS[0] += 1
         raise QpnError(rc, lib().qpn_last_error().decode("utf-8", "replace"))
 
 

@@ -1243,6 +1243,16 @@ __global__ __launch_bounds__(128) void k_aux_tail(AuxArgs p) {
 // rep: the step's reports, written straight into pinned host memory by the step's last kernel (a copy engine launch each -- 3-4 us on the stream -- otherwise):
 // the status word and, when asked for, the 64 partial sums of the loss (qpn_train_step)
 struct AdamReports { int* h_status; double* h_loss; const double* d_loss; };
+// the update of element i from its (scaled, clipped) gradient gi
+__device__ __forceinline__ void adam_update(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v, int64_t i, float gi,
+                                            float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
+    if (wd != 0.f) gi += wd * w[i];
+    const float mi = m[i] + (gi - m[i]) * (1.0f - b1);          // exp_avg.lerp_(grad, 1 - beta1)
+    const float vi = v[i] * b2 + (1.0f - b2) * gi * gi;         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    m[i] = mi; v[i] = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    w[i] = w[i] - (lr / bc1) * (mi / denom);
+}
 __global__ void k_adam(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
                        float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1265,12 +1275,81 @@ __global__ void k_adam(float* __restrict__ w, const float* __restrict__ g, float
     if (i >= n || skip) return;
     float gi = g[i];
     if (den) gi = gi / den[0];                                  // data-parallel: summed row-weighted gradients / summed row count
-    if (wd != 0.f) gi += wd * w[i];
-    const float mi = m[i] + (gi - m[i]) * (1.0f - b1);          // exp_avg.lerp_(grad, 1 - beta1)
-    const float vi = v[i] * b2 + (1.0f - b2) * gi * gi;         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    w[i] = w[i] - (lr / bc1) * (mi / denom);
+    adam_update(w, m, v, i, gi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+}
+
+// ---- gradient-norm clipping: torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type=2) in front of the Adam update (the reference-side loop's
+// `clip_grad_norm_` then `Adam.step`), as ONE extra launch and no host round trip.
+// sum of 256 doubles held one per thread, in ONE fixed order: xor butterfly inside each wave (both partners add the same two values, so every lane ends with the same bits), the four wave sums through LDS
+__device__ __forceinline__ double block_sum_f64(double x, double* red) {
+    for (int sft = 32; sft >= 1; sft >>= 1) x += __shfl_xor(x, sft);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+// part[block] = sum of g[i]^2 over the block's share of the first n floats, in fp64 (an fp32 square is exact in fp64: the sum is good to n * 2^-53).
+// The order of every addition is a function of n alone: element i belongs to quad i / 4, quad q to thread q % (threads of the grid), a thread adds its quads
+// in index order, the short last quad included; then block_sum_f64.  No atomics: the same bits from run to run, and on every data-parallel rank (they hold
+// the same exchanged buffer) wherever its allocator put that buffer -- a 16-byte aligned base reads a quad as one float4, any other base as four floats.
+__global__ __launch_bounds__(256) void k_grad_sumsq(const float* __restrict__ g, int64_t n, double* __restrict__ part) {
+    __shared__ double red[4];
+    const int64_t nq = n >> 2, nthr = (int64_t)gridDim.x * 256, t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double acc = 0.0;
+    if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+        const float4* g4 = reinterpret_cast<const float4*>(g);
+#pragma unroll 4
+        for (int64_t q = t; q < nq; q += nthr) {
+            const float4 x = g4[q];
+            acc += (double)x.x * (double)x.x; acc += (double)x.y * (double)x.y; acc += (double)x.z * (double)x.z; acc += (double)x.w * (double)x.w;
+        }
+    } else {
+#pragma unroll 4
+        for (int64_t q = t; q < nq; q += nthr) {
+            const float x0 = g[4 * q], x1 = g[4 * q + 1], x2 = g[4 * q + 2], x3 = g[4 * q + 3];
+            acc += (double)x0 * (double)x0; acc += (double)x1 * (double)x1; acc += (double)x2 * (double)x2; acc += (double)x3 * (double)x3;
+        }
+    }
+    if (t == nq % nthr) for (int64_t i = nq * 4; i < n; ++i) acc += (double)g[i] * (double)g[i];      // the last n % 4 floats: quad nq, read one by one
+    const double s = block_sum_f64(acc, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// k_adam behind k_grad_sumsq.  EVERY block adds the npart <= 256 partial sums itself, in block_sum_f64's order: all blocks of the launch (and all ranks) derive the
+// same total, hence the same coefficient and the same decision to skip, with no finalising block, counter or fence.
+//   total = sqrt(sum g^2) (/ den[0]: the norm of the AVERAGED gradient);  coef = min(1, max_norm / (total + 1e-6)) in fp64, rounded once;  g <- (g / den[0]) * coef, then weight decay.
+// The gradient buffer is left as it is.  A non-finite total skips the update like a flagged step (bit 16 of the status word, set by block 0; the blocks decide by their own total,
+// not by the word).  Block 0 leaves the total in *d_norm (and the step's pinned report slot).
+__global__ __launch_bounds__(256) void k_adam_clip(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                   float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep,
+                                                   const double* __restrict__ part, int npart, float max_norm, double* __restrict__ d_norm, double* h_norm) {
+    __shared__ double red[4];
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    double total = sqrt(block_sum_f64((int)threadIdx.x < npart ? part[threadIdx.x] : 0.0, red));
+    if (den) total = total / (double)den[0];
+    const bool bad = !isfinite(total);
+    const bool peer = den && den[1] > 0.f;
+    const bool skip = bad || peer || (status && *status);
+    if (blockIdx.x == 0) {
+        if (rep.h_loss && threadIdx.x < 64) rep.h_loss[threadIdx.x] = rep.d_loss[threadIdx.x];
+        if (threadIdx.x == 0) {
+            *d_norm = total;
+            if (h_norm) *h_norm = total;
+            if (status) {
+                int st = *status;
+                if (peer && !st) { st = 8; atomicOr(status, 8); }
+                if (bad) { st |= 1 << 16; atomicOr(status, 1 << 16); }
+                if (rep.h_status) *rep.h_status = st;
+                if (!skip) atomicAdd((unsigned long long*)(status + 2), 1ull);
+            }
+        }
+    }
+    if (i >= n || skip) return;
+    const double c = (double)max_norm / (total + 1e-6);
+    const float coef = c < 1.0 ? (float)c : 1.0f;
+    float gi = g[i];
+    if (den) gi = gi / den[0];
+    gi = __fmul_rn(gi, coef);                                   // (a product of its own: never fused into the weight-decay term, so coef == 1 leaves k_adam's bits)
+    adam_update(w, m, v, i, gi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
 }
 
 // Zero exactly what the backward reads without having written it.  Grad wrt X[j] has two parts:
@@ -1559,6 +1638,21 @@ int qpn_launch_adam(float* w, const float* g, float* m, float* v, int64_t n, int
     const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
     AdamReports rep; rep.h_status = status ? h_status : nullptr; rep.h_loss = d_loss ? h_loss : nullptr; rep.d_loss = d_loss;
     hipLaunchKernelGGL(k_adam, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, g, m, v, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2), den, status, rep);
+    qpn_prof_mark(PG_ADAM, stream);
+    QPN_HIP(hipGetLastError());
+    return QPN_OK;
+}
+
+// part: room for TR_GN_BLOCKS partial sums; d_norm: the handle's norm word
+int qpn_launch_adam_clip(float* w, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps, float wd, const float* den, int* status,
+                         int* h_status, double* h_loss, const double* d_loss, float max_norm, double* part, double* d_norm, double* h_norm, hipStream_t stream) {
+    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
+    AdamReports rep; rep.h_status = status ? h_status : nullptr; rep.h_loss = d_loss ? h_loss : nullptr; rep.d_loss = d_loss;
+    const int64_t want = ((n >> 2) + 1 + 255) / 256;           // a thread per quad (and one for the short last quad) until the grid is full
+    const int nb = want < TR_GN_BLOCKS ? (int)want : TR_GN_BLOCKS;
+    hipLaunchKernelGGL(k_grad_sumsq, dim3(nb), dim3(256), 0, stream, g, n, part);
+    hipLaunchKernelGGL(k_adam_clip, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, g, m, v, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2), den, status, rep,
+                       (const double*)part, nb, max_norm, d_norm, h_norm);
     qpn_prof_mark(PG_ADAM, stream);
     QPN_HIP(hipGetLastError());
     return QPN_OK;

@@ -236,6 +236,8 @@ struct TrainGemm {
 
 int qpn_num_cus();                                   // compute units of the current device (cached per device)
 
+#define TR_GN_BLOCKS 256                             // gradient-norm clipping: the sum of squares leaves k_grad_sumsq as at most this many fp64 partial sums (one per thread of a k_adam_clip block)
+
 // optional per-kernel-group timing (HIP events on the launch stream; bench.py roofline)
 // (one group per LAUNCH of the heavy kernels, so that bench.py can name the single longest kernel: PG_WGRAD = the gate contraction's weight
 //  gradient dW1, then the residual 1x1's, the skip 1x1's, the post-net pair's and the causal table's)

@@ -15,7 +15,11 @@ int qpn_launch_fwd_gemm(const TrainParams& p, const TrainGemm& w, hipStream_t st
 int qpn_launch_bwd_gemm(const TrainParams& p, const TrainBwd& bw, const TrainGemm& w, hipStream_t stream);
 int qpn_launch_adam(float* w, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps, float wd, const float* den, int* status,
                     int* h_status, double* h_loss, const double* d_loss, hipStream_t stream);
+int qpn_launch_adam_clip(float* w, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps, float wd, const float* den, int* status,
+                         int* h_status, double* h_loss, const double* d_loss, float max_norm, double* part, double* d_norm, double* h_norm, hipStream_t stream);
 
+// a pinned loss slot: the 64 partial sums, then the gradient norm of the same step (gradient-norm clipping)
+#define LOSS_SLOT 72
 
 struct TrainState {
     std::vector<int> h_wmap;                  // gather map of the fragment-ordered weights
@@ -35,7 +39,11 @@ struct TrainState {
     int* d_status; double* d_loss;            // d_status: 16 words -- [0] the sticky status word, [2..3] the count of Adam updates applied (k_adam)
     hipStream_t last_stream;                  // the stream of the latest training call (where a collected status word is cleared)
     int* h_status_pinned; hipEvent_t ev_status[2]; bool status_pending[2]; int status_newest;      // qpn_train_status_enqueue / _collect: the deferred check, two slots
-    double* h_loss_pinned; hipEvent_t ev_loss[2]; bool loss_pending[2]; int loss_newest;            // qpn_train_loss_enqueue / _collect: the loss read one step late, two slots of 64 partial sums
+    double* h_loss_pinned; hipEvent_t ev_loss[2]; bool loss_pending[2]; int loss_newest;            // qpn_train_loss_enqueue / _collect: the loss read one step late, two slots of LOSS_SLOT doubles
+    // gradient-norm clipping (qpn_adam_step_clip): d_gnorm = TR_GN_BLOCKS partial sums of squares; the norm word k_adam_clip leaves is d_loss[64] (one copy takes both out)
+    double* d_gnorm; bool gnorm_last;         // gnorm_last: the latest Adam launch on this handle clipped (the norm word is that launch's)
+    bool gnorm_slot[2];                       // loss slot i carries a norm
+    double gnorm_collected; bool gnorm_collected_valid;      // the norm that came with the loss the last qpn_train_loss_collect returned
     bool fwd_valid;
     bool loss_clear;                          // the loss accumulator is zero (cleared by the forward's refresh kernel, consumed by one CE call)
     bool use_gemm;                            // wide stacks (n_resch > 128, or QPN_TRAIN_GEMM=1): the LDS-tiled GEMM path of train_gemm.hip
@@ -360,12 +368,16 @@ static int train_init(qpn_handle* h) {
     t->h_status_pinned = nullptr; t->ev_status[0] = t->ev_status[1] = nullptr; t->status_pending[0] = t->status_pending[1] = false; t->status_newest = 0;
     QPN_HIP(hipHostMalloc((void**)&t->h_status_pinned, 64, hipHostMallocDefault));
     t->h_loss_pinned = nullptr; t->ev_loss[0] = t->ev_loss[1] = nullptr; t->loss_pending[0] = t->loss_pending[1] = false; t->loss_newest = 0;
-    QPN_HIP(hipHostMalloc((void**)&t->h_loss_pinned, 2 * 64 * sizeof(double), hipHostMallocDefault));
+    QPN_HIP(hipHostMalloc((void**)&t->h_loss_pinned, 2 * LOSS_SLOT * sizeof(double), hipHostMallocDefault));
+    t->d_gnorm = nullptr; t->gnorm_last = false; t->gnorm_slot[0] = t->gnorm_slot[1] = false; t->gnorm_collected = 0.0; t->gnorm_collected_valid = false;
+    QPN_HIP(hipMalloc(&t->d_gnorm, TR_GN_BLOCKS * sizeof(double)));
+    QPN_HIP(hipMemset(t->d_gnorm, 0, TR_GN_BLOCKS * sizeof(double)));
     QPN_HIP(hipEventCreateWithFlags(&t->ev_loss[0], hipEventDisableTiming));
     QPN_HIP(hipEventCreateWithFlags(&t->ev_loss[1], hipEventDisableTiming));
     QPN_HIP(hipEventCreateWithFlags(&t->ev_status[0], hipEventDisableTiming));
     QPN_HIP(hipEventCreateWithFlags(&t->ev_status[1], hipEventDisableTiming));
-    QPN_HIP(hipMalloc(&t->d_loss, 64 * sizeof(double)));
+    QPN_HIP(hipMalloc(&t->d_loss, LOSS_SLOT * sizeof(double)));
+    QPN_HIP(hipMemset(t->d_loss, 0, LOSS_SLOT * sizeof(double)));
     if (!t->use_gemm) QPN_HIP(hipMemcpy(t->d_wmap, map.data(), nmap * sizeof(int), hipMemcpyHostToDevice));
     QPN_HIP(hipMemcpy(t->d_bstart, t->h_bstart.data(), t->h_bstart.size() * sizeof(int), hipMemcpyHostToDevice));
     QPN_HIP(hipMemcpy(t->d_blist, t->h_blist.data(), t->h_blist.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -414,7 +426,7 @@ static int train_init(qpn_handle* h) {
 
 void qpn_train_destroy(TrainState* t) {
     if (!t) return;
-    void* bufs[] = {t->d_wmap, t->d_wp, t->d_bstart, t->d_blist, t->d_bp, t->d_gdst, t->d_gdst_list, t->d_gzero, t->d_ws, t->d_tap, t->d_status, t->d_loss, t->d_gmap, t->d_gwp, t->d_ctmap, t->d_ct, t->d_sq};
+    void* bufs[] = {t->d_wmap, t->d_wp, t->d_bstart, t->d_blist, t->d_bp, t->d_gdst, t->d_gdst_list, t->d_gzero, t->d_ws, t->d_tap, t->d_status, t->d_loss, t->d_gmap, t->d_gwp, t->d_ctmap, t->d_ct, t->d_sq, t->d_gnorm};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (t->h_status_pinned) (void)hipHostFree(t->h_status_pinned);
     if (t->h_loss_pinned) (void)hipHostFree(t->h_loss_pinned);
@@ -599,7 +611,9 @@ extern "C" int qpn_train_loss_enqueue(qpn_handle* h, void* stream_) {
     TrainState* t = h->train;
     const int slot = t->loss_newest ^ 1;
     if (t->loss_pending[slot]) QPN_HIP(hipEventSynchronize(t->ev_loss[slot]));      // (an uncollected copy of two calls ago: dropped)
-    QPN_HIP(hipMemcpyAsync(t->h_loss_pinned + 64 * slot, t->d_loss, 64 * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream_));
+    // (behind a clipping Adam launch the step's gradient norm, d_loss[64], leaves in the same copy)
+    QPN_HIP(hipMemcpyAsync(t->h_loss_pinned + LOSS_SLOT * slot, t->d_loss, (t->gnorm_last ? 65 : 64) * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream_));
+    t->gnorm_slot[slot] = t->gnorm_last;
     QPN_HIP(hipEventRecord(t->ev_loss[slot], (hipStream_t)stream_));
     t->loss_pending[slot] = true; t->loss_newest = slot;
     return QPN_OK;
@@ -611,12 +625,14 @@ extern "C" int qpn_train_loss_collect(qpn_handle* h, int newest, double* h_loss,
     if (!h->train) return QPN_OK;
     TrainState* t = h->train;
     const int slot = newest ? t->loss_newest : t->loss_newest ^ 1;
+    t->gnorm_collected_valid = false;
     if (!t->loss_pending[slot]) return QPN_OK;
     QPN_HIP(hipEventSynchronize(t->ev_loss[slot]));
     t->loss_pending[slot] = false;
     double sum = 0.0;
-    for (int i = 0; i < 64; ++i) sum += t->h_loss_pinned[64 * slot + i];
+    for (int i = 0; i < 64; ++i) sum += t->h_loss_pinned[LOSS_SLOT * slot + i];
     *h_loss = sum; *h_valid = 1;
+    if (t->gnorm_slot[slot]) { t->gnorm_collected = t->h_loss_pinned[LOSS_SLOT * slot + 64]; t->gnorm_collected_valid = true; }
     return QPN_OK;
 }
 
@@ -638,6 +654,7 @@ static int status_to_rc(int st) {
     if (st & 1) { qpn_set_error("pitch-dependent tap outside the layer input (dilated factor > maxd or < 0; reference assert qpnet.py:294)"); return QPN_ERANGE; }
     if (st & 4) { qpn_set_error("the one-launch residual stack gave up waiting for a peer workgroup: the flagged step's results are invalid (its Adam update, and that of the steps enqueued behind it until this report, were skipped on the device: parameters and moments are those of the last clean step); the handle runs a launch per layer from here on (QPN_STACK_QUEUE=0 selects that from the start)"); return QPN_ENODEV; }
     if (st & 2) { qpn_set_error("target class outside [0, n_quantize) (reference assert qpnet_train.py:525)"); return QPN_ERANGE; }
+    if (st & (1 << 16)) { qpn_set_error("non-finite gradient norm (an inf or NaN in the gradient): the step's Adam update, and that of the steps enqueued behind it until this report, were skipped on the device: parameters and moments are those of the last clean step"); return QPN_ERANGE; }
     if (st & 8) { qpn_set_error("a peer rank flagged its chunk of this data-parallel step (a tap or target out of range, or an abandoned stack launch there): every rank skipped the update, the replicas are unchanged"); return QPN_ERANGE; }
     return QPN_OK;
 }
@@ -809,10 +826,42 @@ extern "C" int qpn_adam_step(qpn_handle* h, float* d_flat, const float* d_grad, 
 extern "C" int qpn_adam_step_ex(qpn_handle* h, float* d_flat, const float* d_grad, float* d_m, float* d_v, int64_t n,
                                 int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                                 const float* d_grad_denominator, void* stream_) {
+    return qpn_adam_step_clip(h, d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, d_grad_denominator, 0.0f, stream_);
+}
+
+// max_grad_norm > 0: torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) in front of the update (k_grad_sumsq + k_adam_clip); otherwise exactly the launch qpn_adam_step_ex always made
+extern "C" int qpn_adam_step_clip(qpn_handle* h, float* d_flat, const float* d_grad, float* d_m, float* d_v, int64_t n,
+                                  int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                  const float* d_grad_denominator, float max_grad_norm, void* stream_) {
     int rc = need_dev(h); if (rc) return rc;
-    if (!d_flat || !d_grad || !d_m || !d_v || n < 1 || step < 1) { qpn_set_error("bad adam_step arguments"); return QPN_EINVAL; }
-    if (h->train) h->train->last_stream = (hipStream_t)stream_;
+    if (!d_flat || !d_grad || !d_m || !d_v || n < 1 || step < 1 || max_grad_norm != max_grad_norm) { qpn_set_error("bad adam_step arguments"); return QPN_EINVAL; }
+    const bool clip = max_grad_norm > 0.f;
+    if (clip) { rc = train_init(h); if (rc) return rc; }                 // (the partial sums and the norm word live in the training state)
+    if (h->train) { h->train->last_stream = (hipStream_t)stream_; h->train->gnorm_last = clip; }
+    if (clip) return qpn_launch_adam_clip(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, d_grad_denominator, h->train->d_status, nullptr, nullptr, nullptr,
+                                          max_grad_norm, h->train->d_gnorm, h->train->d_loss + 64, nullptr, (hipStream_t)stream_);
     return qpn_launch_adam(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, d_grad_denominator, h->train ? h->train->d_status : nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream_);
+}
+
+// The norm the latest Adam launch on this handle clipped by (drains `stream`); *h_valid = 0 when that launch did not clip, or there was none
+extern "C" int qpn_train_grad_norm(qpn_handle* h, double* h_norm, int* h_valid, void* stream_) {
+    int rc = need_dev(h); if (rc) return rc;
+    if (!h_norm || !h_valid) { qpn_set_error("bad grad_norm arguments"); return QPN_EINVAL; }
+    *h_norm = 0.0; *h_valid = 0;
+    if (!h->train || !h->train->gnorm_last) return QPN_OK;
+    QPN_HIP(hipStreamSynchronize((hipStream_t)stream_));
+    QPN_HIP(hipMemcpy(h_norm, h->train->d_loss + 64, sizeof(double), hipMemcpyDeviceToHost));
+    *h_valid = 1;
+    return QPN_OK;
+}
+// ... and without a wait of its own: the norm of the step whose loss the last qpn_train_loss_collect returned (it left the device in that loss's copy)
+extern "C" int qpn_train_grad_norm_lagged(qpn_handle* h, double* h_norm, int* h_valid) {
+    int rc = need_dev(h); if (rc) return rc;
+    if (!h_norm || !h_valid) { qpn_set_error("bad grad_norm arguments"); return QPN_EINVAL; }
+    *h_norm = 0.0; *h_valid = 0;
+    if (!h->train || !h->train->gnorm_collected_valid) return QPN_OK;
+    *h_norm = h->train->gnorm_collected; *h_valid = 1;
+    return QPN_OK;
 }
 
 // One optimisation step behind ONE call -- what a training loop's body is (reference src/bin/qpnet_train.py:517-531: forward, CrossEntropyLoss, backward,
@@ -827,18 +876,32 @@ extern "C" int qpn_train_step(qpn_handle* h, float* d_flat, int B, int64_t T, in
                               float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
                               int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                               int loss_mode, double* h_loss, int* h_valid, void* stream) {
+    return qpn_train_step_clip(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
+                               step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, 0.0f, nullptr, stream);
+}
+
+// max_grad_norm > 0: the step clips (qpn_adam_step_clip), and *h_grad_norm (may be NULL) receives the norm of the step whose loss *h_loss is -- mode 1: the previous
+// step's, out of the same pinned slot as its loss; mode 2: this step's; mode 0: none.  0 where that step did not clip.
+extern "C" int qpn_train_step_clip(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
+                                   const int64_t* d_x, const float* d_h, const float* d_dfac, const int64_t* d_targets, int64_t tgt_stride,
+                                   float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
+                                   int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                   int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm, void* stream) {
     if (h_valid) *h_valid = 0;
     if (h_loss) *h_loss = 0.0;
-    if (loss_mode < 0 || loss_mode > 2 || (loss_mode && (!h_loss || !h_valid))) { qpn_set_error("bad train_step arguments"); return QPN_EINVAL; }
+    if (h_grad_norm) *h_grad_norm = 0.0;
+    if (loss_mode < 0 || loss_mode > 2 || (loss_mode && (!h_loss || !h_valid)) || max_grad_norm != max_grad_norm) { qpn_set_error("bad train_step arguments"); return QPN_EINVAL; }
+    const bool clip = max_grad_norm > 0.f;
     int rc = need_dev(h); if (rc) return rc;
     rc = qpn_train_status_collect_lagged(h); if (rc) return rc;          // the check of the step before the previous one (never waits for queued work)
     if (!d_targets || !d_dlogits) { qpn_set_error("qpn_train_forward_loss needs targets and a dlogits buffer"); return QPN_EINVAL; }
     rc = train_forward_impl(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_logits, d_targets, tgt_stride, d_dlogits, 0, stream, true); if (rc) return rc;
     rc = qpn_train_backward(h, d_dlogits, d_grad, stream); if (rc) return rc;
     if (loss_mode == 2) {
-        rc = qpn_adam_step_ex(h, d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, nullptr, stream); if (rc) return rc;
+        rc = qpn_adam_step_clip(h, d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, nullptr, max_grad_norm, stream); if (rc) return rc;
         rc = qpn_train_loss(h, h_loss, stream); if (rc) return rc;
         *h_valid = 1;
+        if (clip && h_grad_norm) { int nv = 0; rc = qpn_train_grad_norm(h, h_grad_norm, &nv, stream); if (rc) return rc; }      // (the stream has just been drained)
         return qpn_train_status(h, stream);
     }
     // modes 0 / 1: the Adam kernel -- the step's last -- writes the status word (and the loss partials) into the pinned slots itself: what
@@ -849,15 +912,20 @@ extern "C" int qpn_train_step(qpn_handle* h, float* d_flat, int B, int64_t T, in
     rc = status_collect_slot(t, sslot); if (rc) return rc;               // (two enqueues old: long done)
     const int lslot = t->loss_newest ^ 1;
     if (loss_mode == 1 && t->loss_pending[lslot]) QPN_HIP(hipEventSynchronize(t->ev_loss[lslot]));      // (an uncollected copy of two calls ago: dropped)
-    rc = qpn_launch_adam(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, nullptr, t->d_status, t->h_status_pinned + sslot,
-                         loss_mode == 1 ? t->h_loss_pinned + 64 * lslot : nullptr, loss_mode == 1 ? t->d_loss : nullptr, (hipStream_t)stream);
+    double* const hl = loss_mode == 1 ? t->h_loss_pinned + LOSS_SLOT * lslot : nullptr;
+    t->gnorm_last = clip;
+    if (clip) rc = qpn_launch_adam_clip(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, nullptr, t->d_status, t->h_status_pinned + sslot,
+                                        hl, loss_mode == 1 ? t->d_loss : nullptr, max_grad_norm, t->d_gnorm, t->d_loss + 64, hl ? hl + 64 : nullptr, (hipStream_t)stream);
+    else rc = qpn_launch_adam(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, nullptr, t->d_status, t->h_status_pinned + sslot,
+                              hl, loss_mode == 1 ? t->d_loss : nullptr, (hipStream_t)stream);
     if (rc) return rc;
     QPN_HIP(hipEventRecord(t->ev_status[sslot], (hipStream_t)stream));
     t->status_pending[sslot] = true; t->status_newest = sslot;
     if (loss_mode == 1) {
         QPN_HIP(hipEventRecord(t->ev_loss[lslot], (hipStream_t)stream));
-        t->loss_pending[lslot] = true; t->loss_newest = lslot;
-        return qpn_train_loss_collect(h, 0, h_loss, h_valid);
+        t->loss_pending[lslot] = true; t->loss_newest = lslot; t->gnorm_slot[lslot] = clip;
+        rc = qpn_train_loss_collect(h, 0, h_loss, h_valid); if (rc) return rc;
+        if (h_grad_norm && t->gnorm_collected_valid) *h_grad_norm = t->gnorm_collected;
     }
     return QPN_OK;
 }

@@ -233,6 +233,11 @@ def _build_model(conf, device):
 
 
 # ---------------------------------------------------------------- train / update
+def _is_non_finite_norm(e):
+    """the status error of a step whose gradient norm was inf / NaN (--max_grad_norm): the device applied nothing, the run may go on."""
+    return getattr(e, "code", None) == -4 and "non-finite gradient norm" in str(e)
+
+
 def _train_args(update):
     p = argparse.ArgumentParser()
     for name in ("waveforms", "feats", "stats", "expdir", "config"):
@@ -252,6 +257,7 @@ def _train_args(update):
     p.add_argument("--f0_threshold", default=0, type=int)
     p.add_argument("--lr", default=1e-4, type=float)
     p.add_argument("--weight_decay", default=0.0, type=float)
+    p.add_argument("--max_grad_norm", default=0.0, type=float, help="clip the gradient norm inside the fused step (torch's clip_grad_norm_); 0: off")
     p.add_argument("--iters", default=3000 if update else 200000, type=int)
     p.add_argument("--checkpoint_interval", default=10000, type=int)
     p.add_argument("--intervals", default=100, type=int)
@@ -284,7 +290,16 @@ def run_train(argv=None, update=False):
     from .train import FusedTrainer
     from . import parallel
     model = _build_model(conf, dev).train()
-    trainer = FusedTrainer(model, lr=args.lr, weight_decay=args.weight_decay, world_size=world)
+    trainer = FusedTrainer(model, lr=args.lr, weight_decay=args.weight_decay, world_size=world, max_grad_norm=args.max_grad_norm)
+    clipping = trainer.max_grad_norm > 0.0
+    norm_max, n_clipped, n_seen = 0.0, 0, 0    # (clipping on) the interval's largest gradient norm, how many of its steps were clipped, how many losses it collected
+
+    def note_norm(g):
+        # (a non-finite norm is the largest there is: max() would drop a NaN)
+        nonlocal norm_max, n_clipped
+        if g is not None:
+            norm_max = float("nan") if g != g or norm_max != norm_max else max(norm_max, g)
+            n_clipped += bool(g > trainer.max_grad_norm)
     iterations, loss_record = 0, []
     flossyml = os.path.join(args.expdir, "loss-final.yml")
     if args.resume and os.path.exists(args.resume):
@@ -308,22 +323,45 @@ def run_train(argv=None, update=False):
     for i in range(iterations, args.iters):
         start = time.time()
         bx, bh, bt, bd, bb, maxd = next(stream)
-        batch_loss = trainer.step(bx, bh, bt, bd, bb, want_loss="lagged" if lagged else True, maxd=maxd)
+        try:
+            batch_loss = trainer.step(bx, bh, bt, bd, bb, want_loss="lagged" if lagged else True, maxd=maxd)
+        except Exception as e:
+            if not (clipping and _is_non_finite_norm(e)):
+                raise
+            batch_loss = None                   # the device skipped that update (and those enqueued behind it): training goes on from the last clean state
+            logging.warning("(iter:%d) %s" % (i + 1, e))
         if batch_loss is not None:
             loss += batch_loss
             logging.debug("batch loss = %.3f" % batch_loss)
+            if clipping:
+                n_seen += 1; note_norm(trainer.last_grad_norm)
         total += time.time() - start
         if (i + 1) % args.intervals == 0 or (i + 1) % args.checkpoint_interval == 0 or i + 1 == args.iters:
             last = trainer.flush_loss() if lagged else None
             if last is not None:
                 loss += last
+                if clipping:
+                    n_seen += 1; note_norm(trainer.last_grad_norm)
             # the device-side checks of the last steps (a dilated factor outside the layer input, a target outside [0, n_quantize), an abandoned
             # stack launch: the reference asserts in every step, qpnet.py:294, qpnet_train.py:525) are collected HERE -- before an interval
             # is reported, before a checkpoint and before the final model are written: nothing flagged reaches the disk
-            trainer.check_status()
+            try:
+                trainer.check_status()
+            except Exception as e:
+                if not (clipping and _is_non_finite_norm(e)):
+                    raise
+                logging.warning("(iter:%d) %s" % (i + 1, e))
         if (i + 1) % args.intervals == 0:
-            logging.info("(iter:%d) average loss = %.6f (%.3f sec / batch)" % (i + 1, loss / args.intervals, total / args.intervals))
-            loss_record.append(loss / args.intervals)
+            if clipping:
+                # (a step that raised for a non-finite norm took the loss it would have returned with it: the average is over the losses that arrived)
+                n_loss = n_seen if 0 < n_seen < args.intervals else args.intervals
+                logging.info("(iter:%d) average loss = %.6f (%.3f sec / batch) max grad norm = %.6g, %d of %d steps clipped"
+                             % (i + 1, loss / n_loss, total / args.intervals, norm_max, n_clipped, n_loss))
+                norm_max, n_clipped, n_seen = 0.0, 0, 0
+            else:
+                n_loss = args.intervals
+                logging.info("(iter:%d) average loss = %.6f (%.3f sec / batch)" % (i + 1, loss / args.intervals, total / args.intervals))
+            loss_record.append(loss / n_loss)
             loss = total = 0.0
         if (i + 1) % args.checkpoint_interval == 0 and rank == 0:
             loaders.save_checkpoint(args.expdir, model, trainer, i + 1)

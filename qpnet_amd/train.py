@@ -478,6 +478,16 @@ def qpnet_forward(model, x, h, dilated_factors, blength):
     return QPNetFunction.apply(model, x, h, d, BL, maxd, *params)
 
 
+def _check_max_grad_norm(v):
+    """max_grad_norm as the C ABI takes it: None / 0 -> 0.0 (clipping off); a negative or non-finite value raises."""
+    if v is None:
+        return 0.0
+    v = float(v)
+    if not np.isfinite(v) or v < 0.0:
+        raise ValueError("max_grad_norm must be a finite number >= 0 (None or 0: no clipping), got %r" % (v,))
+    return v
+
+
 # ---------------------------------------------------------------- Adam state in torch.optim.Adam's state_dict layout
 _ADAM_GROUP_DEFAULTS = dict(amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None)
 
@@ -529,13 +539,23 @@ class FlatAdam(torch.optim.Optimizer):
     (src/bin/qpnet_train.py:426-429,531), whose 120-tensor foreach update costs 0.9 ms per step on this GPU.
     Gradients are read from `p.grad`: when they are consecutive views of one flat buffer (what the autograd backward hands
     out) no gather happens.  state_dict()/load_state_dict() use torch.optim.Adam's own layout, so checkpoints written by
-    the reference trainer resume here and vice versa."""
+    the reference trainer resume here and vice versa.
+    max_grad_norm=c: `torch.nn.utils.clip_grad_norm_(model.parameters(), c)` in front of every step, inside the step's launches (qpn_adam_step_clip); p.grad is
+    left unscaled.  A step whose gradient norm is not finite applies nothing and raises QpnError(-4) at the next status collection."""
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
         self.model = model
+        self.max_grad_norm = _check_max_grad_norm(max_grad_norm)      # (a setting of this object, not of the checkpoint: state_dict() keeps torch.optim.Adam's layout)
         super().__init__(list(model.parameters()), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._m = self._v = None
         self._steps = 0
+        self._applied_base = None     # clipping on: (steps, the handle's applied-update count) at the first step (a skipped non-finite step must not advance the bias correction)
+
+    def _applied(self, L, hd, dev):
+        n = C.c_int64(0)
+        with torch.cuda.device(dev):
+            _lib.check(L.qpn_train_applied_updates(hd, C.byref(n), torch.cuda.current_stream(dev).cuda_stream))
+        return int(n.value)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -546,6 +566,17 @@ class FlatAdam(torch.optim.Optimizer):
             raise RuntimeError("FlatAdam.step before the first forward/backward of the model")
         dev = flat.device
         L, hd = model._native(dev)
+        clipping = self.max_grad_norm > 0.0
+        if clipping:
+            # a step whose gradient norm was not finite applies nothing and is reported by whichever call collects the status word next (the next forward, backward,
+            # check_status()): when a status error has been raised anywhere since this optimizer's last step, the step count -- the bias correction's exponent, and what
+            # state_dict() stores -- is set back to the updates the device applied (one stream drain, on that path only)
+            if self._applied_base is None:
+                self._applied_base = (self._steps, self._applied(L, hd, dev), _lib.STATUS_ERRORS[0])      # (once per optimizer: drains the stream)
+            elif _lib.STATUS_ERRORS[0] != self._applied_base[2]:
+                applied = self._applied(L, hd, dev)
+                self._steps = self._applied_base[0] + applied - self._applied_base[1]
+                self._applied_base = (self._steps, applied, _lib.STATUS_ERRORS[0])
         with torch.cuda.device(dev):
             _lib.check(L.qpn_train_status_collect(hd))       # a pending forward check (no-op after a backward has collected it)
         params = model_params(model)
@@ -561,8 +592,11 @@ class FlatAdam(torch.optim.Optimizer):
         self._steps += 1
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
-            _lib.check(L.qpn_adam_step(hd, flat.data_ptr(), g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), flat.numel(),
-                                       self._steps, grp["lr"], grp["betas"][0], grp["betas"][1], grp["eps"], grp["weight_decay"], stream))
+            _lib.check(L.qpn_adam_step_clip(hd, flat.data_ptr(), g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), flat.numel(),
+                                            self._steps, grp["lr"], grp["betas"][0], grp["betas"][1], grp["eps"], grp["weight_decay"], None,
+                                            self.max_grad_norm, stream))
+            if clipping:
+                _lib.check(L.qpn_train_status_enqueue(hd, stream))      # (a non-finite norm is this launch's own finding: the next collection reports it)
         return loss
 
     def _hyper(self):
@@ -591,15 +625,21 @@ class FusedTrainer:
     over ranks with ONE RCCL all-reduce of the flat buffer (the row counts ride in its last element) and divided by the
     global row count inside the Adam kernel: the update is the gradient of the mean CE over ALL ranks' rows, with no
     extra elementwise launch or allocation in the step.
-    state_dict()/load_state_dict() use torch.optim.Adam's layout (resume of reference-made checkpoints and vice versa)."""
+    state_dict()/load_state_dict() use torch.optim.Adam's layout (resume of reference-made checkpoints and vice versa).
+    max_grad_norm=c (None / 0: off): the step clips like `torch.nn.utils.clip_grad_norm_(model.parameters(), c)` between backward and Adam.step -- data-parallel: the
+    norm of the exchanged, averaged gradient -- inside the library's optimiser step; `last_grad_norm` is the norm (before clipping) that belongs to the loss
+    step() / flush_loss() last returned (None when that was None, or clipping is off).  A non-finite norm skips the update and raises like the other status errors.
+    A trainer setting: it is not part of state_dict()."""
 
     # The device-side status word (bad taps / targets; the reference asserts in-line, qpnet.py:294, qpnet_train.py:525) is copied to pinned
     # memory behind every step; a step starts by looking at the copy made TWO steps earlier (the previous step is still queued on the
     # device while the host enqueues this one: waiting for it would idle the GPU).  A bad chunk is raised two steps late at most, not up to 99
     # as when the word was read every 100 steps.  check_status() collects everything outstanding.
 
-    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, process_group=None, world_size=1):
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, process_group=None, world_size=1, max_grad_norm=None):
         self.model = model
+        self.max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        self.last_grad_norm = None
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.step_count = 0
         self.m = self.v = self.g = None
@@ -662,14 +702,29 @@ class FusedTrainer:
             self.step_count += 1
             valid = C.c_int(0)
             mode = 1 if want_loss == "lagged" else (2 if want_loss else 0)
+            clip = self.max_grad_norm
             with torch.cuda.device(dev):
-                rc = L.qpn_train_step(hd, flat.data_ptr(), B, T, h.shape[2], d.shape[1], BL, maxd, x.data_ptr(), h.data_ptr(), d.data_ptr(),
-                                      t.data_ptr(), t.shape[1], self._logits.data_ptr(), self._dlogits.data_ptr(), self.g.data_ptr(),
-                                      self.m.data_ptr(), self.v.data_ptr(), flat.numel(), self.step_count, self.lr, self.betas[0], self.betas[1],
-                                      self.eps, self.wd, mode, C.byref(loss), C.byref(valid), stream)
+                if clip > 0.0:
+                    norm = C.c_double(0.0)
+                    rc = L.qpn_train_step_clip(hd, flat.data_ptr(), B, T, h.shape[2], d.shape[1], BL, maxd, x.data_ptr(), h.data_ptr(), d.data_ptr(),
+                                               t.data_ptr(), t.shape[1], self._logits.data_ptr(), self._dlogits.data_ptr(), self.g.data_ptr(),
+                                               self.m.data_ptr(), self.v.data_ptr(), flat.numel(), self.step_count, self.lr, self.betas[0], self.betas[1],
+                                               self.eps, self.wd, mode, C.byref(loss), C.byref(valid), clip, C.byref(norm), stream)
+                    if not valid.value:
+                        self.last_grad_norm = None
+                    elif mode == 1:
+                        self.last_grad_norm = self._collected_norm(L, hd)      # (None where the step that loss belongs to ran unclipped: the C call hands back 0.0 there)
+                    else:
+                        self.last_grad_norm = norm.value
+                else:
+                    rc = L.qpn_train_step(hd, flat.data_ptr(), B, T, h.shape[2], d.shape[1], BL, maxd, x.data_ptr(), h.data_ptr(), d.data_ptr(),
+                                          t.data_ptr(), t.shape[1], self._logits.data_ptr(), self._dlogits.data_ptr(), self.g.data_ptr(),
+                                          self.m.data_ptr(), self.v.data_ptr(), flat.numel(), self.step_count, self.lr, self.betas[0], self.betas[1],
+                                          self.eps, self.wd, mode, C.byref(loss), C.byref(valid), stream)
             if rc:
                 self._rebase_step_count(L, hd, dev, stream, rc)
             return loss.value if valid.value else None
+        self.last_grad_norm = None
         try:
             return self._step_calls(L, hd, dev, flat, stream, x, h, t, d, B, T, BL, maxd, want_loss, multi, capturing, loss)
         except _lib.QpnError as e:
@@ -726,9 +781,10 @@ class FusedTrainer:
             else:
                 _lib.check(L.qpn_train_backward(hd, self._dlogits.data_ptr(), self.g.data_ptr(), stream))
             self.step_count += 1
-            _lib.check(L.qpn_adam_step_ex(hd, flat.data_ptr(), self.g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), flat.numel(),
-                                          self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                                          self.g.data_ptr() + 4 * flat.numel() if multi else None, stream))
+            clip = self.max_grad_norm
+            _lib.check(L.qpn_adam_step_clip(hd, flat.data_ptr(), self.g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), flat.numel(),
+                                            self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                                            self.g.data_ptr() + 4 * flat.numel() if multi else None, clip, stream))
             if want_loss == "lagged":
                 # this step's loss is copied out behind its kernels; what comes back is the PREVIOUS step's (None at the first step, or right after
                 # flush_loss()): the stream is never drained, and a caller that sums losses over an interval and calls flush_loss() at its end has the same sum
@@ -736,9 +792,15 @@ class FusedTrainer:
                 _lib.check(L.qpn_train_status_enqueue(hd, stream))
                 valid = C.c_int(0)
                 _lib.check(L.qpn_train_loss_collect(hd, 0, C.byref(loss), C.byref(valid)))
+                if clip > 0.0 and valid.value:
+                    self.last_grad_norm = self._collected_norm(L, hd)      # (it left the device in that loss's copy)
                 return loss.value if valid.value else None
             if want_loss:
                 _lib.check(L.qpn_train_loss(hd, C.byref(loss), stream))
+                if clip > 0.0:
+                    norm, nv = C.c_double(0.0), C.c_int(0)
+                    _lib.check(L.qpn_train_grad_norm(hd, C.byref(norm), C.byref(nv), stream))
+                    self.last_grad_norm = norm.value if nv.value else None
                 _lib.check(L.qpn_train_status(hd, stream))   # (the stream has just been drained for the loss: in-step, like the reference)
             elif not capturing:
                 _lib.check(L.qpn_train_status_enqueue(hd, stream))
@@ -761,7 +823,15 @@ class FusedTrainer:
         L, hd = self.model._native(self.model._flat.device)
         loss, valid = C.c_double(0.0), C.c_int(0)
         _lib.check(L.qpn_train_loss_collect(hd, 1, C.byref(loss), C.byref(valid)))
+        if self.max_grad_norm > 0.0:
+            self.last_grad_norm = self._collected_norm(L, hd) if valid.value else None
         return loss.value if valid.value else None
+
+    @staticmethod
+    def _collected_norm(L, hd):
+        norm, nv = C.c_double(0.0), C.c_int(0)
+        _lib.check(L.qpn_train_grad_norm_lagged(hd, C.byref(norm), C.byref(nv)))
+        return norm.value if nv.value else None
 
     def check_status(self):
         """Raise what the device-side check of the last step(want_loss=False) found (see QPNet.check_status); the step count is set back to the
