@@ -123,8 +123,28 @@ int qpn_decode_live(qpn_handle* h, int every);
  * counts never decrease during a call, also not while qpn_decode_finish re-runs a launch that gave up (the re-run produces
  * the same samples bit for bit, so what has been read stays valid).  A launch that gave up leaves *running == 0 with rows
  * short of their n_samples: qpn_decode_finish completes them in d_out.  QPN_ESTATE with no decode in flight or live output
- * not armed for it, QPN_EINVAL for null arguments. */
+ * not armed for it, QPN_EINVAL for null arguments.  After qpn_decode_cancel, *running drops to 0 with rows short in the same way. */
 int qpn_decode_poll(qpn_handle* h, int64_t* h_done, const int32_t** h_samples, int64_t* row_stride, int* running);
+
+/* Non-blocking: ask the decode in flight to stop.  One store to host memory that the kernels read -- no stream work, no host wait.
+ * Every row stops at a publish point of its own: the next one after the request has become visible to the device, or the one after
+ * that (the kernel looks at the word it fetched at the previous publish point, so that no step waits for host memory).  Rows of a
+ * later launch of the plan, and launches that start after the request, publish nothing.  A row's published count is final and never
+ * decreases; samples [0, count) of the row are valid in d_out and in the mirror and are bit for bit what the uncancelled call
+ * produces there; anything at or beyond the count is unspecified.  qpn_decode_finish then returns as soon as the launches have
+ * drained: it never re-runs a call with a request (neither one that stopped on it nor one whose launch had given up before), does
+ * not report the drain as QPN_ENODEV, and returns QPN_OK -- or QPN_ERANGE if a tap left its ring before the stop.  A cancelled call
+ * is over: nothing of it carries into the next call.  Idempotent (a second request is QPN_OK); a request that arrives after the
+ * kernels have ended is QPN_OK and changes nothing.  QPN_ESTATE with no decode in flight, or when the call in flight was enqueued
+ * without live output (only armed calls have publish points; unarmed calls run as they always did).  The handle's thread rule is
+ * unchanged: one thread at a time per handle. */
+int qpn_decode_cancel(qpn_handle* h);
+
+/* After qpn_decode_finish of an armed call, until the next enqueue: h_done[B] = the final count of each row (input order) --
+ * n_samples[b] for every row of a call that ran to its end; *cancelled = 1 exactly when a stop was requested (qpn_decode_cancel)
+ * and at least one row ended short.  QPN_ESTATE while a decode is in flight or when the last call was not armed, QPN_EINVAL for
+ * null arguments. */
+int qpn_decode_final_counts(qpn_handle* h, int64_t* h_done, int* cancelled);
 
 /* Device time (ms) of the persistent decode kernel of the last finished qpn_decode call,
  * measured with HIP events on the launch stream (bench.py roofline). */

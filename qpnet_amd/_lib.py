@@ -35,6 +35,8 @@ SYMBOLS = [
     ("qpn_decode_finish", _i, [_vp, _vp]),
     ("qpn_decode_live", _i, [_vp, _i]),
     ("qpn_decode_poll", _i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    ("qpn_decode_cancel", _i, [_vp]),
+    ("qpn_decode_final_counts", _i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     ("qpn_last_decode_kernel_ms", C.c_float, [_vp]),
     ("qpn_last_decode_plan", C.c_char_p, [_vp]),
     ("qpn_train_forward", _i, [_vp, _vp, _i, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp]),

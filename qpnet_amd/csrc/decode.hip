@@ -156,11 +156,12 @@ __device__ __forceinline__ void causal_rows(const DecodeParams& p, const UttView
 struct Ctx {
     const DecodeParams* p; const UttView* u;
     int lane, wave; int64_t Ttot;
+    int creq, stop;      // the host's stop request: the publishing lane's state (live_put); the workgroup's copy of the LDS stop word
 };
 
 // one slot of the per-step program for this wave; `w` holds the slot's weight tile and is refilled with
 // the tile of slot+3 as soon as it has been consumed (three tiles in flight per wave).
-__device__ __forceinline__ void run_slot(const Ctx& c, int slot, int64_t t, float4 (&w)[4]) {
+__device__ __forceinline__ void run_slot(Ctx& c, int slot, int64_t t, float4 (&w)[4]) {
     const DecodeParams& p = *c.p; const UttView& u = *c.u;
     float* sm = SM; int* smi = SMI;
     const int lane = c.lane;
@@ -178,6 +179,9 @@ __device__ __forceinline__ void run_slot(const Ctx& c, int slot, int64_t t, floa
     if (opf & TF_BARRIER) {
         if (opf & TF_DRAIN) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         wg_barrier();
+        // the stop word is written in the pick phase only (the phase behind the TF_DRAIN barrier): read behind any other barrier, every wave finds
+        // what the previous step's pick left -- the same value in all of them
+        if (p.cancel && !(opf & TF_DRAIN)) c.stop = smi[p.o_samp + 2];
     }
     const int op = opf & 0xff;
     const int C = p.C, Q = p.Q;
@@ -252,7 +256,7 @@ __device__ __forceinline__ void run_slot(const Ctx& c, int slot, int64_t t, floa
             if (p.mode == QPN_MODE_SAMPLING) bi = sample_wave(p.o_lg, Q, p.seed, (unsigned)u.row, (unsigned)i, lane);
             next = bi;
             if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
-            if (lane == 0) { u.out[i] = bi; live_put(p, u, (int)i, bi); }
+            if (lane == 0) { u.out[i] = bi; if (live_put(p, u, (int)i, bi, c.creq)) smi[p.o_samp + 2] = 1; }      // stop on request: the workgroup leaves after the next step
         } else next = u.known[t + 1];
         const int cur = smi[p.o_samp + 1];
         if (t + 2 < c.Ttot) causal_rows(p, u, cur, next, t + 1, lane);     // layer-0 input of the next step
@@ -281,6 +285,11 @@ __global__ __launch_bounds__(QPN_NT) void k_decode(DecodeParams p) {
     __syncthreads();
     const int64_t Ttot = (int64_t)u.n0 + u.n_samples;
     if (Ttot < 3) return;                                   // nothing to predict
+    if (p.cancel) {      // a row that starts after the host's stop request (qpn_decode_cancel) does not run: one lane reads the word, the workgroup leaves together
+        if (tid == 0 && cancel_requested(p)) smi[p.o_samp + 2] = 1;
+        __syncthreads();
+        if (smi[p.o_samp + 2]) return;
+    }
     // state for the first step (t = 1): layer-0 input, aux terms; taps of step 2; pd of step 1 is all-zero
     if (wave == 0) {
         causal_rows(p, u, u.known[0], u.known[1], 1, lane);
@@ -292,7 +301,7 @@ __global__ __launch_bounds__(QPN_NT) void k_decode(DecodeParams p) {
     if (Ttot > 3) stage_taps(p, u, 2, tid, QPN_NT, p.status);
     __syncthreads();
 
-    Ctx c; c.p = &p; c.u = &u; c.lane = lane; c.wave = wave; c.Ttot = Ttot;
+    Ctx c; c.p = &p; c.u = &u; c.lane = lane; c.wave = wave; c.Ttot = Ttot; c.creq = 0; c.stop = 0;
     float4 w0[4], w1[4], w2[4];
     {
         const int* tk = smi + p.o_tasks + wave * 8;
@@ -306,6 +315,7 @@ __global__ __launch_bounds__(QPN_NT) void k_decode(DecodeParams p) {
             run_slot(c, slot + 1, t, w1);
             run_slot(c, slot + 2, t, w2);
         }
+        if (c.stop) break;      // stopped on request at the previous step's publish point (this step has drained: its pick published nothing)
     }
 }
 
@@ -382,6 +392,7 @@ __device__ __forceinline__ void fast_steps(const DecodeParams& p, const FastPara
     float* sm = SM; int* smi = SMI;
     const int L = p.L;
     int stamp_i = 0;
+    int creq = 0;           // the host's stop request: the publishing lane's state (live_put)
 #ifdef QPN_ENABLE_STAMPS   // dev aid (-DQPN_ENABLE_STAMPS + QPN_STAMPS=1): s_memtime at every phase boundary of step 3000,
                            // parked in LDS behind the kernel's own state (no global stores in the timed code), dumped after the step
 #define QPN_STAMP() do { if (p.stamps && t == 3000 && lane == 0 && stamp_i < 120) smi[p.o_stamp + stamp_i * QPN_NW + (wave < QPN_NW ? wave : 0)] = (int)__builtin_amdgcn_s_memtime(); ++stamp_i; } while (0)
@@ -536,6 +547,9 @@ __device__ __forceinline__ void fast_steps(const DecodeParams& p, const FastPara
         }
         QPN_STAMP();
         QPN_STAMP_DUMP();
+        // the LDS stop word is written in the pick below only: read here, between two barriers of the step, every wave finds what the previous
+        // step's pick left -- the same value in all of them -- and the workgroup leaves together once this step has drained
+        const int stop = p.cancel ? __builtin_amdgcn_readfirstlane(smi[p.o_samp + 2]) : 0;
         __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0): the ring rows have left the wave
         wg_barrier();
         // ... layer-0 tiles of the next step fly while the sample is picked, the next layer-0 input looked up and the
@@ -553,17 +567,21 @@ __device__ __forceinline__ void fast_steps(const DecodeParams& p, const FastPara
                 if (p.mode == QPN_MODE_SAMPLING) bi = sample_wave(p.o_lg, Q, p.seed, (unsigned)u.row, (unsigned)i, lane);
                 next = bi;
                 if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
-                if (lane == 0) { u.out[i] = bi; live_put(p, u, (int)i, bi); }
+                if (lane == 0) u.out[i] = bi;
             } else next = u.known[t + 1];
             const int cur = smi[p.o_samp + 1];
             if (t + 2 < Ttot) causal_rows(p, u, cur, next, t + 1, lane);
             if (lane == 0) { smi[p.o_samp] = cur; smi[p.o_samp + 1] = next; }
+            // live output BEHIND the causal rows: the load of the host's stop word, a round trip to host memory that later loads of this wave queue up
+            // behind, is issued once the next step's layer-0 input is in LDS.  Stop on request: the workgroup leaves after the next step
+            if (i >= 0 && lane == 0 && live_put(p, u, i, bi, creq)) smi[p.o_samp + 2] = 1;
         } else {
             const int stid = (wave - 1) * 64 + lane, nst = (NWV - 1) * 64;
             for (int i = stid; i < S; i += nst) { sm[p.o_skf + i] = 0.0f; sm[p.o_ska + i] = 0.0f; }
             if (t + 2 < Ttot) stage_aux(p, u, t + 1, stid, nst);
             if (t + 3 < Ttot) stage_taps(p, u, t + 2, stid, nst, p.status);
         }
+        if (stop) break;    // stopped on request at the previous step's publish point (this step has drained: its pick published nothing)
     }
 #undef QPN_STAMP
 #undef QPN_STAMP_DUMP
@@ -608,6 +626,11 @@ __global__ __launch_bounds__(NWV * 64) void k_decode_fast(DecodeParams p, FastPa
     __syncthreads();
     const int Ttot = u.n0 + u.n_samples;
     if (Ttot < 3) return;
+    if (p.cancel) {      // a row that starts after the host's stop request (qpn_decode_cancel) does not run: one lane reads the word, the workgroup leaves together
+        if (tid == 0 && cancel_requested(p)) smi[p.o_samp + 2] = 1;
+        __syncthreads();
+        if (smi[p.o_samp + 2]) return;
+    }
     if (wave == 0) {
         causal_rows(p, u, u.known[0], u.known[1], 1, lane);
         if (lane == 0) { smi[p.o_samp] = u.known[0]; smi[p.o_samp + 1] = u.known[1]; }
@@ -892,6 +915,7 @@ extern "C" int qpn_create(const qpn_config* cfg, qpn_handle** out) {
     h->d_utts = nullptr; h->utts_cap = 0; h->ev0 = h->ev1 = nullptr; h->last_ms = 0; h->pending = false; h->device = -1; h->train = nullptr;
     h->n_cus = 0; h->pipe_rows = 0; h->h_utts_pinned = nullptr; h->h_utts_cap = 0; h->dec_side = nullptr; h->dec_fork = h->dec_join = nullptr;
     h->live_every = 0; h->live_call = false; h->h_live = h->d_live = nullptr; h->live_cap = 0; h->h_live_done = h->d_live_done = nullptr; h->live_done_cap = 0; h->live_stride = 0;
+    h->h_cancel = h->d_cancel = nullptr; h->cancel_cap = 0; h->live_final = false;
     {   // the environment is read HERE, once per handle: no decode or training call looks at it again
         DecodeKnobs& k = h->dk;
         k.generic = getenv("QPN_DECODE_GENERIC") != nullptr;
@@ -942,6 +966,7 @@ extern "C" void qpn_destroy(qpn_handle* h) {
         if (h->h_utts_pinned) (void)hipHostFree(h->h_utts_pinned);
         if (h->h_live) (void)hipHostFree(h->h_live);
         if (h->h_live_done) (void)hipHostFree(h->h_live_done);
+        if (h->h_cancel) (void)hipHostFree(h->h_cancel);
         if (h->dec_side) (void)hipStreamDestroy(h->dec_side);
         if (h->dec_fork) (void)hipEventDestroy(h->dec_fork);
         if (h->dec_join) (void)hipEventDestroy(h->dec_join);
@@ -1135,9 +1160,11 @@ static int decode_enqueue_impl(qpn_handle* h, int B, int n_x, int64_t F, int64_t
         // running: one decode in flight, and the re-run of qpn_decode_finish comes after a stream synchronisation)
         rc = grow_coherent(&h->h_live, &h->d_live, &h->live_cap, (size_t)B * (size_t)std::max<int64_t>(max_n, 1)); if (rc) return rc;
         rc = grow_coherent(&h->h_live_done, &h->d_live_done, &h->live_done_cap, (size_t)B); if (rc) return rc;
+        rc = grow_coherent(&h->h_cancel, &h->d_cancel, &h->cancel_cap, (size_t)16); if (rc) return rc;      // (the stop request of qpn_decode_cancel: a 64-byte line of its own)
         for (int b = 0; b < B; ++b) __atomic_store_n(&h->h_live_done[b], 0LL, __ATOMIC_RELEASE);
+        __atomic_store_n(h->h_cancel, 0, __ATOMIC_RELEASE);
         h->live_stride = max_n;
-        p.live = h->d_live; p.live_done = h->d_live_done; p.live_every = h->live_every;
+        p.live = h->d_live; p.live_done = h->d_live_done; p.live_every = h->live_every; p.cancel = h->d_cancel;
     }
     UttDesc* utts = h->h_utts_pinned;      // pinned and owned by the handle (one decode in flight per handle): no host synchronisation here
     for (int k = 0; k < B; ++k) {
@@ -1231,6 +1258,7 @@ extern "C" int qpn_decode_enqueue(qpn_handle* h, int B, int n_x, int64_t F, int6
     c.n_samples.assign(h_n_samples, h_n_samples + B); c.maxd = maxd; c.mode = mode; c.seed = seed;
     c.d_teacher = d_teacher; c.d_out = d_out; c.d_logits = d_logits; c.multi_wg = 0; c.coopG = 0;
     h->live_call = h->live_every > 0;
+    h->live_final = false;
     if (h->live_call) {
         if (d_teacher || d_logits) { h->live_call = false; qpn_set_error("live output is not offered together with teacher forcing or the logits output"); return QPN_EINVAL; }
         h->live_seen.assign((size_t)B, 0);
@@ -1266,6 +1294,28 @@ extern "C" int qpn_decode_poll(qpn_handle* h, int64_t* h_done, const int32_t** h
     return QPN_OK;
 }
 
+extern "C" int qpn_decode_cancel(qpn_handle* h) {
+    int rc = need_device(h); if (rc) return rc;
+    if (!h->pending) { qpn_set_error("no decode in flight"); return QPN_ESTATE; }
+    if (!h->live_call) { qpn_set_error("the decode in flight was enqueued without live output (qpn_decode_live): it has no publish points to stop at"); return QPN_ESTATE; }
+    __atomic_store_n(h->h_cancel, 1, __ATOMIC_RELEASE);      // one store to host-coherent memory: no stream work, no wait; the kernels find it at their next publish point
+    return QPN_OK;
+}
+
+extern "C" int qpn_decode_final_counts(qpn_handle* h, int64_t* h_done, int* cancelled) {
+    int rc = need_device(h); if (rc) return rc;
+    if (!h_done || !cancelled) { qpn_set_error("null argument"); return QPN_EINVAL; }
+    if (h->pending) { qpn_set_error("a decode is in flight: call qpn_decode_finish first"); return QPN_ESTATE; }
+    if (!h->live_final) { qpn_set_error("the last decode was not enqueued with live output (qpn_decode_live) and finished"); return QPN_ESTATE; }
+    bool any_short = false;
+    for (int b = 0; b < h->call.B; ++b) {
+        h_done[b] = (int64_t)__atomic_load_n(&h->h_live_done[b], __ATOMIC_ACQUIRE);
+        any_short = any_short || h_done[b] < h->call.n_samples[(size_t)b];
+    }
+    *cancelled = (__atomic_load_n(h->h_cancel, __ATOMIC_ACQUIRE) != 0 && any_short) ? 1 : 0;
+    return QPN_OK;
+}
+
 extern "C" const char* qpn_last_decode_plan(qpn_handle* h) { return h ? h->plan.c_str() : ""; }
 
 extern "C" int qpn_decode_finish(qpn_handle* h, void* stream_) {
@@ -1277,6 +1327,12 @@ extern "C" int qpn_decode_finish(qpn_handle* h, void* stream_) {
     int status = 0;
     QPN_HIP(hipMemcpy(&status, h->d_status, sizeof(int), hipMemcpyDeviceToHost));
     QPN_HIP(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    // A stop request (qpn_decode_cancel) ends the call: a multi-workgroup launch that stopped on it has drained through the give-up path (its peers
+    // set status bit 4 when they see the abort flag), and a launch that had given up before the request is not completed either -- no re-run, and the
+    // drain is not reported as QPN_ENODEV.  The rows' final counts: qpn_decode_final_counts.
+    const bool stop_requested = h->live_call && __atomic_load_n(h->h_cancel, __ATOMIC_ACQUIRE) != 0;
+    h->live_final = h->live_call;
+    if (stop_requested) status &= ~4;
     if ((status & 4) && h->call.multi_wg) {
         // A multi-workgroup launch gave up: its workgroups were not all resident together (CU-masked or shared GPU, another
         // kernel holding CUs).  Every wait in those kernels is bounded, the grid has drained; run the batch again with a

@@ -89,6 +89,10 @@ __global__ __launch_bounds__(COOP_NT) void k_decode_coop(DecodeParams p, FastPar
     const int Ttot = u.n0 + u.n_samples;
     if (Ttot < 3) return;
     if (tid == 0) { smi[o_samp] = u.known[0]; smi[o_samp + 1] = u.known[1]; }
+    // the host's stop request (live_put): the publishing lane's state; a launch that starts after the request raises the abort flag before its
+    // first step, and every workgroup leaves at the end of it
+    int creq = 0;
+    if (tid == 0 && gidx == 0 && cancel_requested(p)) { creq = -1; __hip_atomic_store(c.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     __syncthreads();
     const int q = lane & (R - 1), grp = lane >> logR, qs = lane & (Rs - 1), grps = lane >> logRs;
     const int n_aux = L * 2 * CB;
@@ -256,7 +260,10 @@ __global__ __launch_bounds__(COOP_NT) void k_decode_coop(DecodeParams p, FastPar
                 if (p.mode == QPN_MODE_SAMPLING) bi = sample_wave(o_lg, Q, p.seed, (unsigned)u.row, (unsigned)i, lane);
                 next = bi;
                 if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
-                if (lane == 0 && gidx == 0) { u.out[i] = bi; live_put(p, u, i, bi, c.abort); }
+                if (lane == 0 && gidx == 0) {
+                    u.out[i] = bi;
+                    if (live_put(p, u, i, bi, creq, c.abort)) __hip_atomic_store(c.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // stop on request: drain like a launch that gave up
+                }
             } else next = u.known[t + 1];
             if (lane == 0) {
                 smi[o_samp] = smi[o_samp + 1]; smi[o_samp + 1] = next;

@@ -316,6 +316,10 @@ __global__ __launch_bounds__(CBB_NT) void k_decode_coopb(const DecodeParams p, c
             sm[o_ctl + 2 + pr_] = wv;
         }
     };
+    // the host's stop request (live_put): the state of a wave's publishing lane, one for the utterances it picks; a launch that starts after the
+    // request raises the abort flag before its first step, and every workgroup leaves at the end of it
+    int creq = 0;
+    if (lane == 0 && w == 0 && cancel_requested(p)) { creq = -1; __hip_atomic_store(c.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }      // (every wave's publishing lane)
     // ---------------- pick (qpnet.py:505-516) from the logits in LDS: a wave per utterance, utterances kfirst, kfirst + 8, ...
     auto pick_utts = [&](int t, int kfirst) {
         const unsigned* tg = tagbuf + (t & 1) * CBB_NU;
@@ -332,7 +336,10 @@ __global__ __launch_bounds__(CBB_NT) void k_decode_coopb(const DecodeParams p, c
                 if (p.mode == QPN_MODE_SAMPLING) bi = sample_wave(o_lg + k * Q, Q, p.seed, (unsigned)u.row, (unsigned)i, lane);
                 next = bi;
                 if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
-                if (lane == 0 && w == 0) { u.out[i] = bi; live_put(p, u, i, bi, c.abort); }
+                if (lane == 0 && w == 0) {
+                    u.out[i] = bi;
+                    if (live_put(p, u, i, bi, creq, c.abort)) __hip_atomic_store(c.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // stop on request: drain like a launch that gave up
+                }
             } else next = u.known[t + 1];
             if (lane == 0) { smi[o_samp + 2 * k] = smi[o_samp + 2 * k + 1]; smi[o_samp + 2 * k + 1] = next; }
         }

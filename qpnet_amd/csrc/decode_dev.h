@@ -241,13 +241,29 @@ __device__ __forceinline__ UttView make_view(const DecodeParams& p, const UttDes
 // before the pick in program order.  Where it is a peer's or an upstream role's, this rests on timing, not on the memory model: the flag store
 // and the later stores that carry the step's values on are relaxed stores to different addresses, and the flag store leads them by the rest
 // of that stage's work and every hand-off between there and the pick (microseconds).
-__device__ __forceinline__ void live_put(const DecodeParams& p, const UttView& u, int i, int bi, const int* gave_up = nullptr) {
-    if (!p.live) return;
+//
+// Cancel (qpn_decode_cancel): p.cancel is one word of the same kind of memory that the host sets; armed launches only (null together with
+// p.live).  The lane that publishes reads it with a system-scope load, a round trip to host memory, so the load is issued at one publish
+// point, right behind the count's store, and its value is looked at at the next one: nothing in the step waits for it.  `creq` is that
+// lane's state between publish points: the word as the last publish point's load found it (0 at the start; the host sets 1), or -1 once the
+// stop has been handed on.  Returns true once, at the publish point that finds the word set, AFTER that point's count has been stored: the
+// caller then stops the row -- a multi-workgroup launch by raising its abort flag (every peer drains as after a timeout), a one-CU workgroup
+// through its LDS stop word.  From then on this lane publishes nothing (creq < 0), so the count stored here is the row's last; steps that drain may still store picks
+// behind it.  A row's first look at the word, at its start, is cancel_requested(): a launch that starts after the request publishes nothing.
+__device__ __forceinline__ bool cancel_requested(const DecodeParams& p) {
+    return p.cancel && __hip_atomic_load(p.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;
+}
+__device__ __forceinline__ bool live_put(const DecodeParams& p, const UttView& u, int i, int bi, int& creq, const int* gave_up = nullptr) {
+    if (!p.live) return false;
     __hip_atomic_store(p.live + (u.out - p.out) + i, bi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     if ((unsigned)(i + 1) % (unsigned)p.live_every == 0u || i + 1 == u.n_samples) {
-        if (gave_up && __hip_atomic_load(gave_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+        if (gave_up && __hip_atomic_load(gave_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return false;
+        if (creq < 0) return false;
         __hip_atomic_store(p.live_done + u.row, (long long)(i + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (creq != 0) { creq = -1; return true; }
+        creq = __hip_atomic_load(p.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // (the raw word: any use of it here would wait for it here)
     }
+    return false;
 }
 
 // pitch-dependent tap distance of ring `r` at (padded) time t  (qpnet.py:613-624)

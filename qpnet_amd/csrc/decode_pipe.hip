@@ -491,6 +491,10 @@ __device__ __forceinline__ void post2_pick_role(const DecodeParams& p, const Fas
     const bool sampling = p.mode == QPN_MODE_SAMPLING;
     __syncthreads();
     if (Tmax < 3) return;
+    // the host's stop request (live_put): the publishing lane's state, one for the rows of the group; a launch that starts after the request
+    // raises the abort flag before its first step, and every role drains through its bounded waits
+    int creq = 0;
+    if (tid == 0 && cancel_requested(p)) { creq = -1; __hip_atomic_store(pp.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     for (int t = t_begin; t + 1 < Tmax; ++t) {
         const unsigned tag = (unsigned)t + 1u;
 #pragma unroll
@@ -571,7 +575,10 @@ __device__ __forceinline__ void post2_pick_role(const DecodeParams& p, const Fas
                 u64* nx = X + PX_NX;
                 pst(nx + 65 + lane, tag, sm[o_tab + next * C + lane]);
                 pst(nx + 1 + lane, tag, sm[o_tab + (Q + next) * C + lane]);
-                if (lane == 0) { pst(nx, tag, __int_as_float(next)); u.out[i] = bi; live_put(p, u, i, bi, pp.abort); }
+                if (lane == 0) {
+                    pst(nx, tag, __int_as_float(next)); u.out[i] = bi;
+                    if (live_put(p, u, i, bi, creq, pp.abort)) __hip_atomic_store(pp.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // stop on request: drain like a launch that gave up
+                }
                 if (u.logits) for (int k = lane; k < Q; k += 64) u.logits[(size_t)i * Q + k] = sm[vb + o_lg + k];
             }
         }

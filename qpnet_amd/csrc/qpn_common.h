@@ -126,4 +126,5 @@ struct DecodeParams {
     int32_t* live;          // mirror of `out` ([B][max_n], the element offsets of UttDesc.out)
     long long* live_done;   // [B], indexed by UttDesc.row: samples of that row that are final in the mirror
     int live_every;         // a row publishes its count after every live_every samples, and after its last one
+    const int* cancel;      // the host's stop request (qpn_decode_cancel): one word, non-zero once the caller asked; read at publish points and at a row's start
 };

@@ -54,6 +54,8 @@ struct qpn_handle {
     int32_t* h_live; int32_t* d_live; size_t live_cap;                 // mirror of d_out, [B][max_n] (host address / the device's address of it)
     long long* h_live_done; long long* d_live_done; size_t live_done_cap;   // [B] published counts
     int64_t live_stride;             // max_n of the call in flight
+    int* h_cancel; int* d_cancel; size_t cancel_cap;   // the stop request of qpn_decode_cancel: one host-coherent word, zeroed at every armed enqueue, read by the kernels at their publish points
+    bool live_final;                 // the last decode was armed and has been finished: qpn_decode_final_counts reads its counts (until the next enqueue)
     std::vector<int64_t> live_seen;  // per-row high-water mark of what qpn_decode_poll has reported.  The counts restart only while qpn_decode_finish re-runs a launch that gave up,
                                      // and a handle is not thread-safe: only a caller that polls from a second thread under its own lock around finish could ever see the restart
     struct DecodeCall {              // arguments of the decode in flight: qpn_decode_finish re-runs it on the one-CU kernel when a

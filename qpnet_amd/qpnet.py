@@ -141,6 +141,7 @@ class QPNet(nn.Module):
         self.sampling_seed = None          # set to an int to pin the sampling-mode random stream
         self._n_generate_calls = 0
         self.last_sampling_seed = None
+        self.last_decode_counts, self.last_decode_cancelled = None, False   # generate_live: every row's final count (input order) / whether the call stopped short on request
         self._live_first_piece_s, self._live_mirror_pieces = None, 0      # generate_live (diagnostics): enqueue return -> first piece, pieces of the last call that were read from the mirror while the call was in flight
 
     # ------------------------------------------------------------------ native handle
@@ -291,7 +292,7 @@ class QPNet(nn.Module):
 
     # ------------------------------------------------------------------ live decode output
     def generate_live(self, x, h, n_samples_list, dilated_factors, intervals=None, mode="sampling",
-                      extra_memory=False, every=256, poll_s=0.001):
+                      extra_memory=False, every=256, poll_s=0.001, on_close="finish"):
         """batch_fast_generate as a generator that hands samples over while the decode kernel runs: yields (row, start, samples)
         -- row = index in the input order, samples = a fresh int64 ndarray holding that row's samples [start, start + len) --
         as soon as a poll of the library (qpn_decode_poll) shows new finished samples of a row.  A row's pieces are contiguous
@@ -301,13 +302,20 @@ class QPNet(nn.Module):
         batch_fast_generate, except that n_samples_list is not consumed.  Polling happens in the caller's thread (no background
         thread), with time.sleep(poll_s) between polls that brought nothing; with `intervals` the reference's progress line
         (qpnet.py:519-524) is written as the longest row passes each multiple.  Closing or dropping the generator early finishes
-        the call (the kernel runs to its end: there is no cancel) and leaves the model usable."""
+        the call and leaves the model usable: with on_close="finish" (the default) the kernel runs to its end first; with
+        on_close="cancel" the call is asked to stop (qpn_decode_cancel) and returns after about one or two publish intervals
+        (`every` samples of the longest-running row each) plus the drain of the launch.  A generator that is iterated to its end
+        never cancels.  After the generator has ended, either way, last_decode_counts holds every row's final count in input
+        order (samples below it are valid; n_samples for a call that ran to its end) and last_decode_cancelled whether the call
+        stopped short on request."""
+        if on_close not in ("finish", "cancel"):
+            raise ValueError("on_close must be 'finish' or 'cancel', not %r" % (on_close,))
         if int(every) < 1:
             raise ValueError("every must be >= 1")
         self._native(x.device)          # (CPU tensors are refused here, at the call, not at the first next())
-        return self._live_pieces(x, h, list(n_samples_list), dilated_factors, intervals, mode, extra_memory, int(every), float(poll_s))
+        return self._live_pieces(x, h, list(n_samples_list), dilated_factors, intervals, mode, extra_memory, int(every), float(poll_s), on_close == "cancel")
 
-    def _live_pieces(self, x, h, n_samples_list, dilated_factors, intervals, mode, extra_memory, every, poll_s):
+    def _live_pieces(self, x, h, n_samples_list, dilated_factors, intervals, mode, extra_memory, every, poll_s, cancel_on_close):
         import ctypes as C
         a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory)
         L, hd, dev, B, ns, max_n, out, stream = a["L"], a["hd"], a["dev"], a["B"], a["ns"], a["max_n"], a["out"], a["stream"]
@@ -316,7 +324,7 @@ class QPNet(nn.Module):
         delivered = [0] * B
         longest = max(range(B), key=lambda b: ns[b])
         next_line, t_line = (intervals if intervals is not None and intervals > 0 else 0), time.time()
-        in_flight = False
+        in_flight = enqueued = False
 
         def progress(b, stop):          # the reference's progress line, as the longest row passes each multiple of `intervals`
             nonlocal next_line, t_line
@@ -331,7 +339,8 @@ class QPNet(nn.Module):
             with torch.cuda.device(dev):
                 _lib.check(L.qpn_decode_live(hd, every))
                 _lib.check(L.qpn_decode_enqueue(*a["call"]))
-                in_flight = True
+                in_flight = enqueued = True
+                self.last_decode_counts, self.last_decode_cancelled = None, False
                 t_enqueued = time.time()
                 self._live_first_piece_s, self._live_mirror_pieces = None, 0      # (diagnostics: tools/live_decode.py)
                 self.last_decode_plan = L.qpn_last_decode_plan(hd).decode("utf-8", "replace")
@@ -364,7 +373,13 @@ class QPNet(nn.Module):
         finally:
             with torch.cuda.device(dev):
                 if in_flight:
+                    if cancel_on_close:
+                        L.qpn_decode_cancel(hd)          # every row stops at one of its next publish points; finish then waits for the drain only
                     L.qpn_decode_finish(hd, stream)      # (abandoned, or an error on the way: what it reports has nobody to go to)
+                if enqueued:
+                    cancelled = C.c_int()
+                    if L.qpn_decode_final_counts(hd, done, C.byref(cancelled)) == 0:
+                        self.last_decode_counts, self.last_decode_cancelled = [int(done[b]) for b in range(B)], bool(cancelled.value)
                 L.qpn_decode_live(hd, 0)
 
     # test/diagnostic helper (not part of the reference surface): teacher-forced streaming logits

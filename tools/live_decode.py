@@ -1,5 +1,5 @@
 """Live decode output (QPNet.generate_live) against the blocking call (batch_fast_generate), on one GPU:
-    python tools/live_decode.py [--repeats 5] [--frames 200] [--unarmed-only] > profiles/live_decode.txt
+    python tools/live_decode.py [--repeats 5] [--frames 200] [--unarmed-only] [--cancel] > profiles/live_decode.txt
 
 Paper-size model at B = 1 and B = 20 and the repo-default model at B = 1, 200-frame utterances (21 999 samples each), greedy.  Per case:
   - the time from the return of the enqueue to the first piece, and the pieces per call, with a publish every 64 / 256 / 1024 samples;
@@ -7,9 +7,14 @@ Paper-size model at B = 1 and B = 20 and the repo-default model at B = 1, 200-fr
     (batch_fast_generate).  The variants ALTERNATE inside one process -- repeat 1 of each, then repeat 2 of each, ... -- so that clock and
     temperature drift hits them alike; min / median / max over the repeats, host wall time of the call and device time of its launches.
 --unarmed-only times the blocking call alone (the same inputs on a build without live output).
+--cancel adds, per case and publish interval, calls that are stopped through the C ABI (qpn_decode_cancel) right after their first count has
+appeared: the time from the return of qpn_decode_cancel to the first poll that reports *running == 0, the time to the return of
+qpn_decode_finish, the longest row's count at the request and its final count.
 
 profiles/live_decode.txt is TWO runs in one GPU visit: the output of this tool on this tree, then, behind a comment line that says so, the output (less its
-header line) of a copy of this tool run with --unarmed-only in a checkout of the parent commit, built there: the blocking call before live output existed."""
+header line) of a copy of this tool run with --unarmed-only in a checkout of the parent commit, built there: the blocking call before live output existed.
+Its "decode cancel" part is two runs of the same kind: this tool with --cancel on this tree, then the parent commit's copy of the tool (all four variants, no
+--cancel: the parent cannot) in a checkout of the parent commit, built there."""
 import argparse
 import os
 import sys
@@ -31,6 +36,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--unarmed-only", dest="unarmed_only", action="store_true")
+    ap.add_argument("--cancel", action="store_true")
     args = ap.parse_args()
     import torch
     from qpnet_amd import synth
@@ -60,6 +66,37 @@ def main():
             assert got == sum(ns)
             return dt * 1e3, m.last_decode_kernel_ms
 
+        def cancelled_call(every):
+            """-> ms from the return of qpn_decode_cancel to *running == 0, ms to the return of qpn_decode_finish, the longest row's count at the request, its final count"""
+            import ctypes as C
+            from qpnet_amd import _lib
+            a = m._decode_args(xb, hb, list(ns), bd, "argmax", False)
+            L, hd = a["L"], a["hd"]
+            done, cancelled = (C.c_int64 * B)(), C.c_int()
+            mirror, stride, running = C.POINTER(C.c_int32)(), C.c_int64(), C.c_int()
+            pargs = (hd, done, C.byref(mirror), C.byref(stride), C.byref(running))
+            torch.cuda.synchronize()
+            _lib.check(L.qpn_decode_live(hd, every))
+            _lib.check(L.qpn_decode_enqueue(*a["call"]))
+            while True:
+                _lib.check(L.qpn_decode_poll(*pargs))
+                if max(done) > 0:
+                    break
+            at_request = max(done)
+            _lib.check(L.qpn_decode_cancel(hd))
+            t0 = time.perf_counter()
+            while True:                 # (no sleep between the polls: the poll is what is being timed)
+                _lib.check(L.qpn_decode_poll(*pargs))
+                if not running.value:
+                    break
+            t_run = time.perf_counter()
+            _lib.check(L.qpn_decode_finish(hd, a["stream"]))
+            t_fin = time.perf_counter()
+            _lib.check(L.qpn_decode_final_counts(hd, done, C.byref(cancelled)))
+            _lib.check(L.qpn_decode_live(hd, 0))
+            assert cancelled.value == 1 and max(done) < max(ns), (cancelled.value, max(done))
+            return (t_run - t0) * 1e3, (t_fin - t0) * 1e3, at_request, max(done)
+
         for every in variants:          # warm-up: allocations, code objects
             call(every)
         wall = {v: [] for v in variants}
@@ -72,6 +109,7 @@ def main():
                 wall[every].append(w); kern[every].append(k)
                 if every:
                     first[every].append(m._live_first_piece_s * 1e3); pieces[every].append(m._live_mirror_pieces)
+        stops = {v: [cancelled_call(v) for _ in range(args.repeats + 1)][1:] for v in variants if v and args.cancel}      # (the first one: warm-up)
         print("\n== %s model, B = %d, %d samples per row; plan: %s" % (name, B, ns[0], m.last_decode_plan))
         base = float(np.median(wall[0]))
         print("   unarmed spread (max - min) of the call time: %.3f ms = %.2f %% of its median" % (max(wall[0]) - min(wall[0]), 100 * (max(wall[0]) - min(wall[0])) / base))
@@ -82,6 +120,9 @@ def main():
                 print("   %s median call time vs unarmed: %+.3f ms (%+.2f %%)   first piece after enqueue ms: %s   pieces per call: %d..%d"
                       % (" " * len(tag), float(np.median(wall[every])) - base, 100 * (float(np.median(wall[every])) - base) / base,
                          mmm(first[every]), min(pieces[every]), max(pieces[every])))
+        for every, st in stops.items():
+            print("   cancel every=%-4d request -> running == 0 ms: %s   request -> finish returned ms: %s   count at the request %d..%d, final count %d..%d"
+                  % (every, mmm([r[0] for r in st]), mmm([r[1] for r in st]), min(r[2] for r in st), max(r[2] for r in st), min(r[3] for r in st), max(r[3] for r in st)))
         del m
     return 0
 
