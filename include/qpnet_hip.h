@@ -154,6 +154,14 @@ float qpn_last_decode_kernel_ms(qpn_handle* h);
  * (diagnostics / bench.py; owned by the handle, valid until the next decode call). */
 const char* qpn_last_decode_plan(qpn_handle* h);
 
+/* The launch plan a decode call of B utterances would follow, as the text qpn_last_decode_plan shows after it: attempt 0 = the
+ * first plan, attempt 1 = what qpn_decode_finish runs after a launch of that plan gave up (the text behind "retried: "), or
+ * QPN_ESTATE where no retry exists.  Host arithmetic only: works on a handle created without a GPU.  n_cus > 0 plans for a
+ * device of that many compute units (its pipelined launches hold (n_cus / 40) * 8 groups); n_cus <= 0 means the handle's own
+ * device (QPN_ENODEV without one).  Geometry and knobs are the handle's (the environment as read by qpn_create); the call's
+ * pitch-tap rings are taken to be short enough for the batched cooperative kernel's 32-bit offsets (any maxd below thousands). */
+int qpn_decode_plan_query(qpn_handle* h, int n_cus, int B, int attempt, char* buf, size_t cap);
+
 /*
  * QPNet.forward (reference src/nets/qpnet.py:239-312), teacher forced, fused fp32-MFMA kernels.
  *   d_flat   flat fp32 parameters (state_dict order), read at call time (training updates them)

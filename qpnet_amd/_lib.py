@@ -39,6 +39,7 @@ SYMBOLS = [
     ("qpn_decode_final_counts", _i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     ("qpn_last_decode_kernel_ms", C.c_float, [_vp]),
     ("qpn_last_decode_plan", C.c_char_p, [_vp]),
+    ("qpn_decode_plan_query", _i, [_vp, _i, _i, _i, C.c_char_p, C.c_size_t]),
     ("qpn_train_forward", _i, [_vp, _vp, _i, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     ("qpn_train_backward", _i, [_vp, _vp, _vp, _vp]),
     ("qpn_train_backward_ex", _i, [_vp, _vp, _vp, C.c_float, _i, _vp]),

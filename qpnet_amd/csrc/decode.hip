@@ -788,7 +788,7 @@ static int build_program(qpn_handle* h) {
     // ---- packed weight tiles + task list
     std::vector<int>& map = h->h_map; map.clear();
     const bool cb_ok = qpn_coopb_supported(g);
-    h->cb_ok = cb_ok; h->cb_groups = h->cb_per = 0;
+    h->cb_ok = cb_ok;
     const int cbG = C / 8, cbRC = g.Cp / 16, cbRS = g.Sp / 16;
     const size_t cb_per_w = cb_ok ? ((size_t)3 * L * cbRC + 2 * cbRS) * 64 : 0;      // float4 per workgroup: three tiles per layer + the two post-net tiles
     const size_t cb_base4 = map.size() / 4;
@@ -896,11 +896,7 @@ static int build_program(qpn_handle* h) {
 
 bool qpn_pipe_supported(const Geom& g);
 int qpn_pipe_rows_resident(int n_cus);
-int qpn_launch_decode_pipe(qpn_handle* h, DecodeParams& p, int B, int groups, hipStream_t stream);
-int qpn_coop_group_size(const Geom& g, int limit);
-int qpn_launch_decode_coop(qpn_handle* h, DecodeParams& p, int B, int G, hipStream_t stream);
 bool qpn_coopb_supported(const Geom& g);
-int qpn_launch_decode_coopb(qpn_handle* h, DecodeParams& p, int B, hipStream_t stream);
 
 extern "C" int qpn_create(const qpn_config* cfg, qpn_handle** out) {
     if (!out) { qpn_set_error("null out"); return QPN_EINVAL; }
@@ -913,7 +909,7 @@ extern "C" int qpn_create(const qpn_config* cfg, qpn_handle** out) {
     h->d_pproj = nullptr; h->pproj_cap = 0; h->d_ring = nullptr; h->ring_cap = 0; h->d_known = nullptr; h->known_cap = 0;
     h->d_xch = nullptr; h->xch_cap = 0; h->single_cu_ok = true;
     h->d_utts = nullptr; h->utts_cap = 0; h->ev0 = h->ev1 = nullptr; h->last_ms = 0; h->pending = false; h->device = -1; h->train = nullptr;
-    h->n_cus = 0; h->pipe_rows = 0; h->h_utts_pinned = nullptr; h->h_utts_cap = 0; h->dec_side = nullptr; h->dec_fork = h->dec_join = nullptr;
+    h->n_cus = 0; h->pipe_rows = 0; h->h_utts_pinned = nullptr; h->h_utts_cap = 0;
     h->live_every = 0; h->live_call = false; h->h_live = h->d_live = nullptr; h->live_cap = 0; h->h_live_done = h->d_live_done = nullptr; h->live_done_cap = 0; h->live_stride = 0;
     h->h_cancel = h->d_cancel = nullptr; h->cancel_cap = 0; h->live_final = false;
     {   // the environment is read HERE, once per handle: no decode or training call looks at it again
@@ -924,13 +920,11 @@ extern "C" int qpn_create(const qpn_config* cfg, qpn_handle** out) {
         // (measured on one MI355X, repo-default geometry, us per sample step of the whole batch, batched / per-utterance kernel: B = 1: 89 / 92, 2: 90 / 97, 4: 98 / 110,
         //  8: 115 / 123, 16: 137 / 143, 20: 147 / 200, 32: 165 / 204, 64: 216 / 357 -- profiles/r06_coopb_batches.txt)
         k.coopb = 1; if (const char* e = getenv("QPN_DECODE_COOPB")) k.coopb = atoi(e) > 0 ? atoi(e) : 0;
-        k.coopb_per = 0; if (const char* e = getenv("QPN_DECODE_COOPB_PER")) k.coopb_per = atoi(e);
         k.coopb_delay[0] = 8; k.coopb_delay[1] = 4; k.coopb_delay[2] = 0;
         if (const char* e = getenv("QPN_COOPB_DELAY_G")) k.coopb_delay[0] = atoi(e);
         if (const char* e = getenv("QPN_COOPB_DELAY_X")) k.coopb_delay[1] = atoi(e);
         if (const char* e = getenv("QPN_COOPB_DELAY_T")) k.coopb_delay[2] = atoi(e);
         k.pipe = 1; if (const char* e = getenv("QPN_DECODE_PIPE")) k.pipe = atoi(e) != 0 ? 1 : 0;
-        k.hybrid = getenv("QPN_DECODE_HYBRID") != nullptr;
         k.stamps = getenv("QPN_STAMPS") != nullptr;
         k.test_pipe_gives_up = false;
 #ifdef QPN_TESTING
@@ -940,6 +934,8 @@ extern "C" int qpn_create(const qpn_config* cfg, qpn_handle** out) {
     rc = build_program(h);
     h->decode_ok = rc == QPN_OK;
     if (rc != QPN_OK) h->decode_err = g_err;            // reported by the decode entry points; the training path has its own limits
+    h->pipe_nu = 3;                                      // most utterances a five-role group steps alternately when the batch exceeds the groups
+    if (const char* e = getenv("QPN_PIPE_NU")) { const int v = atoi(e); if (v >= 2 && v <= 3) h->pipe_nu = v; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
         // geometry-only handle: usable for qpn_param_count-style queries, every compute call fails loudly
@@ -949,8 +945,6 @@ extern "C" int qpn_create(const qpn_config* cfg, qpn_handle** out) {
     QPN_HIP(hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->device));
     if (h->n_cus < 1) h->n_cus = 1;
     h->pipe_rows = qpn_pipe_rows_resident(h->n_cus);
-    h->pipe_nu = 3;                                      // most utterances a five-role group steps alternately when the batch exceeds the groups
-    if (const char* e = getenv("QPN_PIPE_NU")) { const int v = atoi(e); if (v >= 2 && v <= 3) h->pipe_nu = v; }
     *out = h;
     return QPN_OK;
 }
@@ -967,9 +961,6 @@ extern "C" void qpn_destroy(qpn_handle* h) {
         if (h->h_live) (void)hipHostFree(h->h_live);
         if (h->h_live_done) (void)hipHostFree(h->h_live_done);
         if (h->h_cancel) (void)hipHostFree(h->h_cancel);
-        if (h->dec_side) (void)hipStreamDestroy(h->dec_side);
-        if (h->dec_fork) (void)hipEventDestroy(h->dec_fork);
-        if (h->dec_join) (void)hipEventDestroy(h->dec_join);
     }
     delete h;
 }
@@ -1041,9 +1032,11 @@ static int grow_coherent(T** hp, T** dp, size_t* cap, size_t need) {
     return QPN_OK;
 }
 
-// One launch of the one-CU kernels (one 1024-thread workgroup per utterance) over the descriptors p.utts[0 .. n)
-static int launch_one_cu(qpn_handle* h, DecodeParams& p, int n, hipStream_t stream) {
+int grow_xch(qpn_handle* h, size_t words) { return grow(&h->d_xch, &h->xch_cap, words); }
+// One launch of the one-CU kernels (one 1024-thread workgroup per utterance) over the descriptors p.utts[l.first .. l.first + l.rows)
+static int launch_one_cu(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, hipStream_t stream) {
     const Geom& g = h->g;
+    const int n = l.rows; p.utts += l.first;
     const bool generic = h->dk.generic;
     const bool fast64 = !generic && g.C == 64 && g.S == 256 && g.Q == 256, fast32 = !generic && g.C == 32 && g.S == 32 && g.Q == 256;
     // the specialised kernel does not use the task table: the residual-1x1 tiles of layers 0..L-2 take its place (and more) when they fit
@@ -1071,14 +1064,25 @@ static int launch_one_cu(qpn_handle* h, DecodeParams& p, int n, hipStream_t stre
     return QPN_OK;
 }
 
-// force_one_cu: the retry of qpn_decode_finish (a multi-workgroup launch gave up) -- one-CU kernels only
-static int decode_enqueue_impl(qpn_handle* h, int B, int n_x, int64_t F, int64_t Td,
-                               const int64_t* d_x, const float* d_h, const void* d_dfac, int d_is_f32,
-                               const int64_t* h_n_samples, int maxd, int mode, uint64_t seed,
-                               const int64_t* d_teacher, int64_t* d_out, float* d_logits, hipStream_t stream, bool force_one_cu, int coop_limit) {
+// what the planner is told: the handle's geometry and knobs, the device facts given (the handle's own, or a query's), the batch and the floats of a row's rings
+static DecodePlanIn plan_inputs(const qpn_handle* h, int n_cus, int pipe_rows, int B, size_t ring_floats) {
     const Geom& g = h->g;
-    int rc;
-    int64_t max_n = 0;
+    DecodePlanIn in = {};
+    in.C = g.C; in.S = g.S; in.Q = g.Q; in.Cp = g.Cp; in.Sp = g.Sp; in.L = g.L;
+    in.single_cu_ok = h->single_cu_ok; in.pipe_supported = qpn_pipe_supported(g); in.coopb_supported = h->cb_ok;
+    in.coopb_fits = decode_coopb_fits(in, h->h_map.size() * sizeof(float), (long long)ring_floats);
+    in.n_cus = n_cus; in.pipe_rows = pipe_rows; in.pipe_nu = h->pipe_nu; in.B = B;
+    in.coop = h->dk.coop; in.coopb = h->dk.coopb; in.pipe = h->dk.pipe; in.generic = h->dk.generic;
+    return in;
+}
+
+// Enqueues the call h->call describes, launch by launch of its plan.  retry: nullptr, or the inputs decode_plan_retry made (qpn_decode_finish)
+static int decode_enqueue_impl(qpn_handle* h, hipStream_t stream, const DecodePlanIn* retry) {
+    const Geom& g = h->g;
+    qpn_handle::DecodeCall& c = h->call;
+    const int B = c.B, n_x = c.n_x, maxd = c.maxd; const int64_t F = c.F, Td = c.Td;
+    const int64_t* h_n_samples = c.n_samples.data(); const int64_t* d_teacher = c.d_teacher; float* d_logits = c.d_logits;
+    int rc; int64_t max_n = 0;
     for (int b = 0; b < B; ++b) {
         int64_t n = h_n_samples[b];
         if (n < 0) { qpn_set_error("negative n_samples"); return QPN_EINVAL; }
@@ -1092,7 +1096,6 @@ static int decode_enqueue_impl(qpn_handle* h, int B, int n_x, int64_t F, int64_t
     int64_t n_pad = RF - n_x + 1; if (n_pad < 0) n_pad = 0;
     const int64_t n0 = n_pad + n_x;
     if (n0 + max_n >= ((int64_t)1 << 31)) { qpn_set_error("sequence too long"); return QPN_EINVAL; }
-    // ring geometry
     DecodeParams p = h->dp;
     size_t ring_floats = 0;
     for (int l = 0; l < g.L; ++l) {
@@ -1101,51 +1104,13 @@ static int decode_enqueue_impl(qpn_handle* h, int B, int n_x, int64_t F, int64_t
         p.rings[l].base = (int)ring_floats; p.rings[l].len = len; p.rings[l].mult = y.dilation; p.rings[l].adaptive = y.adaptive;
         ring_floats += (size_t)len * g.C;
     }
+    c.in = retry ? *retry : plan_inputs(h, h->n_cus, h->pipe_rows, B, ring_floats); c.plan = decode_plan(c.in);
     ring_floats = (ring_floats + 63) & ~(size_t)63;
-    // several workgroups per utterance when one CU cannot hold the step state (or QPN_DECODE_COOP=<G> asks for it)
-    int coopG = h->dk.coop;
-    // (default: up to half the CUs for one utterance -- measured at C = 512, B = 1: 96.7 / 91.6 / 93.1 us per sample with 64 / 128 / 256 workgroups; QPN_DECODE_COOP=<G> asks for more)
-    if (!h->single_cu_ok && coopG == 0) coopG = h->n_cus >= 128 ? h->n_cus / 2 : h->n_cus;
-    if (force_one_cu && h->single_cu_ok) coopG = 0;
-    // wide geometries, batches: the utterances batched into the contractions (decode_coopb.hip) -- up to 16 per group of n_resch / 8 workgroups
-    // (a launch holds 16 utterances per group and as many groups as fit the chip: larger batches take several launches of equal size, longest rows first)
-    const bool coopb = coopG > 0 && !force_one_cu && coop_limit == 0 && h->cb_ok && h->dk.coopb > 0 && B >= h->dk.coopb && h->n_cus >= g.C / 8;
-    const int cb_cap = 16 * (h->n_cus / (g.C / 8) > 0 ? h->n_cus / (g.C / 8) : 1), cb_launches = (B + cb_cap - 1) / cb_cap, cb_rows = (B + cb_launches - 1) / cb_launches;
-    if (coopG > 0) {
-        int cap = coopG; if (B < h->n_cus && h->n_cus / B < cap) cap = h->n_cus / B;       // the whole batch in one launch when it fits the chip
-        if (coop_limit > 0 && cap > coop_limit) cap = coop_limit;                          // retry with fewer workgroups per utterance
-        coopG = qpn_coop_group_size(g, cap < 1 ? 1 : cap);
-    }
-    // ---- launch plan.  Rows are handed to the kernels longest first (descriptors are a permutation of the batch):
-    //   PIPE  rows [0, n_pipe) in waves of <= pipe_rows (five resident workgroups per utterance, decode_pipe.hip)
-    //   ONE   rows [n_pipe, B) on one-CU kernels, on a side stream BESIDE the first pipelined wave when there is one
+    // rows are handed to the kernels longest first (descriptors are a permutation of the batch)
     std::vector<int> order(B);
     for (int b = 0; b < B; ++b) order[b] = b;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b2) { return h_n_samples[a] > h_n_samples[b2]; });
-    const bool pipe_ok = !coopG && !force_one_cu && h->dk.pipe != 0 && qpn_pipe_supported(g) && !h->dk.generic && h->pipe_rows >= 1;
-    int n_pipe = 0, n_waves = 0, wave_rows = 0;
-    if (pipe_ok) {
-        const int cap = h->pipe_rows;                    // five-role groups one launch holds resident
-        const bool hybrid_knob = h->dk.hybrid;      // dev aid: rows beyond `cap` on one-CU kernels beside the launch (round-3 first form)
-        if (B <= cap) { n_pipe = B; n_waves = 1; wave_rows = B; }
-        else if (hybrid_knob && B - cap <= h->n_cus - 5 * cap) { n_pipe = cap; n_waves = 1; wave_rows = cap; }
-        else {
-            // a group takes a second (third) utterance, stepped alternately with the first (a role is busy ~2 us of an utterance's ~8 us
-            // step): up to pipe_nu * cap rows per launch at 10 us (12 us) per step instead of 8.4; beyond that, equal-sized launches
-            // measured step times with 1 / 2 / 3 utterances per group: 8.4 / 10.0 / 15.3 us (profiles/r03_decode_batches.txt); the plan with
-            // the smallest (launches x step time) wins -- three per group only pays where it saves a launch (97..144 rows on 48 groups)
-            static const double step_us[4] = {0.0, 8.4, 10.0, 15.3};
-            double best = 1e300;
-            for (int nu_max = 2; nu_max <= h->pipe_nu; ++nu_max) {
-                const int nw = (B + nu_max * cap - 1) / (nu_max * cap), per = (B + nw - 1) / nw, nu = (per + cap - 1) / cap;
-                const double tt = nw * step_us[nu];
-                if (tt < best) { best = tt; n_waves = nw; wave_rows = per; }
-            }
-            n_pipe = B;
-        }
-    }
-    const int n_one = coopG ? 0 : B - n_pipe;
-    if (!coopG) { rc = grow(&h->d_ring, &h->ring_cap, ring_floats * (size_t)B); if (rc) return rc; }      // pitch-tap histories (one-CU kernels; role S1 of the pipelined one)
+    if (c.plan.needs_ring) { rc = grow(&h->d_ring, &h->ring_cap, ring_floats * (size_t)B); if (rc) return rc; }      // pitch-tap histories (one-CU kernels; role S1 of the pipelined one)
     rc = grow(&h->d_pproj, &h->pproj_cap, (size_t)B * F * g.L * 2 * g.C); if (rc) return rc;
     rc = grow(&h->d_known, &h->known_cap, (size_t)B * n0); if (rc) return rc;
     rc = grow(&h->d_utts, &h->utts_cap, (size_t)B); if (rc) return rc;
@@ -1177,67 +1142,27 @@ static int decode_enqueue_impl(qpn_handle* h, int B, int n_x, int64_t F, int64_t
         u.out = (int64_t)b * max_n;
         u.logits = d_logits ? (int64_t)b * max_n * g.Q : -1;
         u.ring = (int64_t)k * ring_floats;
-        u.n_pad = (int)n_pad; u.n0 = (int)n0; u.n_samples = (int)h_n_samples[b]; u.d_is_f32 = d_is_f32; u.F = F;
+        u.n_pad = (int)n_pad; u.n0 = (int)n0; u.n_samples = (int)h_n_samples[b]; u.d_is_f32 = c.d_is_f32; u.F = F;
         u.row = b; u.pad_ = 0;
     }
     QPN_HIP(hipMemcpyAsync(h->d_utts, utts, (size_t)B * sizeof(UttDesc), hipMemcpyHostToDevice, stream));
-    if (!coopG) QPN_HIP(hipMemsetAsync(h->d_ring, 0, ring_floats * (size_t)B * sizeof(float), stream));
+    if (c.plan.needs_ring) QPN_HIP(hipMemsetAsync(h->d_ring, 0, ring_floats * (size_t)B * sizeof(float), stream));
     QPN_HIP(hipMemsetAsync(h->d_status, 0, 64, stream));
-    hipLaunchKernelGGL(k_known, dim3((unsigned)((n0 + 255) / 256), B), dim3(256), 0, stream, d_x, n_x, (int)n_pad, g.Q, h->d_known);
-    hipLaunchKernelGGL(k_aux_project, dim3((unsigned)F, B), dim3(256), g.Ap * sizeof(float), stream, (const float4*)h->d_wpk, d_h, F,
+    hipLaunchKernelGGL(k_known, dim3((unsigned)((n0 + 255) / 256), B), dim3(256), 0, stream, c.d_x, n_x, (int)n_pad, g.Q, h->d_known);
+    hipLaunchKernelGGL(k_aux_project, dim3((unsigned)F, B), dim3(256), g.Ap * sizeof(float), stream, (const float4*)h->d_wpk, c.d_h, F,
                        h->aux_woff4, h->aux_tiles, h->logRa, g.A, g.Ap, g.C, g.L, h->d_pproj);
     p.wpk = (const float4*)h->d_wpk; p.flat = h->d_flat; p.qb = h->d_qb; p.tasks = h->d_tasks; p.utts = h->d_utts;
-    p.status = h->d_status; p.mode = mode; p.seed = seed; p.bias_src = h->d_bias_src;
+    p.status = h->d_status; p.mode = c.mode; p.seed = c.seed; p.bias_src = h->d_bias_src;
     p.stamps = h->dk.stamps ? (long long*)(h->d_status + 16) : nullptr;
-    p.pproj = h->d_pproj; p.dfac = d_dfac; p.known = h->d_known; p.teacher = d_teacher; p.out = d_out; p.logits = d_logits; p.ring = h->d_ring;
+    p.pproj = h->d_pproj; p.dfac = c.d_dfac; p.known = h->d_known; p.teacher = d_teacher; p.out = c.d_out; p.logits = d_logits; p.ring = h->d_ring;
     QPN_HIP(hipEventRecord(h->ev0, stream));
-    char plan[160];
-    rc = 1;                                                           // (1: the batched kernel does not apply to this call)
-    if (coopb)
-        for (int first = 0; first < B; first += cb_rows) {
-            DecodeParams pw = p; pw.utts = h->d_utts + first;
-            rc = qpn_launch_decode_coopb(h, pw, std::min(cb_rows, B - first), stream);
-            if (rc) break;                                            // (what makes it not apply does not depend on the rows: the first launch decides)
-        }
-    if (rc < 0) return rc;
-    if (rc == 0) {
-        if (cb_launches > 1) snprintf(plan, sizeof(plan), "coopb G=%d launches=%d x %d rows=%d", g.C / 8, cb_launches, cb_rows, B);
-        else snprintf(plan, sizeof(plan), "coopb G=%d groups=%d x %d rows=%d", g.C / 8, h->cb_groups, h->cb_per, B);
-        h->call.multi_wg = 2; h->call.coopG = coopG > 2 ? coopG : 2;      // (a launch that gives up is re-run per utterance: decode_coop.hip)
-    } else if (coopG) {
-        rc = qpn_launch_decode_coop(h, p, B, coopG, stream); if (rc) return rc;
-        snprintf(plan, sizeof(plan), "coop G=%d rows=%d", coopG, B);
-        h->call.multi_wg = coopG > 1 ? 2 : 0; h->call.coopG = coopG;
-    } else {
-        const bool beside = n_pipe > 0 && n_one > 0;       // hybrid: the one-CU rows run on the side stream while the pipelined wave runs
-        if (beside) {
-            if (!h->dec_side) {
-                QPN_HIP(hipStreamCreateWithFlags(&h->dec_side, hipStreamNonBlocking));
-                QPN_HIP(hipEventCreateWithFlags(&h->dec_fork, hipEventDisableTiming));
-                QPN_HIP(hipEventCreateWithFlags(&h->dec_join, hipEventDisableTiming));
-            }
-            QPN_HIP(hipEventRecord(h->dec_fork, stream));
-            QPN_HIP(hipStreamWaitEvent(h->dec_side, h->dec_fork, 0));
-        }
-        for (int w = 0; w < n_waves; ++w) {
-            const int first = w * wave_rows, n = std::min(wave_rows, n_pipe - first);
-            if (n <= 0) break;
-            DecodeParams pw = p; pw.utts = h->d_utts + first;
-            rc = qpn_launch_decode_pipe(h, pw, n, std::min(n, h->pipe_rows), stream); if (rc) return rc;
-        }
-        if (n_one > 0) {
-            DecodeParams po = p; po.utts = h->d_utts + n_pipe;
-            rc = launch_one_cu(h, po, n_one, beside ? h->dec_side : stream); if (rc) return rc;
-        }
-        if (beside) {
-            QPN_HIP(hipEventRecord(h->dec_join, h->dec_side));
-            QPN_HIP(hipStreamWaitEvent(stream, h->dec_join, 0));
-        }
-        snprintf(plan, sizeof(plan), "pipe rows=%d waves=%d x %d (%d per group); one-cu rows=%d%s", n_pipe, n_waves, wave_rows,
-                 n_pipe > 0 ? (wave_rows + h->pipe_rows - 1) / h->pipe_rows : 1, n_one, beside ? " (beside)" : "");
-        h->call.multi_wg = n_pipe > 0 ? 1 : 0; h->call.coopG = 0;
+    for (int i = 0; i < c.plan.launches; ++i) {
+        const DecodeLaunch l = decode_plan_launch(c.in, c.plan, i);
+        rc = c.plan.kind == DECODE_COOPB ? qpn_launch_decode_coopb(h, p, l, stream) : c.plan.kind == DECODE_COOP ? qpn_launch_decode_coop(h, p, l, c.plan.G, stream)
+           : c.plan.kind == DECODE_PIPE ? qpn_launch_decode_pipe(h, p, l, stream) : launch_one_cu(h, p, l, stream);
+        if (rc) return rc;
     }
-    h->plan = plan;
+    char text[160]; decode_plan_text(c.in, c.plan, text, sizeof(text)); h->plan = text;
     QPN_HIP(hipEventRecord(h->ev1, stream));
     h->pending = true;
     return QPN_OK;
@@ -1256,15 +1181,14 @@ extern "C" int qpn_decode_enqueue(qpn_handle* h, int B, int n_x, int64_t F, int6
     qpn_handle::DecodeCall& c = h->call;
     c.B = B; c.n_x = n_x; c.F = F; c.Td = Td; c.d_x = d_x; c.d_h = d_h; c.d_dfac = d_dfac; c.d_is_f32 = d_is_f32;
     c.n_samples.assign(h_n_samples, h_n_samples + B); c.maxd = maxd; c.mode = mode; c.seed = seed;
-    c.d_teacher = d_teacher; c.d_out = d_out; c.d_logits = d_logits; c.multi_wg = 0; c.coopG = 0;
+    c.d_teacher = d_teacher; c.d_out = d_out; c.d_logits = d_logits;
     h->live_call = h->live_every > 0;
     h->live_final = false;
     if (h->live_call) {
         if (d_teacher || d_logits) { h->live_call = false; qpn_set_error("live output is not offered together with teacher forcing or the logits output"); return QPN_EINVAL; }
         h->live_seen.assign((size_t)B, 0);
     }
-    return decode_enqueue_impl(h, B, n_x, F, Td, d_x, d_h, d_dfac, d_is_f32, c.n_samples.data(), maxd, mode, seed, d_teacher, d_out, d_logits,
-                               (hipStream_t)stream_, false, 0);
+    return decode_enqueue_impl(h, (hipStream_t)stream_, nullptr);
 }
 
 extern "C" int qpn_decode_live(qpn_handle* h, int every) {
@@ -1318,6 +1242,19 @@ extern "C" int qpn_decode_final_counts(qpn_handle* h, int64_t* h_done, int* canc
 
 extern "C" const char* qpn_last_decode_plan(qpn_handle* h) { return h ? h->plan.c_str() : ""; }
 
+extern "C" int qpn_decode_plan_query(qpn_handle* h, int n_cus, int B, int attempt, char* buf, size_t cap) {
+    if (!h || !buf || cap < 1 || B < 1 || attempt < 0 || attempt > 1) { qpn_set_error("bad plan query arguments"); return QPN_EINVAL; }
+    if (!h->decode_ok) { qpn_set_error("%s", h->decode_err.c_str()); return QPN_EINVAL; }
+    const int pipe_rows = n_cus > 0 ? (n_cus / 40) * 8 : h->pipe_rows;
+    if (n_cus <= 0) n_cus = h->n_cus;
+    if (n_cus < 1) { qpn_set_error("no HIP device: the query needs n_cus"); return QPN_ENODEV; }
+    DecodePlanIn in = plan_inputs(h, n_cus, pipe_rows, B, 0);      // (no call, no rings: see the header)
+    DecodePlan plan = decode_plan(in);
+    if (attempt && !decode_plan_retry(in, plan)) { qpn_set_error("this plan has no retry: one workgroup per utterance already"); return QPN_ESTATE; }
+    decode_plan_text(in, plan, buf, cap);
+    return QPN_OK;
+}
+
 extern "C" int qpn_decode_finish(qpn_handle* h, void* stream_) {
     int rc = need_device(h); if (rc) return rc;
     if (!h->pending) { qpn_set_error("no decode in flight"); return QPN_ESTATE; }
@@ -1333,18 +1270,13 @@ extern "C" int qpn_decode_finish(qpn_handle* h, void* stream_) {
     const bool stop_requested = h->live_call && __atomic_load_n(h->h_cancel, __ATOMIC_ACQUIRE) != 0;
     h->live_final = h->live_call;
     if (stop_requested) status &= ~4;
-    if ((status & 4) && h->call.multi_wg) {
-        // A multi-workgroup launch gave up: its workgroups were not all resident together (CU-masked or shared GPU, another
-        // kernel holding CUs).  Every wait in those kernels is bounded, the grid has drained; run the batch again with a
-        // smaller footprint -- the one-CU kernels for the paper-size geometry, half the workgroups per utterance otherwise.
-        const qpn_handle::DecodeCall c = h->call;
-        const bool to_one_cu = h->single_cu_ok;
-        if (to_one_cu || c.coopG >= 2) {
+    if (status & 4) {
+        // A multi-workgroup launch gave up: its workgroups were not all resident together (CU-masked or shared GPU, another kernel holding CUs).  Every wait
+        // in those kernels is bounded, the grid has drained; run the batch again with a smaller footprint where decode_plan_retry has one.
+        DecodePlanIn in = h->call.in; DecodePlan again = h->call.plan;
+        if (decode_plan_retry(in, again)) {
             const std::string first_plan = h->plan;
-            h->call.multi_wg = 0;
-            rc = decode_enqueue_impl(h, c.B, c.n_x, c.F, c.Td, c.d_x, c.d_h, c.d_dfac, c.d_is_f32, c.n_samples.data(), c.maxd, c.mode, c.seed,
-                                     c.d_teacher, c.d_out, c.d_logits, stream, to_one_cu, to_one_cu ? 0 : c.coopG / 2);
-            if (rc) return rc;
+            rc = decode_enqueue_impl(h, stream, &in); if (rc) return rc;
             QPN_HIP(hipStreamSynchronize(stream));
             h->pending = false;
             h->plan = first_plan + " -> timed out, retried: " + h->plan;

@@ -278,22 +278,8 @@ __global__ __launch_bounds__(COOP_NT) void k_decode_coop(DecodeParams p, FastPar
 // ------------------------------------------------------------------------------------------ host side
 static int ilog2c(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
-// largest power-of-two group size G <= limit: the gate and residual row slices are whole 4 KiB tiles; a skip / post-net slice may be a fraction of ONE tile
-// (round 5: G = 128 / 256 for the C = 512 geometry -- the workgroup takes the tile that holds its one or two rows and keeps their lane groups)
-int qpn_coop_group_size(const Geom& g, int limit) {
-    const int rpt = 64 / (g.Cp / 16), rpts = 64 / (g.Sp / 16);
-    auto slice_ok = [](int rows, int per_tile) { return rows % per_tile == 0 || (rows < per_tile && per_tile % rows == 0); };
-    int best = 1;
-    for (int G = 1; G <= limit; G *= 2) {
-        if (g.C % G || g.S % G || g.Q % G) break;
-        const int CB = g.C / G, SB = g.S / G, QB = g.Q / G;
-        if ((2 * CB) % rpt || CB % rpt || !slice_ok(SB, rpt) || !slice_ok(SB, rpts) || !slice_ok(QB, rpts)) break;
-        best = G;
-    }
-    return best;
-}
-
-int qpn_launch_decode_coop(qpn_handle* h, DecodeParams& p, int B, int G, hipStream_t stream) {
+// l.rows utterances from l.first on (the kernel's b0), G workgroups each: the caller's launches hold no more than are resident together (one workgroup per CU)
+int qpn_launch_decode_coop(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, int G, hipStream_t stream) {
     const Geom& g = h->g;
     const int L = g.L, C = g.C, S = g.S, Q = g.Q;
     CoopParams c; memset(&c, 0, sizeof(c));
@@ -306,26 +292,16 @@ int qpn_launch_decode_coop(qpn_handle* h, DecodeParams& p, int B, int G, hipStre
     o = (o + 15) & ~15L;
     if (o >= (1L << 31)) { qpn_set_error("cooperative decode: exchange block too large"); return QPN_EINVAL; }
     c.utt_stride = o; c.f_p1b = (int)g.post1_b; c.f_p2b = (int)g.post2_b;
-    const int per_launch = h->n_cus / G > 0 ? h->n_cus / G : 1;        // all workgroups of a launch must be resident together (one per CU)
-    const int nb = B < per_launch ? B : per_launch;
-    const size_t xwords = (size_t)o * nb + 16;
-    if (xwords > h->xch_cap) {
-        if (h->d_xch) (void)hipFree(h->d_xch);
-        h->d_xch = nullptr; h->xch_cap = 0;
-        if (hipMalloc(&h->d_xch, xwords * sizeof(unsigned long long)) != hipSuccess) { qpn_set_error("hipMalloc(%zu MiB) for the decode exchange buffers failed", xwords * 8 >> 20); return QPN_ENOMEM; }
-        h->xch_cap = xwords;
-    }
+    const size_t xwords = (size_t)o * l.rows + 16;
+    int rc = grow_xch(h, xwords); if (rc) return rc;
     c.xch = h->d_xch + 16; c.abort = (int*)h->d_xch;          // first 128 bytes: the abort flag
     // LDS of the kernel
     int lds = 2 * g.Cp + L * g.Cp + g.Cp + 2 * g.Sp + ((Q + 3) & ~3) + ((2 * c.SB + 3) & ~3) + L * 2 * c.CB + 4 + L * (c.CB + c.SB) + c.SB + c.QB;
     const size_t lds_bytes = (size_t)lds * sizeof(float);
     if (lds_bytes > 160 * 1024) { qpn_set_error("cooperative decode: %zu KiB of step state per workgroup exceed LDS (use more workgroups per utterance)", lds_bytes >> 10); return QPN_EINVAL; }
     QPN_HIP(hipFuncSetAttribute((const void*)k_decode_coop, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    for (int b0 = 0; b0 < B; b0 += per_launch) {
-        const int n = B - b0 < per_launch ? B - b0 : per_launch;
-        QPN_HIP(hipMemsetAsync(h->d_xch, 0, xwords * sizeof(unsigned long long), stream));      // tags, rings, abort flag
-        hipLaunchKernelGGL(k_decode_coop, dim3(G, n), dim3(COOP_NT), lds_bytes, stream, p, h->fp, c, b0);
-    }
+    QPN_HIP(hipMemsetAsync(h->d_xch, 0, xwords * sizeof(unsigned long long), stream));      // tags, rings, abort flag
+    hipLaunchKernelGGL(k_decode_coop, dim3(G, l.rows), dim3(COOP_NT), lds_bytes, stream, p, h->fp, c, l.first);
     QPN_HIP(hipGetLastError());
     return QPN_OK;
 }

@@ -24,6 +24,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define CBB_NT 512
 #define CBB_NW (CBB_NT / 64)
 #define CBB_NU 16                     // utterance columns of a tile
+static_assert(CBB_NU == DECODE_COOPB_NU, "the launch planner spreads a batch over groups of CBB_NU utterances");
 #define CBB_SPIN_LIMIT (1u << 20)
 
 struct CoopbParams {
@@ -598,8 +599,10 @@ bool qpn_coopb_supported(const Geom& g) {
     return (size_t)cbb_lds_floats(g.C, g.L) * sizeof(float) <= 160 * 1024;
 }
 
-int qpn_launch_decode_coopb(qpn_handle* h, DecodeParams& p, int B, hipStream_t stream) {
+// l.rows utterances on l.groups groups of C / 8 workgroups, l.per_group each (the plan has checked that 32-bit byte offsets reach: decode_coopb_fits)
+int qpn_launch_decode_coopb(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, hipStream_t stream) {
     const Geom& g = h->g;
+    const int B = l.rows; p.utts += l.first;
     const int L = g.L, C = g.C, S = g.S, Q = g.Q;
     CoopbParams c; memset(&c, 0, sizeof(c));
     c.G = C / 8; c.SB = S / c.G; c.QB = Q / c.G; c.RC = g.Cp / 16; c.RS = g.Sp / 16; c.B = B;
@@ -610,28 +613,14 @@ int qpn_launch_decode_coopb(qpn_handle* h, DecodeParams& p, int B, hipStream_t s
         c.f_resb[l] = (int)g.layers[l].resb; c.f_skipb[l] = (int)g.layers[l].skipb; c.adaptive[l] = g.layers[l].adaptive;
     }
     c.p1 = h->cb_p1; c.p2 = h->cb_p2; c.base4 = h->cb_base4; c.per_w = h->cb_per_w;
-    if (h->h_map.size() * sizeof(float) >= (1ull << 32)) return 1;      // (the fragment blocks are addressed with 32-bit byte offsets)
     c.wpk_bytes = (unsigned)(h->h_map.size() * sizeof(float));
     c.o_g = (int)o; o += (long)L * C; c.o_y1 = (int)o; o += S; c.o_y2 = (int)o; o += S; c.o_lg = (int)o; o += Q;
     o = (o + 15) & ~15L;
-    if (o * CBB_NU * 8 >= (1L << 31)) return 1;             // (a group's exchange block is addressed with 32-bit byte offsets: the caller takes decode_coop.hip)
     c.utt_stride = o; c.f_p1b = (int)g.post1_b; c.f_p2b = (int)g.post2_b;
-    // groups: as many as fit the chip (all workgroups of a launch must be resident together, one per CU), the utterances spread evenly over them
-    const int max_groups = h->n_cus / c.G > 0 ? h->n_cus / c.G : 1;
-    int ngroups = (B + CBB_NU - 1) / CBB_NU;
-    if (ngroups < max_groups) ngroups = max_groups < B ? max_groups : B;
-    if (ngroups > max_groups) ngroups = max_groups;           // (more than 16 per group would be needed: the caller splits the batch)
-    c.NBper = (B + ngroups - 1) / ngroups;
-    if (h->dk.coopb_per > 0 && h->dk.coopb_per <= CBB_NU && (B + h->dk.coopb_per - 1) / h->dk.coopb_per <= max_groups) c.NBper = h->dk.coopb_per;      // (dev knob)
-    if (c.NBper > CBB_NU) { qpn_set_error("batched cooperative decode: %d utterances exceed one launch (%d groups of 16)", B, max_groups); return QPN_EINVAL; }
-    ngroups = (B + c.NBper - 1) / c.NBper;
+    if (l.per_group < 1 || l.per_group > CBB_NU || l.groups * l.per_group < B) { qpn_set_error("internal: %d utterances do not fit %d batched groups of %d", B, l.groups, l.per_group); return QPN_EINVAL; }
+    c.NBper = l.per_group;
     const size_t xwords = (size_t)o * B + 16;
-    if (xwords > h->xch_cap) {
-        if (h->d_xch) (void)hipFree(h->d_xch);
-        h->d_xch = nullptr; h->xch_cap = 0;
-        if (hipMalloc(&h->d_xch, xwords * sizeof(unsigned long long)) != hipSuccess) { qpn_set_error("hipMalloc(%zu MiB) for the decode exchange buffers failed", xwords * 8 >> 20); return QPN_ENOMEM; }
-        h->xch_cap = xwords;
-    }
+    int rc = grow_xch(h, xwords); if (rc) return rc;
     c.xch = h->d_xch + 16; c.abort = (int*)h->d_xch;
     const size_t lds_bytes = (size_t)cbb_lds_floats(C, L) * sizeof(float);
     // first poll of an edge's gather: 8 / 4 x 128 clocks after the exchange waves reach it (QPN_COOPB_DELAY_G / _X / _T, dev).  Polls sent before anything can have been
@@ -652,8 +641,7 @@ int qpn_launch_decode_coopb(qpn_handle* h, DecodeParams& p, int B, hipStream_t s
         QPN_HIP(hipMemcpyAsync(h->d_status, &four, sizeof(int), hipMemcpyHostToDevice, stream));
     }
 #endif
-    hipLaunchKernelGGL(k_decode_coopb, dim3(c.G, ngroups), dim3(CBB_NT), lds_bytes, stream, p, c);
+    hipLaunchKernelGGL(k_decode_coopb, dim3(c.G, l.groups), dim3(CBB_NT), lds_bytes, stream, p, c);
     QPN_HIP(hipGetLastError());
-    h->cb_groups = ngroups; h->cb_per = c.NBper;
     return QPN_OK;
 }

@@ -650,23 +650,17 @@ int qpn_pipe_rows_resident(int n_cus) {
     return (n_cus * per_cu / 40) * 8;
 }
 
-// B utterances on `groups` five-role groups (B <= PIPE_MAX_NU * groups): as even as possible, the shortest rows share
-int qpn_launch_decode_pipe(qpn_handle* h, DecodeParams& p, int B, int groups, hipStream_t stream) {
+// l.rows utterances on l.groups five-role groups, as even as possible: the shortest rows share
+int qpn_launch_decode_pipe(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, hipStream_t stream) {
     const Geom& g = h->g;
+    const int B = l.rows, groups = l.groups, nu = l.per_group; p.utts += l.first;
     PipeParams pp; memset(&pp, 0, sizeof(pp));
-    for (int l = 0; l < 8; ++l) { pp.w_past_il[l] = h->w_past_il[l]; pp.f_resb[l] = (int)g.layers[l].resb; pp.f_skipb[l] = (int)g.layers[l].skipb; }
+    for (int k = 0; k < 8; ++k) { pp.w_past_il[k] = h->w_past_il[k]; pp.f_resb[k] = (int)g.layers[k].resb; pp.f_skipb[k] = (int)g.layers[k].skipb; }
     pp.f_p1b = (int)g.post1_b; pp.f_p2b = (int)g.post2_b; pp.nutt = B;
-    if (groups > B) groups = B;
-    if (groups < 1 || PIPE_MAX_NU * groups < B) { qpn_set_error("internal: %d utterances do not fit %d pipelined groups", B, groups); return QPN_EINVAL; }
+    if (groups < 1 || groups > B || nu < 1 || nu > PIPE_MAX_NU || nu * groups < B) { qpn_set_error("internal: %d utterances do not fit %d pipelined groups", B, groups); return QPN_EINVAL; }
     pp.groups = groups; pp.base = B / groups; pp.rem = B % groups;
-    const int nu = pp.base + (pp.rem ? 1 : 0);
     const size_t xwords = (size_t)PX_STRIDE * B + 16;
-    if (xwords > h->xch_cap) {
-        if (h->d_xch) (void)hipFree(h->d_xch);
-        h->d_xch = nullptr; h->xch_cap = 0;
-        if (hipMalloc(&h->d_xch, xwords * sizeof(unsigned long long)) != hipSuccess) { qpn_set_error("hipMalloc for the decode exchange buffers failed"); return QPN_ENOMEM; }
-        h->xch_cap = xwords;
-    }
+    int rc = grow_xch(h, xwords); if (rc) return rc;
     pp.xch = h->d_xch + 16; pp.abort = (int*)h->d_xch;
     QPN_HIP(hipMemsetAsync(h->d_xch, 0, xwords * sizeof(unsigned long long), stream));
 #ifdef QPN_TESTING

@@ -1,6 +1,7 @@
 // qpn_handle.h -- the library handle (shared by decode.hip and train_host.hip)
 #pragma once
 #include "qpn_common.h"
+#include "decode_plan.h"
 
 struct BiasDesc { int64_t auxb[2], convb[2], convPb[2]; int adaptive; int pad; };
 struct TrainState;
@@ -13,9 +14,7 @@ struct DecodeKnobs {
     int coop;              // QPN_DECODE_COOP=<G>: cooperative decode with up to G workgroups per utterance (0: only where one CU cannot hold the state)
     int coopb;             // QPN_DECODE_COOPB: smallest batch that takes the utterance-batched cooperative kernel (decode_coopb.hip) where it applies (default 1: always; 0 = never -- the per-utterance kernel decode_coop.hip)
     int coopb_delay[3];    // QPN_COOPB_DELAY_G / _X / _T (dev): first poll of the gate / block-output / post-net gathers of that kernel, x 128 clocks after the exchange waves reach it (8 / 4 / 0)
-    int coopb_per;         // QPN_DECODE_COOPB_PER (dev): utterances per group of that kernel (default: the batch spread over as many groups as fit the chip)
     int pipe;              // QPN_DECODE_PIPE: 0 = one-CU kernels, 1 / unset = the five-role pipelined kernel where it applies
-    bool hybrid;           // QPN_DECODE_HYBRID (dev): rows beyond the pipelined capacity on one-CU kernels beside the launch
     bool stamps;           // QPN_STAMPS (dev, -DQPN_ENABLE_STAMPS builds)
     bool test_pipe_gives_up;   // -DQPN_TESTING builds only (QPN_TEST_PIPE_GIVES_UP=1)
 };
@@ -45,9 +44,8 @@ struct qpn_handle {
     int n_cus;                       // hipDeviceAttributeMultiprocessorCount
     int pipe_rows;                   // five-role groups one pipelined launch can hold resident (5 workgroups each), a multiple of 8
     int pipe_nu;                     // utterances per group when the batch exceeds them (1..3)
-    // pinned staging of the utterance descriptors (enqueue does not synchronise) + the side stream of a hybrid launch
+    // pinned staging of the utterance descriptors (enqueue does not synchronise)
     UttDesc* h_utts_pinned; size_t h_utts_cap;
-    hipStream_t dec_side; hipEvent_t dec_fork, dec_join;
     // live output (qpn_decode_live / qpn_decode_poll): host-coherent pinned memory the running kernel writes and the host reads
     int live_every;                  // 0: not armed
     bool live_call;                  // the decode in flight was enqueued armed
@@ -58,13 +56,12 @@ struct qpn_handle {
     bool live_final;                 // the last decode was armed and has been finished: qpn_decode_final_counts reads its counts (until the next enqueue)
     std::vector<int64_t> live_seen;  // per-row high-water mark of what qpn_decode_poll has reported.  The counts restart only while qpn_decode_finish re-runs a launch that gave up,
                                      // and a handle is not thread-safe: only a caller that polls from a second thread under its own lock around finish could ever see the restart
-    struct DecodeCall {              // arguments of the decode in flight: qpn_decode_finish re-runs it on the one-CU kernel when a
+    struct DecodeCall {              // arguments of the decode in flight: qpn_decode_finish re-runs it with the plan of decode_plan_retry when a
         int B, n_x; int64_t F, Td;   // multi-workgroup launch gave up (peers not co-resident: masked / shared GPU)
         const int64_t* d_x; const float* d_h; const void* d_dfac; int d_is_f32;
         std::vector<int64_t> n_samples; int maxd, mode; uint64_t seed;
         const int64_t* d_teacher; int64_t* d_out; float* d_logits;
-        int multi_wg;                // 0: one-CU kernels only, 1: pipelined launch(es) involved, 2: cooperative (G > 1)
-        int coopG;
+        DecodePlanIn in; DecodePlan plan;   // what was planned from, and what the launches followed
     } call;
     std::string plan;                // human-readable launch plan of the last decode (qpn_last_decode_plan)
     bool single_cu_ok;               // the step state fits one CU's LDS (decode.hip kernels); otherwise decode_coop.hip only
@@ -73,7 +70,11 @@ struct qpn_handle {
     // batched cooperative kernel (decode_coopb.hip): workgroup w's A-operand fragments are the cb_per_w float4 from cb_base4 + w * cb_per_w of the packed weights;
     // cb_zc.. = float4 offsets of the tiles inside that block; or cb_ok = false
     bool cb_ok; int cb_zc[QPN_MAX_LAYERS], cb_zp[QPN_MAX_LAYERS], cb_rs[QPN_MAX_LAYERS], cb_p1, cb_p2; long long cb_base4; int cb_per_w;
-    int cb_groups, cb_per;                       // plan of the last batched launch
     bool decode_ok; std::string decode_err;   // geometries the decode kernels do not cover still train (and report why on decode calls)
     struct TrainState* train;        // lazily created by the training entry points (train_host.hip)
 };
+// the launchers of a plan's launches: rows [l.first, l.first + l.rows) of the descriptors behind p.utts, grouped as the plan says
+int qpn_launch_decode_pipe(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, hipStream_t stream);
+int qpn_launch_decode_coop(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, int G, hipStream_t stream);
+int qpn_launch_decode_coopb(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, hipStream_t stream);
+int grow_xch(qpn_handle* h, size_t words);      // the exchange buffer of those kernels holds >= words granules (grow only)

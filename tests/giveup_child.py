@@ -54,6 +54,7 @@ def pipe(cuda):
     bx, bh, bd, ns = synth.decode_batch(cfg, specs)
     outs = m.batch_fast_generate(torch.from_numpy(bx).to(cuda), torch.from_numpy(bh).to(cuda), list(ns), bd, mode="argmax")
     assert "timed out, retried" in m.last_decode_plan and "pipe rows=0" in m.last_decode_plan.split("retried:")[1], m.last_decode_plan
+    assert m.last_decode_plan.split("retried: ")[1] == util.plan_query(m, 5, attempt=1), m.last_decode_plan
     order = np.argsort(ns, kind="stable")
     maxd = int(np.ceil(np.nanmax(bd)))
     for k in range(5):
@@ -79,6 +80,7 @@ def coopb(cuda):
     outs = m.batch_fast_generate(torch.from_numpy(bx).to(cuda), torch.from_numpy(bh).to(cuda), list(ns), bd, mode="argmax")
     plan = m.last_decode_plan
     assert plan.startswith("coopb ") and "timed out, retried: coop G=" in plan, plan
+    assert plan.split("retried: ")[1] == util.plan_query(m, 3, attempt=1), plan
     o_outs = oracle.batch_fast_generate(cfg, flat, bx, bh, list(ns), bd)
     for a, b in zip(outs, o_outs):
         np.testing.assert_array_equal(a, b)

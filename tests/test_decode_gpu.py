@@ -816,6 +816,48 @@ def test_equal_length_rows_beyond_capacity_share_groups(cuda, oracle):
         np.testing.assert_array_equal(outs[k], ref[key])
 
 
+_PLAN_QUERY_CASES = {      # name: (geometry, environment, rows as (feature seed, frames, f0 factor), what the plan starts with)
+    "paper-B3": ("PAPER", {}, [(610 + b, 3 + b, [1.0, 0.5, 1.5][b]) for b in range(3)], "pipe rows=3 waves=1 x 3 (1 per group)"),
+    "paper-B49": ("PAPER", {}, [(620 + b % 7, 2, [1.0, 0.5, 1.5][b % 7 % 3]) for b in range(49)], "pipe rows=49 "),
+    "default-B2": ("DEFAULT", {}, [(631, 1, 1.0), (632, 2, 1.5)], "coopb G=64 groups="),
+    "default-B70": ("DEFAULT", {}, [(631, 1, 1.0) if b % 2 == 0 else (633, 1, 1.5) for b in range(70)], "coopb G=64 "),
+    "default-coop-B2": ("DEFAULT", {"QPN_DECODE_COOPB": "0"}, [(631, 1, 1.0), (632, 2, 1.5)], "coop G="),
+}
+_PLAN_QUERY_ORACLE = {}    # (geometry, row, maxd) -> the oracle's samples: a row that several cases share is computed once (the default geometry costs ~0.1 s a sample)
+
+
+@pytest.mark.parametrize("case", list(_PLAN_QUERY_CASES))
+def test_plan_query_matches_the_plan_that_ran(case, cuda, oracle, monkeypatch):
+    """qpn_decode_plan_query(h, 0, B, 0) is the text qpn_last_decode_plan shows after the call it describes -- on every kind of launch, one launch and two
+    (70 rows of the default geometry exceed the 64 one launch of a 256-CU device holds) -- and the call's samples are the oracle's.  The batches of 49 and 70
+    repeat a few utterances (the plan does not depend on what the rows hold, the oracle's cost does)."""
+    import torch
+    from qpnet_amd import config
+    cfgname, env, specs, plan_start = _PLAN_QUERY_CASES[case]
+    cfg = getattr(config, cfgname)
+    for k in ("QPN_DECODE_COOP", "QPN_DECODE_COOPB", "QPN_DECODE_PIPE", "QPN_PIPE_NU", "QPN_DECODE_GENERIC"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    flat = synth.make_weights(cfg, 29)
+    m = util.build_model(cfg, flat, cuda)
+    bx, bh, bd, ns = synth.decode_batch(cfg, specs)
+    B = len(specs)
+    outs = m.batch_fast_generate(torch.from_numpy(bx).to(cuda), torch.from_numpy(bh).to(cuda), list(ns), bd, mode="argmax")
+    assert m.last_decode_plan == util.plan_query(m, B) and m.last_decode_plan.startswith(plan_start), (m.last_decode_plan, util.plan_query(m, B))
+    if case == "default-B70" and torch.cuda.get_device_properties(cuda).multi_processor_count == 256:
+        assert m.last_decode_plan == "coopb G=64 launches=2 x 35 rows=70"
+    order = np.argsort(ns, kind="stable")
+    assert [len(o) for o in outs] == [ns[b] for b in order]
+    maxd = int(np.ceil(np.nanmax(bd)))
+    for k in range(B):
+        spec = specs[int(order[k])]
+        if (cfgname, spec, maxd) not in _PLAN_QUERY_ORACLE:
+            x, h, d, n = synth.decode_inputs(cfg, spec[1], spec[0], spec[2])
+            _PLAN_QUERY_ORACLE[(cfgname, spec, maxd)] = oracle.decode(cfg, flat, h, d, x, n, maxd=maxd)["samples"]
+        np.testing.assert_array_equal(outs[k], _PLAN_QUERY_ORACLE[(cfgname, spec, maxd)], err_msg="row %d (%s)" % (order[k], m.last_decode_plan))
+
+
 def test_pipelined_launch_that_gives_up_is_rerun_on_one_cu_kernels(cuda):
     """a multi-workgroup launch whose workgroups are not co-resident (CU-masked / shared GPU) times out and drains; the call
     is then re-run on the one-CU kernel instead of failing with QPN_ENODEV.  The give-up is injected by a hook that only the

@@ -15,6 +15,15 @@ def build_model(cfg, flat, device):
     return m.to(device).eval()
 
 
+def plan_query(m, B, attempt=0, n_cus=0):
+    """qpn_decode_plan_query on the model's handle: the plan text of a call of B utterances (attempt 1: of its re-run after a give-up)."""
+    import ctypes as C
+    from qpnet_amd import _lib
+    buf = C.create_string_buffer(256)
+    _lib.check(_lib.lib().qpn_decode_plan_query(m._handle, n_cus, B, attempt, buf, len(buf)))
+    return buf.value.decode()
+
+
 def run_giveup_child(which, env_name):
     """The fault-injection hooks exist only in the -DQPN_TESTING build of the library (qpnet_amd/libqpnet_hip_testing.so, built by
     __graft_entry__.build()): the scenario runs in a child process bound to that build (tests/giveup_child.py)."""
