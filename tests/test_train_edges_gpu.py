@@ -52,10 +52,11 @@ def _chunk(cfgname, B):
     return util.distinct_rows_batch(CFGS[cfgname][0], 500, DSEED[B], 2500, B)
 
 
-def _with_oracle(cfgname, x, h, t, d, b):
-    """the numpy oracle's forward, loss, dL/dlogits and gradient of one input, next to the input (arrays are shared between tests: never written)"""
+def _with_oracle(cfgname, x, h, t, d, b, cfg=None, flat=None):
+    """the numpy oracle's forward, loss, dL/dlogits and gradient of one input, next to the input (arrays are shared between tests: never written).
+    cfg, flat: another geometry / other weights than CFGS[cfgname]'s (tests/saturation_common.py)"""
     from oracle import train_oracle as TO
-    cfg, flat = CFGS[cfgname][0], _flat(cfgname)
+    cfg, flat = cfg or CFGS[cfgname][0], _flat(cfgname) if flat is None else flat
     BL = int(b[0])
     lg, caches = TO.forward(cfg, flat, x, h, d, b)
     loss, dl = TO.ce_loss(lg, t[:, -BL:])
@@ -125,9 +126,10 @@ def _compare(label, o, logits, loss, grad):
     return util.assert_grads_match_oracle(TO, o.cfg, o.flat, o.caches, o.dl, grad, a_scale=2e-5, a_rel=1e-4, og=o.og)
 
 
-def _autograd(label, o, cuda, read_back_maxd=True):
+def _autograd(label, o, cuda, read_back_maxd=True, compare=None, first=None):
     """logits, loss and loss.backward() of a fresh module (a fresh native handle: the launch knobs are read when it is created) against the oracle.
-    read_back_maxd: the exact ceil(max d) (N1 = recA * maxd + recF + BL); False: train.forward_maxd's shape-derived bound (another N1, same logits)"""
+    read_back_maxd: the exact ceil(max d) (N1 = recA * maxd + recF + BL); False: train.forward_maxd's shape-derived bound (another N1, same logits).
+    compare: another set of bounds than _compare's; first(label, o, logits, loss, grad): a check that runs before check_status"""
     import torch
     m = util.build_model(o.cfg, o.flat, cuda).train()
     m.read_back_maxd = read_back_maxd
@@ -135,12 +137,14 @@ def _autograd(label, o, cuda, read_back_maxd=True):
     logits = m(xt, ht, dt, bt)
     loss = torch.nn.CrossEntropyLoss()(logits.reshape(-1, o.cfg.n_quantize), tt[:, -o.BL:].reshape(-1))
     loss.backward()
-    m.check_status()                                            # the device-side gather-bound check must not have fired
     grad = torch.cat([p.grad.reshape(-1) for p in m.parameters()]).cpu().numpy()
-    _compare(label, o, logits.detach().cpu().numpy(), loss.item(), grad)
+    if first is not None:
+        first(label, o, logits.detach().cpu().numpy(), loss.item(), grad)
+    m.check_status()                                            # the device-side gather-bound check must not have fired
+    (compare or _compare)(label, o, logits.detach().cpu().numpy(), loss.item(), grad)
 
 
-def _fused(label, o, cuda, weights_too=False):
+def _fused(label, o, cuda, weights_too=False, compare=None, first=None):
     """FusedTrainer.step (qpn_train_step: the fused post-net tile, both stack queues, the library's Adam) against the oracle: loss, the step's gradient and --
     weights_too -- the parameters after the step against the oracle's Adam, as test_the_fused_step_bench_times_vs_oracle checks them"""
     from oracle import train_oracle as TO
@@ -149,8 +153,10 @@ def _fused(label, o, cuda, weights_too=False):
     tr = FusedTrainer(m, lr=1e-4)
     xt, ht, tt, dt = _to(cuda, o.x, o.h, o.t, o.d)
     loss = tr.step(xt, ht, tt, dt, o.b, want_loss=True, maxd=o.maxd)
+    if first is not None:
+        first(label, o, None, loss, tr.g[:o.flat.size].cpu().numpy())
     tr.check_status()
-    og = _compare(label, o, None, loss, tr.g[:o.flat.size].cpu().numpy())
+    og = (compare or _compare)(label, o, None, loss, tr.g[:o.flat.size].cpu().numpy())
     if weights_too:
         wo = o.flat.copy()
         TO.Adam(wo.size).step(wo, og)

@@ -84,7 +84,7 @@ def assert_grads_match_oracle(TO, cfg, flat, caches, dl, grad, a_scale=2e-5, a_r
             n = int(np.prod(shp))
             a, r = grad[o:o + n], og[o:o + n]
             e, bound = np.abs(a - r).max(), a_scale * scale + a_rel * np.abs(r).max()
-            if e > bound and (bad is None or e / bound > bad[1]):
+            if not e <= bound and (bad is None or not e / bound <= bad[1]):          # (not <=: a NaN in the gradient is a mismatch, not a pass)
                 bad = ("%s: err %.3e > bound %.3e" % (k, e, bound), e / bound)
         return bad
 
@@ -161,3 +161,40 @@ def assert_weights_after_adam(w, w_ref, lr, steps, tight=2e-6, frac=0.06, far=0.
         assert ds.max() <= sig_max, "an element with a significant gradient at every step differs by %.3e > %.1e" % (ds.max(), sig_max)
         if sig_frac > 0:
             assert (ds > tight).mean() <= sig_frac, "%.3f %% of the significant elements differ by more than %.0e" % (100 * (ds > tight).mean(), tight)
+
+
+FORCED_SIGMOID_BIAS = (-120.0, -104.0, -100.0, -95.0, -90.0, -88.0, -60.0, -17.0, 17.0, 90.0)
+FORCED_TANH_BIAS = (-90.0, -50.0, -44.0, -10.0, 10.0, 44.0, 50.0, 90.0)
+LOGIT_BIAS = ((0, 150.0), (37, -150.0), (-1, 149.0))          # class, bias: the dominant class, the suppressed one, the runner-up (Q - 1) one logit below
+
+
+def trained_like_weights(cfg, seed, gate_gain=1.0, post_gain=1.0, forced=False, logit_bias=False):
+    """synth.make_weights(cfg, seed) moved from a freshly initialised network's regime (every gate in its linear region, a uniform softmax) to a trained one's:
+    gate_gain multiplies every gate WEIGHT (the dilated convolutions and the auxiliary 1x1s of the sigmoid and tanh halves; the residual and skip 1x1s stay, so
+    the residual stream stays O(1) and float32 reassociation noise stays at its gain-1 level -- a uniform gain does not do that), post_gain multiplies
+    conv_post_2.weight (the logit spread), forced plants the landmark pre-activations as biases in the first and last fixed and the first and last adaptive
+    layer (sigma exactly 0, a float32 denormal, exp just below and above float32 overflow, sigma exactly 1, tanh exactly +-1), on channels spread over the
+    16-column tiles, and logit_bias makes class 0 dominant, class Q - 1 its runner-up one logit below and class 37 suppressed."""
+    flat = synth.make_weights(cfg, seed).copy()
+    offs, _ = cfg.param_offsets()
+    W = {k: flat[o:o + int(np.prod(s))].reshape(s) for k, (o, s) in offs.items()}
+    for k, w in W.items():
+        if k.endswith("weight") and ("sigmoid" in k or "tanh" in k):
+            w *= np.float32(gate_gain)
+    W["conv_post_2.weight"] *= np.float32(post_gain)
+    if forced:
+        C = cfg.n_resch
+        LF, LA = len(cfg.dilationsF), len(cfg.dilationsA)
+        layers = [("dilF_%s.%d.conv.bias", 0), ("dilF_%s.%d.conv.bias", LF - 1), ("dilA_%s.%d.conv%s.bias", 0), ("dilA_%s.%d.conv%s.bias", LA - 1)]
+        for j, (fmt, i) in enumerate(layers):
+            fixed = fmt.startswith("dilF")
+            bs = W[fmt % (("sigmoid", i) if fixed else ("sigmoid", i, "C"))]
+            bt = W[fmt % (("tanh", i) if fixed else ("tanh", i, "P"))]
+            for n, v in enumerate(FORCED_SIGMOID_BIAS):
+                bs[(7 * j + 3 * n) % C] = v
+            for n, v in enumerate(FORCED_TANH_BIAS):
+                bt[(5 * j + 1 + n) % C] = v
+    if logit_bias:
+        for q, v in LOGIT_BIAS:
+            W["conv_post_2.bias"][q] = v
+    return flat
