@@ -267,6 +267,20 @@ int qpn_train_grad_norm(qpn_handle* h, double* h_norm, int* h_valid, void* strea
  * qpn_train_loss_enqueue takes the norm out in the loss's copy).  *h_valid = 0 when that step did not clip or no loss was returned. */
 int qpn_train_grad_norm_lagged(qpn_handle* h, double* h_norm, int* h_valid);
 
+/* Averaged weights (an exponential moving average of the parameters, what WaveNet-family vocoders are decoded with) kept by the optimiser launch itself:
+ * the thread that has just computed element i's new weight w_new also does, in fp32,
+ *   d_ema[i] <- d_ema[i] + (w_new - d_ema[i]) * (1.0f - ema_decay)          (1.0f - ema_decay is formed once on the host, in fp32)
+ * -- no second pass, no extra launch, copy or host wait.  d_ema: n floats, caller-owned and caller-initialised (a copy of the weights is the usual seed);
+ * 0 < ema_decay < 1.  d_ema = NULL with ema_decay = 0: exactly qpn_adam_step_clip (qpn_adam_step, _ex and _clip are this call with NULL, 0, and launch the
+ * kernels they always did).  Anything else -- a NaN decay, a decay outside (0, 1), or only one of the two given -- returns QPN_EINVAL naming the argument, before the
+ * device or the handle's state is looked at.  Skip rule: a skipped update (the sticky status word set, a peer rank's flag in d_grad_denominator[1], or a
+ * non-finite clipping norm) leaves d_ema untouched together with the weights, both moments and the applied-update count: the average is of APPLIED states.
+ * Weights, moments, reports, norm word and applied-update count are bit for bit those of the call without d_ema; gradient-norm clipping and the
+ * data-parallel denominator compose with it unchanged.  Nothing is stored on the handle: the pointer is used by this call's launch only. */
+int qpn_adam_step_avg(qpn_handle* h, float* d_flat, const float* d_grad, float* d_m, float* d_v, int64_t n,
+                      int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                      const float* d_grad_denominator, float max_grad_norm, float* d_ema, float ema_decay, void* stream);
+
 /* Adam updates APPLIED on this handle so far, counted on the device: a k_adam launch that finds the sticky status word set -- or, behind a data-parallel
  * exchange, a peer rank's flag in the trailer (d_grad_denominator[1] > 0) -- applies nothing (every rank skips a step ANY rank flagged; the others report
  * "a peer rank flagged ..." with QPN_ERANGE).  Drains `stream`.  A caller that keeps the bias correction's step number on the host (the reference:
@@ -293,6 +307,15 @@ int qpn_train_step_clip(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t 
                         float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
                         int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                         int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm, void* stream);
+
+/* qpn_train_step_clip with qpn_adam_step_avg as its optimiser step: d_ema / ema_decay as there (NULL, 0: exactly qpn_train_step_clip, which is this call with
+ * NULL, 0); every loss_mode moves the average. */
+int qpn_train_step_avg(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
+                       const int64_t* d_x, const float* d_h, const float* d_dfac, const int64_t* d_targets, int64_t tgt_stride,
+                       float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
+                       int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm,
+                       float* d_ema, float ema_decay, void* stream);
 
 /* Per-launch-group device timings of the training calls issued between begin and end (HIP events on `stream`; used by bench.py for
  * the roofline).  h_ms[QPN_PG_*] receives milliseconds.  While a profile is being taken a step runs on ONE stream, and every heavy

@@ -1243,18 +1243,25 @@ __global__ __launch_bounds__(128) void k_aux_tail(AuxArgs p) {
 // rep: the step's reports, written straight into pinned host memory by the step's last kernel (a copy engine launch each -- 3-4 us on the stream -- otherwise):
 // the status word and, when asked for, the 64 partial sums of the loss (qpn_train_step)
 struct AdamReports { int* h_status; double* h_loss; const double* d_loss; };
-// the update of element i from its (scaled, clipped) gradient gi
-__device__ __forceinline__ void adam_update(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v, int64_t i, float gi,
-                                            float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
+// the update of element i from its (scaled, clipped) gradient gi; returns the new weight
+__device__ __forceinline__ float adam_update(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v, int64_t i, float gi,
+                                             float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
     if (wd != 0.f) gi += wd * w[i];
     const float mi = m[i] + (gi - m[i]) * (1.0f - b1);          // exp_avg.lerp_(grad, 1 - beta1)
     const float vi = v[i] * b2 + (1.0f - b2) * gi * gi;         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
     m[i] = mi; v[i] = vi;
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    w[i] = w[i] - (lr / bc1) * (mi / denom);
+    const float wn = w[i] - (lr / bc1) * (mi / denom);
+    w[i] = wn;
+    return wn;
 }
-__global__ void k_adam(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
-                       float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep) {
+// Averaged weights (qpn_adam_step_avg): the thread that has just computed element i's new weight moves the average towards it, e += (w_new - e) * omd with
+// omd = 1 - decay formed once on the host.  EMA is a compile-time switch: the <false> bodies are k_adam / k_adam_clip as they always were (e and omd are dead there),
+// the <true> ones differ by that one read-modify-write.  A skipped update returns before it: the average is of APPLIED states.
+template <bool EMA>
+__device__ __forceinline__ void adam_body(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                          float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, const AdamReports& rep,
+                                          float* __restrict__ e, float omd) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     // The device-side status word (sticky until the host reads it: a tap / target out of range, an abandoned stack launch) flags results that must not
     // reach the parameters: the update of a flagged step -- and of the steps enqueued behind it until the host has collected the word, two steps later
@@ -1275,7 +1282,17 @@ __global__ void k_adam(float* __restrict__ w, const float* __restrict__ g, float
     if (i >= n || skip) return;
     float gi = g[i];
     if (den) gi = gi / den[0];                                  // data-parallel: summed row-weighted gradients / summed row count
-    adam_update(w, m, v, i, gi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+    const float wn = adam_update(w, m, v, i, gi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+    if (EMA) e[i] = e[i] + (wn - e[i]) * omd;
+}
+__global__ void k_adam(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                       float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep) {
+    adam_body<false>(w, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, den, status, rep, nullptr, 0.f);
+}
+__global__ void k_adam_ema(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                           float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep,
+                           float* __restrict__ e, float omd) {
+    adam_body<true>(w, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, den, status, rep, e, omd);
 }
 
 // ---- gradient-norm clipping: torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type=2) in front of the Adam update (the reference-side loop's
@@ -1319,10 +1336,11 @@ __global__ __launch_bounds__(256) void k_grad_sumsq(const float* __restrict__ g,
 //   total = sqrt(sum g^2) (/ den[0]: the norm of the AVERAGED gradient);  coef = min(1, max_norm / (total + 1e-6)) in fp64, rounded once;  g <- (g / den[0]) * coef, then weight decay.
 // The gradient buffer is left as it is.  A non-finite total skips the update like a flagged step (bit 16 of the status word, set by block 0; the blocks decide by their own total,
 // not by the word).  Block 0 leaves the total in *d_norm (and the step's pinned report slot).
-__global__ __launch_bounds__(256) void k_adam_clip(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                   float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep,
-                                                   const double* __restrict__ part, int npart, float max_norm, double* __restrict__ d_norm, double* h_norm) {
-    __shared__ double red[4];
+template <bool EMA>
+__device__ __forceinline__ void adam_clip_body(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                               float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, const AdamReports& rep,
+                                               const double* __restrict__ part, int npart, float max_norm, double* __restrict__ d_norm, double* h_norm, double* red,
+                                               float* __restrict__ e, float omd) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     double total = sqrt(block_sum_f64((int)threadIdx.x < npart ? part[threadIdx.x] : 0.0, red));
     if (den) total = total / (double)den[0];
@@ -1349,7 +1367,21 @@ __global__ __launch_bounds__(256) void k_adam_clip(float* __restrict__ w, const 
     float gi = g[i];
     if (den) gi = gi / den[0];
     gi = __fmul_rn(gi, coef);                                   // (a product of its own: never fused into the weight-decay term, so coef == 1 leaves k_adam's bits)
-    adam_update(w, m, v, i, gi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+    const float wn = adam_update(w, m, v, i, gi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+    if (EMA) e[i] = e[i] + (wn - e[i]) * omd;
+}
+__global__ __launch_bounds__(256) void k_adam_clip(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                   float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep,
+                                                   const double* __restrict__ part, int npart, float max_norm, double* __restrict__ d_norm, double* h_norm) {
+    __shared__ double red[4];
+    adam_clip_body<false>(w, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, den, status, rep, part, npart, max_norm, d_norm, h_norm, red, nullptr, 0.f);
+}
+__global__ __launch_bounds__(256) void k_adam_clip_ema(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                       float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep,
+                                                       const double* __restrict__ part, int npart, float max_norm, double* __restrict__ d_norm, double* h_norm,
+                                                       float* __restrict__ e, float omd) {
+    __shared__ double red[4];
+    adam_clip_body<true>(w, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, den, status, rep, part, npart, max_norm, d_norm, h_norm, red, e, omd);
 }
 
 // Zero exactly what the backward reads without having written it.  Grad wrt X[j] has two parts:
@@ -1633,11 +1665,13 @@ int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k
     return qpn_launch_grad_tail(p, bw, &ag, stream, early_reduce, up_side);
 }
 
+// e != nullptr: the averaged weights move with the update (k_adam_ema, omd = 1 - decay); nullptr: the launch this always was
 int qpn_launch_adam(float* w, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps, float wd, const float* den, int* status,
-                    int* h_status, double* h_loss, const double* d_loss, hipStream_t stream) {
+                    int* h_status, double* h_loss, const double* d_loss, float* e, float omd, hipStream_t stream) {
     const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
     AdamReports rep; rep.h_status = status ? h_status : nullptr; rep.h_loss = d_loss ? h_loss : nullptr; rep.d_loss = d_loss;
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, g, m, v, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2), den, status, rep);
+    if (e) hipLaunchKernelGGL(k_adam_ema, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, g, m, v, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2), den, status, rep, e, omd);
+    else hipLaunchKernelGGL(k_adam, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, g, m, v, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2), den, status, rep);
     qpn_prof_mark(PG_ADAM, stream);
     QPN_HIP(hipGetLastError());
     return QPN_OK;
@@ -1645,14 +1679,16 @@ int qpn_launch_adam(float* w, const float* g, float* m, float* v, int64_t n, int
 
 // part: room for TR_GN_BLOCKS partial sums; d_norm: the handle's norm word
 int qpn_launch_adam_clip(float* w, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps, float wd, const float* den, int* status,
-                         int* h_status, double* h_loss, const double* d_loss, float max_norm, double* part, double* d_norm, double* h_norm, hipStream_t stream) {
+                         int* h_status, double* h_loss, const double* d_loss, float max_norm, double* part, double* d_norm, double* h_norm, float* e, float omd, hipStream_t stream) {
     const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
     AdamReports rep; rep.h_status = status ? h_status : nullptr; rep.h_loss = d_loss ? h_loss : nullptr; rep.d_loss = d_loss;
     const int64_t want = ((n >> 2) + 1 + 255) / 256;           // a thread per quad (and one for the short last quad) until the grid is full
     const int nb = want < TR_GN_BLOCKS ? (int)want : TR_GN_BLOCKS;
     hipLaunchKernelGGL(k_grad_sumsq, dim3(nb), dim3(256), 0, stream, g, n, part);
-    hipLaunchKernelGGL(k_adam_clip, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, g, m, v, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2), den, status, rep,
-                       (const double*)part, nb, max_norm, d_norm, h_norm);
+    if (e) hipLaunchKernelGGL(k_adam_clip_ema, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, g, m, v, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2), den, status, rep,
+                              (const double*)part, nb, max_norm, d_norm, h_norm, e, omd);
+    else hipLaunchKernelGGL(k_adam_clip, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, g, m, v, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2), den, status, rep,
+                            (const double*)part, nb, max_norm, d_norm, h_norm);
     qpn_prof_mark(PG_ADAM, stream);
     QPN_HIP(hipGetLastError());
     return QPN_OK;

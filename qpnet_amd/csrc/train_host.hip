@@ -14,9 +14,9 @@ int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k
 int qpn_launch_fwd_gemm(const TrainParams& p, const TrainGemm& w, hipStream_t stream);
 int qpn_launch_bwd_gemm(const TrainParams& p, const TrainBwd& bw, const TrainGemm& w, hipStream_t stream);
 int qpn_launch_adam(float* w, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps, float wd, const float* den, int* status,
-                    int* h_status, double* h_loss, const double* d_loss, hipStream_t stream);
+                    int* h_status, double* h_loss, const double* d_loss, float* e, float omd, hipStream_t stream);
 int qpn_launch_adam_clip(float* w, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps, float wd, const float* den, int* status,
-                         int* h_status, double* h_loss, const double* d_loss, float max_norm, double* part, double* d_norm, double* h_norm, hipStream_t stream);
+                         int* h_status, double* h_loss, const double* d_loss, float max_norm, double* part, double* d_norm, double* h_norm, float* e, float omd, hipStream_t stream);
 
 // a pinned loss slot: the 64 partial sums, then the gradient norm of the same step (gradient-norm clipping)
 #define LOSS_SLOT 72
@@ -829,18 +829,40 @@ extern "C" int qpn_adam_step_ex(qpn_handle* h, float* d_flat, const float* d_gra
     return qpn_adam_step_clip(h, d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, d_grad_denominator, 0.0f, stream_);
 }
 
-// max_grad_norm > 0: torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) in front of the update (k_grad_sumsq + k_adam_clip); otherwise exactly the launch qpn_adam_step_ex always made
 extern "C" int qpn_adam_step_clip(qpn_handle* h, float* d_flat, const float* d_grad, float* d_m, float* d_v, int64_t n,
                                   int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                                   const float* d_grad_denominator, float max_grad_norm, void* stream_) {
-    int rc = need_dev(h); if (rc) return rc;
+    return qpn_adam_step_avg(h, d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, d_grad_denominator, max_grad_norm, nullptr, 0.0f, stream_);
+}
+
+// the averaged-weights arguments of the _avg calls: both absent (NULL, 0: averaging off), or n caller-owned floats and 0 < decay < 1.  Checked before anything
+// about the device or the handle's state.  *omd = 1 - decay, formed once, in fp32: the factor every thread multiplies by
+static int check_ema_args(const float* d_ema, float ema_decay, float* omd) {
+    *omd = 0.0f;
+    if (ema_decay != ema_decay) { qpn_set_error("ema_decay is NaN"); return QPN_EINVAL; }
+    if (!d_ema && ema_decay == 0.0f) return QPN_OK;
+    if (!d_ema) { qpn_set_error("ema_decay is set but d_ema is NULL (averaging off is d_ema = NULL with ema_decay = 0)"); return QPN_EINVAL; }
+    if (!(ema_decay > 0.0f && ema_decay < 1.0f)) { qpn_set_error("ema_decay must lie in (0, 1) when d_ema is given (averaging off is d_ema = NULL with ema_decay = 0)"); return QPN_EINVAL; }
+    *omd = 1.0f - ema_decay;
+    return QPN_OK;
+}
+
+// max_grad_norm > 0: torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) in front of the update (k_grad_sumsq + k_adam_clip); otherwise exactly the launch qpn_adam_step_ex always made.
+// d_ema: the averaged weights move with every APPLIED update, inside the same launch (k_adam_ema / k_adam_clip_ema); NULL with ema_decay 0: the kernels above
+extern "C" int qpn_adam_step_avg(qpn_handle* h, float* d_flat, const float* d_grad, float* d_m, float* d_v, int64_t n,
+                                 int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                 const float* d_grad_denominator, float max_grad_norm, float* d_ema, float ema_decay, void* stream_) {
+    float omd;
+    int rc = check_ema_args(d_ema, ema_decay, &omd); if (rc) return rc;
+    rc = need_dev(h); if (rc) return rc;
     if (!d_flat || !d_grad || !d_m || !d_v || n < 1 || step < 1 || max_grad_norm != max_grad_norm) { qpn_set_error("bad adam_step arguments"); return QPN_EINVAL; }
     const bool clip = max_grad_norm > 0.f;
     if (clip) { rc = train_init(h); if (rc) return rc; }                 // (the partial sums and the norm word live in the training state)
     if (h->train) { h->train->last_stream = (hipStream_t)stream_; h->train->gnorm_last = clip; }
     if (clip) return qpn_launch_adam_clip(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, d_grad_denominator, h->train->d_status, nullptr, nullptr, nullptr,
-                                          max_grad_norm, h->train->d_gnorm, h->train->d_loss + 64, nullptr, (hipStream_t)stream_);
-    return qpn_launch_adam(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, d_grad_denominator, h->train ? h->train->d_status : nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream_);
+                                          max_grad_norm, h->train->d_gnorm, h->train->d_loss + 64, nullptr, d_ema, omd, (hipStream_t)stream_);
+    return qpn_launch_adam(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, d_grad_denominator, h->train ? h->train->d_status : nullptr, nullptr, nullptr, nullptr,
+                           d_ema, omd, (hipStream_t)stream_);
 }
 
 // The norm the latest Adam launch on this handle clipped by (drains `stream`); *h_valid = 0 when that launch did not clip, or there was none
@@ -880,25 +902,38 @@ extern "C" int qpn_train_step(qpn_handle* h, float* d_flat, int B, int64_t T, in
                                step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, 0.0f, nullptr, stream);
 }
 
-// max_grad_norm > 0: the step clips (qpn_adam_step_clip), and *h_grad_norm (may be NULL) receives the norm of the step whose loss *h_loss is -- mode 1: the previous
-// step's, out of the same pinned slot as its loss; mode 2: this step's; mode 0: none.  0 where that step did not clip.
 extern "C" int qpn_train_step_clip(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
                                    const int64_t* d_x, const float* d_h, const float* d_dfac, const int64_t* d_targets, int64_t tgt_stride,
                                    float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
                                    int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                                    int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm, void* stream) {
+    return qpn_train_step_avg(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
+                              step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, max_grad_norm, h_grad_norm, nullptr, 0.0f, stream);
+}
+
+// max_grad_norm > 0: the step clips (qpn_adam_step_clip), and *h_grad_norm (may be NULL) receives the norm of the step whose loss *h_loss is -- mode 1: the previous
+// step's, out of the same pinned slot as its loss; mode 2: this step's; mode 0: none.  0 where that step did not clip.
+// d_ema / ema_decay: qpn_adam_step_avg's (every loss mode moves the average: it is the Adam launch's own work).
+extern "C" int qpn_train_step_avg(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
+                                  const int64_t* d_x, const float* d_h, const float* d_dfac, const int64_t* d_targets, int64_t tgt_stride,
+                                  float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
+                                  int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                  int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm,
+                                  float* d_ema, float ema_decay, void* stream) {
     if (h_valid) *h_valid = 0;
     if (h_loss) *h_loss = 0.0;
     if (h_grad_norm) *h_grad_norm = 0.0;
+    float omd;
+    int rc = check_ema_args(d_ema, ema_decay, &omd); if (rc) return rc;
     if (loss_mode < 0 || loss_mode > 2 || (loss_mode && (!h_loss || !h_valid)) || max_grad_norm != max_grad_norm) { qpn_set_error("bad train_step arguments"); return QPN_EINVAL; }
     const bool clip = max_grad_norm > 0.f;
-    int rc = need_dev(h); if (rc) return rc;
+    rc = need_dev(h); if (rc) return rc;
     rc = qpn_train_status_collect_lagged(h); if (rc) return rc;          // the check of the step before the previous one (never waits for queued work)
     if (!d_targets || !d_dlogits) { qpn_set_error("qpn_train_forward_loss needs targets and a dlogits buffer"); return QPN_EINVAL; }
     rc = train_forward_impl(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_logits, d_targets, tgt_stride, d_dlogits, 0, stream, true); if (rc) return rc;
     rc = qpn_train_backward(h, d_dlogits, d_grad, stream); if (rc) return rc;
     if (loss_mode == 2) {
-        rc = qpn_adam_step_clip(h, d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, nullptr, max_grad_norm, stream); if (rc) return rc;
+        rc = qpn_adam_step_avg(h, d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, nullptr, max_grad_norm, d_ema, ema_decay, stream); if (rc) return rc;
         rc = qpn_train_loss(h, h_loss, stream); if (rc) return rc;
         *h_valid = 1;
         if (clip && h_grad_norm) { int nv = 0; rc = qpn_train_grad_norm(h, h_grad_norm, &nv, stream); if (rc) return rc; }      // (the stream has just been drained)
@@ -915,9 +950,9 @@ extern "C" int qpn_train_step_clip(qpn_handle* h, float* d_flat, int B, int64_t 
     double* const hl = loss_mode == 1 ? t->h_loss_pinned + LOSS_SLOT * lslot : nullptr;
     t->gnorm_last = clip;
     if (clip) rc = qpn_launch_adam_clip(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, nullptr, t->d_status, t->h_status_pinned + sslot,
-                                        hl, loss_mode == 1 ? t->d_loss : nullptr, max_grad_norm, t->d_gnorm, t->d_loss + 64, hl ? hl + 64 : nullptr, (hipStream_t)stream);
+                                        hl, loss_mode == 1 ? t->d_loss : nullptr, max_grad_norm, t->d_gnorm, t->d_loss + 64, hl ? hl + 64 : nullptr, d_ema, omd, (hipStream_t)stream);
     else rc = qpn_launch_adam(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, nullptr, t->d_status, t->h_status_pinned + sslot,
-                              hl, loss_mode == 1 ? t->d_loss : nullptr, (hipStream_t)stream);
+                              hl, loss_mode == 1 ? t->d_loss : nullptr, d_ema, omd, (hipStream_t)stream);
     if (rc) return rc;
     QPN_HIP(hipEventRecord(t->ev_status[sslot], (hipStream_t)stream));
     t->status_pending[sslot] = true; t->status_newest = sslot;

@@ -10,6 +10,7 @@ Same batching / chunking semantics as the reference task scripts, but over array
                        that overlap by RF, x[:-1] / x[1:] input-target shift)
   save_checkpoint / load_checkpoint <- src/bin/qpnet_train.py:338-353,481-499,557-563 ({"model","optimizer","iterations"})
 """
+import logging
 import math
 import os
 
@@ -297,29 +298,55 @@ def mu_law_transform(n_quantize=256):
     return lambda x: encode_mu_law(x, n_quantize)
 
 
+def _ema_entries(optimizer):
+    """{"ema": ..., "ema_decay": ...} of an optimizer object that keeps averaged weights (train.FusedTrainer / FlatAdam with ema_decay), else {}."""
+    get = getattr(optimizer, "ema_state_dict", None)
+    ema = get() if get is not None else None
+    return {"ema": ema, "ema_decay": float(optimizer.ema_decay)} if ema else {}
+
+
 def save_checkpoint(checkpoint_dir, model, optimizer, iterations):
-    """reference _save_checkpoint (qpnet_train.py:338-353)."""
+    """reference _save_checkpoint (qpnet_train.py:338-353).  An optimizer that keeps averaged weights adds "ema" (a second state dict, the model's keys) and
+    "ema_decay" at the top level; "model", "optimizer" and "iterations" are what they always were (the reference's loader reads ["model"] only)."""
     os.makedirs(checkpoint_dir, exist_ok=True)
     path = os.path.join(checkpoint_dir, "checkpoint-%d.pkl" % iterations)
-    torch.save({"model": model.state_dict(), "optimizer": optimizer.state_dict() if optimizer is not None else None,
-                "iterations": iterations}, path)
+    ck = {"model": model.state_dict(), "optimizer": optimizer.state_dict() if optimizer is not None else None,
+          "iterations": iterations}
+    ck.update(_ema_entries(optimizer))
+    torch.save(ck, path)
     return path
 
 
-def save_final(checkpoint_dir, model):
-    """reference final model file: {"model": state_dict} only (qpnet_train.py:557-563)."""
+def save_final(checkpoint_dir, model, optimizer=None):
+    """reference final model file: {"model": state_dict} only (qpnet_train.py:557-563); with the trainer given and averaging on, "ema" / "ema_decay" as in
+    save_checkpoint."""
     os.makedirs(checkpoint_dir, exist_ok=True)
     path = os.path.join(checkpoint_dir, "checkpoint-final.pkl")
-    torch.save({"model": model.state_dict()}, path)
+    ck = {"model": model.state_dict()}
+    ck.update(_ema_entries(optimizer))
+    torch.save(ck, path)
     return path
 
 
-def load_checkpoint(path, model, optimizer=None, map_location="cpu"):
-    """reference --resume (qpnet_train.py:481-499): restores model (+optimizer, iteration count)."""
+def load_checkpoint(path, model, optimizer=None, map_location="cpu", use_ema=False):
+    """reference --resume (qpnet_train.py:481-499): restores model (+optimizer, iteration count).
+    use_ema=True: the model receives the file's averaged weights ("ema") instead of "model" (decoding / validating with the average); a file without them is an error.
+    An optimizer that keeps averaged weights gets the file's back (load_ema); from a file without any it seeds them from the loaded weights."""
     ck = torch.load(path, map_location=map_location, weights_only=False)
-    model.load_state_dict(ck["model"])
+    if use_ema:
+        if not ck.get("ema"):
+            raise KeyError("%s holds no averaged weights (no 'ema' entry: it was not written by a run with --ema_decay)" % path)
+        model.load_state_dict(ck["ema"])
+    else:
+        model.load_state_dict(ck["model"])
     if optimizer is not None and ck.get("optimizer") is not None:
         optimizer.load_state_dict(ck["optimizer"])
+    if optimizer is not None and getattr(optimizer, "ema_decay", 0.0) and hasattr(optimizer, "load_ema"):
+        if ck.get("ema"):
+            optimizer.load_ema(ck["ema"])
+        else:
+            logging.warning("%s holds no averaged weights: the average starts from the loaded weights." % path)
+            optimizer.load_ema(None)
     return int(ck.get("iterations", 0))
 
 

@@ -258,6 +258,7 @@ def _train_args(update):
     p.add_argument("--lr", default=1e-4, type=float)
     p.add_argument("--weight_decay", default=0.0, type=float)
     p.add_argument("--max_grad_norm", default=0.0, type=float, help="clip the gradient norm inside the fused step (torch's clip_grad_norm_); 0: off")
+    p.add_argument("--ema_decay", default=0.0, type=float, help="keep an exponential moving average of the weights inside the fused step, written to the checkpoints as \"ema\" (decode / validate with --ema); 0: off")
     p.add_argument("--iters", default=3000 if update else 200000, type=int)
     p.add_argument("--checkpoint_interval", default=10000, type=int)
     p.add_argument("--intervals", default=100, type=int)
@@ -290,7 +291,7 @@ def run_train(argv=None, update=False):
     from .train import FusedTrainer
     from . import parallel
     model = _build_model(conf, dev).train()
-    trainer = FusedTrainer(model, lr=args.lr, weight_decay=args.weight_decay, world_size=world, max_grad_norm=args.max_grad_norm)
+    trainer = FusedTrainer(model, lr=args.lr, weight_decay=args.weight_decay, world_size=world, max_grad_norm=args.max_grad_norm, ema_decay=args.ema_decay)
     clipping = trainer.max_grad_norm > 0.0
     norm_max, n_clipped, n_seen = 0.0, 0, 0    # (clipping on) the interval's largest gradient norm, how many of its steps were clipped, how many losses it collected
 
@@ -371,9 +372,14 @@ def run_train(argv=None, update=False):
         drift = parallel.replica_drift(ensure_flat(model, dev))
         if drift != 0.0:
             raise RuntimeError("data-parallel replicas drifted apart: max |w_r - w_0| = %g" % drift)
+        if trainer.ema is not None:
+            # ... and the same kernel moved every rank's average by the same weights
+            drift = parallel.replica_drift(trainer.ema)
+            if drift != 0.0:
+                raise RuntimeError("data-parallel replicas' averaged weights drifted apart: max |e_r - e_0| = %g" % drift)
         logging.info("replicas identical on %d ranks." % world)
     if rank == 0:
-        loaders.save_final(args.expdir, model)
+        loaders.save_final(args.expdir, model, trainer)
         logging.info("final checkpoint created.")
         with open(flossyml, "w", encoding="utf-8") as yf:
             yaml.safe_dump([float(v) for v in loss_record], yf)
@@ -387,7 +393,7 @@ def run_update(argv=None):
 
 
 # ---------------------------------------------------------------- validate
-def run_validate(argv=None):
+def _validate_args():
     p = argparse.ArgumentParser()
     for name in ("waveforms", "feats", "stats", "resultdir", "config", "checkpoint"):
         p.add_argument("--" + name, required=True, type=str)
@@ -398,7 +404,12 @@ def run_validate(argv=None):
     p.add_argument("--seed", default=1, type=int)
     p.add_argument("--n_gpus", default=1, type=int)
     p.add_argument("--verbose", default=1, type=int)
-    args = p.parse_args(sys.argv[1:] if argv is None else argv)
+    p.add_argument("--ema", action="store_true", help="score the checkpoint's averaged weights (a run with --ema_decay wrote them)")
+    return p
+
+
+def run_validate(argv=None):
+    args = _validate_args().parse_args(sys.argv[1:] if argv is None else argv)
     _setup_logging(args.verbose)
     # validation is one forward-only pass over the list (reference qpnet_validate.py:409-437): a single process.  --n_gpus is
     # accepted for command-line compatibility; under a multi-rank launcher rank 0 evaluates and writes the yml, the other
@@ -416,8 +427,8 @@ def run_validate(argv=None):
     conf = loaders.load_model_conf(args.config)
     from .train import FusedTrainer
     model = _build_model(conf, dev).eval()
-    loaders.load_checkpoint(args.checkpoint, model, None)
-    logging.info("load %s." % args.checkpoint)
+    loaders.load_checkpoint(args.checkpoint, model, None, use_ema=args.ema)
+    logging.info("load %s%s." % (args.checkpoint, " (averaged weights)" if args.ema else ""))
     trainer = FusedTrainer(model)
     flossyml = os.path.join(args.resultdir, "validation_result.yml")
     results = {}
@@ -437,8 +448,7 @@ def run_validate(argv=None):
 
 
 # ---------------------------------------------------------------- decode
-def run_decode(argv=None):
-    argv = sys.argv[1:] if argv is None else argv
+def _decode_args():
     p = argparse.ArgumentParser()
     for name in ("feats", "stats", "config", "outdir", "checkpoint"):
         p.add_argument("--" + name, required=True, type=str)
@@ -452,7 +462,13 @@ def run_decode(argv=None):
     p.add_argument("--f0_factor", default=1.0, type=float)
     p.add_argument("--f0_dim_index", default=1, type=int)
     p.add_argument("--mode", default="sampling", choices=["sampling", "argmax"], help="the reference script always samples")
-    args = p.parse_args(argv)
+    p.add_argument("--ema", action="store_true", help="decode with the checkpoint's averaged weights (a run with --ema_decay wrote them)")
+    return p
+
+
+def run_decode(argv=None):
+    argv = sys.argv[1:] if argv is None else argv
+    args = _decode_args().parse_args(argv)
     rc = launch_ranks(args.n_gpus, "qpnet_amd.run_decode", argv)
     if rc is not None:
         return rc
@@ -472,7 +488,7 @@ def run_decode(argv=None):
     scaler = loaders.read_scaler_stats(args.stats, conf.feature_type)
     with torch.no_grad():
         model = _build_model(conf, dev).eval()
-        loaders.load_checkpoint(args.checkpoint, model, None)
+        loaders.load_checkpoint(args.checkpoint, model, None, use_ema=args.ema)
         feats = [loaders.read_features(f, conf.feature_type) for f in mine]
         ids = [os.path.basename(f).replace(ext, "") for f in mine]
         from .qpnet import encode_mu_law

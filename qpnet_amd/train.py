@@ -10,6 +10,7 @@ number from the library; a backward whose forward is no longer the current one r
 using the wrong activations."""
 import os
 import weakref
+import collections
 import ctypes as C
 
 import numpy as np
@@ -488,6 +489,48 @@ def _check_max_grad_norm(v):
     return v
 
 
+def _check_ema_decay(v):
+    """ema_decay as the C ABI takes it: None / 0 -> 0.0 (no averaged weights); otherwise it must lie in (0, 1) as an fp32 number too (the kernel's factor is
+    float32(1) - float32(decay))."""
+    if v is None:
+        return 0.0
+    v = float(v)
+    if v == 0.0:
+        return 0.0
+    if not (0.0 < v < 1.0) or not (0.0 < float(np.float32(v)) < 1.0):
+        raise ValueError("ema_decay must lie in (0, 1) (None or 0: no averaged weights), got %r" % (v,))
+    return v
+
+
+# ---------------------------------------------------------------- averaged weights (EMA) shared by FusedTrainer and FlatAdam
+def _ema_home(ema, flat):
+    """the averaged weights next to `flat`: a copy of the weights the first time (or after load_ema(None)), re-homed like the moments when the device changed."""
+    if ema is None or ema.numel() != flat.numel():
+        return flat.detach().clone()
+    if ema.device != flat.device:
+        return ema.to(flat.device)
+    return ema
+
+
+def _ema_to_state_dict(model, ema):
+    """the flat average under the model's state_dict() keys, shapes and order (copies: the buffer goes on moving)."""
+    if ema is None:                                  # averaging on, no step yet: the average of nothing but the seed is the weights
+        return collections.OrderedDict((k, v.detach().clone()) for k, v in model.state_dict().items())
+    return collections.OrderedDict(zip(model.state_dict().keys(), (t.clone() for t in _split_like(model, ema))))
+
+
+def _ema_from_state_dict(model, sd):
+    """inverse of _ema_to_state_dict: one flat fp32 tensor on the model's device (a CPU model: moved at the first step, as the moments are)."""
+    ref = model.state_dict()
+    if list(sd.keys()) != list(ref.keys()):
+        raise ValueError("averaged weights: the keys differ from the model's state_dict()")
+    for k, v in ref.items():
+        if tuple(sd[k].shape) != tuple(v.shape):
+            raise ValueError("averaged weights: %s has shape %s, the model's is %s" % (k, tuple(sd[k].shape), tuple(v.shape)))
+    dev = next(iter(ref.values())).device
+    return torch.cat([sd[k].detach().reshape(-1).to(dev, torch.float32) for k in ref]).contiguous()
+
+
 # ---------------------------------------------------------------- Adam state in torch.optim.Adam's state_dict layout
 _ADAM_GROUP_DEFAULTS = dict(amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None)
 
@@ -541,11 +584,15 @@ class FlatAdam(torch.optim.Optimizer):
     out) no gather happens.  state_dict()/load_state_dict() use torch.optim.Adam's own layout, so checkpoints written by
     the reference trainer resume here and vice versa.
     max_grad_norm=c: `torch.nn.utils.clip_grad_norm_(model.parameters(), c)` in front of every step, inside the step's launches (qpn_adam_step_clip); p.grad is
-    left unscaled.  A step whose gradient norm is not finite applies nothing and raises QpnError(-4) at the next status collection."""
+    left unscaled.  A step whose gradient norm is not finite applies nothing and raises QpnError(-4) at the next status collection.
+    ema_decay=d (0 < d < 1): `.ema`, a flat fp32 average of the weights seeded with them, moves inside the same launch with every APPLIED update
+    (qpn_adam_step_avg: e += (w_new - e) * (1 - d)); ema_state_dict() / load_ema() as FusedTrainer's."""
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, ema_decay=None):
         self.model = model
         self.max_grad_norm = _check_max_grad_norm(max_grad_norm)      # (a setting of this object, not of the checkpoint: state_dict() keeps torch.optim.Adam's layout)
+        self.ema_decay = _check_ema_decay(ema_decay)
+        self.ema = None
         super().__init__(list(model.parameters()), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._m = self._v = None
         self._steps = 0
@@ -592,15 +639,31 @@ class FlatAdam(torch.optim.Optimizer):
         self._steps += 1
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
-            _lib.check(L.qpn_adam_step_clip(hd, flat.data_ptr(), g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), flat.numel(),
-                                            self._steps, grp["lr"], grp["betas"][0], grp["betas"][1], grp["eps"], grp["weight_decay"], None,
-                                            self.max_grad_norm, stream))
+            if self.ema_decay > 0.0:
+                self.ema = _ema_home(self.ema, flat)
+                _lib.check(L.qpn_adam_step_avg(hd, flat.data_ptr(), g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), flat.numel(),
+                                               self._steps, grp["lr"], grp["betas"][0], grp["betas"][1], grp["eps"], grp["weight_decay"], None,
+                                               self.max_grad_norm, self.ema.data_ptr(), self.ema_decay, stream))
+            else:
+                _lib.check(L.qpn_adam_step_clip(hd, flat.data_ptr(), g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), flat.numel(),
+                                                self._steps, grp["lr"], grp["betas"][0], grp["betas"][1], grp["eps"], grp["weight_decay"], None,
+                                                self.max_grad_norm, stream))
             if clipping:
                 _lib.check(L.qpn_train_status_enqueue(hd, stream))      # (a non-finite norm is this launch's own finding: the next collection reports it)
         return loss
 
     def _hyper(self):
         return {k: self.param_groups[0][k] for k in ("lr", "betas", "eps", "weight_decay")}
+
+    def ema_state_dict(self):
+        """the averaged weights under the model's state_dict() keys ({} with averaging off); not part of state_dict(), which keeps torch.optim.Adam's layout."""
+        return _ema_to_state_dict(self.model, self.ema) if self.ema_decay > 0.0 else {}
+
+    def load_ema(self, sd):
+        """restore the average from an ema_state_dict(); None: seed it from the current weights at the next step."""
+        if self.ema_decay <= 0.0:
+            raise RuntimeError("load_ema: this optimizer keeps no averaged weights (ema_decay is off)")
+        self.ema = None if sd is None else _ema_from_state_dict(self.model, sd)
 
     def state_dict(self):
         return adam_state_to_torch(self.model, self._m, self._v, self._steps, self._hyper())
@@ -629,16 +692,22 @@ class FusedTrainer:
     max_grad_norm=c (None / 0: off): the step clips like `torch.nn.utils.clip_grad_norm_(model.parameters(), c)` between backward and Adam.step -- data-parallel: the
     norm of the exchanged, averaged gradient -- inside the library's optimiser step; `last_grad_norm` is the norm (before clipping) that belongs to the loss
     step() / flush_loss() last returned (None when that was None, or clipping is off).  A non-finite norm skips the update and raises like the other status errors.
-    A trainer setting: it is not part of state_dict()."""
+    A trainer setting: it is not part of state_dict().
+    ema_decay=d (None / 0: off; 0 < d < 1): `ema`, a flat fp32 exponential moving average of the weights, seeded with a copy of them at the first step, moves inside
+    the Adam launch itself with every APPLIED update: e += (w_new - e) * (1 - d) -- a step the device skipped (a flagged chunk, a peer's flag, a non-finite norm)
+    leaves it alone.  No launch, copy or wait is added to a step.  ema_state_dict() / load_ema() carry it through checkpoints (loaders.save_checkpoint writes it as
+    "ema" next to "model"), forward_loss(weights="ema") scores it on held-out data; it is not part of state_dict() either."""
 
     # The device-side status word (bad taps / targets; the reference asserts in-line, qpnet.py:294, qpnet_train.py:525) is copied to pinned
     # memory behind every step; a step starts by looking at the copy made TWO steps earlier (the previous step is still queued on the
     # device while the host enqueues this one: waiting for it would idle the GPU).  A bad chunk is raised two steps late at most, not up to 99
     # as when the word was read every 100 steps.  check_status() collects everything outstanding.
 
-    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, process_group=None, world_size=1, max_grad_norm=None):
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, process_group=None, world_size=1, max_grad_norm=None, ema_decay=None):
         self.model = model
         self.max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        self.ema_decay = _check_ema_decay(ema_decay)
+        self.ema = None               # averaging on: the flat average, from the first step (or load_ema) on
         self.last_grad_norm = None
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.step_count = 0
@@ -658,6 +727,8 @@ class FusedTrainer:
                 self.m.copy_(m0); self.v.copy_(v0)
         if self.g is None or self.g.device != flat.device or self.g.numel() != flat.numel() + 4:
             self.g = torch.empty(flat.numel() + 4, dtype=torch.float32, device=flat.device)   # gradient + trailer (row count)
+        if self.ema_decay > 0.0:
+            self.ema = _ema_home(self.ema, flat)
 
     @staticmethod
     def _norm(t, dtype, dev):
@@ -704,13 +775,22 @@ class FusedTrainer:
             mode = 1 if want_loss == "lagged" else (2 if want_loss else 0)
             clip = self.max_grad_norm
             with torch.cuda.device(dev):
-                if clip > 0.0:
+                if clip > 0.0 or self.ema is not None:
                     norm = C.c_double(0.0)
-                    rc = L.qpn_train_step_clip(hd, flat.data_ptr(), B, T, h.shape[2], d.shape[1], BL, maxd, x.data_ptr(), h.data_ptr(), d.data_ptr(),
-                                               t.data_ptr(), t.shape[1], self._logits.data_ptr(), self._dlogits.data_ptr(), self.g.data_ptr(),
-                                               self.m.data_ptr(), self.v.data_ptr(), flat.numel(), self.step_count, self.lr, self.betas[0], self.betas[1],
-                                               self.eps, self.wd, mode, C.byref(loss), C.byref(valid), clip, C.byref(norm), stream)
-                    if not valid.value:
+                    if self.ema is not None:
+                        rc = L.qpn_train_step_avg(hd, flat.data_ptr(), B, T, h.shape[2], d.shape[1], BL, maxd, x.data_ptr(), h.data_ptr(), d.data_ptr(),
+                                                  t.data_ptr(), t.shape[1], self._logits.data_ptr(), self._dlogits.data_ptr(), self.g.data_ptr(),
+                                                  self.m.data_ptr(), self.v.data_ptr(), flat.numel(), self.step_count, self.lr, self.betas[0], self.betas[1],
+                                                  self.eps, self.wd, mode, C.byref(loss), C.byref(valid), clip, C.byref(norm),
+                                                  self.ema.data_ptr(), self.ema_decay, stream)
+                    else:
+                        rc = L.qpn_train_step_clip(hd, flat.data_ptr(), B, T, h.shape[2], d.shape[1], BL, maxd, x.data_ptr(), h.data_ptr(), d.data_ptr(),
+                                                   t.data_ptr(), t.shape[1], self._logits.data_ptr(), self._dlogits.data_ptr(), self.g.data_ptr(),
+                                                   self.m.data_ptr(), self.v.data_ptr(), flat.numel(), self.step_count, self.lr, self.betas[0], self.betas[1],
+                                                   self.eps, self.wd, mode, C.byref(loss), C.byref(valid), clip, C.byref(norm), stream)
+                    if clip <= 0.0:
+                        pass                                         # (averaging without clipping: there is no norm)
+                    elif not valid.value:
                         self.last_grad_norm = None
                     elif mode == 1:
                         self.last_grad_norm = self._collected_norm(L, hd)      # (None where the step that loss belongs to ran unclipped: the C call hands back 0.0 there)
@@ -782,9 +862,14 @@ class FusedTrainer:
                 _lib.check(L.qpn_train_backward(hd, self._dlogits.data_ptr(), self.g.data_ptr(), stream))
             self.step_count += 1
             clip = self.max_grad_norm
-            _lib.check(L.qpn_adam_step_clip(hd, flat.data_ptr(), self.g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), flat.numel(),
-                                            self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                                            self.g.data_ptr() + 4 * flat.numel() if multi else None, clip, stream))
+            den = self.g.data_ptr() + 4 * flat.numel() if multi else None
+            if self.ema is not None:
+                _lib.check(L.qpn_adam_step_avg(hd, flat.data_ptr(), self.g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), flat.numel(),
+                                               self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                                               den, clip, self.ema.data_ptr(), self.ema_decay, stream))
+            else:
+                _lib.check(L.qpn_adam_step_clip(hd, flat.data_ptr(), self.g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), flat.numel(),
+                                                self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, den, clip, stream))
             if want_loss == "lagged":
                 # this step's loss is copied out behind its kernels; what comes back is the PREVIOUS step's (None at the first step, or right after
                 # flush_loss()): the stream is never drained, and a caller that sums losses over an interval and calls flush_loss() at its end has the same sum
@@ -845,12 +930,20 @@ class FusedTrainer:
                 self._rebase_step_count(L, hd, flat.device, torch.cuda.current_stream(flat.device).cuda_stream, 0)
             raise
 
-    def forward_loss(self, x, h, t, d, blength, maxd=None):
-        """forward + mean CE only (validation, reference qpnet_validate.py:409-430)."""
+    def forward_loss(self, x, h, t, d, blength, maxd=None, weights="model"):
+        """forward + mean CE only (validation, reference qpnet_validate.py:409-430).  weights="ema": of the averaged weights (the forward reads the flat vector
+        it is handed at call time; the live weights are not touched); raises when averaging is off."""
+        if weights not in ("model", "ema"):
+            raise ValueError('forward_loss: weights must be "model" or "ema", got %r' % (weights,))
+        if weights == "ema" and self.ema_decay <= 0.0:
+            raise RuntimeError('forward_loss(weights="ema"): this trainer keeps no averaged weights (ema_decay is off)')
         model = self.model
         dev = x.device
         L, hd = model._native(dev)
         flat = ensure_flat(model, dev)
+        if weights == "ema":
+            self.ema = _ema_home(self.ema, flat)
+            flat = self.ema
         join_staged(x, dev, h, t, d)                 # (run_validate feeds staged batches: the copy stream must be joined before anything reads them)
         x = self._norm(x, torch.int64, dev); t = self._norm(t, torch.int64, dev)
         h = self._norm(h, torch.float32, dev); d = self._norm(d, torch.float32, dev)
@@ -875,6 +968,17 @@ class FusedTrainer:
 
     def state_dict(self):
         return adam_state_to_torch(self.model, self.m, self.v, self.step_count, self._hyper())
+
+    def ema_state_dict(self):
+        """the averaged weights under the model's state_dict() keys, shapes and order ({} with averaging off): load it into a model to decode with the average."""
+        return _ema_to_state_dict(self.model, self.ema) if self.ema_decay > 0.0 else {}
+
+    def load_ema(self, sd):
+        """restore the average from an ema_state_dict(); None: seed it from the current weights at the next step.  Works on a CPU model (a checkpoint is loaded
+        before the model has seen the device): the tensor moves at the first step, as the moments do."""
+        if self.ema_decay <= 0.0:
+            raise RuntimeError("load_ema: this trainer keeps no averaged weights (ema_decay is off)")
+        self.ema = None if sd is None else _ema_from_state_dict(self.model, sd)
 
     def load_state_dict(self, sd):
         params = list(self.model.parameters())
