@@ -317,6 +317,32 @@ int qpn_train_step_avg(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F
                        int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm,
                        float* d_ema, float ema_decay, void* stream);
 
+/* Gradient accumulation (no reference counterpart: the reference trainer applies one Adam update per chunk): the gradient of SEVERAL chunks behind one update, as the
+ * sum a data-parallel step takes over ranks, taken over time.  d_acc[i] = first ? d_grad[i] : d_acc[i] + d_grad[i] for i < cnt -- callers pass n_params + 4: the
+ * row-weighted gradient n_r * g_r that qpn_train_backward_ex(grad_scale = n_r, append_scale = 1) left, and its trailer {n_r, flagged_r, 0, 0}.  Plain fp32, one add per
+ * element, no atomics: the same bits from run to run and on every rank.  first != 0 overwrites without reading d_acc (it needs no clearing; NaNs in it do not survive).
+ * qpn_adam_step_avg(d_grad = d_acc, d_grad_denominator = d_acc + n_params) then applies the update of the mean over all the window's rows, and skips it when any of its
+ * chunks was flagged.  Errors (QPN_EINVAL naming the argument, before the device is looked at): a NULL pointer, cnt < 1, d_acc == d_grad. */
+int qpn_grad_accumulate(qpn_handle* h, float* d_acc, const float* d_grad, int64_t cnt, int first, void* stream);
+
+/* qpn_train_step_avg as micro-step `micro` (0-based) of a window of `micro_count` chunks, still ONE call per chunk.  micro_count > 1: every micro-step enqueues
+ * qpn_train_forward_loss (QPN_FWD_BACKWARD_FOLLOWS), qpn_train_backward_ex(grad_scale = B * BL, append_scale = 1) into d_grad and qpn_grad_accumulate(d_acc, d_grad, n + 4,
+ * first = (micro == 0)); only micro == micro_count - 1 also enqueues qpn_adam_step_avg with d_grad = d_acc, d_grad_denominator = d_acc + n and the given max_grad_norm,
+ * d_ema, ema_decay.  d_grad (n + 4 floats) holds this micro-step's row-weighted gradient and trailer afterwards; d_acc: n + 4 caller-owned floats, not d_grad.
+ * `step` is the 1-based UPDATE number, the same for every micro-step of a window.  loss_mode, *h_loss, *h_valid as in qpn_train_step: every micro-step has a loss of its
+ * own.  *h_grad_norm comes only with the loss of a window-closing micro-step (the others ran no norm launch: qpn_train_grad_norm_lagged's "that step did not clip" rule).
+ * A micro-step in front of the closing one has no Adam launch; its last kernel, the accumulate, carries the status word and the loss partials to pinned memory instead.
+ * Skip rule: a flagged micro-step leaves its flag in the trailer, the flags are summed into d_acc[n + 1], and the closing Adam launch skips through its own sticky
+ * status word or that sum: weights, both moments, the average, the norm word's meaning and the applied-update count stay as the last clean update left them, and the
+ * status report is QPN_ERANGE.  d_acc = NULL, micro = 0, micro_count = 1: exactly qpn_train_step_avg.  Errors (QPN_EINVAL naming the argument, before the averaged-weights
+ * checks, the device and the handle's state): micro_count < 1, micro outside [0, micro_count), d_acc == NULL with micro_count > 1, d_acc == d_grad. */
+int qpn_train_step_acc(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
+                       const int64_t* d_x, const float* d_h, const float* d_dfac, const int64_t* d_targets, int64_t tgt_stride,
+                       float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
+                       int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm,
+                       float* d_ema, float ema_decay, float* d_acc, int micro, int micro_count, void* stream);
+
 /* Per-launch-group device timings of the training calls issued between begin and end (HIP events on `stream`; used by bench.py for
  * the roofline).  h_ms[QPN_PG_*] receives milliseconds.  While a profile is being taken a step runs on ONE stream, and every heavy
  * kernel is a group of its own: LAYER_FWD / LAYER_BWD = the residual stack (one work-queue launch each at n_resch 64), WGRAD = the

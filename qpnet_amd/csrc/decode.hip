@@ -655,7 +655,7 @@ void qpn_set_error(const char* fmt, ...) {
     va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof(g_err), fmt, ap); va_end(ap);
 }
 extern "C" const char* qpn_last_error(void) { return g_err; }
-extern "C" int qpn_version(void) { return 1002; }
+extern "C" int qpn_version(void) { return 1003; }
 
 int qpn_build_geom(const qpn_config* c, Geom* g) {
     memset(g, 0, sizeof(*g));

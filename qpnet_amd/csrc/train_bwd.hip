@@ -1384,6 +1384,51 @@ __global__ __launch_bounds__(256) void k_adam_clip_ema(float* __restrict__ w, co
     adam_clip_body<true>(w, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, den, status, rep, part, npart, max_norm, d_norm, h_norm, red, e, omd);
 }
 
+// ---- gradient accumulation (qpn_grad_accumulate / qpn_train_step_acc): acc <- first ? g : acc + g over cnt floats -- the row-weighted gradient of one chunk and its
+// {row count, flags, 0, 0} trailer added to the window's.  One fp32 add per element and nothing else: the result is a function of the two inputs alone (numpy's
+// float32 acc + g), the same bits from run to run and on every rank.  first OVERWRITES -- acc is not read, so whatever an earlier (abandoned) window or the allocator
+// left there, NaNs included, is gone without a memset in the step.  Access as k_grad_sumsq's: quad q belongs to thread q % (threads of the grid), one float4 per
+// buffer when BOTH bases are 16-byte aligned, four floats otherwise (the caller's g may start one float into an allocation); the short last quad one by one.
+// rep: a micro-step that does not close its window has no Adam launch behind it, and this is its last kernel: block 0 carries the step's reports (the status word,
+// the loss partials) into pinned memory as k_adam's block 0 does -- it reports only: no flag is raised, nothing is counted
+__global__ __launch_bounds__(256) void k_grad_accum(float* __restrict__ acc, const float* __restrict__ g, int64_t cnt, int first, const int* __restrict__ status, AdamReports rep) {
+    if (blockIdx.x == 0) {
+        if (rep.h_loss && threadIdx.x < 64) rep.h_loss[threadIdx.x] = rep.d_loss[threadIdx.x];
+        if (threadIdx.x == 0 && status && rep.h_status) *rep.h_status = *status;
+    }
+    const int64_t nq = cnt >> 2, nthr = (int64_t)gridDim.x * 256, t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (((reinterpret_cast<uintptr_t>(acc) | reinterpret_cast<uintptr_t>(g)) & 15) == 0) {
+        float4* a4 = reinterpret_cast<float4*>(acc);
+        const float4* g4 = reinterpret_cast<const float4*>(g);
+        if (first) {
+#pragma unroll 4
+            for (int64_t q = t; q < nq; q += nthr) a4[q] = g4[q];
+        } else {
+#pragma unroll 4
+            for (int64_t q = t; q < nq; q += nthr) {
+                const float4 x = g4[q];
+                float4 a = a4[q];
+                a.x += x.x; a.y += x.y; a.z += x.z; a.w += x.w;
+                a4[q] = a;
+            }
+        }
+    } else if (first) {
+#pragma unroll 4
+        for (int64_t q = t; q < nq; q += nthr) {
+            const float x0 = g[4 * q], x1 = g[4 * q + 1], x2 = g[4 * q + 2], x3 = g[4 * q + 3];
+            acc[4 * q] = x0; acc[4 * q + 1] = x1; acc[4 * q + 2] = x2; acc[4 * q + 3] = x3;
+        }
+    } else {
+#pragma unroll 4
+        for (int64_t q = t; q < nq; q += nthr) {
+            const float x0 = g[4 * q], x1 = g[4 * q + 1], x2 = g[4 * q + 2], x3 = g[4 * q + 3];
+            const float a0 = acc[4 * q], a1 = acc[4 * q + 1], a2 = acc[4 * q + 2], a3 = acc[4 * q + 3];
+            acc[4 * q] = a0 + x0; acc[4 * q + 1] = a1 + x1; acc[4 * q + 2] = a2 + x2; acc[4 * q + 3] = a3 + x3;
+        }
+    }
+    if (t == nq % nthr) for (int64_t i = nq * 4; i < cnt; ++i) acc[i] = first ? g[i] : acc[i] + g[i];      // the last cnt % 4 floats: quad nq, one by one
+}
+
 // Zero exactly what the backward reads without having written it.  Grad wrt X[j] has two parts:
 //   DXA[j] (own-row part): layer j writes rows [s_out(j), N1); layer j-1 (or the causal backward for j = 0) reads from
 //           row s_in(j) (0 for j = 0) -> rows [s_in(j) or 0, s_out(j)) must read as zero;
@@ -1689,6 +1734,19 @@ int qpn_launch_adam_clip(float* w, const float* g, float* m, float* v, int64_t n
                               (const double*)part, nb, max_norm, d_norm, h_norm, e, omd);
     else hipLaunchKernelGGL(k_adam_clip, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, g, m, v, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2), den, status, rep,
                             (const double*)part, nb, max_norm, d_norm, h_norm);
+    qpn_prof_mark(PG_ADAM, stream);
+    QPN_HIP(hipGetLastError());
+    return QPN_OK;
+}
+
+// acc <- first ? g : acc + g over cnt floats (k_grad_accum).  The grid comes from the device, not from cnt: at most 8 blocks of 256 threads per compute unit,
+// fewer while a thread per quad (and one for the short last quad) does not fill them; the rest is the kernel's stride.  status / h_status / h_loss / d_loss: the reports
+// of a micro-step whose last kernel this is (qpn_train_step_acc), all NULL otherwise
+int qpn_launch_grad_accum(float* acc, const float* g, int64_t cnt, int first, const int* status, int* h_status, double* h_loss, const double* d_loss, hipStream_t stream) {
+    AdamReports rep; rep.h_status = status ? h_status : nullptr; rep.h_loss = d_loss ? h_loss : nullptr; rep.d_loss = d_loss;
+    const int64_t want = ((cnt >> 2) + 1 + 255) / 256, cap = (int64_t)qpn_num_cus() * 8;
+    const int nb = (int)(want < cap ? want : cap);
+    hipLaunchKernelGGL(k_grad_accum, dim3(nb), dim3(256), 0, stream, acc, g, cnt, first ? 1 : 0, status, rep);
     qpn_prof_mark(PG_ADAM, stream);
     QPN_HIP(hipGetLastError());
     return QPN_OK;

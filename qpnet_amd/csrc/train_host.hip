@@ -17,6 +17,7 @@ int qpn_launch_adam(float* w, const float* g, float* m, float* v, int64_t n, int
                     int* h_status, double* h_loss, const double* d_loss, float* e, float omd, hipStream_t stream);
 int qpn_launch_adam_clip(float* w, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps, float wd, const float* den, int* status,
                          int* h_status, double* h_loss, const double* d_loss, float max_norm, double* part, double* d_norm, double* h_norm, float* e, float omd, hipStream_t stream);
+int qpn_launch_grad_accum(float* acc, const float* g, int64_t cnt, int first, const int* status, int* h_status, double* h_loss, const double* d_loss, hipStream_t stream);
 
 // a pinned loss slot: the 64 partial sums, then the gradient norm of the same step (gradient-norm clipping)
 #define LOSS_SLOT 72
@@ -655,7 +656,7 @@ static int status_to_rc(int st) {
     if (st & 4) { qpn_set_error("the one-launch residual stack gave up waiting for a peer workgroup: the flagged step's results are invalid (its Adam update, and that of the steps enqueued behind it until this report, were skipped on the device: parameters and moments are those of the last clean step); the handle runs a launch per layer from here on (QPN_STACK_QUEUE=0 selects that from the start)"); return QPN_ENODEV; }
     if (st & 2) { qpn_set_error("target class outside [0, n_quantize) (reference assert qpnet_train.py:525)"); return QPN_ERANGE; }
     if (st & (1 << 16)) { qpn_set_error("non-finite gradient norm (an inf or NaN in the gradient): the step's Adam update, and that of the steps enqueued behind it until this report, were skipped on the device: parameters and moments are those of the last clean step"); return QPN_ERANGE; }
-    if (st & 8) { qpn_set_error("a peer rank flagged its chunk of this data-parallel step (a tap or target out of range, or an abandoned stack launch there): every rank skipped the update, the replicas are unchanged"); return QPN_ERANGE; }
+    if (st & 8) { qpn_set_error("a peer rank flagged its chunk of this data-parallel step, or an earlier micro-step of this accumulation window was flagged (a tap or target out of range, or an abandoned stack launch there): every rank skipped the update, the replicas are unchanged"); return QPN_ERANGE; }
     return QPN_OK;
 }
 
@@ -865,6 +866,19 @@ extern "C" int qpn_adam_step_avg(qpn_handle* h, float* d_flat, const float* d_gr
                            d_ema, omd, (hipStream_t)stream_);
 }
 
+// Gradient accumulation: d_acc <- first ? d_grad : d_acc + d_grad over cnt floats (k_grad_accum; callers pass n + 4: the row-weighted gradient qpn_train_backward_ex
+// left and its trailer).  first overwrites: d_acc needs no clearing.  The arguments are checked before anything about the device
+extern "C" int qpn_grad_accumulate(qpn_handle* h, float* d_acc, const float* d_grad, int64_t cnt, int first, void* stream_) {
+    if (!d_acc) { qpn_set_error("bad grad_accumulate arguments: d_acc is NULL"); return QPN_EINVAL; }
+    if (!d_grad) { qpn_set_error("bad grad_accumulate arguments: d_grad is NULL"); return QPN_EINVAL; }
+    if (cnt < 1) { qpn_set_error("bad grad_accumulate arguments: cnt must be >= 1"); return QPN_EINVAL; }
+    if (d_acc == d_grad) { qpn_set_error("bad grad_accumulate arguments: d_acc is d_grad (the accumulator must be a buffer of its own)"); return QPN_EINVAL; }
+    int rc = need_dev(h); if (rc) return rc;
+    // (a step that ends here ran no Adam launch: the norm word is not this step's -- qpn_train_loss_enqueue / qpn_train_grad_norm report "did not clip")
+    if (h->train) { h->train->last_stream = (hipStream_t)stream_; h->train->gnorm_last = false; }
+    return qpn_launch_grad_accum(d_acc, d_grad, cnt, first, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream_);
+}
+
 // The norm the latest Adam launch on this handle clipped by (drains `stream`); *h_valid = 0 when that launch did not clip, or there was none
 extern "C" int qpn_train_grad_norm(qpn_handle* h, double* h_norm, int* h_valid, void* stream_) {
     int rc = need_dev(h); if (rc) return rc;
@@ -914,26 +928,37 @@ extern "C" int qpn_train_step_clip(qpn_handle* h, float* d_flat, int B, int64_t 
 // max_grad_norm > 0: the step clips (qpn_adam_step_clip), and *h_grad_norm (may be NULL) receives the norm of the step whose loss *h_loss is -- mode 1: the previous
 // step's, out of the same pinned slot as its loss; mode 2: this step's; mode 0: none.  0 where that step did not clip.
 // d_ema / ema_decay: qpn_adam_step_avg's (every loss mode moves the average: it is the Adam launch's own work).
-extern "C" int qpn_train_step_avg(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
-                                  const int64_t* d_x, const float* d_h, const float* d_dfac, const int64_t* d_targets, int64_t tgt_stride,
-                                  float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
-                                  int step, float lr, float beta1, float beta2, float eps, float weight_decay,
-                                  int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm,
-                                  float* d_ema, float ema_decay, void* stream) {
+// d_acc != NULL: micro-step `micro` of a window of micro_count > 1 chunks (qpn_train_step_acc); NULL: the plain step, launch for launch what it always was
+static int train_step_impl(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
+                           const int64_t* d_x, const float* d_h, const float* d_dfac, const int64_t* d_targets, int64_t tgt_stride,
+                           float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
+                           int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                           int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm,
+                           float* d_ema, float ema_decay, float* d_acc, int micro, int micro_count, void* stream) {
     if (h_valid) *h_valid = 0;
     if (h_loss) *h_loss = 0.0;
     if (h_grad_norm) *h_grad_norm = 0.0;
     float omd;
     int rc = check_ema_args(d_ema, ema_decay, &omd); if (rc) return rc;
     if (loss_mode < 0 || loss_mode > 2 || (loss_mode && (!h_loss || !h_valid)) || max_grad_norm != max_grad_norm) { qpn_set_error("bad train_step arguments"); return QPN_EINVAL; }
-    const bool clip = max_grad_norm > 0.f;
+    const bool accum = d_acc != nullptr;                                 // a window of several chunks: the gradient goes through the accumulator ...
+    const bool closing = micro == micro_count - 1;                       // ... and only its last micro-step has an Adam launch
+    const bool clip = closing && max_grad_norm > 0.f;
     rc = need_dev(h); if (rc) return rc;
     rc = qpn_train_status_collect_lagged(h); if (rc) return rc;          // the check of the step before the previous one (never waits for queued work)
     if (!d_targets || !d_dlogits) { qpn_set_error("qpn_train_forward_loss needs targets and a dlogits buffer"); return QPN_EINVAL; }
+    if (accum && (!d_grad || n < 1)) { qpn_set_error("bad train_step arguments: d_grad / n"); return QPN_EINVAL; }
     rc = train_forward_impl(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_logits, d_targets, tgt_stride, d_dlogits, 0, stream, true); if (rc) return rc;
-    rc = qpn_train_backward(h, d_dlogits, d_grad, stream); if (rc) return rc;
+    // accumulating: d_grad <- n_r * g_r with the trailer {n_r, flagged_r, 0, 0} behind it, exactly what a data-parallel rank hands to the exchange -- the window is that
+    // sum taken over time; Adam then reads the accumulator and divides by its trailer (a flag in it skips the update, as a peer rank's does)
+    rc = accum ? qpn_train_backward_ex(h, d_dlogits, d_grad, (float)((int64_t)B * BL), 1, stream) : qpn_train_backward(h, d_dlogits, d_grad, stream); if (rc) return rc;
+    TrainState* t = h->train;
+    const float* const g_adam = accum ? d_acc : d_grad;
+    const float* const den = accum ? d_acc + n : nullptr;
     if (loss_mode == 2) {
-        rc = qpn_adam_step_avg(h, d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, nullptr, max_grad_norm, d_ema, ema_decay, stream); if (rc) return rc;
+        if (accum) { rc = qpn_launch_grad_accum(d_acc, d_grad, n + 4, micro == 0, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream); if (rc) return rc; }
+        if (closing) { rc = qpn_adam_step_avg(h, d_flat, g_adam, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, den, max_grad_norm, d_ema, ema_decay, stream); if (rc) return rc; }
+        else { t->last_stream = (hipStream_t)stream; t->gnorm_last = false; }                         // (no Adam launch: this micro-step has no norm)
         rc = qpn_train_loss(h, h_loss, stream); if (rc) return rc;
         *h_valid = 1;
         if (clip && h_grad_norm) { int nv = 0; rc = qpn_train_grad_norm(h, h_grad_norm, &nv, stream); if (rc) return rc; }      // (the stream has just been drained)
@@ -942,16 +967,20 @@ extern "C" int qpn_train_step_avg(qpn_handle* h, float* d_flat, int B, int64_t T
     // modes 0 / 1: the Adam kernel -- the step's last -- writes the status word (and the loss partials) into the pinned slots itself: what
     // qpn_train_status_enqueue / qpn_train_loss_enqueue do with a copy each, without the two copy-engine launches behind the step
     if (!d_flat || !d_grad || !d_m || !d_v || n < 1 || step < 1) { qpn_set_error("bad adam_step arguments"); return QPN_EINVAL; }
-    TrainState* t = h->train;
     const int sslot = t->status_newest ^ 1;
     rc = status_collect_slot(t, sslot); if (rc) return rc;               // (two enqueues old: long done)
     const int lslot = t->loss_newest ^ 1;
     if (loss_mode == 1 && t->loss_pending[lslot]) QPN_HIP(hipEventSynchronize(t->ev_loss[lslot]));      // (an uncollected copy of two calls ago: dropped)
     double* const hl = loss_mode == 1 ? t->h_loss_pinned + LOSS_SLOT * lslot : nullptr;
     t->gnorm_last = clip;
-    if (clip) rc = qpn_launch_adam_clip(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, nullptr, t->d_status, t->h_status_pinned + sslot,
+    t->last_stream = (hipStream_t)stream;
+    // (the micro-steps in front of the closing one end in the accumulate kernel: it carries the reports; in the closing one the Adam launch does, as ever)
+    if (accum) { rc = qpn_launch_grad_accum(d_acc, d_grad, n + 4, micro == 0, closing ? nullptr : t->d_status, t->h_status_pinned + sslot,
+                                            hl, (!closing && loss_mode == 1) ? t->d_loss : nullptr, (hipStream_t)stream); if (rc) return rc; }
+    if (!closing) rc = QPN_OK;
+    else if (clip) rc = qpn_launch_adam_clip(d_flat, g_adam, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, den, t->d_status, t->h_status_pinned + sslot,
                                         hl, loss_mode == 1 ? t->d_loss : nullptr, max_grad_norm, t->d_gnorm, t->d_loss + 64, hl ? hl + 64 : nullptr, d_ema, omd, (hipStream_t)stream);
-    else rc = qpn_launch_adam(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, nullptr, t->d_status, t->h_status_pinned + sslot,
+    else rc = qpn_launch_adam(d_flat, g_adam, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, den, t->d_status, t->h_status_pinned + sslot,
                               hl, loss_mode == 1 ? t->d_loss : nullptr, d_ema, omd, (hipStream_t)stream);
     if (rc) return rc;
     QPN_HIP(hipEventRecord(t->ev_status[sslot], (hipStream_t)stream));
@@ -963,4 +992,37 @@ extern "C" int qpn_train_step_avg(qpn_handle* h, float* d_flat, int B, int64_t T
         if (h_grad_norm && t->gnorm_collected_valid) *h_grad_norm = t->gnorm_collected;
     }
     return QPN_OK;
+}
+
+extern "C" int qpn_train_step_avg(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
+                                  const int64_t* d_x, const float* d_h, const float* d_dfac, const int64_t* d_targets, int64_t tgt_stride,
+                                  float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
+                                  int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                  int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm,
+                                  float* d_ema, float ema_decay, void* stream) {
+    return train_step_impl(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
+                           step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, max_grad_norm, h_grad_norm, d_ema, ema_decay, nullptr, 0, 1, stream);
+}
+
+// Gradient accumulation: the step above as micro-step `micro` of a window of micro_count chunks.  Every micro-step runs forward + loss, the row-weighted backward
+// (qpn_train_backward_ex(B * BL, 1) into d_grad) and k_grad_accum into d_acc (micro 0 overwrites it); the last one also runs the Adam launch on d_acc, divided by the summed
+// row count in its trailer.  The host side of a micro-step stays ONE foreign call, and a micro-step in front of the last ends in the accumulate kernel, whose block 0
+// carries the status word and the loss partials to pinned memory as the Adam kernel does elsewhere: no copy-engine launch is added.
+// The window's own arguments are checked first, then the averaged-weights ones, then the rest -- all before the device or the handle's state is looked at.
+extern "C" int qpn_train_step_acc(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
+                                  const int64_t* d_x, const float* d_h, const float* d_dfac, const int64_t* d_targets, int64_t tgt_stride,
+                                  float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
+                                  int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                  int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm,
+                                  float* d_ema, float ema_decay, float* d_acc, int micro, int micro_count, void* stream) {
+    if (h_valid) *h_valid = 0;
+    if (h_loss) *h_loss = 0.0;
+    if (h_grad_norm) *h_grad_norm = 0.0;
+    if (micro_count < 1) { qpn_set_error("bad train_step_acc arguments: micro_count must be >= 1"); return QPN_EINVAL; }
+    if (micro < 0 || micro >= micro_count) { qpn_set_error("bad train_step_acc arguments: micro must lie in [0, micro_count)"); return QPN_EINVAL; }
+    if (!d_acc && micro_count > 1) { qpn_set_error("bad train_step_acc arguments: d_acc is NULL with micro_count > 1"); return QPN_EINVAL; }
+    if (d_acc && d_acc == d_grad) { qpn_set_error("bad train_step_acc arguments: d_acc is d_grad (the accumulator must be a buffer of its own)"); return QPN_EINVAL; }
+    return train_step_impl(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
+                           step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, max_grad_norm, h_grad_norm, d_ema, ema_decay,
+                           micro_count > 1 ? d_acc : nullptr, micro, micro_count, stream);
 }

@@ -7,7 +7,8 @@ Same command-line flags and on-disk artefacts as the reference task scripts
   src/bin/qpnet_decode.py   (per-GPU split :258-259,322-331; wav writing :315-320)
 but the loop body is the fused step behind the C ABI (FusedTrainer) and multi-GPU is one process per GPU
 (torch.distributed / RCCL): rank r consumes chunks r, r+N, ... of the generator stream and the flat gradient is
-all-reduced once per step; decode splits the utterance list over ranks with no communication.
+all-reduced once per step (with --accum_steps K: once per window of K chunks, and an iteration is one update); decode splits the utterance list over ranks with no
+communication.
 
     python -m qpnet_amd.run_train    --waveforms .. --feats .. --stats .. --expdir .. --config .. [--n_gpus N]
     python -m qpnet_amd.run_update   ... --pretrain checkpoint-final.pkl
@@ -259,6 +260,7 @@ def _train_args(update):
     p.add_argument("--weight_decay", default=0.0, type=float)
     p.add_argument("--max_grad_norm", default=0.0, type=float, help="clip the gradient norm inside the fused step (torch's clip_grad_norm_); 0: off")
     p.add_argument("--ema_decay", default=0.0, type=float, help="keep an exponential moving average of the weights inside the fused step, written to the checkpoints as \"ema\" (decode / validate with --ema); 0: off")
+    p.add_argument("--accum_steps", default=1, type=int, help="gradient accumulation: one Adam update per K batches of the stream (an iteration is then one update: --iters, --intervals, --checkpoint_interval and the checkpoints count updates); 1: off")
     p.add_argument("--iters", default=3000 if update else 200000, type=int)
     p.add_argument("--checkpoint_interval", default=10000, type=int)
     p.add_argument("--intervals", default=100, type=int)
@@ -291,9 +293,12 @@ def run_train(argv=None, update=False):
     from .train import FusedTrainer
     from . import parallel
     model = _build_model(conf, dev).train()
-    trainer = FusedTrainer(model, lr=args.lr, weight_decay=args.weight_decay, world_size=world, max_grad_norm=args.max_grad_norm, ema_decay=args.ema_decay)
+    trainer = FusedTrainer(model, lr=args.lr, weight_decay=args.weight_decay, world_size=world, max_grad_norm=args.max_grad_norm, ema_decay=args.ema_decay,
+                           accum_steps=args.accum_steps)
     clipping = trainer.max_grad_norm > 0.0
+    K = trainer.accum_steps                    # batches per iteration: an iteration is one UPDATE (a window of K micro-steps), so checkpoints fall on window boundaries
     norm_max, n_clipped, n_seen = 0.0, 0, 0    # (clipping on) the interval's largest gradient norm, how many of its steps were clipped, how many losses it collected
+    n_got = 0                                  # (K > 1) the micro-step losses that arrived in the interval: its reported loss is their mean
 
     def note_norm(g):
         # (a non-finite norm is the largest there is: max() would drop a NaN)
@@ -301,6 +306,13 @@ def run_train(argv=None, update=False):
         if g is not None:
             norm_max = float("nan") if g != g or norm_max != norm_max else max(norm_max, g)
             n_clipped += bool(g > trainer.max_grad_norm)
+
+    def note_loss(v):
+        # (K > 1: only a window-closing micro-step has a norm -- the None of the others is no step of the clipping statistics)
+        nonlocal loss, n_got, n_seen
+        loss += v; n_got += 1
+        if clipping and (K == 1 or trainer.last_grad_norm is not None):
+            n_seen += 1; note_norm(trainer.last_grad_norm)
     iterations, loss_record = 0, []
     flossyml = os.path.join(args.expdir, "loss-final.yml")
     if args.resume and os.path.exists(args.resume):
@@ -323,26 +335,25 @@ def run_train(argv=None, update=False):
     lagged = os.environ.get("QPN_RUN_TRAIN_SYNC_LOSS", "0") != "1"
     for i in range(iterations, args.iters):
         start = time.time()
-        bx, bh, bt, bd, bb, maxd = next(stream)
-        try:
-            batch_loss = trainer.step(bx, bh, bt, bd, bb, want_loss="lagged" if lagged else True, maxd=maxd)
-        except Exception as e:
-            if not (clipping and _is_non_finite_norm(e)):
-                raise
-            batch_loss = None                   # the device skipped that update (and those enqueued behind it): training goes on from the last clean state
-            logging.warning("(iter:%d) %s" % (i + 1, e))
-        if batch_loss is not None:
-            loss += batch_loss
-            logging.debug("batch loss = %.3f" % batch_loss)
-            if clipping:
-                n_seen += 1; note_norm(trainer.last_grad_norm)
+        while True:                             # the K batches of this iteration's window (K = 1: the one batch)
+            bx, bh, bt, bd, bb, maxd = next(stream)
+            try:
+                batch_loss = trainer.step(bx, bh, bt, bd, bb, want_loss="lagged" if lagged else True, maxd=maxd)
+            except Exception as e:
+                if not (clipping and _is_non_finite_norm(e)):
+                    raise
+                batch_loss = None               # the device skipped that update (and those enqueued behind it): training goes on from the last clean state
+                logging.warning("(iter:%d) %s" % (i + 1, e))
+            if batch_loss is not None:
+                note_loss(batch_loss)
+                logging.debug("batch loss = %.3f" % batch_loss)
+            if trainer.micro_step == 0:         # the window closed (or a status error abandoned it: the iteration ends with it)
+                break
         total += time.time() - start
         if (i + 1) % args.intervals == 0 or (i + 1) % args.checkpoint_interval == 0 or i + 1 == args.iters:
             last = trainer.flush_loss() if lagged else None
             if last is not None:
-                loss += last
-                if clipping:
-                    n_seen += 1; note_norm(trainer.last_grad_norm)
+                note_loss(last)
             # the device-side checks of the last steps (a dilated factor outside the layer input, a target outside [0, n_quantize), an abandoned
             # stack launch: the reference asserts in every step, qpnet.py:294, qpnet_train.py:525) are collected HERE -- before an interval
             # is reported, before a checkpoint and before the final model are written: nothing flagged reaches the disk
@@ -355,15 +366,17 @@ def run_train(argv=None, update=False):
         if (i + 1) % args.intervals == 0:
             if clipping:
                 # (a step that raised for a non-finite norm took the loss it would have returned with it: the average is over the losses that arrived)
-                n_loss = n_seen if 0 < n_seen < args.intervals else args.intervals
+                n_upd = n_seen if 0 < n_seen < args.intervals else args.intervals
+                n_loss = n_upd if K == 1 else max(n_got, 1)
                 logging.info("(iter:%d) average loss = %.6f (%.3f sec / batch) max grad norm = %.6g, %d of %d steps clipped"
-                             % (i + 1, loss / n_loss, total / args.intervals, norm_max, n_clipped, n_loss))
+                             % (i + 1, loss / n_loss, total / (args.intervals * K), norm_max, n_clipped, n_upd))
                 norm_max, n_clipped, n_seen = 0.0, 0, 0
             else:
-                n_loss = args.intervals
-                logging.info("(iter:%d) average loss = %.6f (%.3f sec / batch)" % (i + 1, loss / args.intervals, total / args.intervals))
+                n_loss = args.intervals if K == 1 else max(n_got, 1)
+                logging.info("(iter:%d) average loss = %.6f (%.3f sec / batch)" % (i + 1, loss / n_loss, total / (args.intervals * K)))
             loss_record.append(loss / n_loss)
             loss = total = 0.0
+            n_got = 0
         if (i + 1) % args.checkpoint_interval == 0 and rank == 0:
             loaders.save_checkpoint(args.expdir, model, trainer, i + 1)
     if world > 1:

@@ -502,6 +502,13 @@ def _check_ema_decay(v):
     return v
 
 
+def _check_accum_steps(v):
+    """accum_steps as the C ABI's micro_count: a plain int >= 1 (a bool, a float or None is not one)."""
+    if type(v) is not int or v < 1:
+        raise ValueError("accum_steps must be an int >= 1 (1: one update per chunk), got %r" % (v,))
+    return v
+
+
 # ---------------------------------------------------------------- averaged weights (EMA) shared by FusedTrainer and FlatAdam
 def _ema_home(ema, flat):
     """the averaged weights next to `flat`: a copy of the weights the first time (or after load_ema(None)), re-homed like the moments when the device changed."""
@@ -696,17 +703,32 @@ class FusedTrainer:
     ema_decay=d (None / 0: off; 0 < d < 1): `ema`, a flat fp32 exponential moving average of the weights, seeded with a copy of them at the first step, moves inside
     the Adam launch itself with every APPLIED update: e += (w_new - e) * (1 - d) -- a step the device skipped (a flagged chunk, a peer's flag, a non-finite norm)
     leaves it alone.  No launch, copy or wait is added to a step.  ema_state_dict() / load_ema() carry it through checkpoints (loaders.save_checkpoint writes it as
-    "ema" next to "model"), forward_loss(weights="ema") scores it on held-out data; it is not part of state_dict() either."""
+    "ema" next to "model"), forward_loss(weights="ema") scores it on held-out data; it is not part of state_dict() either.
+    accum_steps=K (a plain int >= 1; 1: off): gradient accumulation -- step() becomes a MICRO-step, and one Adam update is applied per window of K of them, to the
+    gradient of the mean CE over all the window's rows (chunks of unequal batch_length get their row weights: the window is the sum a data-parallel step takes over
+    ranks, taken over time, so one GPU follows the trajectory of a K-rank run).  `micro_step` is the position in the open window (0 .. K-1); step_count, the bias
+    correction and state_dict()'s step numbers count UPDATES.  Single rank: still one foreign call per micro-step (qpn_train_step_acc); a micro-step that does not
+    close its window returns its own loss, and last_grad_norm is None with it (no norm launch ran).  world_size > 1: every micro-step runs call by call, only the closing
+    one exchanges -- the accumulator, ONCE per window -- and runs Adam; the two-bucket split is not used (it is taken as agreed to be off: K is the same on every rank,
+    so every rank issues the same single collective per window).  Clipping and the average apply to the update, i.e. once per window.  A flagged micro-step leaves its
+    flag in the accumulator's trailer and the closing Adam launch skips.  After a device-side status error (QpnError -4 / -2 from any call) the open window is ABANDONED:
+    the next step() is micro-step 0 and overwrites the accumulator, the chunks accumulated so far are dropped as the flagged chunk itself is.  Under stream capture
+    with K > 1 step() raises (one captured graph cannot hold both kinds of micro-step).  A trainer setting like max_grad_norm: not part of state_dict(), no accumulator
+    reaches a checkpoint.  K = 1 makes exactly the calls made without the option."""
 
     # The device-side status word (bad taps / targets; the reference asserts in-line, qpnet.py:294, qpnet_train.py:525) is copied to pinned
     # memory behind every step; a step starts by looking at the copy made TWO steps earlier (the previous step is still queued on the
     # device while the host enqueues this one: waiting for it would idle the GPU).  A bad chunk is raised two steps late at most, not up to 99
     # as when the word was read every 100 steps.  check_status() collects everything outstanding.
 
-    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, process_group=None, world_size=1, max_grad_norm=None, ema_decay=None):
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, process_group=None, world_size=1, max_grad_norm=None, ema_decay=None,
+                 accum_steps=1):
         self.model = model
         self.max_grad_norm = _check_max_grad_norm(max_grad_norm)
         self.ema_decay = _check_ema_decay(ema_decay)
+        self.accum_steps = _check_accum_steps(accum_steps)
+        self._micro = 0               # position in the open accumulation window
+        self.acc = None               # accum_steps > 1: the window's summed row-weighted gradient + trailer
         self.ema = None               # averaging on: the flat average, from the first step (or load_ema) on
         self.last_grad_norm = None
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
@@ -718,6 +740,13 @@ class FusedTrainer:
         self._applied_base = None     # (step_count, the handle's applied-update count) at this trainer's first step / after a re-base (see _rebase_step_count)
         self._early = None            # the stream the early bucket of the gradient exchange runs on (world_size > 1)
         self._two_buckets = None      # agreed over the process group at the first data-parallel step (every rank must issue the same collectives)
+        if self.accum_steps > 1:
+            self._two_buckets = False  # (accumulating: one exchange of the accumulator per window, on every rank)
+
+    @property
+    def micro_step(self):
+        """position of the next step() in the open accumulation window: 0 .. accum_steps - 1 (always 0 with accum_steps = 1)"""
+        return self._micro
 
     def _buffers(self, flat):
         if self.m is None or self.m.device != flat.device or self.m.numel() != flat.numel():
@@ -729,6 +758,9 @@ class FusedTrainer:
             self.g = torch.empty(flat.numel() + 4, dtype=torch.float32, device=flat.device)   # gradient + trailer (row count)
         if self.ema_decay > 0.0:
             self.ema = _ema_home(self.ema, flat)
+        if self.accum_steps > 1 and (self.acc is None or self.acc.device != flat.device or self.acc.numel() != flat.numel() + 4):
+            self.acc = torch.empty(flat.numel() + 4, dtype=torch.float32, device=flat.device)     # (micro-step 0 overwrites it: never cleared)
+            self._micro = 0
 
     @staticmethod
     def _norm(t, dtype, dev):
@@ -767,6 +799,11 @@ class FusedTrainer:
         # (a step being captured into a hipGraph -- torch.cuda.graph -- may not wait for events or read anything back: no status bookkeeping, the
         #  caller checks with check_status() outside the graph; the library runs the stack as a launch per layer while a stream is capturing)
         capturing = torch.cuda.is_current_stream_capturing()
+        if capturing and self.accum_steps > 1:
+            raise RuntimeError("qpnet_amd.FusedTrainer(accum_steps=%d): a step cannot be captured into a graph while accumulating (the micro-steps of a window "
+                               "do not make the same launches)" % self.accum_steps)
+        if not multi and not capturing and self.accum_steps > 1:
+            return self._micro_step_call(L, hd, dev, flat, stream, x, h, t, d, B, T, BL, maxd, want_loss, loss)
         if not multi and not capturing:
             # the whole step behind ONE foreign call (qpn_train_step: the same calls in the same order as below): while it runs, the interpreter is free
             # for the loader thread -- the runner loop was bound by the two threads' interleaved Python, not by the device
@@ -809,8 +846,43 @@ class FusedTrainer:
             return self._step_calls(L, hd, dev, flat, stream, x, h, t, d, B, T, BL, maxd, want_loss, multi, capturing, loss)
         except _lib.QpnError as e:
             if e.code in (-4, -2):                     # (QPN_ERANGE / QPN_ENODEV: what the device-side status word raises)
+                self._micro = 0                        # (the open accumulation window is abandoned)
                 self._rebase_step_count(L, hd, dev, stream, 0)
             raise
+
+    def _micro_step_call(self, L, hd, dev, flat, stream, x, h, t, d, B, T, BL, maxd, want_loss, loss):
+        """accum_steps > 1 on one rank: the micro-step behind ONE foreign call (qpn_train_step_acc).  The update number it passes is the same for every micro-step
+        of a window; step_count moves when the window closes."""
+        K, micro = self.accum_steps, self._micro
+        closing = micro == K - 1
+        valid, norm = C.c_int(0), C.c_double(0.0)
+        mode = 1 if want_loss == "lagged" else (2 if want_loss else 0)
+        clip = self.max_grad_norm
+        with torch.cuda.device(dev):
+            rc = L.qpn_train_step_acc(hd, flat.data_ptr(), B, T, h.shape[2], d.shape[1], BL, maxd, x.data_ptr(), h.data_ptr(), d.data_ptr(),
+                                      t.data_ptr(), t.shape[1], self._logits.data_ptr(), self._dlogits.data_ptr(), self.g.data_ptr(),
+                                      self.m.data_ptr(), self.v.data_ptr(), flat.numel(), self.step_count + 1, self.lr, self.betas[0], self.betas[1],
+                                      self.eps, self.wd, mode, C.byref(loss), C.byref(valid), clip, C.byref(norm),
+                                      self.ema.data_ptr() if self.ema is not None else None, self.ema_decay if self.ema is not None else 0.0,
+                                      self.acc.data_ptr(), micro, K, stream)
+        if rc in (-4, -2):
+            self._micro = 0                            # a device-side status error: the open window is abandoned, the next step() overwrites the accumulator
+        elif closing:
+            self._micro = 0
+            self.step_count += 1
+        else:
+            self._micro = micro + 1
+        if clip <= 0.0:
+            pass
+        elif not valid.value:
+            self.last_grad_norm = None
+        elif mode == 1:
+            self.last_grad_norm = self._collected_norm(L, hd)      # (None where the micro-step that loss belongs to did not close a window)
+        else:
+            self.last_grad_norm = norm.value if closing else None
+        if rc:
+            self._rebase_step_count(L, hd, dev, stream, rc)
+        return loss.value if valid.value else None
 
     def _rebase_step_count(self, L, hd, dev, stream, rc):
         """A device-side status error: the Adam kernel skipped the flagged step's update and that of every step enqueued behind it until the host collected the
@@ -833,7 +905,19 @@ class FusedTrainer:
             _lib.check(L.qpn_train_forward_loss(hd, flat.data_ptr(), B, T, h.shape[2], d.shape[1], BL, maxd,
                                                 x.data_ptr(), h.data_ptr(), d.data_ptr(), t.data_ptr(), t.shape[1],
                                                 self._logits.data_ptr(), 2, self._dlogits.data_ptr(), stream))      # (2: the backward of this forward follows, same dL/dlogits)
-            if multi:
+            accum = self.accum_steps > 1
+            closing = not accum or self._micro == self.accum_steps - 1
+            if accum:
+                # a micro-step of an accumulation window (world_size > 1): the rank's row-weighted gradient and trailer are added to the accumulator; the closing
+                # micro-step exchanges the ACCUMULATOR -- one all-reduce per window, on every rank -- and Adam divides by the row count summed over ranks and micro-steps
+                from . import parallel
+                _lib.check(L.qpn_train_backward_ex(hd, self._dlogits.data_ptr(), self.g.data_ptr(), float(B * BL), 1, stream))
+                _lib.check(L.qpn_grad_accumulate(hd, self.acc.data_ptr(), self.g.data_ptr(), flat.numel() + 4, 1 if self._micro == 0 else 0, stream))
+                if closing and multi:
+                    parallel.exchange(self.acc, self.pg)
+                    self.last_buckets = (0, 0)
+                    L.qpn_train_profile_mark(hd, 9, stream)      # QPN_PG_ALLREDUCE
+            elif multi:
                 from .parallel import exchange_two_buckets
                 first, count = C.c_int64(0), C.c_int64(0)
                 if self._early is None:
@@ -860,15 +944,19 @@ class FusedTrainer:
                 L.qpn_train_profile_mark(hd, 9, stream)      # QPN_PG_ALLREDUCE (no-op unless a profile is being taken)
             else:
                 _lib.check(L.qpn_train_backward(hd, self._dlogits.data_ptr(), self.g.data_ptr(), stream))
-            self.step_count += 1
             clip = self.max_grad_norm
-            den = self.g.data_ptr() + 4 * flat.numel() if multi else None
-            if self.ema is not None:
-                _lib.check(L.qpn_adam_step_avg(hd, flat.data_ptr(), self.g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), flat.numel(),
+            gbuf = self.acc if accum else self.g
+            den = gbuf.data_ptr() + 4 * flat.numel() if (multi or accum) else None
+            if not closing:
+                self._micro += 1                       # (no Adam launch: the window stays open)
+            elif self.ema is not None:
+                self.step_count += 1; self._micro = 0
+                _lib.check(L.qpn_adam_step_avg(hd, flat.data_ptr(), gbuf.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), flat.numel(),
                                                self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
                                                den, clip, self.ema.data_ptr(), self.ema_decay, stream))
             else:
-                _lib.check(L.qpn_adam_step_clip(hd, flat.data_ptr(), self.g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), flat.numel(),
+                self.step_count += 1; self._micro = 0
+                _lib.check(L.qpn_adam_step_clip(hd, flat.data_ptr(), gbuf.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), flat.numel(),
                                                 self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, den, clip, stream))
             if want_loss == "lagged":
                 # this step's loss is copied out behind its kernels; what comes back is the PREVIOUS step's (None at the first step, or right after
@@ -926,6 +1014,7 @@ class FusedTrainer:
         except _lib.QpnError as e:
             flat = getattr(self.model, "_flat", None)
             if e.code in (-4, -2) and flat is not None and flat.is_cuda:
+                self._micro = 0                        # (an open accumulation window is abandoned)
                 L, hd = self.model._native(flat.device)
                 self._rebase_step_count(L, hd, flat.device, torch.cuda.current_stream(flat.device).cuda_stream, 0)
             raise
