@@ -6,7 +6,7 @@ data (seeds, small inputs, expected outputs) and are what travels to the GPU box
 Inputs are regenerated from seeds by qpnet_amd.synth (np.random.RandomState: frozen streams),
 so fixtures store only what cannot be regenerated: the reference's outputs.
 
-    python tests/golden/make_golden.py [--only decode|decode2|decode_d|forward|train|kat|kat_ties|default|deep]
+    python tests/golden/make_golden.py [--only decode|decode2|decode_d|forward|train|kat|kat_ties|default|deep|aux]
 """
 import argparse
 import os
@@ -28,7 +28,7 @@ from qpnet_amd import synth  # noqa: E402
 from qpnet_amd.config import TINY, PAPER, QPNetConfig  # noqa: E402
 sys.path.insert(0, HERE)
 from cases import (DECODE_CASES, DECODE_CASES2, DECODE_CASES_D, FORWARD_CASES, TRAIN_CASES, FORWARD_CASES_D, TRAIN_CASES_D,  # noqa: E402
-                   FORWARD_CASES_DEEP, TRAIN_CASES_DEEP, DECODE_CASES_DEEP, decode2_inputs)
+                   FORWARD_CASES_DEEP, TRAIN_CASES_DEEP, DECODE_CASES_DEEP, FORWARD_CASES_AUX, TRAIN_CASES_AUX, DECODE_CASES_AUX, decode2_inputs)
 
 torch.set_num_threads(8)
 torch.set_grad_enabled(False)
@@ -110,9 +110,16 @@ def gen_kat_ties():
 
 
 
-def gen_decode(cases=DECODE_CASES, fname="decode.npz"):
+def _save(out, fname):
+    """fname None: the caller collects several generators' entries in `out` and writes the file itself"""
+    if fname is not None:
+        np.savez_compressed(os.path.join(HERE, fname), **out)
+        print(fname, "written")
+
+
+def gen_decode(cases=DECODE_CASES, fname="decode.npz", out=None):
     from qpnet_amd import harness
-    out = {}
+    out = {} if out is None else out
     for name, cfg, wseed, utts, extra in cases:
         flat = synth.make_weights(cfg, wseed)
         m = build_ref(cfg, flat)
@@ -131,8 +138,7 @@ def gen_decode(cases=DECODE_CASES, fname="decode.npz"):
             out["%s_out%d" % (name, i)] = np.asarray(s).astype(np.int16)
         out[name + "_nleft"] = np.array(nlist, dtype=np.int64)
         print(name, [len(s) for s in streams], "n_samples_list after:", nlist)
-    np.savez_compressed(os.path.join(HERE, fname), **out)
-    print(fname, "written")
+    _save(out, fname)
 
 
 
@@ -156,8 +162,8 @@ def gen_decode2():
     print("decode2.npz written")
 
 
-def gen_forward(cases=FORWARD_CASES, fname="forward.npz"):
-    out = {}
+def gen_forward(cases=FORWARD_CASES, fname="forward.npz", out=None):
+    out = {} if out is None else out
     for name, cfg, wseed, dseed, bl, ml in cases:
         flat = synth.make_weights(cfg, wseed)
         m = build_ref(cfg, flat)
@@ -170,17 +176,16 @@ def gen_forward(cases=FORWARD_CASES, fname="forward.npz"):
         out[name + "_loss"] = np.float64(loss.item())
         out[name + "_bl"] = np.int64(BL)
         print(name, "forward", logits.shape, "loss", loss.item())
-    np.savez_compressed(os.path.join(HERE, fname), **out)
-    print(fname, "written")
+    _save(out, fname)
 
 
 
 
-def gen_train(cases=TRAIN_CASES, fname="train.npz", max_length=30000):
+def gen_train(cases=TRAIN_CASES, fname="train.npz", max_length=30000, out=None):
     """A few real optimisation steps: CE(mean) -> backward -> Adam(lr 1e-4)
     (reference src/bin/qpnet_train.py:426-430,517-531)."""
     torch.set_grad_enabled(True)
-    out = {}
+    out = {} if out is None else out
     for name, cfg, wseed, dseed, bl, nsteps in cases:
         flat = synth.make_weights(cfg, wseed)
         m = build_ref(cfg, flat)
@@ -208,9 +213,18 @@ def gen_train(cases=TRAIN_CASES, fname="train.npz", max_length=30000):
         out[name + "_losses"] = np.array(losses)
         out[name + "_wfinal_sample"] = w[::97].astype(np.float32)
         print(name, "train losses", losses)
-    np.savez_compressed(os.path.join(HERE, fname), **out)
     torch.set_grad_enabled(False)
-    print(fname, "written")
+    _save(out, fname)
+
+
+def gen_aux():
+    """aux.npz: every AUX_CASES geometry (n_aux and upsampling_factor other than 39 and 110) through the three generators above, in one file"""
+    from cases import AUX_MAX_LENGTH
+    out = {}
+    gen_forward(FORWARD_CASES_AUX, None, out)
+    gen_train(TRAIN_CASES_AUX, None, AUX_MAX_LENGTH, out)
+    gen_decode(DECODE_CASES_AUX, None, out)
+    _save(out, "aux.npz")
 
 
 if __name__ == "__main__":
@@ -219,7 +233,7 @@ if __name__ == "__main__":
     a = ap.parse_args()
     todo = [a.only] if a.only else ["kat", "kat_ties", "decode", "decode2", "decode_d", "forward", "train", "default", "deep"]
     for t in todo:
-        {"kat": gen_kat, "kat_ties": gen_kat_ties, "decode": gen_decode, "decode2": gen_decode2, "forward": gen_forward, "train": gen_train,
+        {"kat": gen_kat, "aux": gen_aux, "kat_ties": gen_kat_ties, "decode": gen_decode, "decode2": gen_decode2, "forward": gen_forward, "train": gen_train,
          "decode_d": lambda: gen_decode(DECODE_CASES_D, "decode_d.npz"),
          "default": lambda: (gen_forward(FORWARD_CASES_D, "forward_d.npz"), gen_train(TRAIN_CASES_D, "train_d.npz", 2000)),
          "deep": lambda: (gen_forward(FORWARD_CASES_DEEP, "forward_deep.npz"), gen_train(TRAIN_CASES_DEEP, "train_deep.npz", 22500),

@@ -29,7 +29,13 @@ def test_no_torch_types_in_abi():
     assert "torch" not in hdr.lower() and "at::" not in hdr and "#include <hip" not in hdr
 
 
-@pytest.mark.parametrize("cfg", [TINY, PAPER, DEFAULT])
+def _aux_cfgs():
+    import dataclasses
+    from cases import AUX_CASES
+    return [c[1] for c in AUX_CASES] + [dataclasses.replace(PAPER, upsampling_factor=0)]
+
+
+@pytest.mark.parametrize("cfg", [TINY, PAPER, DEFAULT] + _aux_cfgs())
 def test_param_count(cfg):
     L = _lib.lib()
     assert L.qpn_param_count(C.byref(_lib.make_config(cfg))) == cfg.n_params

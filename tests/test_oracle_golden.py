@@ -3,7 +3,7 @@ reference (tests/golden/make_golden.py).  This is what pins the oracle (SURVEY.m
 import numpy as np
 import pytest
 
-from cases import DECODE_CASES, DECODE_CASES2, DECODE_CASES_D, FORWARD_CASES, TRAIN_CASES, decode2_inputs
+from cases import DECODE_CASES, DECODE_CASES2, DECODE_CASES_D, FORWARD_CASES, TRAIN_CASES, AUX_CASES, AUX_BATCH_LENGTH, AUX_MAX_LENGTH, AUX_STEPS, decode2_inputs
 from qpnet_amd import synth
 import util
 
@@ -306,3 +306,72 @@ def test_train_oracle_deep_network(golden_dir):
             assert np.abs(grad[::97] - ref).max() <= 1e-4 * np.abs(ref).max()
     np.testing.assert_allclose(losses, g[name + "_losses"], atol=1e-4, rtol=0)
     util.assert_weights_after_adam(flat[::97], g[name + "_wfinal_sample"], 1e-4, nsteps, significant=util.significant_elements(cfg, grads)[::97])
+
+
+# ---------------------------------------------------------------- n_aux and upsampling_factor other than 39 and 110 (aux.npz)
+_AUX_IDS = [c[0] for c in AUX_CASES]
+
+
+@pytest.mark.parametrize("case", AUX_CASES, ids=_AUX_IDS)
+def test_train_oracle_other_aux_geometries(case, golden_dir):
+    """numpy oracle vs the reference's logits / loss / gradient sample / two Adam steps at (n_aux, upsampling_factor) = (28, 80), (65, 16), (17, 120):
+    the bounds of the default and the deep geometry above"""
+    from oracle import train_oracle as TO
+    name, cfg, wseed, fseed, tseed, _ = case
+    g = np.load(golden_dir + "/aux.npz")
+    flat = synth.make_weights(cfg, wseed)
+    x, h, t, d, b = synth.train_inputs(cfg, AUX_BATCH_LENGTH, fseed, AUX_MAX_LENGTH)
+    BL = int(b[0])
+    assert BL == int(g[name + "_bl"]) and h.shape[1] == cfg.n_aux and h.shape[2] * cfg.upsampling_factor >= x.shape[1]
+    lg, _ = TO.forward(cfg, flat, x, h, d, b)
+    np.testing.assert_allclose(lg, g[name + "_logits"], atol=5e-5, rtol=0)
+    loss, _ = TO.ce_loss(lg, t[:, -BL:])
+    assert abs(float(loss) - float(g[name + "_loss"])) < 1e-4
+    opt = TO.Adam(flat.size)
+    losses, grads = [], []
+    for step in range(AUX_STEPS):
+        x, h, t, d, b = synth.train_inputs(cfg, AUX_BATCH_LENGTH, tseed + step, AUX_MAX_LENGTH)
+        loss, grad = TO.train_step(cfg, flat, opt, x, h, t, d, b)
+        losses.append(loss); grads.append(grad)
+        if step == 0:
+            ref = g[name + "_grad0_sample"]
+            assert np.abs(grad[::97] - ref).max() <= 1e-4 * np.abs(ref).max()
+    np.testing.assert_allclose(losses, g[name + "_losses"], atol=1e-4, rtol=0)
+    np.testing.assert_allclose(flat[::97], g[name + "_wfinal_sample"], atol=2e-6, rtol=0)
+
+
+@pytest.mark.parametrize("case", AUX_CASES, ids=_AUX_IDS)
+def test_train_torch_oracle_other_aux_geometries(case, golden_dir):
+    """oracle/train_torch.py against the same fixture: loss of every step, the gradient sample of step 0, the weights after the Adam steps"""
+    from oracle import train_torch as TT
+    name, cfg, wseed, fseed, tseed, _ = case
+    g = np.load(golden_dir + "/aux.npz")
+    tr = TT.Trainer(cfg, synth.make_weights(cfg, wseed))
+    losses = []
+    for step in range(AUX_STEPS):
+        x, h, t, d, b = synth.train_inputs(cfg, AUX_BATCH_LENGTH, tseed + step, AUX_MAX_LENGTH)
+        if step == 0:
+            loss, grad = tr.loss_and_grad(x, h, t, d, b)
+            ref = g[name + "_grad0_sample"]
+            assert np.abs(np.asarray(grad)[::97] - ref).max() <= 1e-4 * np.abs(ref).max()
+            tr.opt.step()
+        else:
+            loss = tr.step(x, h, t, d, b)
+        losses.append(loss)
+    np.testing.assert_allclose(losses, g[name + "_losses"], atol=1e-4, rtol=0)
+    np.testing.assert_allclose(tr.flat.detach().numpy()[::97], g[name + "_wfinal_sample"], atol=2e-6, rtol=0)
+
+
+@pytest.mark.parametrize("case", AUX_CASES, ids=_AUX_IDS)
+def test_oracle_decode_other_aux_geometries_equals_reference_streams(case, oracle, golden_dir):
+    """the C oracle against the reference's greedy streams of two rows of unequal length (h zero padded to the longer row's frames): bit for bit"""
+    name, cfg, wseed, _, _, utts = case
+    g = np.load(golden_dir + "/aux.npz")
+    flat = synth.make_weights(cfg, wseed)
+    bx, bh, bd, ns = util.decode_batch(cfg, utts)
+    assert bh.shape[1] == cfg.n_aux and len(set(ns)) == 2
+    nlist = list(ns)
+    outs = oracle.batch_fast_generate(cfg, flat, bx, bh, nlist, bd)
+    assert nlist == list(g[name + "_nleft"])
+    for i, s in enumerate(outs):
+        np.testing.assert_array_equal(s, g["%s_out%d" % (name, i)].astype(np.int64))

@@ -1144,17 +1144,19 @@ def _u0_inputs(cfg_u, bl, seed, ml):
     return cfg0, x, h0, t, d, b
 
 
-@pytest.mark.parametrize("cfgname", ["tiny", "paper"])
+@pytest.mark.parametrize("cfgname", ["tiny", "paper", "paper-a28"])
 def test_upsampling_factor_zero_train_vs_oracle(cfgname, cuda):
     """upsampling_factor = 0 (reference src/nets/qpnet.py:203,263: no ConvTranspose2d, h is consumed as given, aligned at its END):
     logits, loss and every gradient tensor against the numpy oracle; the state_dict has no upsampling.* keys."""
     import torch
     from oracle import train_oracle as TO
     from qpnet_amd.config import TINY, PAPER
-    cfg0, x, h0, t, d, b = _u0_inputs(TINY if cfgname == "tiny" else PAPER, 700, 33, 5000)
+    import dataclasses
+    cfg_u = {"tiny": TINY, "paper": PAPER, "paper-a28": dataclasses.replace(PAPER, n_aux=28)}[cfgname]      # (paper-a28: sample-rate features of another width)
+    cfg0, x, h0, t, d, b = _u0_inputs(cfg_u, 700, 33, 5000)
     flat = synth.make_weights(cfg0, 17)
     m = util.build_model(cfg0, flat, cuda).train()
-    assert not any(k.startswith("upsampling") for k in m.state_dict())
+    assert not any(k.startswith("upsampling") for k in m.state_dict()) and h0.shape[1] == cfg0.n_aux
     BL = int(b[0])
     xt, ht, tt, dt, bt = _to(cuda, x, h0, t, d, b)
     logits = m(xt, ht, dt, bt)
