@@ -117,6 +117,18 @@ int qpn_decode_finish(qpn_handle* h, void* stream);
  * the host).  QPN_ESTATE while a decode is in flight. */
 int qpn_decode_live(qpn_handle* h, int every);
 
+/* Sampling controls: temperature and top-k of the draw of QPN_MODE_SAMPLING, for the decode calls enqueued on this handle from now on
+ * (sticky, like qpn_decode_live; (1.0f, 0) restores the default draw, which is bit for bit the draw of a handle that never called this).
+ * With invT = 1.0f / temperature (fp32, formed here) the class weights are e_c = qexp((l_c - max l) * invT); top_k = k in 1..n_quantize-1
+ * keeps the classes whose logit is >= the k-th largest (counted with multiplicity; classes tied with it are all kept) and gives the others
+ * weight 0; top_k = 0 or n_quantize keeps every class.  The draw stays the fixed-order inverse-CDF draw with the Philox counter (step, row):
+ * reproducible bit for bit on the CPU, the same on every decode kernel, with teacher forcing, the logits output, live
+ * output and cancel, and in the re-run after a launch that gave up.  The values travel as kernel arguments.  QPN_MODE_ARGMAX calls ignore
+ * them.  Arguments are checked before the device is looked at (works on a handle created without a GPU): QPN_EINVAL naming `temperature`
+ * when it is NaN, infinite, <= 0 or so small that 1.0f / temperature is not finite, or `top_k` when it is < 0 or > n_quantize; QPN_ESTATE
+ * while a decode is in flight. */
+int qpn_decode_sampling(qpn_handle* h, float temperature, int top_k);
+
 /* Non-blocking.  For the decode in flight: h_done[B] = samples of each row (input order) that are final in the mirror;
  * *h_samples / *row_stride = the mirror (int32 sample ids, row b at *h_samples + b * *row_stride; host memory owned by the
  * handle, valid until the next enqueue); *running = 0 once everything the enqueue put on the stream has completed.  The
@@ -387,6 +399,15 @@ int qpn_train_profile_end(qpn_handle* h, float* h_ms, int n, void* stream);
 /* _dilated_index (src/nets/qpnet.py:592-604, tensor path) and _generate_dilated_index
  * (src/nets/qpnet.py:613-618): d (B x L) float32 -> int64 (B x L), NOT replicated over
  * channels (the reference's .repeat over n_ch is redundant). */
+/* The draw of sampling decode on logits the caller provides: row r of the row-major (n_rows x Q) fp32 matrix d_logits is drawn with the
+ * Philox counter (step0 + r, row) and key `seed` -- what a decode call with that seed picks at step step0 + r of batch row `row` when
+ * these are its logits there -- into d_out[r].  One wave per row runs the device function the decode kernels' picks run (the default
+ * draw for (1.0f, 0), the controlled one otherwise).  Q in {64,128,192,256} as for sampling decode; temperature / top_k as for
+ * qpn_decode_sampling, checked (like every argument: n_rows >= 1, row >= 0, step0 >= 0, step0 + n_rows <= 2^31) before a device is
+ * looked for.  For sampling from teacher-forced logits (qpn_train_forward, the logits output of qpn_decode).  Asynchronous on `stream`. */
+int qpn_sample_logits(const float* d_logits, int64_t n_rows, int Q, uint64_t seed, int row, int64_t step0, float temperature, int top_k,
+                      int64_t* d_out, void* stream);
+
 int qpn_dilated_index_train(const float* d_d, int B, int64_t L, int dilation, int64_t* d_out, void* stream);
 int qpn_dilated_index_gen_f32(const float* d_d, int64_t n, int dilation, int64_t* d_out, void* stream);
 int qpn_dilated_index_gen_f64(const double* d_d, int64_t n, int dilation, int32_t* d_out, void* stream);

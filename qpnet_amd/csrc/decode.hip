@@ -21,6 +21,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <cmath>
 
 #include "decode_dev.h"
 
@@ -253,7 +254,7 @@ __device__ __forceinline__ void run_slot(Ctx& c, int slot, int64_t t, float4 (&w
         if (i >= 0 && u.logits) for (int k = lane; k < Q; k += 64) u.logits[(size_t)i * Q + k] = sm[p.o_lg + k];
         int next;
         if (i >= 0) {
-            if (p.mode == QPN_MODE_SAMPLING) bi = sample_wave(p.o_lg, Q, p.seed, (unsigned)u.row, (unsigned)i, lane);
+            if (p.mode != QPN_MODE_ARGMAX) bi = sample_pick(p, p.o_lg, Q, (unsigned)u.row, (unsigned)i, lane);
             next = bi;
             if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
             if (lane == 0) { u.out[i] = bi; if (live_put(p, u, (int)i, bi, c.creq)) smi[p.o_samp + 2] = 1; }      // stop on request: the workgroup leaves after the next step
@@ -564,7 +565,7 @@ __device__ __forceinline__ void fast_steps(const DecodeParams& p, const FastPara
             if (i >= 0 && u.logits) for (int k = lane; k < Q; k += 64) u.logits[(size_t)i * Q + k] = sm[p.o_lg + k];
             int next;
             if (i >= 0) {
-                if (p.mode == QPN_MODE_SAMPLING) bi = sample_wave(p.o_lg, Q, p.seed, (unsigned)u.row, (unsigned)i, lane);
+                if (p.mode != QPN_MODE_ARGMAX) bi = sample_pick(p, p.o_lg, Q, (unsigned)u.row, (unsigned)i, lane);
                 next = bi;
                 if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
                 if (lane == 0) u.out[i] = bi;
@@ -655,7 +656,7 @@ void qpn_set_error(const char* fmt, ...) {
     va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof(g_err), fmt, ap); va_end(ap);
 }
 extern "C" const char* qpn_last_error(void) { return g_err; }
-extern "C" int qpn_version(void) { return 1003; }
+extern "C" int qpn_version(void) { return 1004; }
 
 int qpn_build_geom(const qpn_config* c, Geom* g) {
     memset(g, 0, sizeof(*g));
@@ -912,6 +913,7 @@ extern "C" int qpn_create(const qpn_config* cfg, qpn_handle** out) {
     h->n_cus = 0; h->pipe_rows = 0; h->h_utts_pinned = nullptr; h->h_utts_cap = 0;
     h->live_every = 0; h->live_call = false; h->h_live = h->d_live = nullptr; h->live_cap = 0; h->h_live_done = h->d_live_done = nullptr; h->live_done_cap = 0; h->live_stride = 0;
     h->h_cancel = h->d_cancel = nullptr; h->cancel_cap = 0; h->live_final = false;
+    h->samp_inv_temp = 1.0f; h->samp_top_k = 0;
     {   // the environment is read HERE, once per handle: no decode or training call looks at it again
         DecodeKnobs& k = h->dk;
         k.generic = getenv("QPN_DECODE_GENERIC") != nullptr;
@@ -1153,6 +1155,8 @@ static int decode_enqueue_impl(qpn_handle* h, hipStream_t stream, const DecodePl
                        h->aux_woff4, h->aux_tiles, h->logRa, g.A, g.Ap, g.C, g.L, h->d_pproj);
     p.wpk = (const float4*)h->d_wpk; p.flat = h->d_flat; p.qb = h->d_qb; p.tasks = h->d_tasks; p.utts = h->d_utts;
     p.status = h->d_status; p.mode = c.mode; p.seed = c.seed; p.bias_src = h->d_bias_src;
+    p.inv_temp = c.inv_temp; p.top_k = c.top_k;
+    if (c.mode == QPN_MODE_SAMPLING && (c.inv_temp != 1.0f || c.top_k != 0)) p.mode = QPN_MODE_SAMPLING_CTL;
     p.stamps = h->dk.stamps ? (long long*)(h->d_status + 16) : nullptr;
     p.pproj = h->d_pproj; p.dfac = c.d_dfac; p.known = h->d_known; p.teacher = d_teacher; p.out = c.d_out; p.logits = d_logits; p.ring = h->d_ring;
     QPN_HIP(hipEventRecord(h->ev0, stream));
@@ -1181,6 +1185,7 @@ extern "C" int qpn_decode_enqueue(qpn_handle* h, int B, int n_x, int64_t F, int6
     qpn_handle::DecodeCall& c = h->call;
     c.B = B; c.n_x = n_x; c.F = F; c.Td = Td; c.d_x = d_x; c.d_h = d_h; c.d_dfac = d_dfac; c.d_is_f32 = d_is_f32;
     c.n_samples.assign(h_n_samples, h_n_samples + B); c.maxd = maxd; c.mode = mode; c.seed = seed;
+    c.inv_temp = h->samp_inv_temp; c.top_k = h->samp_top_k;
     c.d_teacher = d_teacher; c.d_out = d_out; c.d_logits = d_logits;
     h->live_call = h->live_every > 0;
     h->live_final = false;
@@ -1196,6 +1201,25 @@ extern "C" int qpn_decode_live(qpn_handle* h, int every) {
     if (every < 0) { qpn_set_error("every must be >= 1 (arm) or 0 (disarm)"); return QPN_EINVAL; }
     if (h->pending) { qpn_set_error("a decode is in flight: call qpn_decode_finish first"); return QPN_ESTATE; }
     h->live_every = every;
+    return QPN_OK;
+}
+
+// the argument checks qpn_decode_sampling and qpn_sample_logits share: -> 1 / temperature, and top_k with "every class" (0 or Q) as 0
+static int sampling_controls(float temperature, int top_k, int Q, float* inv_temp, int* k) {
+    if (!(temperature > 0.0f) || std::isinf(temperature)) { qpn_set_error("temperature must be a finite number > 0 (got %g)", (double)temperature); return QPN_EINVAL; }
+    const float inv = 1.0f / temperature;
+    if (!std::isfinite(inv)) { qpn_set_error("temperature %g is too small: 1 / temperature is not a finite float", (double)temperature); return QPN_EINVAL; }
+    if (top_k < 0 || top_k > Q) { qpn_set_error("top_k must be 0 (off) or 1..n_quantize = %d (got %d)", Q, top_k); return QPN_EINVAL; }
+    *inv_temp = inv; *k = top_k == Q ? 0 : top_k;
+    return QPN_OK;
+}
+
+extern "C" int qpn_decode_sampling(qpn_handle* h, float temperature, int top_k) {
+    if (!h) { qpn_set_error("null handle"); return QPN_EINVAL; }
+    float inv; int k;
+    int rc = sampling_controls(temperature, top_k, h->g.Q, &inv, &k); if (rc) return rc;
+    if (h->pending) { qpn_set_error("a decode is in flight: call qpn_decode_finish first"); return QPN_ESTATE; }
+    h->samp_inv_temp = inv; h->samp_top_k = k;
     return QPN_OK;
 }
 
@@ -1326,9 +1350,34 @@ __global__ void k_didx_gen64(const double* __restrict__ d, int64_t n, int dilati
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (int32_t)rint(-d[i] * (double)dilation);
 }
+// ---------------------------------------------------------------- stand-alone draw from given logits
+// one wave per row: the row goes to LDS where the decode kernels keep their logits, and the wave calls the device function their picks call
+__global__ __launch_bounds__(64) void k_sample_logits(const float* __restrict__ lg, int Q, unsigned long long seed, unsigned row, unsigned step0,
+                                                      float inv_temp, int top_k, int64_t* __restrict__ out) {
+    const int lane = threadIdx.x;
+    const float* src = lg + (size_t)blockIdx.x * Q;
+    for (int i = lane; i < Q; i += 64) SM[i] = src[i];
+    __syncthreads();
+    const unsigned step = step0 + blockIdx.x;
+    const int bi = (inv_temp != 1.0f || top_k != 0) ? sample_wave_ctl(0, Q, sample_uniform(seed, row, step), inv_temp, top_k, lane)
+                                                     : sample_wave(0, Q, seed, row, step, lane);
+    if (lane == 0) out[blockIdx.x] = bi;
+}
 static int dev_ok() {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n < 1) { qpn_set_error("no HIP device: libqpnet_hip has no CPU fallback"); return QPN_ENODEV; }
+    return QPN_OK;
+}
+extern "C" int qpn_sample_logits(const float* d_logits, int64_t n_rows, int Q, uint64_t seed, int row, int64_t step0, float temperature, int top_k,
+                                 int64_t* d_out, void* stream) {
+    if (Q < 64 || Q % 64 || Q > 256) { qpn_set_error("sampling needs Q = n_quantize in {64,128,192,256}"); return QPN_EINVAL; }
+    float inv; int k;
+    int rc = sampling_controls(temperature, top_k, Q, &inv, &k); if (rc) return rc;
+    if (!d_logits || !d_out || n_rows < 1 || row < 0 || step0 < 0 || step0 + n_rows > ((int64_t)1 << 31)) { qpn_set_error("bad arguments (n_rows >= 1, row >= 0, 0 <= step0, step0 + n_rows <= 2^31)"); return QPN_EINVAL; }
+    rc = dev_ok(); if (rc) return rc;
+    hipLaunchKernelGGL(k_sample_logits, dim3((unsigned)n_rows), dim3(64), (size_t)Q * sizeof(float), (hipStream_t)stream, d_logits, Q, (unsigned long long)seed,
+                       (unsigned)row, (unsigned)step0, inv, k, d_out);
+    QPN_HIP(hipGetLastError());
     return QPN_OK;
 }
 extern "C" int qpn_dilated_index_train(const float* d_d, int B, int64_t L, int dilation, int64_t* d_out, void* stream) {

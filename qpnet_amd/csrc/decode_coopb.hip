@@ -334,7 +334,7 @@ __global__ __launch_bounds__(CBB_NT) void k_decode_coopb(const DecodeParams p, c
             if (i >= 0 && u.logits && w == 0) for (int q = lane; q < Q; q += 64) u.logits[(size_t)i * Q + q] = sm[o_lg + k * Q + q];
             int next;
             if (i >= 0) {
-                if (p.mode == QPN_MODE_SAMPLING) bi = sample_wave(o_lg + k * Q, Q, p.seed, (unsigned)u.row, (unsigned)i, lane);
+                if (p.mode != QPN_MODE_ARGMAX) bi = sample_pick(p, o_lg + k * Q, Q, (unsigned)u.row, (unsigned)i, lane);
                 next = bi;
                 if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
                 if (lane == 0 && w == 0) {

@@ -213,6 +213,86 @@ __device__ __forceinline__ int sample_wave(int o_lg, int Q, unsigned long long s
     return sample_wave_u(o_lg, Q, sample_uniform(seed, row, step), lane);
 }
 
+// ---------------------------------------------------------------- sampling controls (qpn_decode_sampling)
+// The draw above with a temperature (invT = 1 / T, formed on the host) and a top-k cut: e_c = qexp((l_c - m) * invT) for the classes of the
+// kept set K = { c : l_c >= k-th largest logit } (ties with the k-th are all kept; k == 0 or k >= Q: every class), 0 otherwise; the pick is the
+// first class OF K whose running cumulative exceeds th, or the highest class of K when none does.  invT == 1 and k == 0 give sample_wave_u's
+// bits, but the call sites take that function then (sample_pick below): this one is reached by calls that set a control.
+//
+// The k-th largest logit is selected in registers.  A logit maps to a 32-bit key whose unsigned order is the float order (-0.0 is made +0.0
+// first; the lanes' padding slots hold key 0, below every finite or infinite float's); the threshold key is built from the top bit down:
+// a candidate stays when at least k keys reach it -- `per` compares and `per` scalar pop-counts, every intermediate wave-uniform, no LDS and no
+// cross-lane data movement.  A candidate that exactly k keys reach ends the search early: those k keys are the k largest, and nothing tied
+// with the smallest of them lies outside (it would reach the candidate too), so { key >= candidate } is K.  Distinct logits end it after the
+// bits that tell the k-th from the (k+1)-th largest apart; rows with ties at the k-th value run all 32.
+__device__ __forceinline__ unsigned sample_key(float v) {
+    unsigned b = __float_as_uint(v);
+    if (b == 0x80000000u) b = 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ int sample_wave_ctl(int o_lg, int Q, float u, float invT, int k, int lane) {
+    const float* lg = SM + o_lg;
+    const int per = Q >> 6;
+    float l[4], e[4];
+    unsigned key[4];
+    float m = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { l[j] = j < per ? lg[lane * per + j] : -INFINITY; m = fmaxf(m, l[j]); key[j] = j < per ? sample_key(l[j]) : 0u; }
+    m = fmaxf(m, dpp_f<0xB1>(m)); m = fmaxf(m, dpp_f<0x4E>(m)); m = fmaxf(m, dpp_f<0x124>(m)); m = fmaxf(m, dpp_f<0x128>(m));
+    m = fmaxf(fmaxf(rl_f(m, 0), rl_f(m, 16)), fmaxf(rl_f(m, 32), rl_f(m, 48)));
+    unsigned thr = 0u;              // K = { key >= thr }: key 0 keeps every class
+    if (k > 0 && k < Q) {
+        for (int bit = 31; bit >= 0; --bit) {
+            const unsigned cand = thr | (1u << bit);
+            int cnt = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(key[j] >= cand));      // (padding slots: key 0 < cand)
+            if (cnt >= k) thr = cand;
+            if (cnt == k) break;
+        }
+    }
+    bool keep[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { keep[j] = j < per && key[j] >= thr; e[j] = keep[j] ? qexp((l[j] - m) * invT) : 0.0f; }
+    float a = e[0];
+#pragma unroll
+    for (int j = 1; j < 4; ++j) if (j < per) a = a + e[j];
+    float v = a;
+    { const float up = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, true)); if (lane >= 1) v = v + up; }
+    for (int d = 2; d < 64; d <<= 1) { const float up = __shfl_up(v, d); if (lane >= d) v = v + up; }
+    const float total = rl_f(v, 63);
+    float c = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, true));
+    if (lane == 0) c = 0.0f;
+    const float th = u * total;
+    int idx = 0x7fffffff, hi = -1;      // first class of K past the threshold / highest class of K, of this lane
+#pragma unroll
+    for (int j = 0; j < 4; ++j) if (j < per) {
+        c = c + e[j];
+        if (keep[j]) { hi = lane * per + j; if (idx == 0x7fffffff && c > th) idx = lane * per + j; }
+    }
+#define QPN_IMIN(CTRL) { const int o_ = __builtin_amdgcn_update_dpp(0x7fffffff, idx, CTRL, 0xf, 0xf, false); idx = o_ < idx ? o_ : idx; }
+    QPN_IMIN(0xB1) QPN_IMIN(0x4E) QPN_IMIN(0x124) QPN_IMIN(0x128)
+#undef QPN_IMIN
+    {
+        const int i0 = __builtin_amdgcn_readlane(idx, 0), i1 = __builtin_amdgcn_readlane(idx, 16), i2 = __builtin_amdgcn_readlane(idx, 32), i3 = __builtin_amdgcn_readlane(idx, 48);
+        const int a01 = i0 < i1 ? i0 : i1, a23 = i2 < i3 ? i2 : i3;
+        idx = a01 < a23 ? a01 : a23;
+    }
+    if (idx != 0x7fffffff) return idx;
+    // no class fired (th rounded up to the scanned total, the lanes' running sums to less): the highest class of K.  Lanes hold ascending
+    // class ranges, so that is the `hi` of the highest lane that kept anything
+    const unsigned long long any = __builtin_amdgcn_ballot_w64(hi >= 0);
+    return any ? __builtin_amdgcn_readlane(hi, 63 - __builtin_clzll(any)) : Q - 1;
+}
+// what the decode kernels' picks call when p.mode is not QPN_MODE_ARGMAX.  The host folds "a control is set" into the mode word the picks test anyway
+// (QPN_MODE_SAMPLING_CTL, qpn_common.h): one wave-uniform compare of a kernel argument selects the draw, a default call runs sample_wave / sample_wave_u
+// untouched, and the controls themselves (DecodeParams.inv_temp / top_k, kernel arguments too: a captured launch replays them) are read on the
+// controlled path only
+__device__ __forceinline__ int sample_pick(const DecodeParams& p, int o_lg, int Q, unsigned row, unsigned step, int lane) {
+    if (p.mode == QPN_MODE_SAMPLING) return sample_wave(o_lg, Q, p.seed, row, step, lane);
+    return sample_wave_ctl(o_lg, Q, sample_uniform(p.seed, row, step), p.inv_temp, p.top_k, lane);
+}
+
 struct UttView {            // per-utterance pointers derived from kernel-argument bases (global address space)
     const float* pproj; const void* dfac; const int* known; const int64_t* teacher; int64_t* out; float* logits; float* ring;
     int n_pad, n0, n_samples, d_is_f32, row;

@@ -451,7 +451,7 @@ __device__ __forceinline__ void skip_fixed_role(const DecodeParams& p, const Fas
 }
 
 // ------------------------------------------------------------------------------------------------ P: post 1x1 #2, pick, causal rows
-template <int NU>
+template <int NU, bool CTL>      // CTL: the launch draws with a sampling control set (QPN_MODE_SAMPLING_CTL: sample_wave_ctl); a kernel of its own, see k_decode_pipe_c
 __device__ __forceinline__ void post2_pick_role(const DecodeParams& p, const FastParams& f, const PipeParams& pp, const PipeUtt (&cx)[NU]) {
     constexpr int C = 64;
     float* sm = SM; int* smi = SMI;
@@ -488,7 +488,7 @@ __device__ __forceinline__ void post2_pick_role(const DecodeParams& p, const Fas
     int Tmax = 0, t_begin = 0x7fffffff;
 #pragma unroll
     for (int v = 0; v < NU; ++v) { Tmax = cx[v].Ttot > Tmax ? cx[v].Ttot : Tmax; const int tb = cx[v].u.n0 - 1 > 1 ? cx[v].u.n0 - 1 : 1; t_begin = tb < t_begin ? tb : t_begin; }
-    const bool sampling = p.mode == QPN_MODE_SAMPLING;
+    const bool sampling = CTL || p.mode == QPN_MODE_SAMPLING;
     __syncthreads();
     if (Tmax < 3) return;
     // the host's stop request (live_put): the publishing lane's state, one for the rows of the group; a launch that starts after the request
@@ -544,7 +544,8 @@ __device__ __forceinline__ void post2_pick_role(const DecodeParams& p, const Fas
             wg_barrier();                                         // LDS only (the polls' / hand-offs' global traffic is not waited for)
             if (wave == 0) {
                 int bi;
-                if (sampling) bi = sample_wave_u(vb + o_lg, Q, uni, lane);
+                if constexpr (CTL) bi = sample_wave_ctl(vb + o_lg, Q, uni, p.inv_temp, p.top_k, lane);
+                else if (sampling) bi = sample_wave_u(vb + o_lg, Q, uni, lane);
                 else {
                     float bv;
                     {   // lane owns four consecutive classes (one ds_read_b128); lowest index among maxima
@@ -588,7 +589,7 @@ __device__ __forceinline__ void post2_pick_role(const DecodeParams& p, const Fas
     }
 }
 
-template <int NU>
+template <int NU, bool CTL = false>
 __device__ __forceinline__ void pipe_group(const DecodeParams& p, const FastParams& f, const PipeParams& pp, int role, int row0, int n_active) {
     PipeUtt cx[NU];
 #pragma unroll
@@ -602,7 +603,7 @@ __device__ __forceinline__ void pipe_group(const DecodeParams& p, const FastPara
     if (role == 0) stack_role<false, NU>(p, f, pp, cx);
     else if (role == 1) stack_role<true, NU>(p, f, pp, cx);
     else if (role == 2) skip_post1_role<NU>(p, f, pp, cx);
-    else if (role == 3) post2_pick_role<NU>(p, f, pp, cx);
+    else if (role == 3) post2_pick_role<NU, CTL>(p, f, pp, cx);
     else skip_fixed_role<NU>(p, f, pp, cx);
 }
 
@@ -622,6 +623,24 @@ __global__ __launch_bounds__(PIPE_NT) void k_decode_pipe_n(DecodeParams p, FastP
     const int first_big = pp.groups - pp.rem;
     const int row0 = gi * pp.base + (gi > first_big ? gi - first_big : 0), cnt = pp.base + (gi >= first_big ? 1 : 0);
     pipe_group<NU>(p, f, pp, role, row0, cnt);
+}
+// ... and the launches of a call that set a sampling control (qpn_decode_sampling; p.mode == QPN_MODE_SAMPLING_CTL): the same roles with the
+// controlled draw in the pick.  Kernels of their own for the same reason: the five roles share one whole-kernel register allocation (the K role
+// takes all 256 VGPRs, the scalar registers spill), and the selection loop inlined behind a runtime branch cost the DEFAULT calls 0.4 % (greedy)
+// to 0.7 % (sampling) of their step time (three alternating runs against the parent build, B = 20: 8.25 / 8.67 us against 8.22 / 8.60).  With
+// the draw chosen at compile time the default kernels hold no instruction of it.  NU = 1: the block mapping of k_decode_pipe
+template <int NU>
+__global__ __launch_bounds__(PIPE_NT) void k_decode_pipe_c(DecodeParams p, FastParams f, PipeParams pp) {
+    const int chunk = blockIdx.x / 40, within = blockIdx.x - chunk * 40, role = within >> 3, gi = chunk * 8 + (within & 7);
+    if constexpr (NU == 1) {
+        if (gi >= pp.nutt) return;
+        pipe_group<1, true>(p, f, pp, role, gi, 1);
+    } else {
+        if (gi >= pp.groups) return;
+        const int first_big = pp.groups - pp.rem;
+        const int row0 = gi * pp.base + (gi > first_big ? gi - first_big : 0), cnt = pp.base + (gi >= first_big ? 1 : 0);
+        pipe_group<NU, true>(p, f, pp, role, row0, cnt);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -673,10 +692,16 @@ int qpn_launch_decode_pipe(qpn_handle* h, DecodeParams p, const DecodeLaunch& l,
     }
 #endif
     const size_t lds = pipe_lds_bytes(nu);
-    const void* kfn = nu == 1 ? (const void*)k_decode_pipe : nu == 2 ? (const void*)k_decode_pipe_n<2> : (const void*)k_decode_pipe_n<3>;
+    const bool ctl = p.mode == QPN_MODE_SAMPLING_CTL;
+    const void* kfn = ctl ? (nu == 1 ? (const void*)k_decode_pipe_c<1> : nu == 2 ? (const void*)k_decode_pipe_c<2> : (const void*)k_decode_pipe_c<3>)
+                          : (nu == 1 ? (const void*)k_decode_pipe : nu == 2 ? (const void*)k_decode_pipe_n<2> : (const void*)k_decode_pipe_n<3>);
     QPN_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));    // per device: set at every launch
     const int nchunks = (groups + 7) / 8;
-    if (nu == 1) hipLaunchKernelGGL(k_decode_pipe, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, h->fp, pp);
+    if (ctl) {
+        if (nu == 1) hipLaunchKernelGGL(k_decode_pipe_c<1>, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, h->fp, pp);
+        else if (nu == 2) hipLaunchKernelGGL(k_decode_pipe_c<2>, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, h->fp, pp);
+        else hipLaunchKernelGGL(k_decode_pipe_c<3>, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, h->fp, pp);
+    } else if (nu == 1) hipLaunchKernelGGL(k_decode_pipe, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, h->fp, pp);
     else if (nu == 2) hipLaunchKernelGGL(k_decode_pipe_n<2>, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, h->fp, pp);
     else hipLaunchKernelGGL(k_decode_pipe_n<3>, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, h->fp, pp);
     QPN_HIP(hipGetLastError());

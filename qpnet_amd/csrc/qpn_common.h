@@ -48,6 +48,7 @@ int qpn_build_geom(const qpn_config* cfg, Geom* g);
 __host__ __device__ static inline int qpn_pad_k(int K) { int R = 1; while (16 * R < K) R *= 2; return 16 * R; }
 
 // ---------------------------------------------------------------- decode program
+#define QPN_MODE_SAMPLING_CTL 2   // DecodeParams.mode only, never an ABI value: QPN_MODE_SAMPLING with a sampling control set (qpn_decode_sampling)
 enum {
     OP_NOP = 0, OP_PAST, OP_Z, OP_RES, OP_SKIP, OP_POST1, OP_POST2, OP_CAUSAL, OP_ARGMAX, OP_STAGE
 };
@@ -121,6 +122,7 @@ struct DecodeParams {
     int o_wres;             // specialised kernel: residual-1x1 tiles of layers 0..L-2 resident in LDS (float offset, 16-byte aligned)
     const int* bias_src;    // [n_bias] flat indices of the biases mirrored in LDS
     unsigned long long seed;
+    float inv_temp; int top_k;   // sampling controls (qpn_decode_sampling): 1 / temperature and the top-k cut, 1.0f / 0 = off (sample_wave_ctl, decode_dev.h)
     RingDesc rings[QPN_MAX_LAYERS];
     // live output (qpn_decode_live), all null / 0 when it is not armed.  Host-coherent pinned memory that the host reads WHILE the launch runs:
     int32_t* live;          // mirror of `out` ([B][max_n], the element offsets of UttDesc.out)

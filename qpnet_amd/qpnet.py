@@ -216,14 +216,18 @@ class QPNet(nn.Module):
 
     # ------------------------------------------------------------------ autoregressive decode
     def batch_fast_generate(self, x, h, n_samples_list, dilated_factors,
-                            intervals=None, mode="sampling", extra_memory=False):
+                            intervals=None, mode="sampling", extra_memory=False, *, temperature=1.0, top_k=0):
         """Batch fast generation (reference qpnet.py:314-559).
 
         x (B,T0) long seed, h (B,n_aux,F) float, n_samples_list list[int] (consumed exactly like
         the reference does), dilated_factors (B,T): numpy float64 when extra_memory is False,
         float tensor otherwise.  Returns the list of int64 ndarrays in completion order
-        (ascending length, ties in input order)."""
-        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory)
+        (ascending length, ties in input order).
+
+        temperature, top_k (keyword-only, not in the reference; mode="sampling" only): the draw is taken from softmax(logits / temperature)
+        over the classes whose logit is at least the top_k-th largest (ties with it kept; 0 = every class), inside the decode kernel
+        (qpn_decode_sampling).  The defaults are the reference's draw.  The values hold for this call only."""
+        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature, top_k)
         L, hd, dev, B, ns, max_n, out, stream = a["L"], a["hd"], a["dev"], a["B"], a["ns"], a["max_n"], a["out"], a["stream"]
         t_start = a["t_start"]
         with torch.cuda.device(dev):
@@ -246,16 +250,34 @@ class QPNet(nn.Module):
         n_samples_list.append(keep)
         return result
 
-    def _decode_args(self, x, h, n_samples_list, dilated_factors, mode, extra_memory):
+    def _sampling_controls(self, mode, temperature, top_k):
+        """temperature / top_k of a decode call, checked on the host before anything touches the device -> (float, int)."""
+        try:
+            t = float(temperature)
+        except (TypeError, ValueError):
+            raise ValueError("temperature must be a number, not %r" % (temperature,))
+        with np.errstate(all="ignore"):
+            ok = np.isfinite(np.float32(t)) and t > 0 and np.isfinite(np.float32(1.0) / np.float32(t))
+        if not ok:
+            raise ValueError("temperature must be a finite float32 > 0 whose reciprocal is finite, not %r" % (temperature,))
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 0 <= int(top_k) <= self.n_quantize:
+            raise ValueError("top_k must be an int in 0..n_quantize = %d (0: off), not %r" % (self.n_quantize, top_k))
+        if mode == "argmax" and (t != 1.0 or int(top_k) != 0):
+            raise ValueError("temperature / top_k shape the draw of mode='sampling'; mode='argmax' takes neither")
+        return t, int(top_k)
+
+    def _decode_args(self, x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature=1.0, top_k=0):
         """What batch_fast_generate and generate_live do before the library call: mode check, maxd, dtype and device moves, the
         output buffer, the sampling seed, binding the weights.  -> dict; "call" is the argument tuple of qpn_decode / qpn_decode_enqueue, the rest
         keeps the tensors behind its pointers alive."""
         if mode not in ("sampling", "argmax"):
             logging.error("mode should be sampling or argmax")
             sys.exit(1)
+        temperature, top_k = self._sampling_controls(mode, temperature, top_k)
         import ctypes as C
         dev = x.device
         L, hd = self._native(dev)
+        _lib.check(L.qpn_decode_sampling(hd, temperature, top_k))      # this call's values, set before every enqueue: nothing is left over from the last call
         B = len(n_samples_list)
         assert x.shape[0] == B and h.shape[0] == B
         # maxd exactly as the reference computes it (qpnet.py:347-350)
@@ -292,7 +314,7 @@ class QPNet(nn.Module):
 
     # ------------------------------------------------------------------ live decode output
     def generate_live(self, x, h, n_samples_list, dilated_factors, intervals=None, mode="sampling",
-                      extra_memory=False, every=256, poll_s=0.001, on_close="finish"):
+                      extra_memory=False, every=256, poll_s=0.001, on_close="finish", *, temperature=1.0, top_k=0):
         """batch_fast_generate as a generator that hands samples over while the decode kernel runs: yields (row, start, samples)
         -- row = index in the input order, samples = a fresh int64 ndarray holding that row's samples [start, start + len) --
         as soon as a poll of the library (qpn_decode_poll) shows new finished samples of a row.  A row's pieces are contiguous
@@ -307,17 +329,19 @@ class QPNet(nn.Module):
         (`every` samples of the longest-running row each) plus the drain of the launch.  A generator that is iterated to its end
         never cancels.  After the generator has ended, either way, last_decode_counts holds every row's final count in input
         order (samples below it are valid; n_samples for a call that ran to its end) and last_decode_cancelled whether the call
-        stopped short on request."""
+        stopped short on request.  temperature / top_k: as in batch_fast_generate."""
         if on_close not in ("finish", "cancel"):
             raise ValueError("on_close must be 'finish' or 'cancel', not %r" % (on_close,))
         if int(every) < 1:
             raise ValueError("every must be >= 1")
+        if mode in ("sampling", "argmax"):
+            self._sampling_controls(mode, temperature, top_k)          # (bad values are refused here, at the call, not at the first next())
         self._native(x.device)          # (CPU tensors are refused here, at the call, not at the first next())
-        return self._live_pieces(x, h, list(n_samples_list), dilated_factors, intervals, mode, extra_memory, int(every), float(poll_s), on_close == "cancel")
+        return self._live_pieces(x, h, list(n_samples_list), dilated_factors, intervals, mode, extra_memory, int(every), float(poll_s), on_close == "cancel", temperature, top_k)
 
-    def _live_pieces(self, x, h, n_samples_list, dilated_factors, intervals, mode, extra_memory, every, poll_s, cancel_on_close):
+    def _live_pieces(self, x, h, n_samples_list, dilated_factors, intervals, mode, extra_memory, every, poll_s, cancel_on_close, temperature=1.0, top_k=0):
         import ctypes as C
-        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory)
+        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature, top_k)
         L, hd, dev, B, ns, max_n, out, stream = a["L"], a["hd"], a["dev"], a["B"], a["ns"], a["max_n"], a["out"], a["stream"]
         done = (C.c_int64 * B)()
         mirror, stride, running = C.POINTER(C.c_int32)(), C.c_int64(), C.c_int()
