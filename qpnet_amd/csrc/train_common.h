@@ -37,8 +37,8 @@ struct TrainParams {
     // global buffers
     const float* flat;        // parameters (state_dict order)
     const float4* wp;         // fragment-ordered weights
-    const float* ct;          // causal conv table transposed to [tap][class][C] (a row per looked-up class: coalesced)
-    float* bp;                // packed biases (hoist: k_aux_proj adds b_up * sum_a Va[n][a] to the gate biases)
+    const float* ct;          // causal conv table transposed to [tap][class][C] (a row per looked-up class: coalesced); written by k_refresh, read by k_train_prep -- k_step_prep builds its slices in LDS instead
+    float* bp;                // packed biases (hoist: + b_up * sum_a Va[n][a] on the gate biases -- k_step_prep's bias role, or aux_proj_block behind k_refresh)
     const int64_t* x; const float* h; const float* d;
     float* X;                 // [L+1][B][N1][C]
     float* SG; float* TH;     // [L][B][N1][C]: sigma, and -- on the tile path -- the gate PRODUCT sigma * tanh (tr_gate_bwd below; the GEMM path of the wide stacks keeps tanh here and the product in TrainGemm::G)
@@ -120,6 +120,9 @@ static inline AuxArgs tr_aux_args(const TrainParams& p, const TrainBwd* bw, cons
     a.C = p.C; a.A = p.A; a.L = p.L; a.B = p.B; a.F = p.F; a.U = p.U; a.N1 = p.N1; a.nfr = p.nfr; a.ffirst = p.ffirst; a.up_w = p.up_w; a.up_b = p.up_b; a.g = ag;
     return a;
 }
+// What the per-step refresh gathers from the flat parameters (k_refresh, or the refresh roles of k_step_prep): the fragment-ordered weight blocks through
+// their map, the packed biases through their CSR lists (into TrainParams::bp); `loss`: the 64 partial sums of the coming step's loss, cleared
+struct RefreshArgs { const int* wmap; float* wout; int64_t nw; const int* bstart; const int* blist; int nb; double* loss; };
 // Launch-plan knobs, parsed ONCE per handle from the environment (train_init): nothing in the per-step launch path calls getenv().
 // All optional; the defaults are the measured best.  tests/test_train_gpu.py builds a fresh model (= a fresh handle) per arrangement.
 struct TrainKnobs {
@@ -135,6 +138,7 @@ struct TrainKnobs {
     bool xcd_swizzle;                 // QPN_NO_XCD_SWIZZLE=1 clears it
     bool ce_separate;                 // QPN_CE_SEPARATE=1: cross entropy as its own kernel behind the forward
     bool event_fence;                 // QPN_EVENT_FENCE=1: system-scope fence at the fork / join events
+    bool prep_fuse;                   // QPN_PREP_FUSE=0: the per-step refresh (k_refresh) and the chunk's preparation (k_train_prep) as two launches instead of k_step_prep's one
     bool aux_hoist;                   // QPN_AUX_HOIST=0: the auxiliary 1x1 contracted at sample rate (K = 176) even where the frame-rate form applies
     bool test_stack_gives_up;         // -DQPN_TESTING builds only (QPN_TEST_STACK_GIVES_UP=1): the queue launches' published flags are made unrecognisable
 };

@@ -26,6 +26,7 @@ __device__ __forceinline__ float tanhf_(float z) { return 2.0f * __builtin_amdgc
 // (qpnet.py:134-158): L x nfr x 2C x n_aux MACs per batch item instead of L x N1 x 2C x 48.  A role of k_train_prep's launch: one workgroup per
 // (AUXP_FPB frames, layer, batch item); thread = (gate row n, half of the frames).
 #define AUXP_FPB 8                                    // frames per workgroup
+template <bool BIAS>      // BIAS: this launch also adds the constant term to the packed gate bias (k_train_prep; k_step_prep's bias role has it)
 __device__ __forceinline__ void aux_proj_block(const TrainParams& p, const AuxGeom& ag, int fxb, int l, int b, float* sm) {
     // sm: Va_l [2C][A] (A odd: conflict-free column reads; even A: two-way), h tile [A][AUXP_FPB]
     const int fx0 = fxb * AUXP_FPB, tid = threadIdx.x, n = tid & 127, fh = tid >> 7, C = p.C, A = p.A, CA = C * A;
@@ -56,7 +57,7 @@ __device__ __forceinline__ void aux_proj_block(const TrainParams& p, const AuxGe
 #pragma unroll
     for (int f = 0; f < 4; ++f) if (fx0 + 4 * fh + f <= p.nfr) out[(size_t)f * 2 * C] = acc[f];
     // the constant part of the upsampled features, b_up * sum_a Va[n][a], joins the packed gate bias (written by k_refresh, earlier on this stream): one writer per (layer, gate row)
-    if (fxb == 0 && b == 0 && fh == 0) p.bp[ag.bias1[l] + n] += p.flat[p.up_b] * vs;
+    if (BIAS && fxb == 0 && b == 0 && fh == 0) p.bp[ag.bias1[l] + n] += p.flat[p.up_b] * vs;
 }
 
 // Elementwise over (row, 4 channels): every access is a coalesced 16-byte load / store, no per-row serialisation.
@@ -65,32 +66,27 @@ __device__ __forceinline__ void aux_proj_block(const TrainParams& p, const AuxGe
 //   items [.., + N1*L)               : tap row of layer l at row n: pitch-dependent (adaptive) or n - dilation (fixed) -- a table for
 //                                      every layer lets the consumers load taps without a branch (+ the class ids XC for the table gradient)
 //   aux hoist: the workgroups behind the first `nprep` are aux_proj_block's
-__global__ __launch_bounds__(256) void k_train_prep(TrainParams p, AuxGeom ag, int nprep) {
-    const int b = blockIdx.y;
-    if ((int)blockIdx.x >= nprep) {
-        extern __shared__ float sm[];
-        const int idx = blockIdx.x - nprep, nfxb = (p.nfr + 1 + AUXP_FPB - 1) / AUXP_FPB;
-        aux_proj_block(p, ag, idx % nfxb, idx / nfxb, b, sm);
-        return;
-    }
+//   X0 = false (k_step_prep): without the first kind of items -- the launch's table workgroups compute X0 and XC
+template <bool X0>
+__device__ __forceinline__ void prep_items(const TrainParams& p, const int bx, const int nprep, const int b) {
     const int C = p.C, Q = p.Q, N1 = p.N1, Ap = p.Ap;
     const int C4 = C / 4, A4 = Ap / 4;
     const int nX = N1 * C4, nH = p.hoist ? 0 : N1 * A4;          // (aux hoist: no sample-rate aux rows; the frame-rate projections are k_aux_proj's)
     const int total = nX + nH + N1 * p.L;
     if (p.hoist && b == 0)         // row -> {w_up[j], j}: the upsampling weight and within-frame offset of every row (and of 16 rows past the end: the pattern continues)
-        for (int n = blockIdx.x * 256 + threadIdx.x; n < N1 + 16; n += nprep * 256) {
+        for (int n = bx * 256 + threadIdx.x; n < N1 + 16; n += nprep * 256) {
             const int q = p.F * p.U - N1 + n, j = q - (q / p.U) * p.U;
             p.WJ[n] = make_float2(p.flat[p.up_w + j], __int_as_float(j));
         }
-    if (p.qctl && blockIdx.x == 0 && b == 0 && threadIdx.x < 32) p.qctl[threadIdx.x < 16 ? threadIdx.x : 1024 + (threadIdx.x - 16) * TR_QHEAD_STRIDE] = 0u;      // abort word / counters / sub-queue heads of this step's stack queues (train_stack.hip)
+    if (p.qctl && bx == 0 && b == 0 && threadIdx.x < 32) p.qctl[threadIdx.x < 16 ? threadIdx.x : 1024 + (threadIdx.x - 16) * TR_QHEAD_STRIDE] = 0u;      // abort word / counters / sub-queue heads of this step's stack queues (train_stack.hip)
     if (p.qtab && b == 0)          // tile table of the one-launch residual stack (train_stack.hip)
-        for (int pos = blockIdx.x * 256 + threadIdx.x; pos <= p.qtotal; pos += nprep * 256) {
+        for (int pos = bx * 256 + threadIdx.x; pos <= p.qtotal; pos += nprep * 256) {
             int4 ea, eb; tr_queue_entry_fwd(p, pos, ea, eb);
             p.qtab[2 * pos] = ea; p.qtab[2 * pos + 1] = eb;
             if (p.qtab_b) { tr_queue_entry_bwd(p, pos, ea, eb); p.qtab_b[2 * pos] = ea; p.qtab_b[2 * pos + 1] = eb; }
         }
-    for (int it = blockIdx.x * 256 + threadIdx.x; it < total; it += nprep * 256) {
-        if (it < nX) {
+    for (int it = (X0 ? 0 : nX) + bx * 256 + threadIdx.x; it < total; it += nprep * 256) {
+        if (X0 && it < nX) {
             const int n = it / C4, c = (it - n * C4) * 4;
             const int64_t xo = (int64_t)p.T - p.N0 + n;
             int64_t s0 = p.x[(size_t)b * p.T + xo] % Q, s1 = p.x[(size_t)b * p.T + xo + 1] % Q;
@@ -135,6 +131,133 @@ __global__ __launch_bounds__(256) void k_train_prep(TrainParams p, AuxGeom ag, i
             p.TAP[ly.tap_off + (size_t)b * N1 + n] = tap;
         }
     }
+}
+__global__ __launch_bounds__(256) void k_train_prep(TrainParams p, AuxGeom ag, int nprep) {
+    const int b = blockIdx.y;
+    if ((int)blockIdx.x >= nprep) {
+        extern __shared__ float sm[];
+        const int idx = blockIdx.x - nprep, nfxb = (p.nfr + 1 + AUXP_FPB - 1) / AUXP_FPB;
+        aux_proj_block<true>(p, ag, idx % nfxb, idx / nfxb, b, sm);
+        return;
+    }
+    prep_items<true>(p, blockIdx.x, nprep, b);
+}
+
+// ------------------------------------------------------------------------------------------------ the step's first launch: refresh + prep
+// k_refresh and k_train_prep were two launches because of two small dependencies: X0 looked its rows up in the transposed causal table the refresh
+// had written, and the aux hoist added its constant term onto a packed bias the refresh had stored.  Here every workgroup takes ONE role by block
+// index and no role waits for another (roles with the longest dependent chain first: a scheduling hint only):
+//   table     : X0 / XC.  A workgroup owns X0_CS channels and up to X0_RPG consecutive rows of the flattened (batch item, row) range.  Its slice of
+//               the causal parameter block [C][Q][2] is CONTIGUOUS (channel-major): read once with coalesced 16-byte loads and transposed into LDS as
+//               [tap][class][X0_ST] (row stride 17: a wave's writes -- one channel, every second class -- spread over 32 of the 64 banks; a stride of 16 puts them on two).  The
+//               classes of the rows are requested with the first table words.  Then X0[row][c] = (r0 + r1) + bias from LDS, today's order.
+//               (A whole [2][Q][C] table per workgroup would be 128 KB of dynamic LDS for EVERY workgroup of the launch -- one per CU, also for the
+//               gather roles that live on occupancy; a 16-channel slice is 34 KB at Q = 256: four workgroups per CU.  The L2 reads are the same:
+//               workgroups x slice bytes.  8-channel slices, -DX0_CS=8 -DX0_ST=9, fit under the aux role's 21 KB, seven per CU: measured slower,
+//               12.7 against 11.2 us -- twice the table workgroups, 32-byte row pieces.)
+//   aux       : aux_proj_block, without the bias term
+//   bias      : packed bias sums (CSR), and for the gate-bias entries of a hoisted step + b_up * sum_a Va_l[n][a] -- the list sum first, then
+//               += up_b * vs with vs accumulated over a = 0 .. A-1: the stored value is bit-identical to k_refresh's followed by aux_proj_block's;
+//               the 64 items behind the biases clear the loss accumulator
+//   weights   : fragment-ordered weight blocks, four elements per thread (one int4 of the map, four gathers in flight, one 16-byte store)
+//   items     : prep_items<false>: aux rows (no hoist), tap tables, WJ, queue tables / heads / abort word
+#ifndef X0_CS
+#define X0_CS 16          // channels of a table slice
+#define X0_ST 17          // row stride of the slice's table in LDS
+#endif
+#define X0_RPG 512        // rows of a table workgroup at most
+struct StepPrepPlan { int nx0, rpg, naux, nbias, nwt, nprep; };     // workgroups per role (items: per batch item); rpg: rows of a table workgroup
+
+__device__ __forceinline__ void x0_block(const TrainParams& p, const int blk, const int rpg, float* sm) {
+    const int C = p.C, Q = p.Q, N1 = p.N1, tid = threadIdx.x;
+    const int nsl = C / X0_CS, grp = blk / nsl, c0 = (blk - grp * nsl) * X0_CS;
+    const int R = p.B * N1, r0 = grp * rpg, nr = R - r0 < rpg ? R - r0 : rpg;
+    float* tab = sm; int* cls = (int*)(sm + 2 * Q * X0_ST);          // cls: [2][rpg] classes of the rows' two taps
+    const float4* src = (const float4*)(p.flat + p.causal_w + (size_t)c0 * Q * 2);      // (16-byte aligned: checked by the host)
+    const int n4 = X0_CS * Q / 2;                                     // float4 words of the slice
+    const float bb = p.flat[p.causal_b + c0 + (tid & (X0_CS - 1))];
+    for (int base = 0; base < n4; base += 256 * 8) {
+        float4 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { const int e4 = base + 256 * k + tid; v[k] = src[e4 < n4 ? e4 : 0]; }
+        if (base == 0)
+            for (int j = tid; j < nr; j += 256) {
+                const int r = r0 + j, b = r / N1, n = r - b * N1;
+                const int64_t xo = (int64_t)p.T - p.N0 + n;
+                int64_t s0 = p.x[(size_t)b * p.T + xo] % Q, s1 = p.x[(size_t)b * p.T + xo + 1] % Q;
+                if (s0 < 0) s0 += Q;
+                if (s1 < 0) s1 += Q;
+                cls[j] = (int)s0; cls[rpg + j] = (int)s1;
+            }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int e4 = base + 256 * k + tid;
+            if (e4 < n4) {      // a float4 = {(q, tap 0), (q, tap 1), (q + 1, tap 0), (q + 1, tap 1)} of one channel
+                const int e = 4 * e4, cl = e / (2 * Q), q = (e - cl * 2 * Q) >> 1;
+                float* d = tab + q * X0_ST + cl;
+                d[0] = v[k].x; d[Q * X0_ST] = v[k].y; d[X0_ST] = v[k].z; d[(Q + 1) * X0_ST] = v[k].w;
+            }
+        }
+    }
+    __syncthreads();
+    const int c = tid & (X0_CS - 1);
+    for (int j = tid / X0_CS; j < nr; j += 256 / X0_CS) {
+        const int s0 = cls[j], s1 = cls[rpg + j], r = r0 + j;
+        p.X[(size_t)r * C + c0 + c] = (tab[s0 * X0_ST + c] + tab[(Q + s1) * X0_ST + c]) + bb;       // tap 0 = older sample (qpnet.py:110-132)
+        if (c0 == 0 && c == 0) {
+            const int b = r / N1, n = r - b * N1;
+            p.XC[(size_t)b * (N1 + 1) + n] = s0; if (n == N1 - 1) p.XC[(size_t)b * (N1 + 1) + N1] = s1;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_step_prep(TrainParams p, AuxGeom ag, RefreshArgs rf, StepPrepPlan pl) {
+    extern __shared__ float sm[];
+    int blk = blockIdx.x;
+    const int tid = threadIdx.x;
+    if (blk < pl.nx0) { x0_block(p, blk, pl.rpg, sm); return; }
+    blk -= pl.nx0;
+    if (blk < pl.naux) {
+        const int nfxb = (p.nfr + 1 + AUXP_FPB - 1) / AUXP_FPB, per_b = nfxb * p.L, b = blk / per_b, idx = blk - b * per_b;
+        aux_proj_block<false>(p, ag, idx % nfxb, idx / nfxb, b, sm);
+        return;
+    }
+    blk -= pl.naux;
+    if (blk < pl.nbias) {
+        const int i = blk * 256 + tid, C = p.C, A = p.A;
+        if (i >= rf.nb) { if (i < rf.nb + 64) rf.loss[i - rf.nb] = 0.0; return; }
+        int lg = -1, ng = 0;                       // gate-bias entry of a hoisted step: layer, gate row (sigma rows, then tanh rows)
+        if (p.hoist) for (int l = 0; l < p.L; ++l) { const int n = i - ag.bias1[l]; if (n >= 0 && n < 2 * C) { lg = l; ng = n; } }
+        float va[64];                              // (hoist: n_aux <= 64) the row's aux weights, requested before the list is walked
+        if (lg >= 0) {
+            const float* s = p.flat + (ng < C ? ag.auxS[lg] + ng * A : ag.auxT[lg] + (ng - C) * A);
+#pragma unroll
+            for (int a = 0; a < 64; ++a) va[a] = s[a < A ? a : 0];
+        }
+        float acc = 0.f;
+        for (int j = rf.bstart[i]; j < rf.bstart[i + 1]; ++j) acc += p.flat[rf.blist[j]];
+        if (lg >= 0) {
+            float vs = 0.f;
+#pragma unroll
+            for (int a = 0; a < 64; ++a) if (a < A) vs += va[a];
+            acc += p.flat[p.up_b] * vs;
+        }
+        p.bp[i] = acc;
+        return;
+    }
+    blk -= pl.nbias;
+    if (blk < pl.nwt) {
+        const int64_t i4 = (int64_t)blk * 256 + tid, i = i4 * 4;
+        if (i + 4 <= rf.nw) {
+            const int4 m = ((const int4*)rf.wmap)[i4];
+            const float t0 = p.flat[m.x >= 0 ? m.x : 0], t1 = p.flat[m.y >= 0 ? m.y : 0], t2 = p.flat[m.z >= 0 ? m.z : 0], t3 = p.flat[m.w >= 0 ? m.w : 0];
+            ((float4*)rf.wout)[i4] = make_float4(m.x >= 0 ? t0 : 0.f, m.y >= 0 ? t1 : 0.f, m.z >= 0 ? t2 : 0.f, m.w >= 0 ? t3 : 0.f);
+        } else for (int64_t k = i; k < rf.nw; ++k) { const int m = rf.wmap[k]; rf.wout[k] = m >= 0 ? p.flat[m] : 0.0f; }      // ragged end
+        return;
+    }
+    blk -= pl.nwt;
+    const int b = blk / pl.nprep;
+    prep_items<false>(p, blk - b * pl.nprep, pl.nprep, b);
 }
 
 // One gated residual block on one tile of TM = 16*MT time rows starting at row n0 of batch item b.
@@ -731,15 +854,46 @@ void qpn_launch_prep(const TrainParams& p, const AuxGeom& ag, hipStream_t stream
     hipLaunchKernelGGL(k_train_prep, dim3(blocks + naux, p.B), dim3(256), lds, stream, p, ag, blocks);
 }
 
+// the fused first launch (k_step_prep): whether this geometry takes it, and the launch.  Four workgroups of the launch per CU must stay resident
+// (its gather roles live on occupancy): 40 KB of dynamic LDS at most -- n_quantize up to 288 at 16 channels per table slice; larger tables keep
+// k_refresh + k_train_prep
+static size_t step_prep_lds_x0(const TrainParams& p, int rpg) { return ((size_t)2 * p.Q * X0_ST + 2 * (size_t)rpg) * sizeof(float); }
+static int step_prep_rpg(const TrainParams& p) {
+    const int64_t R = (int64_t)p.B * p.N1;
+    const int64_t rpg = (R + 127) / 128;                    // ~128 row groups: 128 x (C / 16) workgroups x 32 KB of L2 reads = 16 MB
+    return (int)(rpg < 16 ? 16 : rpg > X0_RPG ? X0_RPG : rpg);
+}
+bool qpn_step_prep_fits(const TrainParams& p) {
+    if (p.C % X0_CS || p.Q % 2 || p.causal_w % 4 || ((uintptr_t)p.flat & 15) || (p.hoist && p.A > 64)) return false;
+    return step_prep_lds_x0(p, X0_RPG) <= 40 * 1024;
+}
+void qpn_launch_step_prep(const TrainParams& p, const AuxGeom& ag, const RefreshArgs& rf, hipStream_t stream) {
+    StepPrepPlan pl;
+    pl.rpg = step_prep_rpg(p);
+    pl.nx0 = (int)(((int64_t)p.B * p.N1 + pl.rpg - 1) / pl.rpg) * (p.C / X0_CS);
+    pl.naux = p.hoist ? (p.nfr + 1 + AUXP_FPB - 1) / AUXP_FPB * p.L * p.B : 0;
+    pl.nbias = (rf.nb + 64 + 255) / 256;
+    pl.nwt = (int)((rf.nw + 1023) / 1024);
+    const long items = (long)p.N1 * ((p.hoist ? 0 : p.Ap / 4) + p.L);
+    pl.nprep = (int)((items + 255) / 256 < 4096 ? (items + 255) / 256 : 4096);
+    if (pl.nprep < 1) pl.nprep = 1;
+    size_t lds = step_prep_lds_x0(p, pl.rpg);
+    const size_t lds_aux = p.hoist ? (size_t)(2 * p.C * p.A + p.A * AUXP_FPB + 8) * sizeof(float) : 0;
+    if (lds_aux > lds) lds = lds_aux;
+    hipLaunchKernelGGL(k_step_prep, dim3((unsigned)(pl.nx0 + pl.naux + pl.nbias + pl.nwt + pl.nprep * p.B)), dim3(256), lds, stream, p, ag, rf, pl);
+}
+
 bool qpn_stack_fwd_fits(const TrainParams& p);
 int qpn_launch_stack_fwd(const TrainParams& p, const StackQ& q, const TrainKnobs& k, hipStream_t stream);
 
 void qpn_launch_post_fb(const TrainParams& p, const TrainBwd& bw, hipStream_t stream);      // train_bwd.hip: k_post_fb_w
 
 // fuse_post_bwd: the post-net's backward runs inside this launch sequence too (the caller has checked the geometry: the wide tiles, cross entropy fused)
-int qpn_launch_fwd(const TrainParams& p, const TrainKnobs& k, const AuxGeom& ag, const StackQ* sq, hipStream_t stream, const TrainBwd* fuse_post_bwd) {
+// rf != nullptr: the per-step refresh has NOT been launched: it runs as roles of the prep launch (k_step_prep; the caller has asked qpn_step_prep_fits)
+int qpn_launch_fwd(const TrainParams& p, const TrainKnobs& k, const AuxGeom& ag, const StackQ* sq, hipStream_t stream, const TrainBwd* fuse_post_bwd, const RefreshArgs* rf) {
     const int C = p.C, S = p.S;
-    qpn_launch_prep(p, ag, stream);
+    if (rf) qpn_launch_step_prep(p, ag, *rf, stream);
+    else qpn_launch_prep(p, ag, stream);
     qpn_prof_mark(PG_PREP, stream);
     // 16-row tiles everywhere (twice the workgroups of 32-row tiles, all co-resident: measured 8-15 % faster for the layer and post-net kernels)
     const size_t lds_layer = (size_t)16 * (tr_lda(p.Ktp) + tr_lda(C)) * sizeof(float);

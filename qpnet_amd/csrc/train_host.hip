@@ -7,7 +7,8 @@
 #include <algorithm>
 #include <string.h>
 
-int qpn_launch_fwd(const TrainParams& p, const TrainKnobs& k, const AuxGeom& ag, const StackQ* sq, hipStream_t stream, const TrainBwd* fuse_post_bwd);
+int qpn_launch_fwd(const TrainParams& p, const TrainKnobs& k, const AuxGeom& ag, const StackQ* sq, hipStream_t stream, const TrainBwd* fuse_post_bwd, const RefreshArgs* rf);
+bool qpn_step_prep_fits(const TrainParams& p);
 void qpn_stack_fill(TrainParams& p);
 int qpn_launch_ce(const float* logits, const int64_t* tgt, int64_t tgt_stride, int B, int BL, int Q, float* dlogits, double* loss, int* status, bool loss_cleared, hipStream_t stream);
 int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k, const AuxGeom& ag, const StackQ* sq, hipStream_t stream, bool post_done);
@@ -86,6 +87,7 @@ void qpn_train_knobs_parse(TrainKnobs& k) {
     k.ce_separate = getenv("QPN_CE_SEPARATE") != nullptr;
     k.event_fence = env_int("QPN_EVENT_FENCE", 0) == 1;
     k.aux_hoist = env_int("QPN_AUX_HOIST", 1) != 0;
+    k.prep_fuse = env_int("QPN_PREP_FUSE", 1) != 0;
     k.test_stack_gives_up = false;
 #ifdef QPN_TESTING
     k.test_stack_gives_up = env_int("QPN_TEST_STACK_GIVES_UP", 0) == 1;
@@ -547,14 +549,20 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
         bq.flags = f.flags + t->sq_per_dir; bq.head = f.head + 8 * TR_QHEAD_STRIDE; bq.abort = f.abort; bq.stats = t->d_sq + 8; bq.epoch = epoch; bq.total = p.qtotal; bq.tab = p.qtab_b;
     }
     p.flat = d_flat; p.wp = (const float4*)t->d_wp; p.bp = t->d_bp; p.x = d_x; p.h = d_h; p.d = d_dfac; p.logits = d_logits;
-    // ---- refresh the fragment-ordered weights / packed biases from the current parameters
+    // ---- refresh the fragment-ordered weights / packed biases from the current parameters: a launch of its own, or (tile path, causal table slices
+    //      that fit: qpn_step_prep_fits; QPN_PREP_FUSE=0 switches it off) roles of the prep launch -- then nothing is launched here
+    RefreshArgs rf;
+    bool fuse_prep;
     {
         const int* wmap = t->use_gemm ? t->d_gmap : t->d_wmap;
         float* wout = t->use_gemm ? t->d_gwp : t->d_wp;
         const int64_t nw = (int64_t)(t->use_gemm ? t->h_gmap.size() : t->h_wmap.size()), nct = (int64_t)2 * g.Q * g.C;
         const int64_t tot = nw + nct + t->n_bias + 16 + 64;
-        hipLaunchKernelGGL(k_refresh, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, d_flat, wmap, wout, nw, t->d_ctmap, t->d_ct, nct,
-                           t->d_bstart, t->d_blist, t->d_bp, t->n_bias, t->d_status, t->d_loss);
+        rf.wmap = wmap; rf.wout = wout; rf.nw = nw; rf.bstart = t->d_bstart; rf.blist = t->d_blist; rf.nb = t->n_bias; rf.loss = t->d_loss;
+        fuse_prep = t->knobs.prep_fuse && !t->use_gemm && qpn_step_prep_fits(p);
+        if (!fuse_prep)
+            hipLaunchKernelGGL(k_refresh, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, d_flat, wmap, wout, nw, t->d_ctmap, t->d_ct, nct,
+                               t->d_bstart, t->d_blist, t->d_bp, t->n_bias, t->d_status, t->d_loss);
         p.ct = t->d_ct;
     }
     qpn_prof_mark(PG_PREP, stream);
@@ -565,7 +573,7 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
     if (fuse_ce && !want_logits) p.logits = nullptr;
     const bool fuse_post = fuse_bwd && fuse_ce && d_dlogits && t->knobs.post_fuse && t->knobs.post_wide && t->knobs.zero_in_post && g.S == 256 && g.Q == 256 && g.C == 64 && (p.LC == 256 || p.LC == 512);
     t->post_bwd_done = false;
-    rc = t->use_gemm ? qpn_launch_fwd_gemm(p, t->gm, stream) : qpn_launch_fwd(p, t->knobs, t->ag, &t->sqf, stream, fuse_post ? &t->bw : nullptr);
+    rc = t->use_gemm ? qpn_launch_fwd_gemm(p, t->gm, stream) : qpn_launch_fwd(p, t->knobs, t->ag, &t->sqf, stream, fuse_post ? &t->bw : nullptr, fuse_prep ? &rf : nullptr);
     if (!rc) { t->post_bwd_done = fuse_post; t->post_bwd_dlogits = d_dlogits; }
     p.ce_tgt = nullptr; p.logits = d_logits;
     if (rc) return rc;

@@ -92,8 +92,8 @@ wg = [(k, v) for k, v in per.get("train", {}).items() if "k_wgrad" in k]
 if wg:
     steps = 3.0    # 1 warmup + 2 timed steps in the PMC runs (the profiled extra steps of bench.py are included: see calls)
     calls = max(v["calls"] for _, v in wg)
-    nsteps = max(per["train"].get("k_train_prep", {}).get("calls", 0), 1)          # steps of the profiled command (timed + warm-up + bench.py's per-group steps)
-    GROUP = (("k_train_prep", "prep+pack"), ("k_refresh", "prep+pack"), ("k_aux_tail", "grad_tail"), ("k_stack_fwd", "k_layer_fwd"), ("k_layer_fwd", "k_layer_fwd"), ("k_post_fwd", "k_post_fwd"),
+    nsteps = max(per["train"].get("k_step_prep", {}).get("calls", 0) + per["train"].get("k_train_prep", {}).get("calls", 0), 1)          # steps of the profiled command (timed + warm-up + bench.py's per-group steps)
+    GROUP = (("k_step_prep", "prep+pack"), ("k_train_prep", "prep+pack"), ("k_refresh", "prep+pack"), ("k_aux_tail", "grad_tail"), ("k_stack_fwd", "k_layer_fwd"), ("k_layer_fwd", "k_layer_fwd"), ("k_post_fwd", "k_post_fwd"),
              ("k_ce", "k_ce"), ("k_post_bwd", "k_post_bwd"), ("k_wgrad", "k_wgrad"), ("k_stack_bwd", "k_layer_bwd"), ("k_layer_bwd", "k_layer_bwd"),
              ("k_reduce_grad", "grad_tail"), ("k_up_bwd", "grad_tail"), ("k_causal_bwd", "grad_tail"), ("k_zero_dx", "k_post_bwd"), ("k_adam", "k_adam"))
     by_group = defaultdict(float)
