@@ -210,7 +210,10 @@ int qpn_train_status(qpn_handle* h, void* stream);
 /* The same check without draining the stream: _enqueue copies the status word (sticky: kernels OR into it, only a read
  * clears it) to pinned memory behind the work enqueued so far and returns; _collect waits for that copy alone and
  * reports it.  The module calls _collect at the start of a forward and _enqueue behind it: an out-of-range tap of
- * step i is raised at step i+1 (reference: assert at step i, qpnet.py:294), and no step is serialised for it. */
+ * step i is raised at step i+1 (reference: assert at step i, qpnet.py:294), and no step is serialised for it.
+ * A word that is reported is cleared with a memset on the stream of the handle's latest training call -- a qpn_train_step* call that
+ * finds it: on that call's own stream, in front of the step run on it next.  A caller that moves a handle from one stream to another
+ * orders the two itself (the step reads what the step before it wrote). */
 int qpn_train_status_enqueue(qpn_handle* h, void* stream);
 int qpn_train_status_collect(qpn_handle* h);
 /* ... every enqueued check EXCEPT the newest one: never waits for the work the device still has queued (a fused training loop calls it

@@ -953,6 +953,9 @@ static int train_step_impl(qpn_handle* h, float* d_flat, int B, int64_t T, int64
     const bool closing = micro == micro_count - 1;                       // ... and only its last micro-step has an Adam launch
     const bool clip = closing && max_grad_norm > 0.f;
     rc = need_dev(h); if (rc) return rc;
+    // a flagged word found here is cleared on THIS call's stream, in front of the step the caller runs on it next: the stream of the call before may be another
+    // one, busy with work of the caller's own, and a clear queued behind that work lands after the next step's Adam launch has read the word
+    if (h->train) h->train->last_stream = (hipStream_t)stream;
     rc = qpn_train_status_collect_lagged(h); if (rc) return rc;          // the check of the step before the previous one (never waits for queued work)
     if (!d_targets || !d_dlogits) { qpn_set_error("qpn_train_forward_loss needs targets and a dlogits buffer"); return QPN_EINVAL; }
     if (accum && (!d_grad || n < 1)) { qpn_set_error("bad train_step arguments: d_grad / n"); return QPN_EINVAL; }
