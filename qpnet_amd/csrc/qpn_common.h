@@ -5,13 +5,12 @@
 #include <string>
 #include <vector>
 #include "../../include/qpnet_hip.h"
+#include "qpn_geom.h"             // LayerGeom / Geom / QPN_MAX_LAYERS / qpn_build_geom / qpn_pad_k, and the declaration of qpn_set_error
 
-#define QPN_MAX_LAYERS 48
 #define QPN_NW 16                 // waves per decode workgroup
 #define QPN_NT (QPN_NW * 64)
 
 // ---------------------------------------------------------------- error plumbing
-void qpn_set_error(const char* fmt, ...);
 #define QPN_HIP(call)                                                                      \
     do {                                                                                   \
         hipError_t _e = (call);                                                            \
@@ -20,32 +19,6 @@ void qpn_set_error(const char* fmt, ...);
             return _e == hipErrorOutOfMemory ? QPN_ENOMEM : QPN_ENODEV;                    \
         }                                                                                  \
     } while (0)
-
-// ---------------------------------------------------------------- geometry
-struct LayerGeom {
-    int adaptive;      // 0 fixed, 1 pitch-adaptive
-    int dilation;      // 2^k
-    // flat offsets (floats) into the state_dict-ordered parameter vector
-    // fixed:    convS/convT = (C,C,2) weights (tap0 older), biasS/biasT
-    // adaptive: convC/convP per half
-    int64_t wS, bS, wT, bT;            // fixed: dil*_sigmoid/tanh .conv.weight/.bias ; adaptive: convC
-    int64_t wSP, bSP, wTP, bTP;        // adaptive only: convP
-    int64_t auxS, auxSb, auxT, auxTb;  // (C,A,1), (C)
-    int64_t skip, skipb, res, resb;    // (S,C,1),(S),(C,C,1),(C)
-};
-
-struct Geom {
-    qpn_config cfg;
-    int C, S, Q, A, U, LF, LA, L;
-    int Cp, Sp, Ap;            // K paddings (16 * power of two)
-    int recF, recA;
-    int64_t causal_w, causal_b, up_w, up_b, post1_w, post1_b, post2_w, post2_b;
-    int64_t n_params;
-    LayerGeom layers[QPN_MAX_LAYERS];
-};
-
-int qpn_build_geom(const qpn_config* cfg, Geom* g);
-__host__ __device__ static inline int qpn_pad_k(int K) { int R = 1; while (16 * R < K) R *= 2; return 16 * R; }
 
 // ---------------------------------------------------------------- decode program
 #define QPN_MODE_SAMPLING_CTL 2   // DecodeParams.mode only, never an ABI value: QPN_MODE_SAMPLING with a sampling control set (qpn_decode_sampling)

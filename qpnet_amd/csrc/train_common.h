@@ -8,10 +8,9 @@
 // every step (weights change every step; 0.5 M floats).
 #pragma once
 #include "qpn_common.h"
+#include "train_plan.h"      // TR_MAXL, TR_EB_SLOTS, TrainSlabs, AuxGeom, TrainGemm, TrainKnobs: the host-only layout types, and the planner that fills them
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define TR_MAXL QPN_MAX_LAYERS   // layers supported by the training kernels (the reference's deepest shipped stack, Rd10Rr3Ed4Er1, has 34: src/utils/param_model.py:66-72)
 
 // leading dimension for an LDS A-tile read "row = lane&15, k = lane>>4" with ds_read_b32:
 // ld == 2 (mod 32) makes the 32-lane groups conflict free (MI355X_MICROARCH.md §LDS).
@@ -74,14 +73,6 @@ struct TrainParams {
     TrLayer layers[TR_MAXL];
 };
 
-// slab offsets (floats) of every weight-grad block; host side only
-struct TrainSlabs {
-    int g_w1[TR_MAXL], g_b1[TR_MAXL], g_wr[TR_MAXL], g_br[TR_MAXL], g_ws[TR_MAXL], g_bs;
-    int g_p1, g_bp1, g_p2, g_bp2;
-    int g_early0, g_early1;           // slab range [g_early0, g_early1): skip 1x1 / skip bias / post-net blocks, complete before the layer backward ends
-    int g_cw, g_cb;                   // causal conv table [tap][C][Q] and bias, or -1: histogram kernel (k_causal_bwd)
-};
-
 struct TrainBwd {            // backward-only buffers / maps (see train_bwd.hip)
     const float* dlogits; float* gflat;
     float* DXA[2]; float* DXB[2];     // [B][N1][C] grads w.r.t. a layer input: own-position part / scattered pitch-tap part
@@ -106,9 +97,7 @@ struct TrainBwd {            // backward-only buffers / maps (see train_bwd.hip)
 };
 
 
-// aux hoist: what k_aux_proj / k_aux_tail need of every layer (flat offsets of the aux 1x1 weights, offset of the packed gate bias, first valid row of the call) ...
-struct AuxGeom { int auxS[TR_MAXL], auxT[TR_MAXL], bias1[TR_MAXL], s_out[TR_MAXL]; };
-// ... and their (compact) kernel arguments
+// the (compact) kernel arguments of k_aux_proj / k_aux_tail (AuxGeom: train_plan.h)
 struct AuxArgs {
     const float* flat; const float* h; float* PA; float* bp; const float* DPA; const float* EB; const float* GW; float* gflat;
     float gscale; int C, A, L, B, F, U, N1, nfr, ffirst; int64_t up_w, up_b;
@@ -123,25 +112,6 @@ static inline AuxArgs tr_aux_args(const TrainParams& p, const TrainBwd* bw, cons
 // What the per-step refresh gathers from the flat parameters (k_refresh, or the refresh roles of k_step_prep): the fragment-ordered weight blocks through
 // their map, the packed biases through their CSR lists (into TrainParams::bp); `loss`: the 64 partial sums of the coming step's loss, cleared
 struct RefreshArgs { const int* wmap; float* wout; int64_t nw; const int* bstart; const int* blist; int nb; double* loss; };
-// Launch-plan knobs, parsed ONCE per handle from the environment (train_init): nothing in the per-step launch path calls getenv().
-// All optional; the defaults are the measured best.  tests/test_train_gpu.py builds a fresh model (= a fresh handle) per arrangement.
-struct TrainKnobs {
-    bool serial;                      // QPN_TRAIN_SERIAL=1: every launch of a step on the caller's stream (also forced while a profile is taken)
-    bool stack_q_fwd, stack_q_bwd;    // QPN_STACK_QUEUE=0 / QPN_STACK_QUEUE_BWD=0: a launch per layer instead of the work-queue launches (train_stack.hip)
-    int stack_wgs, stack_wgs_bwd;     // QPN_STACK_WGS / QPN_STACK_WGS_BWD: grid sizes of the queue launches (0: 2 / 1.5 workgroups per CU)
-    bool persist_fwd, persist_bwd;    // QPN_LAYER_PERSIST=0 / QPN_LAYER_BWD_PERSIST=0: the tile-per-workgroup layer kernels at n_resch 64
-    bool wgrad_generic;               // QPN_WGRAD_GENERIC=1: the run-time-tiled weight-gradient kernel (k_wgrad2)
-    int wgrad_chunks, wgrad_chunks_side;   // QPN_WGRAD_CHUNKS / QPN_WGRAD_CHUNKS_SIDE: time chunks (= partial slabs) of the weight gradients
-    bool post_fuse;                        // QPN_POST_FUSE=0: qpn_train_step runs the post-net's forward and backward as two kernels (k_post_fwd_w, k_post_bwd_w) instead of k_post_fb_w
-    bool up_side, reduce_early, wr_side;   // QPN_UP_SIDE=0 / QPN_REDUCE_EARLY=0 / QPN_WR_SIDE=0: where the backward's small launches run
-    bool post_pair, zero_in_post, post_wide;   // QPN_POST_WGRAD_PAIR=0 / QPN_ZERO_IN_POST=0 / QPN_POST_WIDE=0
-    bool xcd_swizzle;                 // QPN_NO_XCD_SWIZZLE=1 clears it
-    bool ce_separate;                 // QPN_CE_SEPARATE=1: cross entropy as its own kernel behind the forward
-    bool event_fence;                 // QPN_EVENT_FENCE=1: system-scope fence at the fork / join events
-    bool prep_fuse;                   // QPN_PREP_FUSE=0: the per-step refresh (k_refresh) and the chunk's preparation (k_train_prep) as two launches instead of k_step_prep's one
-    bool aux_hoist;                   // QPN_AUX_HOIST=0: the auxiliary 1x1 contracted at sample rate (K = 176) even where the frame-rate form applies
-    bool test_stack_gives_up;         // -DQPN_TESTING builds only (QPN_TEST_STACK_GIVES_UP=1): the queue launches' published flags are made unrecognisable
-};
 void qpn_train_knobs_parse(TrainKnobs& k);
 
 #define TR_QHEAD_STRIDE 1056   // words between sub-queue heads (4224 bytes: different memory channels)
@@ -221,16 +191,6 @@ __device__ __forceinline__ void tr_queue_entry_bwd(const TrainParams& p, int pos
     a = make_int4(n0, l | (bi << 8) | (l == p.L - 1 ? 1 << 24 : 0) | (valid ? 1 << 25 : 0) | (ly.adaptive ? 1 << 26 : 0), first, n);
     b = make_int4((l * p.B + bi) * p.N1, ly.tap_off + bi * p.N1, p.hoist ? tr_pa_off(p, l, bi, n0) : bi * p.N1, bi * p.BL * p.LC + l * p.C);
 }
-
-// K-major, zero-padded weight blocks of the GEMM path (train_gemm.hip; n_resch > 128): float offsets into `wp`
-struct TrainGemm {
-    const float* wp;                  // packed weights (refreshed from the flat parameters every step)
-    float* G;                         // [L][B][N1][C] gate outputs sigma*tanh (A operand of the residual / skip contractions)
-    int K1;                           // 2C + n_aux padded to 32: K of the gate GEMM
-    int N1g, Cg, Sg, Qg, LCg, Ktg;    // column counts padded to 128: gate tiles, C, S, Q, L*C, 2C + n_aux
-    long w1[TR_MAXL], w1t[TR_MAXL], wr[TR_MAXL], wrt[TR_MAXL];
-    long ws, wst, p1, p1t, p2, p2t;
-};
 
 // Workgroup barrier that orders LDS traffic only.  hipcc's __syncthreads() also drains vmcnt: every global load / store the wave
 // has in flight -- in the persistent kernels that is the NEXT tile's prefetch, requested a moment earlier precisely so that it
@@ -312,7 +272,6 @@ __device__ __forceinline__ float tr_wave_sum(float a) {
 //   gp[0..3] partial row sums of dZ[row][.] * PA[frame(row)][.] over this wave's 32 columns (the same value in all 16 lanes of a row group)
 //   e[0..1]  the tile's column sums of dZ (sigma, tanh) for column lane & 15 -- valid in lanes 0..15 --: a third row of A' holds ones
 struct TrAuxBwd { float d[4]; float gp[4]; float e[2]; };
-#define TR_EB_SLOTS 32       // the gate-bias accumulators E are spread over this many slabs per layer (workgroup index mod): ~40 float atomics per address and layer
 __device__ __forceinline__ TrAuxBwd tr_aux_bwd(const float2 (&wj)[4], const float (&pa)[4], const float (&dzs)[4], const float (&dzt)[4], int lane) {
     TrAuxBwd o;
     f32x4 as = (f32x4){0, 0, 0, 0}, at = (f32x4){0, 0, 0, 0};

@@ -5,6 +5,7 @@
 #include "train_common.h"
 #include "qpn_handle.h"
 #include <algorithm>
+#include <memory>
 #include <string.h>
 
 int qpn_launch_fwd(const TrainParams& p, const TrainKnobs& k, const AuxGeom& ag, const StackQ* sq, hipStream_t stream, const TrainBwd* fuse_post_bwd, const RefreshArgs* rf);
@@ -22,45 +23,43 @@ int qpn_launch_grad_accum(float* acc, const float* g, int64_t cnt, int first, co
 
 // a pinned loss slot: the 64 partial sums, then the gradient norm of the same step (gradient-norm clipping)
 #define LOSS_SLOT 72
+static double loss_sum(const double* parts) { double sum = 0.0; for (int i = 0; i < 64; ++i) sum += parts[i]; return sum; }      // the loss of a step: its 64 partial sums, in order
 
+// Every member has a default: a state under construction is destroyable at any point (qpn_train_destroy frees what is there)
 struct TrainState {
-    std::vector<int> h_wmap;                  // gather map of the fragment-ordered weights
-    std::vector<int> h_bstart, h_blist;       // CSR of the packed biases
-    std::vector<int> h_gsrc;
-    int* d_wmap; float* d_wp; int* d_bstart; int* d_blist; float* d_bp; int n_bias;
-    int* d_gdst; int* d_gdst_list; int* d_gzero; int n_gzero;
-    bool hoist;                               // the auxiliary 1x1 runs at frame rate (TrainParams::hoist)
-    TrainParams tp;                           // template with block offsets filled in
-    TrainBwd bw;
-    TrainSlabs slabs;                         // slab offsets of the weight-gradient blocks (bw.sl points here)
-    TrainKnobs knobs;                         // launch-plan knobs, parsed once (qpn_train_knobs_parse)
-    AuxGeom ag;                               // aux hoist: per-layer offsets for k_aux_proj / k_aux_tail (s_out refreshed per forward)
+    TrainLayout lay;                          // what train_plan decided (train_plan.h): the path, hoist, block / bias / slab offsets (bw.sl points at lay.slabs), early_first
+    int64_t n_map = 0;                        // entries of the uploaded gather map (fragment-ordered blocks, or the GEMM path's K-major ones): what the refresh gathers
+    int* d_wmap = nullptr; float* d_wp = nullptr; int* d_bstart = nullptr; int* d_blist = nullptr; float* d_bp = nullptr;
+    int* d_gdst = nullptr; int* d_gdst_list = nullptr; int* d_gzero = nullptr; int n_gzero = 0;
+    TrainParams tp = {};                      // template with block offsets filled in
+    TrainBwd bw = {};
+    TrainKnobs knobs = {};                    // launch-plan knobs, parsed once (qpn_train_knobs_parse)
+    AuxGeom ag = {};                          // aux hoist: per-layer offsets for k_aux_proj / k_aux_tail (s_out refreshed per forward)
     // workspaces (grow only)
-    float* d_ws; size_t ws_cap;               // one arena, carved per call
-    int* d_tap; size_t tap_cap;
-    int* d_status; double* d_loss;            // d_status: 16 words -- [0] the sticky status word, [2..3] the count of Adam updates applied (k_adam)
-    hipStream_t last_stream;                  // the stream of the latest training call (where a collected status word is cleared)
-    int* h_status_pinned; hipEvent_t ev_status[2]; bool status_pending[2]; int status_newest;      // qpn_train_status_enqueue / _collect: the deferred check, two slots
-    double* h_loss_pinned; hipEvent_t ev_loss[2]; bool loss_pending[2]; int loss_newest;            // qpn_train_loss_enqueue / _collect: the loss read one step late, two slots of LOSS_SLOT doubles
+    float* d_ws = nullptr; size_t ws_cap = 0; // one arena, carved per call (train_arena)
+    int* d_tap = nullptr; size_t tap_cap = 0;
+    int* d_status = nullptr; double* d_loss = nullptr;   // d_status: 16 words -- [0] the sticky status word, [2..3] the count of Adam updates applied (k_adam)
+    hipStream_t last_stream = nullptr;        // the stream of the latest training call (where a collected status word is cleared)
+    int* h_status_pinned = nullptr; hipEvent_t ev_status[2] = {}; bool status_pending[2] = {}; int status_newest = 0;      // qpn_train_status_enqueue / _collect: the deferred check, two slots
+    double* h_loss_pinned = nullptr; hipEvent_t ev_loss[2] = {}; bool loss_pending[2] = {}; int loss_newest = 0;            // qpn_train_loss_enqueue / _collect: the loss read one step late, two slots of LOSS_SLOT doubles
     // gradient-norm clipping (qpn_adam_step_clip): d_gnorm = TR_GN_BLOCKS partial sums of squares; the norm word k_adam_clip leaves is d_loss[64] (one copy takes both out)
-    double* d_gnorm; bool gnorm_last;         // gnorm_last: the latest Adam launch on this handle clipped (the norm word is that launch's)
-    bool gnorm_slot[2];                       // loss slot i carries a norm
-    double gnorm_collected; bool gnorm_collected_valid;      // the norm that came with the loss the last qpn_train_loss_collect returned
-    bool fwd_valid;
-    bool loss_clear;                          // the loss accumulator is zero (cleared by the forward's refresh kernel, consumed by one CE call)
-    bool use_gemm;                            // wide stacks (n_resch > 128, or QPN_TRAIN_GEMM=1): the LDS-tiled GEMM path of train_gemm.hip
-    int* d_ctmap; float* d_ct;                // causal conv table [tap][class][C] and its gather map
-    std::vector<int> h_gmap; int* d_gmap; float* d_gwp;   // its K-major weight blocks
-    TrainGemm gm;
-    int64_t generation;                       // bumped by every qpn_train_forward: identifies whose activations the workspace holds
-    hipStream_t side; hipEvent_t ev_fork, ev_join, ev_mid;   // side stream for the weight gradients that overlap the layer backward
-    hipEvent_t ev_early; int early_recorded; int64_t early_first;   // qpn_train_early_bucket: the flat-gradient tail that is final before the layer backward ends
-    int64_t bwd_generation;                                  // generation of the forward the last backward belonged to
-    const float* post_bwd_dlogits;                           // ... on this dL/dlogits buffer
-    bool post_bwd_done;                                      // the last forward ran the post-net's backward too (k_post_fb_w: qpn_train_step)
-    bool stack_disabled;                                     // a stack-queue launch gave up once (status bit 4): this handle keeps to a launch per layer
-    unsigned* d_sq; size_t sq_pos_cap, sq_per_dir;                           // stack work queues (train_stack.hip): [16 control words | forward flags | backward flags]
-    StackQ sqf, sqb;
+    double* d_gnorm = nullptr; bool gnorm_last = false;      // gnorm_last: the latest Adam launch on this handle clipped (the norm word is that launch's)
+    bool gnorm_slot[2] = {};                  // loss slot i carries a norm
+    double gnorm_collected = 0.0; bool gnorm_collected_valid = false;      // the norm that came with the loss the last qpn_train_loss_collect returned
+    bool fwd_valid = false;
+    bool loss_clear = false;                  // the loss accumulator is zero (cleared by the forward's refresh kernel, consumed by one CE call)
+    int* d_ctmap = nullptr; float* d_ct = nullptr;           // causal conv table [tap][class][C] and its gather map
+    int* d_gmap = nullptr; float* d_gwp = nullptr;           // GEMM path (lay.use_gemm: n_resch > 128, or QPN_TRAIN_GEMM=1): the K-major weight blocks of train_gemm.hip and their map
+    TrainGemm gm = {};
+    int64_t generation = 0;                   // bumped by every qpn_train_forward: identifies whose activations the workspace holds
+    hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_mid = nullptr;   // side stream for the weight gradients that overlap the layer backward
+    hipEvent_t ev_early = nullptr; int early_recorded = 0;   // qpn_train_early_bucket: the flat-gradient tail (from lay.early_first) that is final before the layer backward ends
+    int64_t bwd_generation = -1;                             // generation of the forward the last backward belonged to
+    const float* post_bwd_dlogits = nullptr;                 // ... on this dL/dlogits buffer
+    bool post_bwd_done = false;                              // the last forward ran the post-net's backward too (k_post_fb_w: qpn_train_step)
+    bool stack_disabled = false;                             // a stack-queue launch gave up once (status bit 4): this handle keeps to a launch per layer
+    unsigned* d_sq = nullptr; size_t sq_pos_cap = 0, sq_per_dir = 0;         // stack work queues (train_stack.hip): [16 control words | forward flags | backward flags]
+    StackQ sqf = {}, sqb = {};
 };
 
 // The environment is read HERE, once per handle: the launch path of a step never calls getenv().
@@ -172,248 +171,69 @@ __global__ void k_refresh(const float* __restrict__ flat, const int* __restrict_
     (void)status;
     if (i >= 16 && i < 16 + 64) loss[i - 16] = 0.0;
 }
-// B[k][n] (K x N valid) -> K-major block [Kp][Np], zero padded; returns the float offset
-template <class F>
-static long kmajor_pack(std::vector<int>& map, int K, int Kp, int N, int Np, F src) {
-    const long off = (long)map.size();
-    map.resize(map.size() + (size_t)Kp * Np, -1);
-    int* m = map.data() + off;
-    for (int k = 0; k < K; ++k)
-        for (int n = 0; n < N; ++n) m[(size_t)k * Np + n] = (int)src(k, n);
-    return off;
-}
-static inline int pad_to(int v, int q) { return (v + q - 1) / q * q; }
-
-// B[k][n] (K x N, both multiples of 16) -> fragment order; returns float4 offset
-template <class F>
-static int frag_pack(std::vector<int>& map, int K, int N, F src) {
-    const int NT = N / 16, off4 = (int)(map.size() / 4);
-    map.resize(map.size() + (size_t)K * N);
-    int* m = map.data() + (size_t)off4 * 4;
-    for (int ks4 = 0; ks4 < K / 16; ++ks4)
-        for (int nt = 0; nt < NT; ++nt)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 4; ++e) {
-                    int k = 16 * ks4 + 4 * e + (lane >> 4), n = 16 * nt + (lane & 15);
-                    m[(((size_t)ks4 * NT + nt) * 64 + lane) * 4 + e] = (int)src(k, n);
-                }
-    return off4;
+// device copy of a host map, with `spare` more entries behind it (never read); the buffer is the state's at once: whatever fails later, the guard of train_init frees it
+static int upload(int** d, const std::vector<int>& v, size_t spare = 0) {
+    QPN_HIP(hipMalloc(d, (v.size() + spare) * sizeof(int)));
+    if (!v.empty()) QPN_HIP(hipMemcpy(*d, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
+    return QPN_OK;
 }
 
+// Per-handle training setup: plan the layout (train_plan.h -- all of the arithmetic, CPU-tested), upload its maps, create the events and streams.
+// The state under construction is the guard's: every early return destroys it with what it had allocated
 static int train_init(qpn_handle* h) {
     if (h->train) return QPN_OK;
     const Geom& g = h->g;
-    const int C = g.C, S = g.S, Q = g.Q, A = g.A, L = g.L;
-    if (L > TR_MAXL) { qpn_set_error("training kernels support up to %d residual layers", TR_MAXL); return QPN_EINVAL; }
-    if (C % 16 || S % 16 || Q % 16) { qpn_set_error("training kernels need n_resch, n_skipch, n_quantize multiples of 16"); return QPN_EINVAL; }
-    TrainState* t = new TrainState();
-    memset(&t->tp, 0, sizeof(t->tp)); memset(&t->bw, 0, sizeof(t->bw));
-    t->d_wmap = nullptr; t->d_wp = nullptr; t->d_bstart = t->d_blist = nullptr; t->d_bp = nullptr;
-    t->d_gdst = t->d_gdst_list = t->d_gzero = nullptr; t->n_gzero = 0;
-    t->d_ws = nullptr; t->ws_cap = 0; t->d_tap = nullptr; t->tap_cap = 0; t->d_status = nullptr; t->d_loss = nullptr; t->fwd_valid = false; t->loss_clear = false;
-    t->generation = 0; t->side = nullptr; t->ev_fork = t->ev_join = t->ev_mid = nullptr; t->ev_early = nullptr; t->early_recorded = 0; t->early_first = -1;
-    t->d_sq = nullptr; t->sq_pos_cap = 0; t->sq_per_dir = 0; t->bwd_generation = -1; t->stack_disabled = false; memset(&t->sqf, 0, sizeof(t->sqf)); memset(&t->sqb, 0, sizeof(t->sqb));
+    std::unique_ptr<TrainState, void (*)(TrainState*)> t(new TrainState(), qpn_train_destroy);
     qpn_train_knobs_parse(t->knobs);
-    memset(&t->slabs, 0, sizeof(t->slabs));
-    t->use_gemm = (C > 128 || getenv("QPN_TRAIN_GEMM")) && !getenv("QPN_TRAIN_TILES");
-    t->d_gmap = nullptr; t->d_gwp = nullptr; t->d_ctmap = nullptr; t->d_ct = nullptr; memset(&t->gm, 0, sizeof(t->gm));
-    if (t->use_gemm && (C % 32 || S % 32 || Q % 32)) { qpn_set_error("the GEMM training path needs n_resch, n_skipch, n_quantize multiples of 32"); delete t; return QPN_EINVAL; }
+    const TrainPlan pl = train_plan(g, t->knobs, (g.C > 128 || getenv("QPN_TRAIN_GEMM")) && !getenv("QPN_TRAIN_TILES"));
+    if (pl.rc) return pl.rc;
+    t->lay = pl; t->ag = pl.ag; t->gm = pl.gm;
     TrainParams& p = t->tp;
-    const int Ap = (A + 3) / 4 * 4;               // aux columns padded to the MFMA k-step
-    // the auxiliary 1x1 at frame rate (TrainParams::hoist): the n_resch-64 register-resident kernels, at most two frames per 16-row tile
-    t->hoist = !t->use_gemm && C == 64 && g.U >= 16 && A <= 64 && t->knobs.aux_hoist && t->knobs.persist_fwd && t->knobs.persist_bwd;
-    p.hoist = t->hoist ? 1 : 0;
-    p.C = C; p.S = S; p.Q = Q; p.A = A; p.Ap = Ap; p.L = L; p.U = g.U;
-    p.Kt = t->hoist ? 2 * C : 2 * C + Ap; p.Ktp = (p.Kt + 15) / 16 * 16; p.LC = L * C;
+    p.hoist = pl.hoist ? 1 : 0;
+    p.C = g.C; p.S = g.S; p.Q = g.Q; p.A = g.A; p.Ap = pl.Ap; p.L = g.L; p.U = g.U;
+    p.Kt = pl.Kt; p.Ktp = pl.Ktp; p.LC = pl.LC;
     p.causal_w = g.causal_w; p.causal_b = g.causal_b; p.up_w = g.up_w; p.up_b = g.up_b;
-    std::vector<int>& map = t->h_wmap;
-    std::vector<std::vector<int>> biases;      // packed bias i <- list of flat indices
-    auto add_bias = [&](int n, auto f) { int off = (int)biases.size(); for (int i = 0; i < n; ++i) biases.push_back(f(i)); return off; };
-    const int Ktp = p.Ktp;
-    int n_adapt = 0;
-    for (int l = 0; l < L; ++l) {
-        const LayerGeom y = g.layers[l];
+    for (int l = 0; l < g.L; ++l) {
+        const TrainPlanLayer& s = pl.layers[l];
         TrLayer& ly = p.layers[l];
-        ly.adaptive = y.adaptive; ly.dilation = y.dilation;
-        ly.tap_off = y.adaptive ? n_adapt++ : -1;     // scaled by B*N1 per call
-        auto w1src = [&](int k, int n) -> int64_t {   // B[k][n] of z = [x_cur | x_past | aux] . W1
-            const int half = n / C, r = n % C;
-            if (k < C) return y.adaptive ? (half ? y.wT : y.wS) + (int64_t)r * C + k : (half ? y.wT : y.wS) + ((int64_t)r * C + k) * 2 + 1;
-            if (k < 2 * C) { const int kk = k - C; return y.adaptive ? (half ? y.wTP : y.wSP) + (int64_t)r * C + kk : (half ? y.wT : y.wS) + ((int64_t)r * C + kk) * 2; }
-            if (k < 2 * C + A) return (half ? y.auxT : y.auxS) + (int64_t)r * A + (k - 2 * C);
-            return -1;
-        };
-        ly.w1_f4 = frag_pack(map, Ktp, 2 * C, w1src);
-        ly.w1t_f4 = frag_pack(map, 2 * C, Ktp, [&](int k, int n) { return w1src(n, k); });
-        ly.wr_f4 = frag_pack(map, C, C, [&](int k, int n) { return y.res + (int64_t)n * C + k; });
-        ly.wrt_f4 = frag_pack(map, C, C, [&](int k, int n) { return y.res + (int64_t)k * C + n; });
-        ly.bias1 = add_bias(2 * C, [&](int n) {
-            const int half = n / C, r = n % C;
-            std::vector<int> v{(int)((half ? y.bT : y.bS) + r), (int)((half ? y.auxTb : y.auxSb) + r)};
-            if (y.adaptive) v.push_back((int)((half ? y.bTP : y.bSP) + r));
-            return v; });
-        ly.biasr = add_bias(C, [&](int n) { return std::vector<int>{(int)(y.resb + n)}; });
+        ly.adaptive = s.adaptive; ly.dilation = s.dilation; ly.tap_off = -1;      // (tap_off, s_in, s_out: per call)
+        ly.w1_f4 = s.w1_f4; ly.w1t_f4 = s.w1t_f4; ly.wr_f4 = s.wr_f4; ly.wrt_f4 = s.wrt_f4; ly.bias1 = s.bias1; ly.biasr = s.biasr;
     }
-    p.ws_f4 = frag_pack(map, L * C, S, [&](int k, int n) { return g.layers[k / C].skip + (int64_t)n * C + (k % C); });
-    p.wst_f4 = frag_pack(map, S, L * C, [&](int k, int n) { return g.layers[n / C].skip + (int64_t)k * C + (n % C); });
-    p.p1_f4 = frag_pack(map, S, S, [&](int k, int n) { return g.post1_w + (int64_t)n * S + k; });
-    p.p1t_f4 = frag_pack(map, S, S, [&](int k, int n) { return g.post1_w + (int64_t)k * S + n; });
-    p.p2_f4 = frag_pack(map, S, Q, [&](int k, int n) { return g.post2_w + (int64_t)n * S + k; });
-    p.p2t_f4 = frag_pack(map, Q, S, [&](int k, int n) { return g.post2_w + (int64_t)k * S + n; });
-    p.bias_s = add_bias(S, [&](int n) { std::vector<int> v; for (int l = 0; l < L; ++l) v.push_back((int)(g.layers[l].skipb + n)); return v; });
-    p.bias_p1 = add_bias(S, [&](int n) { return std::vector<int>{(int)(g.post1_b + n)}; });
-    p.bias_p2 = add_bias(Q, [&](int n) { return std::vector<int>{(int)(g.post2_b + n)}; });
-    if (t->use_gemm) {
-        TrainGemm& gm = t->gm;
-        std::vector<int>& gmap = t->h_gmap;
-        const int Apad = pad_to(Ap, 32);
-        gm.K1 = 2 * C + Apad; gm.N1g = pad_to(C, 64) * 2; gm.Cg = pad_to(C, 128); gm.Sg = pad_to(S, 128); gm.Qg = pad_to(Q, 128);
-        gm.LCg = pad_to(L * C, 128); gm.Ktg = pad_to(2 * C + Ap, 128);
-        for (int l = 0; l < L; ++l) {
-            const LayerGeom y = g.layers[l];
-            auto w1src = [&](int k, int n) -> int64_t {        // z column n (natural: half*C + r), input column k of [x_cur | x_past | aux]
-                const int half = n / C, r = n % C;
-                if (k < C) return y.adaptive ? (half ? y.wT : y.wS) + (int64_t)r * C + k : (half ? y.wT : y.wS) + ((int64_t)r * C + k) * 2 + 1;
-                if (k < 2 * C) { const int kk = k - C; return y.adaptive ? (half ? y.wTP : y.wSP) + (int64_t)r * C + kk : (half ? y.wT : y.wS) + ((int64_t)r * C + kk) * 2; }
-                if (k < 2 * C + A) return (half ? y.auxT : y.auxS) + (int64_t)r * A + (k - 2 * C);
-                return -1;
-            };
-            // gate GEMM: rows k = [x_cur C | x_past C | aux (n_aux, padded to 32)], columns in 128-wide tiles [sigma c0..c0+63 | tanh c0..c0+63]
-            gm.w1[l] = kmajor_pack(gmap, 2 * C + A, gm.K1, gm.N1g, gm.N1g, [&](int k, int q) -> int64_t {
-                const int tile = q / 128, w = q % 128, half = w / 64, c = 64 * tile + w % 64;
-                return c < C ? w1src(k, half * C + c) : -1; });
-            gm.w1t[l] = kmajor_pack(gmap, 2 * C, 2 * C, 2 * C + A, gm.Ktg, [&](int k, int n) { return w1src(n, k); });
-            gm.wr[l] = kmajor_pack(gmap, C, C, C, gm.Cg, [&](int k, int n) { return y.res + (int64_t)n * C + k; });
-            gm.wrt[l] = kmajor_pack(gmap, C, C, C, gm.Cg, [&](int k, int n) { return y.res + (int64_t)k * C + n; });
-        }
-        gm.ws = kmajor_pack(gmap, L * C, L * C, S, gm.Sg, [&](int k, int n) { return g.layers[k / C].skip + (int64_t)n * C + (k % C); });
-        gm.wst = kmajor_pack(gmap, S, S, L * C, gm.LCg, [&](int k, int n) { return g.layers[n / C].skip + (int64_t)k * C + (n % C); });
-        gm.p1 = kmajor_pack(gmap, S, S, S, gm.Sg, [&](int k, int n) { return g.post1_w + (int64_t)n * S + k; });
-        gm.p1t = kmajor_pack(gmap, S, S, S, gm.Sg, [&](int k, int n) { return g.post1_w + (int64_t)k * S + n; });
-        gm.p2 = kmajor_pack(gmap, S, S, Q, gm.Qg, [&](int k, int n) { return g.post2_w + (int64_t)n * S + k; });
-        gm.p2t = kmajor_pack(gmap, Q, Q, S, gm.Sg, [&](int k, int n) { return g.post2_w + (int64_t)k * S + n; });
-    }
-    memset(&t->ag, 0, sizeof(t->ag));
-    for (int l = 0; l < L; ++l) { t->ag.auxS[l] = (int)g.layers[l].auxS; t->ag.auxT[l] = (int)g.layers[l].auxT; t->ag.bias1[l] = p.layers[l].bias1; }
-    t->n_bias = (int)biases.size();
-    t->h_bstart.assign(1, 0);
-    for (auto& v : biases) { for (int x : v) t->h_blist.push_back(x); t->h_bstart.push_back((int)t->h_blist.size()); }
+    p.ws_f4 = pl.ws_f4; p.wst_f4 = pl.wst_f4; p.p1_f4 = pl.p1_f4; p.p1t_f4 = pl.p1t_f4; p.p2_f4 = pl.p2_f4; p.p2t_f4 = pl.p2t_f4;
+    p.bias_s = pl.bias_s; p.bias_p1 = pl.bias_p1; p.bias_p2 = pl.bias_p2;
+    t->bw.sl = &t->lay.slabs; t->bw.gstage = pl.gstage; t->bw.nch = pl.nch; t->bw.n_params = g.n_params;
 
-    // ---- weight-grad staging space ("slab") and the flat-grad gather map
-    TrainBwd& bw = t->bw;
-    TrainSlabs& sl = t->slabs;
-    bw.sl = &t->slabs;
-    int go = 0;
-    auto gtake = [&](int n) { int r = go; go += (n + 63) & ~63; return r; };
-    std::vector<int>& gs = t->h_gsrc;          // flat-grad entry <- slab element; -1: no slab feeds it (zeroed, then written by a kernel of its own); -2: k_aux_tail stores it
-    gs.assign(g.n_params, -1);
-    for (int l = 0; l < L; ++l) {
-        sl.g_w1[l] = gtake(2 * C * Ktp);   // dW1[n][k] (n = z row, k = A-tile column), row-major [2C][Ktp]
-        sl.g_b1[l] = gtake(2 * C);
-        sl.g_wr[l] = gtake(C * C);         // dWr[o][c]
-        sl.g_br[l] = gtake(C);
+    int rc;
+    const std::vector<int>& wmap = pl.use_gemm ? pl.h_gmap : pl.h_wmap;
+    t->n_map = (int64_t)wmap.size();
+    if (pl.use_gemm) {
+        rc = upload(&t->d_gmap, wmap); if (rc) return rc;
+        QPN_HIP(hipMalloc(&t->d_gwp, wmap.size() * sizeof(float)));
+        t->gm.wp = t->d_gwp;
     }
-    sl.g_early0 = go;
-    for (int l = 0; l < L; ++l) sl.g_ws[l] = gtake(S * C);         // dWs_l[s][c]
-    for (int l = 0; l < L; ++l) {
-        const LayerGeom y = g.layers[l];
-        // (slab order: first the blocks that need the layer backward -- dW1, dWr of every layer -- then, contiguous, the ones the side
-        //  stream finishes early: skip 1x1 of every layer, skip bias, post-net; that range is reduced early as well, under the layer backward)
-        for (int n = 0; n < 2 * C; ++n) {
-            const int half = n / C, r = n % C;
-            if (t->hoist) for (int a = 0; a < A; ++a) gs[(half ? y.auxT : y.auxS) + (int64_t)r * A + a] = -2;
-            for (int k = 0; k < (t->hoist ? 2 * C : 2 * C + A); ++k) {
-                int64_t dst;
-                if (k < C) dst = y.adaptive ? (half ? y.wT : y.wS) + (int64_t)r * C + k : (half ? y.wT : y.wS) + ((int64_t)r * C + k) * 2 + 1;
-                else if (k < 2 * C) { const int kk = k - C; dst = y.adaptive ? (half ? y.wTP : y.wSP) + (int64_t)r * C + kk : (half ? y.wT : y.wS) + ((int64_t)r * C + kk) * 2; }
-                else dst = (half ? y.auxT : y.auxS) + (int64_t)r * A + (k - 2 * C);
-                gs[dst] = sl.g_w1[l] + n * Ktp + k;
-            }
-            gs[(half ? y.bT : y.bS) + r] = sl.g_b1[l] + n;
-            gs[(half ? y.auxTb : y.auxSb) + r] = sl.g_b1[l] + n;
-            if (y.adaptive) gs[(half ? y.bTP : y.bSP) + r] = sl.g_b1[l] + n;
-        }
-        for (int o = 0; o < C; ++o) { for (int c = 0; c < C; ++c) gs[y.res + (int64_t)o * C + c] = sl.g_wr[l] + o * C + c; gs[y.resb + o] = sl.g_br[l] + o; }
-        for (int s = 0; s < S; ++s) for (int c = 0; c < C; ++c) gs[y.skip + (int64_t)s * C + c] = sl.g_ws[l] + s * C + c;
-    }
-    sl.g_bs = gtake(S);
-    for (int l = 0; l < L; ++l) for (int s = 0; s < S; ++s) gs[g.layers[l].skipb + s] = sl.g_bs + s;
-    sl.g_p1 = gtake(S * S); sl.g_bp1 = gtake(S); sl.g_p2 = gtake(Q * S); sl.g_bp2 = gtake(Q);
-    sl.g_early1 = go;
-    // the post-net blocks close the flat parameter order (state_dict order, qpnet.py): with the trailer behind them one contiguous early bucket
-    t->early_first = (g.post1_b == g.post1_w + (int64_t)S * S && g.post2_w == g.post1_b + S && g.post2_b == g.post2_w + (int64_t)Q * S && g.post2_b + Q == g.n_params) ? g.post1_w : -1;
-    for (int o = 0; o < S; ++o) { for (int s = 0; s < S; ++s) gs[g.post1_w + (int64_t)o * S + s] = sl.g_p1 + o * S + s; gs[g.post1_b + o] = sl.g_bp1 + o; }
-    for (int q = 0; q < Q; ++q) { for (int s = 0; s < S; ++s) gs[g.post2_w + (int64_t)q * S + s] = sl.g_p2 + q * S + s; gs[g.post2_b + q] = sl.g_bp2 + q; }
-    // causal conv table: dW[c][q][tap] = sum_t dX0[t][c] * onehot(x[t-1+tap])[q] is one more time contraction (k_wgrad3 mode 4)
-    // when its tiles fit (C = 64, Q a multiple of 128); otherwise the LDS-histogram kernel owns it (gs stays -1)
-    sl.g_cw = sl.g_cb = -1;
-    if (C == 64 && Q % 128 == 0 && !t->use_gemm) {
-        sl.g_cw = gtake(2 * C * Q); sl.g_cb = gtake(C);
-        for (int c = 0; c < C; ++c) {
-            for (int q = 0; q < Q; ++q) for (int tp = 0; tp < 2; ++tp) gs[g.causal_w + ((int64_t)c * Q + q) * 2 + tp] = sl.g_cw + tp * C * Q + c * Q + q;
-            gs[g.causal_b + c] = sl.g_cb + c;
-        }
-    }
-    bw.gstage = go; bw.nch = t->use_gemm ? 4 : 64; bw.n_params = g.n_params;
-    if (t->knobs.wgrad_chunks > 0) bw.nch = t->knobs.wgrad_chunks;      // tuning knob: time chunks (= partial slabs)
-    // the upsampling kernel's gradient is written by a dedicated kernel (gs stays -1: k_up_bwd adds onto the zeroed entries; hoist: k_aux_tail stores them)
-    if (t->hoist) for (int j = 0; j < g.U; ++j) gs[g.up_w + j] = -2;      // (the upsampling bias stays -1: zeroed by the reduction, k_aux_tail adds onto it)
-
-    const size_t nmap = t->use_gemm ? 4 : map.size();      // (the GEMM path keeps its own K-major blocks)
-    QPN_HIP(hipMalloc(&t->d_wmap, nmap * sizeof(int)));
-    QPN_HIP(hipMalloc(&t->d_wp, nmap * sizeof(float)));
-    QPN_HIP(hipMalloc(&t->d_bstart, t->h_bstart.size() * sizeof(int)));
-    QPN_HIP(hipMalloc(&t->d_blist, t->h_blist.size() * sizeof(int)));
-    QPN_HIP(hipMalloc(&t->d_bp, (size_t)t->n_bias * sizeof(float)));
+    const size_t nfrag = pl.use_gemm ? 4 : wmap.size();      // (the GEMM path keeps its own K-major blocks: a token buffer stands in for the fragment-ordered ones)
+    rc = upload(&t->d_wmap, pl.h_wmap, nfrag - pl.h_wmap.size()); if (rc) return rc;
+    QPN_HIP(hipMalloc(&t->d_wp, nfrag * sizeof(float)));
+    rc = upload(&t->d_bstart, pl.h_bstart); if (rc) return rc;
+    rc = upload(&t->d_blist, pl.h_blist); if (rc) return rc;
+    QPN_HIP(hipMalloc(&t->d_bp, (size_t)pl.n_bias * sizeof(float)));
+    rc = upload(&t->d_gdst, pl.gdst_start); if (rc) return rc;
+    rc = upload(&t->d_gdst_list, pl.gdst_list); if (rc) return rc;
+    rc = upload(&t->d_gzero, pl.gzero, 1); if (rc) return rc;
+    t->n_gzero = (int)pl.gzero.size();
+    rc = upload(&t->d_ctmap, pl.h_ctmap); if (rc) return rc;
+    QPN_HIP(hipMalloc(&t->d_ct, pl.h_ctmap.size() * sizeof(float)));
     QPN_HIP(hipMalloc(&t->d_status, 64));
     QPN_HIP(hipMemset(t->d_status, 0, 64));
-    t->last_stream = nullptr;
-    t->h_status_pinned = nullptr; t->ev_status[0] = t->ev_status[1] = nullptr; t->status_pending[0] = t->status_pending[1] = false; t->status_newest = 0;
     QPN_HIP(hipHostMalloc((void**)&t->h_status_pinned, 64, hipHostMallocDefault));
-    t->h_loss_pinned = nullptr; t->ev_loss[0] = t->ev_loss[1] = nullptr; t->loss_pending[0] = t->loss_pending[1] = false; t->loss_newest = 0;
     QPN_HIP(hipHostMalloc((void**)&t->h_loss_pinned, 2 * LOSS_SLOT * sizeof(double), hipHostMallocDefault));
-    t->d_gnorm = nullptr; t->gnorm_last = false; t->gnorm_slot[0] = t->gnorm_slot[1] = false; t->gnorm_collected = 0.0; t->gnorm_collected_valid = false;
     QPN_HIP(hipMalloc(&t->d_gnorm, TR_GN_BLOCKS * sizeof(double)));
     QPN_HIP(hipMemset(t->d_gnorm, 0, TR_GN_BLOCKS * sizeof(double)));
-    QPN_HIP(hipEventCreateWithFlags(&t->ev_loss[0], hipEventDisableTiming));
-    QPN_HIP(hipEventCreateWithFlags(&t->ev_loss[1], hipEventDisableTiming));
-    QPN_HIP(hipEventCreateWithFlags(&t->ev_status[0], hipEventDisableTiming));
-    QPN_HIP(hipEventCreateWithFlags(&t->ev_status[1], hipEventDisableTiming));
     QPN_HIP(hipMalloc(&t->d_loss, LOSS_SLOT * sizeof(double)));
     QPN_HIP(hipMemset(t->d_loss, 0, LOSS_SLOT * sizeof(double)));
-    if (!t->use_gemm) QPN_HIP(hipMemcpy(t->d_wmap, map.data(), nmap * sizeof(int), hipMemcpyHostToDevice));
-    QPN_HIP(hipMemcpy(t->d_bstart, t->h_bstart.data(), t->h_bstart.size() * sizeof(int), hipMemcpyHostToDevice));
-    QPN_HIP(hipMemcpy(t->d_blist, t->h_blist.data(), t->h_blist.size() * sizeof(int), hipMemcpyHostToDevice));
-    {   // inverse of gsrc for the slab-order reduction, CSR: a slab element feeds one parameter, or several (a gate's conv / aux /
-        // past-tap conv biases share one gradient, every layer's skip bias shares one); entries nothing feeds are listed for zeroing
-        std::vector<int> start((size_t)go + 1, 0), list, gz;
-        for (int64_t i = 0; i < g.n_params; ++i) { if (gs[i] >= 0) ++start[(size_t)gs[i] + 1]; else if (gs[i] == -1) gz.push_back((int)i); }
-        for (int k = 0; k < go; ++k) start[(size_t)k + 1] += start[k];
-        list.resize((size_t)start[go] + 1);
-        std::vector<int> fill(start.begin(), start.end() - 1);
-        for (int64_t i = 0; i < g.n_params; ++i) if (gs[i] >= 0) list[(size_t)fill[gs[i]]++] = (int)i;
-        QPN_HIP(hipMalloc(&t->d_gdst, start.size() * sizeof(int)));
-        QPN_HIP(hipMemcpy(t->d_gdst, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice));
-        QPN_HIP(hipMalloc(&t->d_gdst_list, list.size() * sizeof(int)));
-        QPN_HIP(hipMemcpy(t->d_gdst_list, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice));
-        t->n_gzero = (int)gz.size();
-        QPN_HIP(hipMalloc(&t->d_gzero, (gz.size() + 1) * sizeof(int)));
-        if (!gz.empty()) QPN_HIP(hipMemcpy(t->d_gzero, gz.data(), gz.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
-    if (t->use_gemm) {
-        QPN_HIP(hipMalloc(&t->d_gmap, t->h_gmap.size() * sizeof(int)));
-        QPN_HIP(hipMalloc(&t->d_gwp, t->h_gmap.size() * sizeof(float)));
-        QPN_HIP(hipMemcpy(t->d_gmap, t->h_gmap.data(), t->h_gmap.size() * sizeof(int), hipMemcpyHostToDevice));
-        t->gm.wp = t->d_gwp;
-        std::vector<int>().swap(t->h_wmap);                 // the fragment-ordered blocks of the tile kernels are not used on this path
-    }
-    {
-        std::vector<int> ctm((size_t)2 * Q * C);
-        for (int tp = 0; tp < 2; ++tp) for (int q = 0; q < Q; ++q) for (int c = 0; c < C; ++c)
-            ctm[((size_t)tp * Q + q) * C + c] = (int)(g.causal_w + ((int64_t)c * Q + q) * 2 + tp);
-        QPN_HIP(hipMalloc(&t->d_ctmap, ctm.size() * sizeof(int)));
-        QPN_HIP(hipMalloc(&t->d_ct, ctm.size() * sizeof(float)));
-        QPN_HIP(hipMemcpy(t->d_ctmap, ctm.data(), ctm.size() * sizeof(int), hipMemcpyHostToDevice));
+    for (int i = 0; i < 2; ++i) {
+        QPN_HIP(hipEventCreateWithFlags(&t->ev_loss[i], hipEventDisableTiming));
+        QPN_HIP(hipEventCreateWithFlags(&t->ev_status[i], hipEventDisableTiming));
     }
     QPN_HIP(hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking));          // on the handle's device (current at this call)
     // the fork / join events only order kernels of THIS device's streams: no system-scope fence (cache write-back for the host) at each record
@@ -423,7 +243,7 @@ static int train_init(qpn_handle* h) {
     QPN_HIP(hipEventCreateWithFlags(&t->ev_join, evf));
     QPN_HIP(hipEventCreateWithFlags(&t->ev_mid, evf));
     QPN_HIP(hipEventCreateWithFlags(&t->ev_early, evf));
-    h->train = t;
+    h->train = t.release();
     return QPN_OK;
 }
 
@@ -473,7 +293,7 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
     }
     TrainParams& p = t->tp;
     p.B = B; p.T = (int)T; p.F = (int)F; p.Td = (int)Td; p.BL = BL; p.N0 = (int)N0; p.N1 = (int)N0 - 1; p.maxd = maxd;
-    const int C = g.C, S = g.S, L = g.L, N1 = p.N1;
+    const int L = g.L, N1 = p.N1;
     int s = 0, nA = 0;
     for (int l = 0; l < L; ++l) {
         TrLayer& ly = p.layers[l];
@@ -481,24 +301,18 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
         ly.tap_off = (nA++) * B * N1;          // every layer gets a tap table (fixed layers: n - dilation), so the kernels load taps unconditionally
         t->ag.s_out[l] = ly.s_out;
     }
-    if (t->hoist) {
+    if (t->lay.hoist) {
         if (N1 >= (1 << 24)) { qpn_set_error("chunk too long for the register-resident layer kernels (%d rows; QPN_AUX_HOIST=0 QPN_LAYER_PERSIST=0 QPN_LAYER_BWD_PERSIST=0 selects the tile-per-workgroup kernels)", N1); return QPN_EINVAL; }
         p.ffirst = (int)(((int64_t)F * g.U - N1) / g.U); p.nfr = (int)F - p.ffirst;
     } else { p.ffirst = 0; p.nfr = 0; }
-    // ---- carve the arena
-    const size_t nPA = t->hoist ? (size_t)L * B * (p.nfr + 1) * 2 * C : 0, nWJ = t->hoist ? (size_t)2 * (N1 + 16) : 0, nGW = t->hoist ? (size_t)L * B * N1 : 0;
-    const size_t nX = (size_t)(L + 1) * B * N1 * C, nG = (size_t)L * B * N1 * C, nH = t->hoist ? 64 : (size_t)B * N1 * p.Ap, nS = (size_t)B * BL * S;
-    TrainBwd& bw = t->bw;
-    const size_t nDX = (size_t)B * N1 * C, nDZ = (size_t)B * N1 * 2 * C, nDGS = (size_t)B * BL * L * C, nSlab = (size_t)bw.nch * bw.gstage;
-    const size_t nXC = (size_t)B * (N1 + 1);
-    const size_t nScr = (size_t)B * 1024 * 2 * 128;
-    size_t need = nScr + nX + 2 * nG + nH + 2 * (nS + 96 * (size_t)S + 64) + 2 * (size_t)(L + 1) * nDX + (size_t)L * nDZ + 2 * nS + nDGS + nH + nSlab + nXC + (t->use_gemm ? nG : 0) + 2 * nPA + nWJ + nGW + (size_t)L * TR_EB_SLOTS * 2 * C + 8192;
-    if (need > t->ws_cap) {
+    // ---- carve the arena: ONE list (train_arena) gives its size and every buffer's place
+    const TrainArena a = train_arena(t->lay, g, B, N1, BL, p.nfr);
+    if (a.total > t->ws_cap) {
         if (t->d_ws) (void)hipFree(t->d_ws);
         t->d_ws = nullptr; t->ws_cap = 0;
-        hipError_t e = hipMalloc(&t->d_ws, need * sizeof(float));
-        if (e != hipSuccess) { qpn_set_error("hipMalloc(%zu MiB) for the training workspace failed", need * 4 >> 20); return QPN_ENOMEM; }
-        t->ws_cap = need;
+        hipError_t e = hipMalloc(&t->d_ws, a.total * sizeof(float));
+        if (e != hipSuccess) { qpn_set_error("hipMalloc(%zu MiB) for the training workspace failed", a.total * 4 >> 20); return QPN_ENOMEM; }
+        t->ws_cap = a.total;
     }
     const size_t ntap = (size_t)std::max(nA, 1) * B * N1;
     if (ntap > t->tap_cap) {
@@ -507,17 +321,15 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
         QPN_HIP(hipMalloc(&t->d_tap, ntap * sizeof(int)));
         t->tap_cap = ntap;
     }
-    float* w = t->d_ws;
-    auto carve = [&](size_t n) { float* r = w; w += (n + 63) & ~(size_t)63; return r; };
-    p.X = carve(nX); p.SG = carve(nG); p.TH = carve(nG); p.HUP = carve(nH); p.S0 = carve(nS + 96 * (size_t)S); p.Y0 = carve(nS + 96 * (size_t)S);       // + one (80-row) tile of rows: the post-net backward prefetches its masks unclamped
-    bw.DXA[0] = carve((size_t)(L + 1) * nDX); bw.DXB[0] = carve((size_t)(L + 1) * nDX); bw.DXA[1] = bw.DXB[1] = nullptr;   // DXB directly follows DXA (one memset)
-    bw.DZ = carve((size_t)L * nDZ); bw.DS0 = carve(nS); bw.DY0 = carve(nS); bw.DGS = carve(nDGS); bw.DHUP = carve(nH); bw.slab = carve(nSlab);
-    p.XC = (int*)carve(nXC);
-    p.scratch_rows = carve(nScr);
-    if (t->use_gemm) t->gm.G = carve(nG);
-    p.PA = nullptr; p.WJ = nullptr; bw.DPA = nullptr; bw.GW = nullptr;
-    bw.EB = nullptr;
-    if (t->hoist) { p.PA = carve(nPA); bw.DPA = carve(nPA + (size_t)L * TR_EB_SLOTS * 2 * C); bw.EB = bw.DPA + nPA; p.WJ = (float2*)carve(nWJ); bw.GW = carve(nGW); }
+    TrainBwd& bw = t->bw;
+    float* const w = t->d_ws;
+    p.X = a.at(w, TA_X); p.SG = a.at(w, TA_SG); p.TH = a.at(w, TA_TH); p.HUP = a.at(w, TA_HUP); p.S0 = a.at(w, TA_S0); p.Y0 = a.at(w, TA_Y0);
+    bw.DXA[0] = a.at(w, TA_DXA); bw.DXB[0] = a.at(w, TA_DXB); bw.DXA[1] = bw.DXB[1] = nullptr;
+    bw.DZ = a.at(w, TA_DZ); bw.DS0 = a.at(w, TA_DS0); bw.DY0 = a.at(w, TA_DY0); bw.DGS = a.at(w, TA_DGS); bw.DHUP = a.at(w, TA_DHUP); bw.slab = a.at(w, TA_SLAB);
+    p.XC = (int*)a.at(w, TA_XC);
+    p.scratch_rows = a.at(w, TA_SCRATCH);
+    if (t->lay.use_gemm) t->gm.G = a.at(w, TA_G);
+    p.PA = a.at(w, TA_PA); bw.DPA = a.at(w, TA_DPA); bw.EB = a.at(w, TA_EB); p.WJ = (float2*)a.at(w, TA_WJ); bw.GW = a.at(w, TA_GW);      // (null unless hoist)
     p.TAP = t->d_tap; p.status = t->d_status;
     t->last_stream = stream;
     {   // stack work queues (train_stack.hip): a flag word per (layer, batch item, 16-row tile) and direction, compared with a per-forward epoch
@@ -554,26 +366,26 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
     RefreshArgs rf;
     bool fuse_prep;
     {
-        const int* wmap = t->use_gemm ? t->d_gmap : t->d_wmap;
-        float* wout = t->use_gemm ? t->d_gwp : t->d_wp;
-        const int64_t nw = (int64_t)(t->use_gemm ? t->h_gmap.size() : t->h_wmap.size()), nct = (int64_t)2 * g.Q * g.C;
-        const int64_t tot = nw + nct + t->n_bias + 16 + 64;
-        rf.wmap = wmap; rf.wout = wout; rf.nw = nw; rf.bstart = t->d_bstart; rf.blist = t->d_blist; rf.nb = t->n_bias; rf.loss = t->d_loss;
-        fuse_prep = t->knobs.prep_fuse && !t->use_gemm && qpn_step_prep_fits(p);
+        const int* wmap = t->lay.use_gemm ? t->d_gmap : t->d_wmap;
+        float* wout = t->lay.use_gemm ? t->d_gwp : t->d_wp;
+        const int64_t nw = t->n_map, nct = (int64_t)2 * g.Q * g.C;
+        const int64_t tot = nw + nct + t->lay.n_bias + 16 + 64;
+        rf.wmap = wmap; rf.wout = wout; rf.nw = nw; rf.bstart = t->d_bstart; rf.blist = t->d_blist; rf.nb = t->lay.n_bias; rf.loss = t->d_loss;
+        fuse_prep = t->knobs.prep_fuse && !t->lay.use_gemm && qpn_step_prep_fits(p);
         if (!fuse_prep)
             hipLaunchKernelGGL(k_refresh, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, d_flat, wmap, wout, nw, t->d_ctmap, t->d_ct, nct,
-                               t->d_bstart, t->d_blist, t->d_bp, t->n_bias, t->d_status, t->d_loss);
+                               t->d_bstart, t->d_blist, t->d_bp, t->lay.n_bias, t->d_status, t->d_loss);
         p.ct = t->d_ct;
     }
     qpn_prof_mark(PG_PREP, stream);
     t->fwd_valid = false; t->loss_clear = true;
     ++t->generation;
-    const bool fuse_ce = d_targets && !t->use_gemm && g.Q <= g.S && g.Q % 256 == 0 && !t->knobs.ce_separate;
+    const bool fuse_ce = d_targets && !t->lay.use_gemm && g.Q <= g.S && g.Q % 256 == 0 && !t->knobs.ce_separate;
     p.ce_tgt = fuse_ce ? d_targets : nullptr; p.ce_stride = tgt_stride; p.ce_dlogits = d_dlogits; p.ce_loss = t->d_loss;
     if (fuse_ce && !want_logits) p.logits = nullptr;
     const bool fuse_post = fuse_bwd && fuse_ce && d_dlogits && t->knobs.post_fuse && t->knobs.post_wide && t->knobs.zero_in_post && g.S == 256 && g.Q == 256 && g.C == 64 && (p.LC == 256 || p.LC == 512);
     t->post_bwd_done = false;
-    rc = t->use_gemm ? qpn_launch_fwd_gemm(p, t->gm, stream) : qpn_launch_fwd(p, t->knobs, t->ag, &t->sqf, stream, fuse_post ? &t->bw : nullptr, fuse_prep ? &rf : nullptr);
+    rc = t->lay.use_gemm ? qpn_launch_fwd_gemm(p, t->gm, stream) : qpn_launch_fwd(p, t->knobs, t->ag, &t->sqf, stream, fuse_post ? &t->bw : nullptr, fuse_prep ? &rf : nullptr);
     if (!rc) { t->post_bwd_done = fuse_post; t->post_bwd_dlogits = d_dlogits; }
     p.ce_tgt = nullptr; p.logits = d_logits;
     if (rc) return rc;
@@ -605,9 +417,7 @@ extern "C" int qpn_train_loss(qpn_handle* h, double* h_loss, void* stream_) {
     double parts[64];
     QPN_HIP(hipMemcpyAsync(parts, h->train->d_loss, sizeof(parts), hipMemcpyDeviceToHost, stream));
     QPN_HIP(hipStreamSynchronize(stream));
-    double sum = 0.0;
-    for (int i = 0; i < 64; ++i) sum += parts[i];
-    *h_loss = sum;
+    *h_loss = loss_sum(parts);
     return QPN_OK;
 }
 
@@ -638,9 +448,7 @@ extern "C" int qpn_train_loss_collect(qpn_handle* h, int newest, double* h_loss,
     if (!t->loss_pending[slot]) return QPN_OK;
     QPN_HIP(hipEventSynchronize(t->ev_loss[slot]));
     t->loss_pending[slot] = false;
-    double sum = 0.0;
-    for (int i = 0; i < 64; ++i) sum += t->h_loss_pinned[LOSS_SLOT * slot + i];
-    *h_loss = sum; *h_valid = 1;
+    *h_loss = loss_sum(t->h_loss_pinned + LOSS_SLOT * slot); *h_valid = 1;
     if (t->gnorm_slot[slot]) { t->gnorm_collected = t->h_loss_pinned[LOSS_SLOT * slot + 64]; t->gnorm_collected_valid = true; }
     return QPN_OK;
 }
@@ -743,9 +551,7 @@ extern "C" int qpn_ce_loss(qpn_handle* h, const float* d_logits, const int64_t* 
         double parts[64];
         QPN_HIP(hipMemcpyAsync(parts, h->train->d_loss, sizeof(parts), hipMemcpyDeviceToHost, stream));
         QPN_HIP(hipStreamSynchronize(stream));
-        double sum = 0.0;
-        for (int i = 0; i < 64; ++i) sum += parts[i];
-        *h_loss = sum;
+        *h_loss = loss_sum(parts);
     }
     return QPN_OK;
 }
@@ -802,13 +608,13 @@ extern "C" int qpn_train_backward_ex(qpn_handle* h, const float* d_dlogits, floa
     bw.dlogits = d_dlogits; bw.gflat = d_flatgrad; bw.gdst = t->d_gdst; bw.gdst_list = t->d_gdst_list; bw.gzero = t->d_gzero; bw.n_gzero = t->n_gzero;
     bw.gscale = grad_scale; bw.append_scale = append_scale; bw.status = h->train->d_status;
     bw.side = t->side; bw.ev_fork = t->ev_fork; bw.ev_join = t->ev_join; bw.ev_mid = t->ev_mid;
-    t->early_recorded = 0; bw.ev_early = t->ev_early; bw.early_recorded = (append_scale && t->early_first >= 0) ? &t->early_recorded : nullptr;
+    t->early_recorded = 0; bw.ev_early = t->ev_early; bw.early_recorded = (append_scale && t->lay.early_first >= 0) ? &t->early_recorded : nullptr;
     // (the backward queue's heads and flags belong to ONE backward per forward: a repeated backward of the same forward runs a launch per layer)
     const bool first_bwd = t->bwd_generation != t->generation;
     t->bwd_generation = t->generation;
     const bool post_done = t->post_bwd_done && first_bwd && d_dlogits == t->post_bwd_dlogits;      // (a repeated backward, or another dL/dlogits: the separate kernel)
     t->post_bwd_done = false;
-    return t->use_gemm ? qpn_launch_bwd_gemm(t->tp, bw, t->gm, (hipStream_t)stream_)
+    return t->lay.use_gemm ? qpn_launch_bwd_gemm(t->tp, bw, t->gm, (hipStream_t)stream_)
                        : qpn_launch_bwd(t->tp, bw, t->knobs, t->ag, first_bwd ? &t->sqb : nullptr, (hipStream_t)stream_, post_done);
 }
 
@@ -818,14 +624,14 @@ extern "C" int qpn_train_early_bucket(qpn_handle* h, int64_t* first, int64_t* co
     *first = 0; *count = 0;
     TrainState* t = h->train;
     if (!t || !t->early_recorded) return QPN_OK;            // this backward finished nothing early (one stream, no upsampling kernel, a plain backward): one exchange
-    *first = t->early_first; *count = t->bw.n_params - t->early_first + 4;
+    *first = t->lay.early_first; *count = t->bw.n_params - t->lay.early_first + 4;
     QPN_HIP(hipStreamWaitEvent((hipStream_t)stream_, t->ev_early, 0));
     return QPN_OK;
 }
 
 // first element of the flat-gradient tail that a backward finishes early (the post-net blocks; the 4-float trailer follows them), or -1: a
 // property of the model's parameter layout, known once the handle has trained a step -- what data-parallel ranks agree on before they split the exchange
-extern "C" int64_t qpn_train_early_first(qpn_handle* h) { return (h && h->train && h->device >= 0) ? h->train->early_first : -1; }
+extern "C" int64_t qpn_train_early_first(qpn_handle* h) { return (h && h->train && h->device >= 0) ? h->train->lay.early_first : -1; }
 
 extern "C" int qpn_adam_step(qpn_handle* h, float* d_flat, const float* d_grad, float* d_m, float* d_v, int64_t n,
                              int step, float lr, float beta1, float beta2, float eps, float weight_decay, void* stream_) {
