@@ -129,6 +129,18 @@ int qpn_decode_live(qpn_handle* h, int every);
  * while a decode is in flight. */
 int qpn_decode_sampling(qpn_handle* h, float temperature, int top_k);
 
+/* qpn_decode_sampling with the two cuts that adapt to the width of the distribution; qpn_decode_sampling(h, T, k) is this call with (1.0f, 0.0f),
+ * which switches both off.  On the weights e_c above (0 outside the top-k set; the maximum's is exactly 1.0f):
+ *   min_p in [0, 1] keeps the classes with e_c >= min_p, i.e. whose probability is at least min_p times the most probable class's (0: off);
+ *   top_p in (0, 1] then keeps the classes with e_c >= w*, where w* is the largest weight of the row whose mass S(w*) -- the fixed-order fp32
+ *   sum of the weights >= w*, DESIGN.md section 3 -- reaches top_p * S(0): the most probable classes whose mass reaches the fraction top_p of
+ *   the whole, classes tied with the last of them all kept (1: off).
+ * The draw is then the same fixed-order draw over what is left, reproducible bit for bit on the CPU like the rest, on every decode kernel.  Sticky,
+ * kernel arguments, remembered for the re-run of a launch that gave up, ignored by QPN_MODE_ARGMAX, all as above.  Checked before the device is
+ * looked at: QPN_EINVAL naming `temperature` / `top_k` as above, `top_p` when it is NaN, <= 0 or > 1, `min_p` when it is NaN, < 0 or > 1;
+ * QPN_ESTATE while a decode is in flight. */
+int qpn_decode_sampling_ex(qpn_handle* h, float temperature, int top_k, float top_p, float min_p);
+
 /* Non-blocking.  For the decode in flight: h_done[B] = samples of each row (input order) that are final in the mirror;
  * *h_samples / *row_stride = the mirror (int32 sample ids, row b at *h_samples + b * *row_stride; host memory owned by the
  * handle, valid until the next enqueue); *running = 0 once everything the enqueue put on the stream has completed.  The
@@ -410,6 +422,9 @@ int qpn_train_profile_end(qpn_handle* h, float* h_ms, int n, void* stream);
  * looked for.  For sampling from teacher-forced logits (qpn_train_forward, the logits output of qpn_decode).  Asynchronous on `stream`. */
 int qpn_sample_logits(const float* d_logits, int64_t n_rows, int Q, uint64_t seed, int row, int64_t step0, float temperature, int top_k,
                       int64_t* d_out, void* stream);
+/* ... with top_p / min_p as for qpn_decode_sampling_ex, checked in the same place; qpn_sample_logits is this call with (1.0f, 0.0f). */
+int qpn_sample_logits_ex(const float* d_logits, int64_t n_rows, int Q, uint64_t seed, int row, int64_t step0, float temperature, int top_k,
+                         float top_p, float min_p, int64_t* d_out, void* stream);
 
 int qpn_dilated_index_train(const float* d_d, int B, int64_t L, int dilation, int64_t* d_out, void* stream);
 int qpn_dilated_index_gen_f32(const float* d_d, int64_t n, int dilation, int64_t* d_out, void* stream);

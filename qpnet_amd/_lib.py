@@ -35,6 +35,7 @@ SYMBOLS = [
     ("qpn_decode_finish", _i, [_vp, _vp]),
     ("qpn_decode_live", _i, [_vp, _i]),
     ("qpn_decode_sampling", _i, [_vp, C.c_float, _i]),
+    ("qpn_decode_sampling_ex", _i, [_vp, C.c_float, _i, C.c_float, C.c_float]),
     ("qpn_decode_poll", _i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     ("qpn_decode_cancel", _i, [_vp]),
     ("qpn_decode_final_counts", _i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
@@ -82,6 +83,7 @@ SYMBOLS = [
     ("qpn_train_profile_mark", _i, [_vp, _i, _vp]),
     ("qpn_train_profile_end", _i, [_vp, C.POINTER(C.c_float), _i, _vp]),
     ("qpn_sample_logits", _i, [_vp, _i64, _i, _u64, _i, _i64, C.c_float, _i, _vp, _vp]),
+    ("qpn_sample_logits_ex", _i, [_vp, _i64, _i, _u64, _i, _i64, C.c_float, _i, C.c_float, C.c_float, _vp, _vp]),
     ("qpn_dilated_index_train", _i, [_vp, _i, _i64, _i, _vp, _vp]),
     ("qpn_dilated_index_gen_f32", _i, [_vp, _i64, _i, _vp, _vp]),
     ("qpn_dilated_index_gen_f64", _i, [_vp, _i64, _i, _vp, _vp]),

@@ -656,7 +656,7 @@ void qpn_set_error(const char* fmt, ...) {
     va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof(g_err), fmt, ap); va_end(ap);
 }
 extern "C" const char* qpn_last_error(void) { return g_err; }
-extern "C" int qpn_version(void) { return 1004; }
+extern "C" int qpn_version(void) { return 1005; }
 
 extern "C" int64_t qpn_param_count(const qpn_config* cfg) {
     Geom g; if (qpn_build_geom(cfg, &g) != QPN_OK) return -1; return g.n_params;
@@ -858,7 +858,7 @@ extern "C" int qpn_create(const qpn_config* cfg, qpn_handle** out) {
     h->n_cus = 0; h->pipe_rows = 0; h->h_utts_pinned = nullptr; h->h_utts_cap = 0;
     h->live_every = 0; h->live_call = false; h->h_live = h->d_live = nullptr; h->live_cap = 0; h->h_live_done = h->d_live_done = nullptr; h->live_done_cap = 0; h->live_stride = 0;
     h->h_cancel = h->d_cancel = nullptr; h->cancel_cap = 0; h->live_final = false;
-    h->samp_inv_temp = 1.0f; h->samp_top_k = 0;
+    h->samp_inv_temp = 1.0f; h->samp_top_k = 0; h->samp_top_p = 1.0f; h->samp_min_p = 0.0f;
     {   // the environment is read HERE, once per handle: no decode or training call looks at it again
         DecodeKnobs& k = h->dk;
         k.generic = getenv("QPN_DECODE_GENERIC") != nullptr;
@@ -1100,8 +1100,8 @@ static int decode_enqueue_impl(qpn_handle* h, hipStream_t stream, const DecodePl
                        h->aux_woff4, h->aux_tiles, h->logRa, g.A, g.Ap, g.C, g.L, h->d_pproj);
     p.wpk = (const float4*)h->d_wpk; p.flat = h->d_flat; p.qb = h->d_qb; p.tasks = h->d_tasks; p.utts = h->d_utts;
     p.status = h->d_status; p.mode = c.mode; p.seed = c.seed; p.bias_src = h->d_bias_src;
-    p.inv_temp = c.inv_temp; p.top_k = c.top_k;
-    if (c.mode == QPN_MODE_SAMPLING && (c.inv_temp != 1.0f || c.top_k != 0)) p.mode = QPN_MODE_SAMPLING_CTL;
+    p.inv_temp = c.inv_temp; p.top_k = c.top_k; p.top_p = c.top_p; p.min_p = c.min_p;
+    if (c.mode == QPN_MODE_SAMPLING && (c.inv_temp != 1.0f || c.top_k != 0 || c.top_p != 1.0f || c.min_p != 0.0f)) p.mode = QPN_MODE_SAMPLING_CTL;
     p.stamps = h->dk.stamps ? (long long*)(h->d_status + 16) : nullptr;
     p.pproj = h->d_pproj; p.dfac = c.d_dfac; p.known = h->d_known; p.teacher = d_teacher; p.out = c.d_out; p.logits = d_logits; p.ring = h->d_ring;
     QPN_HIP(hipEventRecord(h->ev0, stream));
@@ -1130,7 +1130,7 @@ extern "C" int qpn_decode_enqueue(qpn_handle* h, int B, int n_x, int64_t F, int6
     qpn_handle::DecodeCall& c = h->call;
     c.B = B; c.n_x = n_x; c.F = F; c.Td = Td; c.d_x = d_x; c.d_h = d_h; c.d_dfac = d_dfac; c.d_is_f32 = d_is_f32;
     c.n_samples.assign(h_n_samples, h_n_samples + B); c.maxd = maxd; c.mode = mode; c.seed = seed;
-    c.inv_temp = h->samp_inv_temp; c.top_k = h->samp_top_k;
+    c.inv_temp = h->samp_inv_temp; c.top_k = h->samp_top_k; c.top_p = h->samp_top_p; c.min_p = h->samp_min_p;
     c.d_teacher = d_teacher; c.d_out = d_out; c.d_logits = d_logits;
     h->live_call = h->live_every > 0;
     h->live_final = false;
@@ -1149,24 +1149,27 @@ extern "C" int qpn_decode_live(qpn_handle* h, int every) {
     return QPN_OK;
 }
 
-// the argument checks qpn_decode_sampling and qpn_sample_logits share: -> 1 / temperature, and top_k with "every class" (0 or Q) as 0
-static int sampling_controls(float temperature, int top_k, int Q, float* inv_temp, int* k) {
+// the argument checks qpn_decode_sampling(_ex) and qpn_sample_logits(_ex) share: -> 1 / temperature, and top_k with "every class" (0 or Q) as 0
+static int sampling_controls(float temperature, int top_k, float top_p, float min_p, int Q, float* inv_temp, int* k) {
     if (!(temperature > 0.0f) || std::isinf(temperature)) { qpn_set_error("temperature must be a finite number > 0 (got %g)", (double)temperature); return QPN_EINVAL; }
     const float inv = 1.0f / temperature;
     if (!std::isfinite(inv)) { qpn_set_error("temperature %g is too small: 1 / temperature is not a finite float", (double)temperature); return QPN_EINVAL; }
     if (top_k < 0 || top_k > Q) { qpn_set_error("top_k must be 0 (off) or 1..n_quantize = %d (got %d)", Q, top_k); return QPN_EINVAL; }
+    if (!(top_p > 0.0f) || top_p > 1.0f) { qpn_set_error("top_p must lie in (0, 1] (1: off; got %g)", (double)top_p); return QPN_EINVAL; }
+    if (!(min_p >= 0.0f) || min_p > 1.0f) { qpn_set_error("min_p must lie in [0, 1] (0: off; got %g)", (double)min_p); return QPN_EINVAL; }
     *inv_temp = inv; *k = top_k == Q ? 0 : top_k;
     return QPN_OK;
 }
 
-extern "C" int qpn_decode_sampling(qpn_handle* h, float temperature, int top_k) {
+extern "C" int qpn_decode_sampling_ex(qpn_handle* h, float temperature, int top_k, float top_p, float min_p) {
     if (!h) { qpn_set_error("null handle"); return QPN_EINVAL; }
     float inv; int k;
-    int rc = sampling_controls(temperature, top_k, h->g.Q, &inv, &k); if (rc) return rc;
+    int rc = sampling_controls(temperature, top_k, top_p, min_p, h->g.Q, &inv, &k); if (rc) return rc;
     if (h->pending) { qpn_set_error("a decode is in flight: call qpn_decode_finish first"); return QPN_ESTATE; }
-    h->samp_inv_temp = inv; h->samp_top_k = k;
+    h->samp_inv_temp = inv; h->samp_top_k = k; h->samp_top_p = top_p; h->samp_min_p = min_p;
     return QPN_OK;
 }
+extern "C" int qpn_decode_sampling(qpn_handle* h, float temperature, int top_k) { return qpn_decode_sampling_ex(h, temperature, top_k, 1.0f, 0.0f); }
 
 extern "C" int qpn_decode_poll(qpn_handle* h, int64_t* h_done, const int32_t** h_samples, int64_t* row_stride, int* running) {
     int rc = need_device(h); if (rc) return rc;
@@ -1298,14 +1301,15 @@ __global__ void k_didx_gen64(const double* __restrict__ d, int64_t n, int dilati
 // ---------------------------------------------------------------- stand-alone draw from given logits
 // one wave per row: the row goes to LDS where the decode kernels keep their logits, and the wave calls the device function their picks call
 __global__ __launch_bounds__(64) void k_sample_logits(const float* __restrict__ lg, int Q, unsigned long long seed, unsigned row, unsigned step0,
-                                                      float inv_temp, int top_k, int64_t* __restrict__ out) {
+                                                      float inv_temp, int top_k, float top_p, float min_p, int64_t* __restrict__ out) {
     const int lane = threadIdx.x;
     const float* src = lg + (size_t)blockIdx.x * Q;
     for (int i = lane; i < Q; i += 64) SM[i] = src[i];
     __syncthreads();
     const unsigned step = step0 + blockIdx.x;
-    const int bi = (inv_temp != 1.0f || top_k != 0) ? sample_wave_ctl(0, Q, sample_uniform(seed, row, step), inv_temp, top_k, lane)
-                                                     : sample_wave(0, Q, seed, row, step, lane);
+    const int bi = (inv_temp != 1.0f || top_k != 0 || top_p != 1.0f || min_p != 0.0f)
+                       ? sample_wave_ctl<true>(0, Q, sample_uniform(seed, row, step), inv_temp, top_k, top_p, min_p, lane)
+                       : sample_wave(0, Q, seed, row, step, lane);
     if (lane == 0) out[blockIdx.x] = bi;
 }
 static int dev_ok() {
@@ -1313,17 +1317,21 @@ static int dev_ok() {
     if (hipGetDeviceCount(&n) != hipSuccess || n < 1) { qpn_set_error("no HIP device: libqpnet_hip has no CPU fallback"); return QPN_ENODEV; }
     return QPN_OK;
 }
-extern "C" int qpn_sample_logits(const float* d_logits, int64_t n_rows, int Q, uint64_t seed, int row, int64_t step0, float temperature, int top_k,
-                                 int64_t* d_out, void* stream) {
+extern "C" int qpn_sample_logits_ex(const float* d_logits, int64_t n_rows, int Q, uint64_t seed, int row, int64_t step0, float temperature, int top_k,
+                                    float top_p, float min_p, int64_t* d_out, void* stream) {
     if (Q < 64 || Q % 64 || Q > 256) { qpn_set_error("sampling needs Q = n_quantize in {64,128,192,256}"); return QPN_EINVAL; }
     float inv; int k;
-    int rc = sampling_controls(temperature, top_k, Q, &inv, &k); if (rc) return rc;
+    int rc = sampling_controls(temperature, top_k, top_p, min_p, Q, &inv, &k); if (rc) return rc;
     if (!d_logits || !d_out || n_rows < 1 || row < 0 || step0 < 0 || step0 + n_rows > ((int64_t)1 << 31)) { qpn_set_error("bad arguments (n_rows >= 1, row >= 0, 0 <= step0, step0 + n_rows <= 2^31)"); return QPN_EINVAL; }
     rc = dev_ok(); if (rc) return rc;
     hipLaunchKernelGGL(k_sample_logits, dim3((unsigned)n_rows), dim3(64), (size_t)Q * sizeof(float), (hipStream_t)stream, d_logits, Q, (unsigned long long)seed,
-                       (unsigned)row, (unsigned)step0, inv, k, d_out);
+                       (unsigned)row, (unsigned)step0, inv, k, top_p, min_p, d_out);
     QPN_HIP(hipGetLastError());
     return QPN_OK;
+}
+extern "C" int qpn_sample_logits(const float* d_logits, int64_t n_rows, int Q, uint64_t seed, int row, int64_t step0, float temperature, int top_k,
+                                 int64_t* d_out, void* stream) {
+    return qpn_sample_logits_ex(d_logits, n_rows, Q, seed, row, step0, temperature, top_k, 1.0f, 0.0f, d_out, stream);
 }
 extern "C" int qpn_dilated_index_train(const float* d_d, int B, int64_t L, int dilation, int64_t* d_out, void* stream) {
     int rc = dev_ok(); if (rc) return rc;

@@ -230,7 +230,48 @@ __device__ __forceinline__ unsigned sample_key(float v) {
     if (b == 0x80000000u) b = 0u;
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
-__device__ __forceinline__ int sample_wave_ctl(int o_lg, int Q, float u, float invT, int k, int lane) {
+// top_p / min_p (qpn_decode_sampling_ex), on the weights e[] of the kept set, in registers.
+// nucleus_mass is S(w) of the spec for the weight whose bit pattern is `cand`: weights below it count as 0.0f, a lane's `per` weights are summed left to
+// right, and the 64 lane sums in a balanced pairwise tree -- lane ^ 1, lane ^ 2 (quad permutes), then the other quad of the half row (row_half_mirror: the
+// quads are uniform by then), the other half of the row (row_mirror), and the four rows as (r0 + r1) + (r2 + r3).  fp32 addition is commutative, so both
+// sides of every pair compute the same bits.  Weights are non-negative floats: their bit patterns order as unsigned integers.
+__device__ __forceinline__ float nucleus_mass(const float (&e)[4], const unsigned (&eb)[4], unsigned cand, int per) {
+    float a = eb[0] >= cand ? e[0] : 0.0f;
+#pragma unroll
+    for (int j = 1; j < 4; ++j) if (j < per) a = a + (eb[j] >= cand ? e[j] : 0.0f);
+    a = a + dpp_f<0xB1>(a); a = a + dpp_f<0x4E>(a); a = a + dpp_f<0x141>(a); a = a + dpp_f<0x140>(a);
+    return (rl_f(a, 0) + rl_f(a, 16)) + (rl_f(a, 32) + rl_f(a, 48));
+}
+// min_p: a class stays when its weight is >= min_p (the maximum's weight is exactly 1.0f: it always stays).  top_p: N = { e >= w* }, w* the largest weight
+// of the row with S(w*) >= top_p * S(0).  The threshold key is built from bit 30 down like the top-k threshold, a candidate staying when its mass reaches
+// the target; every intermediate is wave-uniform.  Sets { e >= cand } are nested, so a candidate that as many weights reach as the current threshold (or as
+// the last rejected candidate) has that one's set and is decided by its ballot count; the search ends when exactly one weight separates the two, because
+// every later candidate then has one set or the other.  The empty set counts as rejected (its mass 0 is below every target: top_p > 0, S(0) >= 1).
+__device__ __forceinline__ void nucleus_cut(float (&e)[4], bool (&keep)[4], float top_p, float min_p, int per) {
+    unsigned eb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { keep[j] = keep[j] && e[j] >= min_p; e[j] = keep[j] ? e[j] : 0.0f; eb[j] = __float_as_uint(e[j]); }
+    if (!(top_p < 1.0f)) return;
+    const float target = top_p * nucleus_mass(e, eb, 0u, per);
+    unsigned thr = 0u;
+    int c_thr = 0, c_rej = 0;       // how many weights reach thr (at thr == 0: the positive ones, which carry all of S(0)) / the last rejected candidate
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c_thr += __builtin_popcountll(__builtin_amdgcn_ballot_w64(eb[j] != 0u));
+    for (int bit = 30; bit >= 0 && c_thr - c_rej > 1; --bit) {
+        const unsigned cand = thr | (1u << bit);
+        int cnt = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(eb[j] >= cand));
+        const bool stays = cnt == c_thr || (cnt != c_rej && nucleus_mass(e, eb, cand, per) >= target);
+        if (stays) { thr = cand; c_thr = cnt; } else c_rej = cnt;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { keep[j] = keep[j] && eb[j] >= thr; e[j] = keep[j] ? e[j] : 0.0f; }
+}
+// NUC: this instantiation holds the top_p / min_p cut (behind one wave-uniform test of the two values); the pipelined kernels of the calls that set neither
+// are compiled without it (k_decode_pipe_c<NU, false>), every other caller takes NUC = true
+template <bool NUC>
+__device__ __forceinline__ int sample_wave_ctl(int o_lg, int Q, float u, float invT, int k, float top_p, float min_p, int lane) {
     const float* lg = SM + o_lg;
     const int per = Q >> 6;
     float l[4], e[4];
@@ -254,6 +295,7 @@ __device__ __forceinline__ int sample_wave_ctl(int o_lg, int Q, float u, float i
     bool keep[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) { keep[j] = j < per && key[j] >= thr; e[j] = keep[j] ? qexp((l[j] - m) * invT) : 0.0f; }
+    if constexpr (NUC) if (top_p < 1.0f || min_p > 0.0f) nucleus_cut(e, keep, top_p, min_p, per);       // the kept set becomes N, the rest of the draw is the same
     float a = e[0];
 #pragma unroll
     for (int j = 1; j < 4; ++j) if (j < per) a = a + e[j];
@@ -287,10 +329,10 @@ __device__ __forceinline__ int sample_wave_ctl(int o_lg, int Q, float u, float i
 // what the decode kernels' picks call when p.mode is not QPN_MODE_ARGMAX.  The host folds "a control is set" into the mode word the picks test anyway
 // (QPN_MODE_SAMPLING_CTL, qpn_common.h): one wave-uniform compare of a kernel argument selects the draw, a default call runs sample_wave / sample_wave_u
 // untouched, and the controls themselves (DecodeParams.inv_temp / top_k, kernel arguments too: a captured launch replays them) are read on the
-// controlled path only
+// controlled path only (top_p / min_p of qpn_decode_sampling_ex as well)
 __device__ __forceinline__ int sample_pick(const DecodeParams& p, int o_lg, int Q, unsigned row, unsigned step, int lane) {
     if (p.mode == QPN_MODE_SAMPLING) return sample_wave(o_lg, Q, p.seed, row, step, lane);
-    return sample_wave_ctl(o_lg, Q, sample_uniform(p.seed, row, step), p.inv_temp, p.top_k, lane);
+    return sample_wave_ctl<true>(o_lg, Q, sample_uniform(p.seed, row, step), p.inv_temp, p.top_k, p.top_p, p.min_p, lane);
 }
 
 struct UttView {            // per-utterance pointers derived from kernel-argument bases (global address space)

@@ -451,7 +451,7 @@ __device__ __forceinline__ void skip_fixed_role(const DecodeParams& p, const Fas
 }
 
 // ------------------------------------------------------------------------------------------------ P: post 1x1 #2, pick, causal rows
-template <int NU, bool CTL>      // CTL: the launch draws with a sampling control set (QPN_MODE_SAMPLING_CTL: sample_wave_ctl); a kernel of its own, see k_decode_pipe_c
+template <int NU, int CTL>       // CTL: the launch draws with a sampling control set (QPN_MODE_SAMPLING_CTL: sample_wave_ctl; 2: with the top_p / min_p cut); kernels of their own, see k_decode_pipe_c
 __device__ __forceinline__ void post2_pick_role(const DecodeParams& p, const FastParams& f, const PipeParams& pp, const PipeUtt (&cx)[NU]) {
     constexpr int C = 64;
     float* sm = SM; int* smi = SMI;
@@ -488,7 +488,7 @@ __device__ __forceinline__ void post2_pick_role(const DecodeParams& p, const Fas
     int Tmax = 0, t_begin = 0x7fffffff;
 #pragma unroll
     for (int v = 0; v < NU; ++v) { Tmax = cx[v].Ttot > Tmax ? cx[v].Ttot : Tmax; const int tb = cx[v].u.n0 - 1 > 1 ? cx[v].u.n0 - 1 : 1; t_begin = tb < t_begin ? tb : t_begin; }
-    const bool sampling = CTL || p.mode == QPN_MODE_SAMPLING;
+    const bool sampling = CTL != 0 || p.mode == QPN_MODE_SAMPLING;
     __syncthreads();
     if (Tmax < 3) return;
     // the host's stop request (live_put): the publishing lane's state, one for the rows of the group; a launch that starts after the request
@@ -544,7 +544,7 @@ __device__ __forceinline__ void post2_pick_role(const DecodeParams& p, const Fas
             wg_barrier();                                         // LDS only (the polls' / hand-offs' global traffic is not waited for)
             if (wave == 0) {
                 int bi;
-                if constexpr (CTL) bi = sample_wave_ctl(vb + o_lg, Q, uni, p.inv_temp, p.top_k, lane);
+                if constexpr (CTL != 0) bi = sample_wave_ctl<CTL == 2>(vb + o_lg, Q, uni, p.inv_temp, p.top_k, p.top_p, p.min_p, lane);
                 else if (sampling) bi = sample_wave_u(vb + o_lg, Q, uni, lane);
                 else {
                     float bv;
@@ -589,7 +589,7 @@ __device__ __forceinline__ void post2_pick_role(const DecodeParams& p, const Fas
     }
 }
 
-template <int NU, bool CTL = false>
+template <int NU, int CTL = 0>
 __device__ __forceinline__ void pipe_group(const DecodeParams& p, const FastParams& f, const PipeParams& pp, int role, int row0, int n_active) {
     PipeUtt cx[NU];
 #pragma unroll
@@ -628,18 +628,20 @@ __global__ __launch_bounds__(PIPE_NT) void k_decode_pipe_n(DecodeParams p, FastP
 // controlled draw in the pick.  Kernels of their own for the same reason: the five roles share one whole-kernel register allocation (the K role
 // takes all 256 VGPRs, the scalar registers spill), and the selection loop inlined behind a runtime branch cost the DEFAULT calls 0.4 % (greedy)
 // to 0.7 % (sampling) of their step time (three alternating runs against the parent build, B = 20: 8.25 / 8.67 us against 8.22 / 8.60).  With
-// the draw chosen at compile time the default kernels hold no instruction of it.  NU = 1: the block mapping of k_decode_pipe
-template <int NU>
+// the draw chosen at compile time the default kernels hold no instruction of it.  NU = 1: the block mapping of k_decode_pipe.
+// NUC: the calls that set top_p or min_p (qpn_decode_sampling_ex) get instantiations of their own for the same reason once more -- k_decode_pipe_c<2, false>
+// already spills, and with the cut's search loop compiled in only where a call asked for it, temperature / top_k calls run the instruction stream they ran
+template <int NU, bool NUC>
 __global__ __launch_bounds__(PIPE_NT) void k_decode_pipe_c(DecodeParams p, FastParams f, PipeParams pp) {
     const int chunk = blockIdx.x / 40, within = blockIdx.x - chunk * 40, role = within >> 3, gi = chunk * 8 + (within & 7);
     if constexpr (NU == 1) {
         if (gi >= pp.nutt) return;
-        pipe_group<1, true>(p, f, pp, role, gi, 1);
+        pipe_group<1, NUC ? 2 : 1>(p, f, pp, role, gi, 1);
     } else {
         if (gi >= pp.groups) return;
         const int first_big = pp.groups - pp.rem;
         const int row0 = gi * pp.base + (gi > first_big ? gi - first_big : 0), cnt = pp.base + (gi >= first_big ? 1 : 0);
-        pipe_group<NU, true>(p, f, pp, role, row0, cnt);
+        pipe_group<NU, NUC ? 2 : 1>(p, f, pp, role, row0, cnt);
     }
 }
 
@@ -692,18 +694,16 @@ int qpn_launch_decode_pipe(qpn_handle* h, DecodeParams p, const DecodeLaunch& l,
     }
 #endif
     const size_t lds = pipe_lds_bytes(nu);
-    const bool ctl = p.mode == QPN_MODE_SAMPLING_CTL;
-    const void* kfn = ctl ? (nu == 1 ? (const void*)k_decode_pipe_c<1> : nu == 2 ? (const void*)k_decode_pipe_c<2> : (const void*)k_decode_pipe_c<3>)
-                          : (nu == 1 ? (const void*)k_decode_pipe : nu == 2 ? (const void*)k_decode_pipe_n<2> : (const void*)k_decode_pipe_n<3>);
-    QPN_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));    // per device: set at every launch
+    typedef void (*PipeKernel)(DecodeParams, FastParams, PipeParams);
+    static const PipeKernel kernels[3][3] = {       // [0: default draw or argmax, 1: a sampling control set, 2: top_p or min_p among them][nu - 1]
+        { k_decode_pipe, k_decode_pipe_n<2>, k_decode_pipe_n<3> },
+        { k_decode_pipe_c<1, false>, k_decode_pipe_c<2, false>, k_decode_pipe_c<3, false> },
+        { k_decode_pipe_c<1, true>, k_decode_pipe_c<2, true>, k_decode_pipe_c<3, true> } };
+    const int draw = p.mode != QPN_MODE_SAMPLING_CTL ? 0 : (p.top_p != 1.0f || p.min_p != 0.0f) ? 2 : 1;
+    const PipeKernel kfn = kernels[draw][nu - 1];
+    QPN_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));    // per device: set at every launch
     const int nchunks = (groups + 7) / 8;
-    if (ctl) {
-        if (nu == 1) hipLaunchKernelGGL(k_decode_pipe_c<1>, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, h->fp, pp);
-        else if (nu == 2) hipLaunchKernelGGL(k_decode_pipe_c<2>, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, h->fp, pp);
-        else hipLaunchKernelGGL(k_decode_pipe_c<3>, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, h->fp, pp);
-    } else if (nu == 1) hipLaunchKernelGGL(k_decode_pipe, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, h->fp, pp);
-    else if (nu == 2) hipLaunchKernelGGL(k_decode_pipe_n<2>, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, h->fp, pp);
-    else hipLaunchKernelGGL(k_decode_pipe_n<3>, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, h->fp, pp);
+    hipLaunchKernelGGL(kfn, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, h->fp, pp);
     QPN_HIP(hipGetLastError());
     return QPN_OK;
 }

@@ -21,7 +21,7 @@
     } while (0)
 
 // ---------------------------------------------------------------- decode program
-#define QPN_MODE_SAMPLING_CTL 2   // DecodeParams.mode only, never an ABI value: QPN_MODE_SAMPLING with a sampling control set (qpn_decode_sampling)
+#define QPN_MODE_SAMPLING_CTL 2   // DecodeParams.mode only, never an ABI value: QPN_MODE_SAMPLING with a sampling control set (qpn_decode_sampling / _ex: any of the four)
 enum {
     OP_NOP = 0, OP_PAST, OP_Z, OP_RES, OP_SKIP, OP_POST1, OP_POST2, OP_CAUSAL, OP_ARGMAX, OP_STAGE
 };
@@ -96,6 +96,7 @@ struct DecodeParams {
     const int* bias_src;    // [n_bias] flat indices of the biases mirrored in LDS
     unsigned long long seed;
     float inv_temp; int top_k;   // sampling controls (qpn_decode_sampling): 1 / temperature and the top-k cut, 1.0f / 0 = off (sample_wave_ctl, decode_dev.h)
+    float top_p, min_p;          // ... and the nucleus and relative-probability cuts (qpn_decode_sampling_ex), 1.0f / 0.0f = off (nucleus_cut, decode_dev.h)
     RingDesc rings[QPN_MAX_LAYERS];
     // live output (qpn_decode_live), all null / 0 when it is not armed.  Host-coherent pinned memory that the host reads WHILE the launch runs:
     int32_t* live;          // mirror of `out` ([B][max_n], the element offsets of UttDesc.out)

@@ -53,6 +53,7 @@ struct qpn_handle {
     long long* h_live_done; long long* d_live_done; size_t live_done_cap;   // [B] published counts
     int64_t live_stride;             // max_n of the call in flight
     int* h_cancel; int* d_cancel; size_t cancel_cap;   // the stop request of qpn_decode_cancel: one host-coherent word, zeroed at every armed enqueue, read by the kernels at their publish points
+    float samp_top_p, samp_min_p;          // ... and top_p / min_p (qpn_decode_sampling_ex; 1.0f / 0.0f: off)
     float samp_inv_temp; int samp_top_k;   // sampling controls of the decode calls enqueued from now on (qpn_decode_sampling): 1 / temperature, top-k cut (0: off; k == n_quantize is stored as 0)
     bool live_final;                 // the last decode was armed and has been finished: qpn_decode_final_counts reads its counts (until the next enqueue)
     std::vector<int64_t> live_seen;  // per-row high-water mark of what qpn_decode_poll has reported.  The counts restart only while qpn_decode_finish re-runs a launch that gave up,
@@ -62,6 +63,7 @@ struct qpn_handle {
         const int64_t* d_x; const float* d_h; const void* d_dfac; int d_is_f32;
         std::vector<int64_t> n_samples; int maxd, mode; uint64_t seed;
         float inv_temp; int top_k;      // the handle's sampling controls at the enqueue: a re-run draws with the same ones
+        float top_p, min_p;
         const int64_t* d_teacher; int64_t* d_out; float* d_logits;
         DecodePlanIn in; DecodePlan plan;   // what was planned from, and what the launches followed
     } call;

@@ -216,7 +216,7 @@ class QPNet(nn.Module):
 
     # ------------------------------------------------------------------ autoregressive decode
     def batch_fast_generate(self, x, h, n_samples_list, dilated_factors,
-                            intervals=None, mode="sampling", extra_memory=False, *, temperature=1.0, top_k=0):
+                            intervals=None, mode="sampling", extra_memory=False, *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0):
         """Batch fast generation (reference qpnet.py:314-559).
 
         x (B,T0) long seed, h (B,n_aux,F) float, n_samples_list list[int] (consumed exactly like
@@ -226,8 +226,11 @@ class QPNet(nn.Module):
 
         temperature, top_k (keyword-only, not in the reference; mode="sampling" only): the draw is taken from softmax(logits / temperature)
         over the classes whose logit is at least the top_k-th largest (ties with it kept; 0 = every class), inside the decode kernel
-        (qpn_decode_sampling).  The defaults are the reference's draw.  The values hold for this call only."""
-        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature, top_k)
+        (qpn_decode_sampling).  min_p in [0, 1] then keeps the classes whose probability is at least min_p times the most probable class's
+        (0 = off), and top_p in (0, 1] the most probable of those whose mass reaches the fraction top_p of the whole, ties with the last one
+        kept (1 = off; qpn_decode_sampling_ex): two cuts that follow the width of the distribution where top_k's count
+        is fixed.  The defaults are the reference's draw.  The values hold for this call only."""
+        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature, top_k, top_p, min_p)
         L, hd, dev, B, ns, max_n, out, stream = a["L"], a["hd"], a["dev"], a["B"], a["ns"], a["max_n"], a["out"], a["stream"]
         t_start = a["t_start"]
         with torch.cuda.device(dev):
@@ -250,8 +253,9 @@ class QPNet(nn.Module):
         n_samples_list.append(keep)
         return result
 
-    def _sampling_controls(self, mode, temperature, top_k):
-        """temperature / top_k of a decode call, checked on the host before anything touches the device -> (float, int)."""
+    def _sampling_controls(self, mode, temperature, top_k, top_p=1.0, min_p=0.0):
+        """temperature / top_k / top_p / min_p of a decode call, checked on the host before anything touches the device -> (float, int, float, float).
+        top_p and min_p are rounded to float32 first, which is what the library sees: the rounded value is what is checked and returned."""
         try:
             t = float(temperature)
         except (TypeError, ValueError):
@@ -262,22 +266,32 @@ class QPNet(nn.Module):
             raise ValueError("temperature must be a finite float32 > 0 whose reciprocal is finite, not %r" % (temperature,))
         if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 0 <= int(top_k) <= self.n_quantize:
             raise ValueError("top_k must be an int in 0..n_quantize = %d (0: off), not %r" % (self.n_quantize, top_k))
-        if mode == "argmax" and (t != 1.0 or int(top_k) != 0):
-            raise ValueError("temperature / top_k shape the draw of mode='sampling'; mode='argmax' takes neither")
-        return t, int(top_k)
+        cuts = []
+        for name, v, lo_open in (("top_p", top_p, True), ("min_p", min_p, False)):
+            try:
+                with np.errstate(all="ignore"):
+                    f = float(np.float32(float(v)))
+            except (TypeError, ValueError):
+                raise ValueError("%s must be a number, not %r" % (name, v))
+            if not ((0.0 < f if lo_open else 0.0 <= f) and f <= 1.0):      # (NaN fails both)
+                raise ValueError("%s must be a float32 in %s0, 1] (%s: off), not %r" % (name, "(" if lo_open else "[", "1" if lo_open else "0", v))
+            cuts.append(f)
+        if mode == "argmax" and (t != 1.0 or int(top_k) != 0 or cuts != [1.0, 0.0]):
+            raise ValueError("temperature / top_k / top_p / min_p shape the draw of mode='sampling'; mode='argmax' takes none of them")
+        return t, int(top_k), cuts[0], cuts[1]
 
-    def _decode_args(self, x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature=1.0, top_k=0):
+    def _decode_args(self, x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0):
         """What batch_fast_generate and generate_live do before the library call: mode check, maxd, dtype and device moves, the
         output buffer, the sampling seed, binding the weights.  -> dict; "call" is the argument tuple of qpn_decode / qpn_decode_enqueue, the rest
         keeps the tensors behind its pointers alive."""
         if mode not in ("sampling", "argmax"):
             logging.error("mode should be sampling or argmax")
             sys.exit(1)
-        temperature, top_k = self._sampling_controls(mode, temperature, top_k)
+        temperature, top_k, top_p, min_p = self._sampling_controls(mode, temperature, top_k, top_p, min_p)
         import ctypes as C
         dev = x.device
         L, hd = self._native(dev)
-        _lib.check(L.qpn_decode_sampling(hd, temperature, top_k))      # this call's values, set before every enqueue: nothing is left over from the last call
+        _lib.check(L.qpn_decode_sampling_ex(hd, temperature, top_k, top_p, min_p))      # this call's values, set before every enqueue: nothing is left over from the last call
         B = len(n_samples_list)
         assert x.shape[0] == B and h.shape[0] == B
         # maxd exactly as the reference computes it (qpnet.py:347-350)
@@ -314,7 +328,7 @@ class QPNet(nn.Module):
 
     # ------------------------------------------------------------------ live decode output
     def generate_live(self, x, h, n_samples_list, dilated_factors, intervals=None, mode="sampling",
-                      extra_memory=False, every=256, poll_s=0.001, on_close="finish", *, temperature=1.0, top_k=0):
+                      extra_memory=False, every=256, poll_s=0.001, on_close="finish", *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0):
         """batch_fast_generate as a generator that hands samples over while the decode kernel runs: yields (row, start, samples)
         -- row = index in the input order, samples = a fresh int64 ndarray holding that row's samples [start, start + len) --
         as soon as a poll of the library (qpn_decode_poll) shows new finished samples of a row.  A row's pieces are contiguous
@@ -329,19 +343,19 @@ class QPNet(nn.Module):
         (`every` samples of the longest-running row each) plus the drain of the launch.  A generator that is iterated to its end
         never cancels.  After the generator has ended, either way, last_decode_counts holds every row's final count in input
         order (samples below it are valid; n_samples for a call that ran to its end) and last_decode_cancelled whether the call
-        stopped short on request.  temperature / top_k: as in batch_fast_generate."""
+        stopped short on request.  temperature / top_k / top_p / min_p: as in batch_fast_generate."""
         if on_close not in ("finish", "cancel"):
             raise ValueError("on_close must be 'finish' or 'cancel', not %r" % (on_close,))
         if int(every) < 1:
             raise ValueError("every must be >= 1")
         if mode in ("sampling", "argmax"):
-            self._sampling_controls(mode, temperature, top_k)          # (bad values are refused here, at the call, not at the first next())
+            self._sampling_controls(mode, temperature, top_k, top_p, min_p)          # (bad values are refused here, at the call, not at the first next())
         self._native(x.device)          # (CPU tensors are refused here, at the call, not at the first next())
-        return self._live_pieces(x, h, list(n_samples_list), dilated_factors, intervals, mode, extra_memory, int(every), float(poll_s), on_close == "cancel", temperature, top_k)
+        return self._live_pieces(x, h, list(n_samples_list), dilated_factors, intervals, mode, extra_memory, int(every), float(poll_s), on_close == "cancel", temperature, top_k, top_p, min_p)
 
-    def _live_pieces(self, x, h, n_samples_list, dilated_factors, intervals, mode, extra_memory, every, poll_s, cancel_on_close, temperature=1.0, top_k=0):
+    def _live_pieces(self, x, h, n_samples_list, dilated_factors, intervals, mode, extra_memory, every, poll_s, cancel_on_close, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0):
         import ctypes as C
-        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature, top_k)
+        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature, top_k, top_p, min_p)
         L, hd, dev, B, ns, max_n, out, stream = a["L"], a["hd"], a["dev"], a["B"], a["ns"], a["max_n"], a["out"], a["stream"]
         done = (C.c_int64 * B)()
         mirror, stride, running = C.POINTER(C.c_int32)(), C.c_int64(), C.c_int()

@@ -478,6 +478,8 @@ def _decode_args():
     p.add_argument("--ema", action="store_true", help="decode with the checkpoint's averaged weights (a run with --ema_decay wrote them)")
     p.add_argument("--temperature", default=1.0, type=float, help="sampling mode: draw from softmax(logits / temperature); 1: the reference's draw")
     p.add_argument("--top_k", default=0, type=int, help="sampling mode: draw among the classes with the top_k largest logits only (ties kept); 0: off")
+    p.add_argument("--top_p", default=1.0, type=float, help="sampling mode: draw among the most probable classes whose mass reaches this fraction (ties kept); 1: off")
+    p.add_argument("--min_p", default=0.0, type=float, help="sampling mode: draw among the classes at least this fraction as probable as the most probable one; 0: off")
     return p
 
 
@@ -514,7 +516,7 @@ def run_decode(argv=None):
         for feat_ids, bx, bh, ns, bd in gen:
             logging.info("decoding start!")
             outs = model.batch_fast_generate(bx, bh, ns, bd, intervals=args.intervals, mode=args.mode, extra_memory=args.extra_memory,
-                                             temperature=args.temperature, top_k=args.top_k)
+                                             temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, min_p=args.min_p)
             for feat_id, samples in zip(feat_ids, outs):
                 name = args.outdir.replace("feat_id", feat_id)
                 loaders.write_wav(name, args.fs, samples, conf.n_quantize)

@@ -1,9 +1,9 @@
-"""What the sampling controls (temperature, top_k) cost per generated sample, on one GPU:
+"""What the sampling controls (temperature, top_k, top_p, min_p) cost per generated sample, on one GPU:
     python tools/sampling_controls_cost.py [--repeats 5] [--default-only] [--out profiles/sampling_controls.txt]
 
-Paper-size model at B = 20 x 600 frames and the repo-default model at B = 20 x 100 frames, mode="sampling".  Four settings -- the default
-draw, temperature 0.7, top_k 64, and both -- ALTERNATE inside one process (call 1 of each, then call 2 of each, ...) so that clock and
-temperature drift hits them alike.  Per setting: microseconds per sample step (device time of the call's launches, qpn_last_decode_kernel_ms,
+Paper-size model at B = 20 x 600 frames and the repo-default model at B = 20 x 100 frames, mode="sampling".  The settings -- the default
+draw, temperature 0.7, top_k 64, both, min_p 0.05, top_p 0.9, and top_p 0.9 on top of temperature 0.7 and top_k 64 -- ALTERNATE inside one
+process (call 1 of each, then call 2 of each, ...) so that clock and temperature drift hits them alike.  Per setting: microseconds per sample step (device time of the call's launches, qpn_last_decode_kernel_ms,
 over the longest row's samples), min / median / max over the repeats, the difference of the medians to the default draw, and the spread of
 the repeated default calls, which is what a difference has to exceed to mean anything.
 --default-only times the default draw alone (the same inputs on a build without the controls).
@@ -11,7 +11,9 @@ the repeated default calls, which is what a difference has to exceed to mean any
 profiles/sampling_controls.txt is one GPU visit: the output of this tool on this tree; then, behind comment lines that say so, the output (less
 its header line) of a copy of this tool run with --default-only in a checkout of the parent commit, built there; then the decode figures
 of `python bench.py --mode decode --full` (samples/s of the timed greedy steps, and of the sampling-mode run) on both trees; then default calls
-alone in fresh processes that alternate between the two trees, which shows what a process's placement on the chip is worth."""
+alone in fresh processes that alternate between the two trees, which shows what a process's placement on the chip is worth.
+profiles/top_p_min_p.txt is another visit: this tool (--out) on the tree that added top_p and min_p and the parent's copy of it in a checkout of
+the parent, built there, in fresh processes that alternate between the two trees."""
 import argparse
 import os
 import sys
@@ -22,7 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SETTINGS = [("default draw", {}), ("temperature 0.7", dict(temperature=0.7)), ("top_k 64", dict(top_k=64)),
-            ("temperature 0.7, top_k 64", dict(temperature=0.7, top_k=64))]
+            ("temperature 0.7, top_k 64", dict(temperature=0.7, top_k=64)), ("min_p 0.05", dict(min_p=0.05)), ("top_p 0.9", dict(top_p=0.9)),
+            ("temperature 0.7, top_k 64, top_p 0.9", dict(temperature=0.7, top_k=64, top_p=0.9))]
 
 
 def mmm(v):
@@ -71,7 +74,7 @@ def main():
         lines.append("   spread (max - min) of the default calls: %.4f us = %.2f %% of their median" % (max(d) - min(d), 100 * (max(d) - min(d)) / base))
         for label, _ in settings:
             med = float(np.median(us[label]))
-            lines.append("   %-26s us/step: %s   vs default: %+.4f us (%+.2f %%)" % (label, mmm(us[label]), med - base, 100 * (med - base) / base))
+            lines.append("   %-36s us/step: %s   vs default: %+.4f us (%+.2f %%)" % (label, mmm(us[label]), med - base, 100 * (med - base) / base))
         del m
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
