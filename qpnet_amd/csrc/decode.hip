@@ -22,6 +22,7 @@
 #include <string.h>
 #include <algorithm>
 #include <cmath>
+#include <memory>
 
 #include "decode_dev.h"
 
@@ -663,202 +664,27 @@ extern "C" int64_t qpn_param_count(const qpn_config* cfg) {
 }
 
 
-
-static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-
-// append the tiles of one matrix to the gather map; returns the float4 offset of its first tile.
-// src(row, k) -> flat index (k < K) ; rows in PACKED order.
-template <class F>
-static int pack_matrix(std::vector<int>& map, int rows, int K, int Kp, F src) {
-    const int R = Kp / 16, rpt = 64 / R, tiles = rows / rpt;
-    const int off4 = (int)(map.size() / 4);
-    map.resize(map.size() + (size_t)tiles * 1024);
-    int* m = map.data() + (size_t)off4 * 4;
-    for (int t = 0; t < tiles; ++t)
-        for (int j = 0; j < 4; ++j)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 4; ++e) {
-                    int row = t * rpt + lane / R, q = lane % R, k = 16 * q + 4 * j + e;
-                    int64_t s = k < K ? src(row, k) : -1;
-                    m[((size_t)(t * 4 + j) * 64 + lane) * 4 + e] = (int)s;
-                }
-    return off4;
-}
-
-// 16-row tiles as the MFMA's A operand (decode_coopb.hip).  ALL the fragments of one workgroup are contiguous (blocks of `per_w` float4 from `base4`: the
-// workgroup streams 1.5 MB per generated sample and should not walk a new page for every matrix); inside a block, the tile at `rel4` holds, per 16-deep
-// chunk c, word c * 64 + lane: element e = M[row m = lane & 15][16 c + 4 e + (lane >> 4)].  src(w, m, k) -> flat index, or -1 (a zero: padding rows)
-template <class F>
-static void fill_mtiles(std::vector<int>& map, size_t base4, size_t per_w, size_t rel4, int G, int R, F src) {
-    for (int w = 0; w < G; ++w) {
-        int* mm = map.data() + (base4 + (size_t)w * per_w + rel4) * 4;
-        for (int c = 0; c < R; ++c)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 4; ++e)
-                    mm[((size_t)c * 64 + lane) * 4 + e] = (int)src(w, lane & 15, 16 * c + 4 * e + (lane >> 4));
-    }
-}
-bool qpn_coopb_supported(const Geom& g);
-
-static int build_program(qpn_handle* h) {
-    Geom& g = h->g;
-    const int C = g.C, S = g.S, Q = g.Q, A = g.A, L = g.L;
-    const int Rc = g.Cp / 16, Rs = g.Sp / 16, Ra = g.Ap / 16;
-    if (Rc > 32 || Rs > 64 || Ra > 64) { qpn_set_error("n_resch <= 512, n_skipch/n_aux <= 1024 supported by the decode kernel"); return QPN_EINVAL; }
-    if ((2 * C) % (64 / Rc) || C % (64 / Rc) || S % (64 / Rc) || S % (64 / Rs) || Q % (64 / Rs) || (2 * C) % (64 / Ra)) {
-        qpn_set_error("channel counts must be multiples of the tile height (n_resch %% %d, n_skipch %% %d, n_quantize %% %d)",
-                      64 / Rc, std::max(64 / Rc, 64 / Rs), 64 / Rs);
-        return QPN_EINVAL;
-    }
-    if (g.n_params >= (int64_t)1 << 31) { qpn_set_error("model too large for 32-bit gather map"); return QPN_EINVAL; }
-    // ---- LDS layout (float offsets, all multiples of 4): step state first (zeroed at start) ...
-    DecodeParams& p = h->dp;
-    memset(&p, 0, sizeof(p));
-    int o = 0;
-    auto take = [&](int n) { int r = o; o += (n + 3) & ~3; return r; };
-    p.o_xbuf = take((L + 1) * g.Cp); p.o_xp = take(L * g.Cp); p.o_pd = take(2 * L * 2 * C); p.o_auxv = take(L * 2 * C);
-    p.o_g = take(g.Cp); p.o_skf = take(S); p.o_ska = take(S); p.o_y1 = take(g.Sp); p.o_y2 = take(g.Sp); p.o_lg = take(Q);
-    p.o_samp = take(4); p.o_sel = take(L); p.o_gl = take(L * g.Cp); p.state_floats = o;
-    // ... then the biases the epilogues add (so no global load sits behind the weight prefetch queue)
-    std::vector<int>& bsrc = h->h_bias_src; bsrc.clear();
-    auto bias_block = [&](int64_t flat_off, int n) { int r = p.o_bias + (int)bsrc.size(); for (int i = 0; i < n; ++i) bsrc.push_back((int)(flat_off + i)); return r; };
-    p.o_bias = o;
-    std::vector<int> lds_br(L), lds_bs(L);
-    for (int l = 0; l < L; ++l) { lds_br[l] = bias_block(g.layers[l].resb, C); lds_bs[l] = bias_block(g.layers[l].skipb, S); }
-    const int lds_b1 = bias_block(g.post1_b, S), lds_b2 = bias_block(g.post2_b, Q);
-    p.n_bias = (int)bsrc.size();
-    o += (p.n_bias + 3) & ~3;
-    p.C = C; p.Cp = g.Cp; p.S = S; p.Q = Q; p.L = L; p.U = g.U;
+// the DecodeParams every call starts from: the geometry and the program's LDS layout, member by member -- the one place the two structs meet (pointers and the
+// members of a call stay null / 0)
+static DecodeParams decode_params_template(const Geom& g, const DecodeProgram& d) {
+    DecodeParams p = {};
+    const DecodeLds& s = d.lds;
+    p.n_slots = d.n_slots;
+    p.C = g.C; p.Cp = g.Cp; p.S = g.S; p.Q = g.Q; p.L = g.L; p.U = g.U;
     p.causal_w = g.causal_w; p.causal_b = g.causal_b; p.up_w = g.up_w;
-
-    // ---- packed weight tiles + task list
-    std::vector<int>& map = h->h_map; map.clear();
-    const bool cb_ok = qpn_coopb_supported(g);
-    h->cb_ok = cb_ok;
-    const int cbG = C / 8, cbRC = g.Cp / 16, cbRS = g.Sp / 16;
-    const size_t cb_per_w = cb_ok ? ((size_t)3 * L * cbRC + 2 * cbRS) * 64 : 0;      // float4 per workgroup: three tiles per layer + the two post-net tiles
-    const size_t cb_base4 = map.size() / 4;
-    if (cb_ok) {
-        map.resize(map.size() + cb_per_w * cbG * 4, -1);
-        h->cb_base4 = (long long)cb_base4; h->cb_per_w = (int)cb_per_w;
-    }
-    std::vector<std::vector<Task>> phases;
-    auto tile_tasks = [&](std::vector<Task>& ph, int op, int off4, int rows, int Kp, int xoff, int a, int b, int c, int d, int flags) {
-        const int R = Kp / 16, rpt = 64 / R, tiles = rows / rpt;
-        for (int t = 0; t < tiles; ++t) {
-            Task k; k.op = op | TF_HASW | flags | (ilog2(R) << 16); k.woff4 = off4 + t * 256; k.xoff = xoff; k.row0 = t * rpt;
-            k.a = a; k.b = b; k.c = c; k.d = d; ph.push_back(k);
-        }
-    };
-    for (int l = 0; l < L; ++l) {
-        const LayerGeom y = g.layers[l];
-        auto srcw = [&](int half, int r, int k, int past) -> int64_t {
-            if (!y.adaptive) return (half ? y.wT : y.wS) + ((int64_t)r * C + k) * 2 + (past ? 0 : 1);
-            if (past) return (half ? y.wTP : y.wSP) + (int64_t)r * C + k;
-            return (half ? y.wT : y.wS) + (int64_t)r * C + k;
-        };
-        int off_past = pack_matrix(map, 2 * C, C, g.Cp, [&](int row, int k) { return srcw(row / C, row % C, k, 1); });
-        int off_cur = pack_matrix(map, 2 * C, C, g.Cp, [&](int row, int k) { return srcw(row & 1, row >> 1, k, 0); });
-        h->w_past_il[l] = pack_matrix(map, 2 * C, C, g.Cp, [&](int row, int k) { return srcw(row & 1, row >> 1, k, 1); });   // cooperative kernel: (sigma_c, tanh_c) rows together
-        int off_res = pack_matrix(map, C, C, g.Cp, [&](int row, int k) { return y.res + (int64_t)row * C + k; });
-        int off_skip = pack_matrix(map, S, C, g.Cp, [&](int row, int k) { return y.skip + (int64_t)row * C + k; });
-        if (cb_ok) {      // the batched cooperative kernel's A-operand fragments (decode_coopb.hip): workgroup w = channels 8 w .. 8 w + 7
-            const int SBc = S / cbG;
-            h->cb_zc[l] = (3 * l + 0) * cbRC * 64; h->cb_zp[l] = (3 * l + 1) * cbRC * 64; h->cb_rs[l] = (3 * l + 2) * cbRC * 64;      // (relative to the workgroup's block)
-            fill_mtiles(map, cb_base4, cb_per_w, h->cb_zc[l], cbG, cbRC, [&](int w, int m, int k) -> int64_t { return k < C ? srcw(m >> 3, 8 * w + (m & 7), k, 0) : -1; });
-            fill_mtiles(map, cb_base4, cb_per_w, h->cb_zp[l], cbG, cbRC, [&](int w, int m, int k) -> int64_t { return k < C ? srcw(m >> 3, 8 * w + (m & 7), k, 1) : -1; });
-            fill_mtiles(map, cb_base4, cb_per_w, h->cb_rs[l], cbG, cbRC, [&](int w, int m, int k) -> int64_t {
-                if (k >= C) return -1;
-                if (m < 8) return y.res + (int64_t)(8 * w + m) * C + k;
-                return m - 8 < SBc ? y.skip + (int64_t)(SBc * w + m - 8) * C + k : -1; });
-        }
-        // Z phase: this step's pre-activations + the NEXT step's past-tap dots of the same layer (the
-        // past rows are known one step early, so these tiles fill the waves the z tiles leave idle)
-        std::vector<Task> zp, rp;
-        h->fp.w_cur[l] = off_cur; h->fp.w_past[l] = off_past; h->fp.w_res[l] = off_res; h->fp.w_skip[l] = off_skip;
-        h->fp.b_res[l] = lds_br[l]; h->fp.b_skip[l] = lds_bs[l]; h->fp.adaptive[l] = y.adaptive;
-        tile_tasks(zp, OP_Z, off_cur, 2 * C, g.Cp, p.o_xbuf + l * g.Cp, l * 2 * C, 0, p.o_g, 0, 0);
-        tile_tasks(zp, OP_PAST, off_past, 2 * C, g.Cp, p.o_xp + l * g.Cp, l * 2 * C, p.o_xbuf + l * g.Cp, l, 0, 0);
-        tile_tasks(rp, OP_RES, off_res, C, g.Cp, p.o_g, p.o_xbuf + l * g.Cp, lds_br[l], p.o_xbuf + (l + 1) * g.Cp, l + 1 < L ? l + 1 : -1, 0);
-        const bool last = l == L - 1;
-        int acc = y.adaptive ? p.o_ska : p.o_skf;
-        int other = last ? (y.adaptive ? (g.LF > 0 ? p.o_skf : -1) : -1) : 0;
-        tile_tasks(rp, OP_SKIP, off_skip, S, g.Cp, p.o_g, acc, lds_bs[l], other, p.o_y1, last ? TF_LAST : 0);
-        phases.push_back(zp); phases.push_back(rp);
-    }
-    if (cb_ok) {
-        const int SBc = S / cbG, QBc = Q / cbG;
-        h->cb_p1 = 3 * L * cbRC * 64; h->cb_p2 = h->cb_p1 + cbRS * 64;
-        fill_mtiles(map, cb_base4, cb_per_w, h->cb_p1, cbG, cbRS, [&](int w, int m, int k) -> int64_t { return (m < SBc && k < S) ? g.post1_w + (int64_t)(SBc * w + m) * S + k : -1; });
-        fill_mtiles(map, cb_base4, cb_per_w, h->cb_p2, cbG, cbRS, [&](int w, int m, int k) -> int64_t { return (m < QBc && k < S) ? g.post2_w + (int64_t)(QBc * w + m) * S + k : -1; });
-    }
-    int off_p1 = pack_matrix(map, S, S, g.Sp, [&](int row, int k) { return g.post1_w + (int64_t)row * S + k; });
-    int off_p2 = pack_matrix(map, Q, S, g.Sp, [&](int row, int k) { return g.post2_w + (int64_t)row * S + k; });
-    h->fp.w_p1 = off_p1; h->fp.w_p2 = off_p2; h->fp.b_p1 = lds_b1; h->fp.b_p2 = lds_b2;
-    std::vector<Task> p1, p2, pa;
-    tile_tasks(p1, OP_POST1, off_p1, S, g.Sp, p.o_y1, 0, lds_b1, p.o_y2, 0, 0);
-    tile_tasks(p2, OP_POST2, off_p2, Q, g.Sp, p.o_y2, 0, lds_b2, p.o_lg, 0, 0);
-    { Task k; memset(&k, 0, sizeof(k)); k.op = OP_ARGMAX; pa.push_back(k);
-      for (int w = 1; w < QPN_NW; ++w) { Task s; memset(&s, 0, sizeof(s)); s.op = OP_STAGE; s.a = 1; s.b = QPN_NW - 1; pa.push_back(s); } }
-    // aux matrices (natural rows) for the frame-rate projection kernels
-    h->logRa = ilog2(Ra); h->aux_tiles = 2 * C / (64 / Ra);
-    h->aux_woff4 = -1;
-    for (int l = 0; l < L; ++l) {
-        const LayerGeom y = g.layers[l];
-        int off = pack_matrix(map, 2 * C, A, g.Ap, [&](int row, int k) { return (row / C ? y.auxT : y.auxS) + (int64_t)(row % C) * A + k; });
-        if (l == 0) h->aux_woff4 = off;
-    }
-    phases.push_back(p1); phases.push_back(p2); phases.push_back(pa);
-    // lay the phases out as slots x waves; the ARGMAX/STAGE phase keeps its fixed wave assignment
-    h->h_tasks.clear();
-    int slot = 0;
-    for (size_t pi = 0; pi < phases.size(); ++pi) {
-        const std::vector<Task>& ph = phases[pi];
-        const bool is_last = pi + 1 == phases.size();
-        int ns = (int)((ph.size() + QPN_NW - 1) / QPN_NW);
-        h->h_tasks.resize((size_t)(slot + ns) * QPN_NW);
-        for (int s = 0; s < ns; ++s)
-            for (int w = 0; w < QPN_NW; ++w) {
-                size_t idx = (size_t)s * QPN_NW + w;
-                Task k; memset(&k, 0, sizeof(k)); k.op = OP_NOP;
-                if (idx < ph.size()) k = ph[idx];
-                if (s == 0) k.op |= TF_BARRIER | (is_last ? TF_DRAIN : 0);
-                h->h_tasks[(size_t)(slot + s) * QPN_NW + w] = k;
-            }
-        slot += ns;
-    }
-    while (slot % 3) {      // the kernel unrolls the slot loop by 3 (three weight tiles in flight per wave)
-        h->h_tasks.resize((size_t)(slot + 1) * QPN_NW);
-        for (int w = 0; w < QPN_NW; ++w) { Task k; memset(&k, 0, sizeof(k)); h->h_tasks[(size_t)slot * QPN_NW + w] = k; }
-        ++slot;
-    }
-    h->n_slots = slot;
-    p.n_slots = slot;
-    p.o_tasks = o; o += slot * QPN_NW * 8;
-    p.lds_floats = o;
-    h->single_cu_ok = (size_t)o * 4 <= 160 * 1024;        // otherwise: several workgroups per utterance (decode_coop.hip)
-    return QPN_OK;
+    p.o_xbuf = s.o_xbuf; p.o_xp = s.o_xp; p.o_pd = s.o_pd; p.o_auxv = s.o_auxv; p.o_g = s.o_g; p.o_skf = s.o_skf; p.o_ska = s.o_ska; p.o_y1 = s.o_y1; p.o_y2 = s.o_y2;
+    p.o_lg = s.o_lg; p.o_samp = s.o_samp; p.o_sel = s.o_sel; p.o_gl = s.o_gl; p.state_floats = s.state_floats;
+    p.o_bias = s.o_bias; p.n_bias = s.n_bias; p.o_tasks = s.o_tasks; p.lds_floats = s.lds_floats;
+    return p;
 }
 
-bool qpn_pipe_supported(const Geom& g);
-int qpn_pipe_rows_resident(int n_cus);
-bool qpn_coopb_supported(const Geom& g);
-
+// The handle under construction is the guard's: every early return destroys it
 extern "C" int qpn_create(const qpn_config* cfg, qpn_handle** out) {
     if (!out) { qpn_set_error("null out"); return QPN_EINVAL; }
     *out = nullptr;
-    qpn_handle* h = new qpn_handle();
+    std::unique_ptr<qpn_handle, void (*)(qpn_handle*)> h(new qpn_handle(), qpn_destroy);
     int rc = qpn_build_geom(cfg, &h->g);
-    if (rc != QPN_OK) { delete h; return rc; }
-    h->d_map = nullptr; h->d_wpk = nullptr; h->d_tasks = nullptr; h->d_qb = nullptr; h->d_bd = nullptr; h->d_status = nullptr; h->d_bias_src = nullptr;
-    h->d_flat = nullptr; h->have_weights = false;
-    h->d_pproj = nullptr; h->pproj_cap = 0; h->d_ring = nullptr; h->ring_cap = 0; h->d_known = nullptr; h->known_cap = 0;
-    h->d_xch = nullptr; h->xch_cap = 0; h->single_cu_ok = true;
-    h->d_utts = nullptr; h->utts_cap = 0; h->ev0 = h->ev1 = nullptr; h->last_ms = 0; h->pending = false; h->device = -1; h->train = nullptr;
-    h->n_cus = 0; h->pipe_rows = 0; h->h_utts_pinned = nullptr; h->h_utts_cap = 0;
-    h->live_every = 0; h->live_call = false; h->h_live = h->d_live = nullptr; h->live_cap = 0; h->h_live_done = h->d_live_done = nullptr; h->live_done_cap = 0; h->live_stride = 0;
-    h->h_cancel = h->d_cancel = nullptr; h->cancel_cap = 0; h->live_final = false;
-    h->samp_inv_temp = 1.0f; h->samp_top_k = 0; h->samp_top_p = 1.0f; h->samp_min_p = 0.0f;
+    if (rc != QPN_OK) return rc;
     {   // the environment is read HERE, once per handle: no decode or training call looks at it again
         DecodeKnobs& k = h->dk;
         k.generic = getenv("QPN_DECODE_GENERIC") != nullptr;
@@ -878,25 +704,25 @@ extern "C" int qpn_create(const qpn_config* cfg, qpn_handle** out) {
         k.test_pipe_gives_up = getenv("QPN_TEST_PIPE_GIVES_UP") != nullptr;
 #endif
     }
-    rc = build_program(h);
-    h->decode_ok = rc == QPN_OK;
-    if (rc != QPN_OK) h->decode_err = g_err;            // reported by the decode entry points; the training path has its own limits
-    h->pipe_nu = 3;                                      // most utterances a five-role group steps alternately when the batch exceeds the groups
+    // the decode program is decided here, without a device (decode_program.h).  A geometry it refuses still trains: the decode entry points report prog.err
+    h->prog = decode_program(h->g, qpn_coopb_supported(h->g));
+    if (h->prog.rc == QPN_OK) h->dp = decode_params_template(h->g, h->prog);
+    else qpn_set_error("%s", h->prog.err);
     if (const char* e = getenv("QPN_PIPE_NU")) { const int v = atoi(e); if (v >= 2 && v <= 3) h->pipe_nu = v; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
         // geometry-only handle: usable for qpn_param_count-style queries, every compute call fails loudly
-        h->device = -1; *out = h; return QPN_OK;
+        *out = h.release(); return QPN_OK;
     }
     QPN_HIP(hipGetDevice(&h->device));
     QPN_HIP(hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->device));
     if (h->n_cus < 1) h->n_cus = 1;
     h->pipe_rows = qpn_pipe_rows_resident(h->n_cus);
-    *out = h;
+    *out = h.release();
     return QPN_OK;
 }
 
-extern "C" void qpn_destroy(qpn_handle* h) {
+extern "C" void qpn_destroy(qpn_handle* h) {      // (every member may still be null)
     if (!h) return;
     if (h->device >= 0) {
         void* bufs[] = {h->d_map, h->d_wpk, h->d_tasks, h->d_qb, h->d_bd, h->d_status, h->d_bias_src, h->d_pproj, h->d_ring, h->d_known, h->d_utts, h->d_xch};
@@ -918,41 +744,59 @@ static int need_device(qpn_handle* h) {
     return QPN_OK;
 }
 
+// What the first qpn_set_weights puts on the device.  It belongs to this guard until commit() hands all of it to the handle at once: a call that fails half-way
+// frees what it had, and leaves a handle whose next call allocates again
+struct DecodeUploads {
+    int* map = nullptr; float* wpk = nullptr; Task* tasks = nullptr; float* qb = nullptr; BiasDesc* bd = nullptr; int* status = nullptr; int* bias_src = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    void commit(qpn_handle* h) {
+        h->d_map = map; h->d_wpk = wpk; h->d_tasks = tasks; h->d_qb = qb; h->d_bd = bd; h->d_status = status; h->d_bias_src = bias_src; h->ev0 = ev0; h->ev1 = ev1;
+        *this = DecodeUploads();
+    }
+    ~DecodeUploads() {
+        void* bufs[] = {map, wpk, tasks, qb, bd, status, bias_src};
+        for (void* b : bufs) if (b) (void)hipFree(b);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+};
+// device buffer of n elements, a copy of src[0 .. n) where src is given
+template <class T>
+static int upload(T** d, size_t n, const T* src) {
+    QPN_HIP(hipMalloc(d, n * sizeof(T)));
+    if (src && n) QPN_HIP(hipMemcpy(*d, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return QPN_OK;
+}
+
 extern "C" int qpn_set_weights(qpn_handle* h, const float* d_flat, size_t n, void* stream_) {
     int rc = need_device(h); if (rc) return rc;
-    if (!h->decode_ok) { qpn_set_error("%s", h->decode_err.c_str()); return QPN_EINVAL; }
+    DecodeProgram& d = h->prog;
+    if (d.rc != QPN_OK) { qpn_set_error("%s", d.err); return QPN_EINVAL; }
     if (!d_flat || (int64_t)n != h->g.n_params) { qpn_set_error("flat parameter vector must have %lld floats, got %zu", (long long)h->g.n_params, n); return QPN_EINVAL; }
     hipStream_t stream = (hipStream_t)stream_;
     const Geom& g = h->g;
-    const size_t nmap = h->h_map.size();
     if (!h->d_map) {
-        QPN_HIP(hipMalloc(&h->d_map, nmap * sizeof(int)));
-        QPN_HIP(hipMalloc(&h->d_wpk, nmap * sizeof(float)));
-        QPN_HIP(hipMalloc(&h->d_tasks, h->h_tasks.size() * sizeof(Task)));
-        QPN_HIP(hipMalloc(&h->d_qb, (size_t)g.L * 2 * g.C * sizeof(float)));
-        QPN_HIP(hipMalloc(&h->d_bd, (size_t)g.L * sizeof(BiasDesc)));
-        QPN_HIP(hipMalloc(&h->d_status, 64 + 128 * QPN_NW * sizeof(long long)));
-        QPN_HIP(hipMalloc(&h->d_bias_src, h->h_bias_src.size() * sizeof(int)));
-        QPN_HIP(hipMemcpy(h->d_bias_src, h->h_bias_src.data(), h->h_bias_src.size() * sizeof(int), hipMemcpyHostToDevice));
-        QPN_HIP(hipMemcpy(h->d_map, h->h_map.data(), nmap * sizeof(int), hipMemcpyHostToDevice));
-        QPN_HIP(hipMemcpy(h->d_tasks, h->h_tasks.data(), h->h_tasks.size() * sizeof(Task), hipMemcpyHostToDevice));
-        std::vector<BiasDesc> bd(g.L);
-        for (int l = 0; l < g.L; ++l) {
-            const LayerGeom& y = g.layers[l];
-            bd[l].auxb[0] = y.auxSb; bd[l].auxb[1] = y.auxTb; bd[l].convb[0] = y.bS; bd[l].convb[1] = y.bT;
-            bd[l].convPb[0] = y.bSP; bd[l].convPb[1] = y.bTP; bd[l].adaptive = y.adaptive; bd[l].pad = 0;
-        }
-        QPN_HIP(hipMemcpy(h->d_bd, bd.data(), bd.size() * sizeof(BiasDesc), hipMemcpyHostToDevice));
-        QPN_HIP(hipEventCreate(&h->ev0)); QPN_HIP(hipEventCreate(&h->ev1));
+        DecodeUploads u;
+        rc = upload(&u.map, d.n_map, d.map.data()); if (rc) return rc;
+        rc = upload(&u.wpk, d.n_map, (const float*)nullptr); if (rc) return rc;
+        rc = upload(&u.tasks, d.n_tasks, d.tasks.data()); if (rc) return rc;
+        rc = upload(&u.qb, (size_t)g.L * 2 * g.C, (const float*)nullptr); if (rc) return rc;
+        rc = upload(&u.bd, (size_t)g.L, d.bd); if (rc) return rc;
+        rc = upload(&u.status, 16 + 128 * QPN_NW * sizeof(long long) / sizeof(int), (const int*)nullptr); if (rc) return rc;      // the status line, then the dev stamps
+        rc = upload(&u.bias_src, d.bias_src.size(), d.bias_src.data()); if (rc) return rc;
+        QPN_HIP(hipEventCreate(&u.ev0)); QPN_HIP(hipEventCreate(&u.ev1));
+        u.commit(h);
+        std::vector<int>().swap(d.map); std::vector<Task>().swap(d.tasks); std::vector<int>().swap(d.bias_src);      // on the device now: n_map, n_tasks and lds.n_bias are what is used from here on
     }
     h->d_flat = d_flat;
-    hipLaunchKernelGGL(k_pack_gather, dim3((unsigned)((nmap + 255) / 256)), dim3(256), 0, stream, d_flat, h->d_map, h->d_wpk, (int64_t)nmap);
+    hipLaunchKernelGGL(k_pack_gather, dim3((unsigned)((d.n_map + 255) / 256)), dim3(256), 0, stream, d_flat, h->d_map, h->d_wpk, (int64_t)d.n_map);
     hipLaunchKernelGGL(k_fold_bias, dim3(g.L), dim3(256), g.Ap * sizeof(float), stream, (const float4*)h->d_wpk, d_flat, h->d_bd,
-                       h->aux_woff4, h->aux_tiles, h->logRa, g.A, g.Ap, g.C, g.U > 0 ? d_flat + g.up_b : (const float*)nullptr, h->d_qb);
+                       d.aux_woff4, d.aux_tiles, d.logRa, g.A, g.Ap, g.C, g.U > 0 ? d_flat + g.up_b : (const float*)nullptr, h->d_qb);
     QPN_HIP(hipGetLastError());
     h->have_weights = true;                              // (stream-ordered: later decode calls on this stream see the packed tiles)
     return QPN_OK;
 }
+
 
 template <class T>
 static int grow(T** p, size_t* cap, size_t need) {
@@ -961,6 +805,17 @@ static int grow(T** p, size_t* cap, size_t need) {
     *p = nullptr; *cap = 0;
     hipError_t e = hipMalloc(p, need * sizeof(T));
     if (e != hipSuccess) { qpn_set_error("hipMalloc(%zu bytes) failed: %s", need * sizeof(T), hipGetErrorString(e)); return QPN_ENOMEM; }
+    *cap = need;
+    return QPN_OK;
+}
+
+// pinned staging buffer of >= need elements (grow only)
+template <class T>
+static int grow_pinned(T** hp, size_t* cap, size_t need) {
+    if (need <= *cap) return QPN_OK;
+    if (*hp) (void)hipHostFree(*hp);
+    *hp = nullptr; *cap = 0;
+    QPN_HIP(hipHostMalloc((void**)hp, need * sizeof(T), hipHostMallocDefault));
     *cap = need;
     return QPN_OK;
 }
@@ -995,18 +850,12 @@ static int launch_one_cu(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, h
     const int use_floats = resl ? p.o_wres + nres_tiles * 1024 : p.lds_floats;
     p.o_stamp = use_floats;
     const size_t lds_bytes = ((size_t)use_floats + stamp_floats) * sizeof(float);
-    const void* kfn = fast64 ? (resl ? (const void*)k_decode_fast<64, 256, 256, 16, true> : (const void*)k_decode_fast<64, 256, 256, 16, false>)
-                    : fast32 ? (resl ? (const void*)k_decode_fast<32, 32, 256, 16, true> : (const void*)k_decode_fast<32, 32, 256, 16, false>)
-                    : (const void*)k_decode;
-    if (lds_bytes > 48 * 1024) QPN_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    if (fast64) {
-        if (resl) hipLaunchKernelGGL((k_decode_fast<64, 256, 256, 16, true>), dim3(n), dim3(1024), lds_bytes, stream, p, h->fp);
-        else hipLaunchKernelGGL((k_decode_fast<64, 256, 256, 16, false>), dim3(n), dim3(1024), lds_bytes, stream, p, h->fp);
-    } else if (fast32) {
-        if (resl) hipLaunchKernelGGL((k_decode_fast<32, 32, 256, 16, true>), dim3(n), dim3(1024), lds_bytes, stream, p, h->fp);
-        else hipLaunchKernelGGL((k_decode_fast<32, 32, 256, 16, false>), dim3(n), dim3(1024), lds_bytes, stream, p, h->fp);
-    } else
-        hipLaunchKernelGGL(k_decode, dim3(n), dim3(QPN_NT), lds_bytes, stream, p);
+    typedef void (*FastKernel)(DecodeParams, FastParams);      // the ONE choice: a straight-line kernel, or (null) the interpreter
+    const FastKernel fast = fast64 ? (resl ? k_decode_fast<64, 256, 256, 16, true> : k_decode_fast<64, 256, 256, 16, false>)
+                          : fast32 ? (resl ? k_decode_fast<32, 32, 256, 16, true> : k_decode_fast<32, 32, 256, 16, false>) : nullptr;
+    if (lds_bytes > 48 * 1024) QPN_HIP(hipFuncSetAttribute(fast ? (const void*)fast : (const void*)k_decode, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    if (fast) hipLaunchKernelGGL(fast, dim3(n), dim3(QPN_NT), lds_bytes, stream, p, h->prog.fp);
+    else hipLaunchKernelGGL(k_decode, dim3(n), dim3(QPN_NT), lds_bytes, stream, p);
     QPN_HIP(hipGetLastError());
     return QPN_OK;
 }
@@ -1016,8 +865,8 @@ static DecodePlanIn plan_inputs(const qpn_handle* h, int n_cus, int pipe_rows, i
     const Geom& g = h->g;
     DecodePlanIn in = {};
     in.C = g.C; in.S = g.S; in.Q = g.Q; in.Cp = g.Cp; in.Sp = g.Sp; in.L = g.L;
-    in.single_cu_ok = h->single_cu_ok; in.pipe_supported = qpn_pipe_supported(g); in.coopb_supported = h->cb_ok;
-    in.coopb_fits = decode_coopb_fits(in, h->h_map.size() * sizeof(float), (long long)ring_floats);
+    in.single_cu_ok = h->prog.single_cu_ok; in.pipe_supported = qpn_pipe_supported(g); in.coopb_supported = h->prog.cb_ok;
+    in.coopb_fits = decode_coopb_fits(in, h->prog.n_map * sizeof(float), (long long)ring_floats);
     in.n_cus = n_cus; in.pipe_rows = pipe_rows; in.pipe_nu = h->pipe_nu; in.B = B;
     in.coop = h->dk.coop; in.coopb = h->dk.coopb; in.pipe = h->dk.pipe; in.generic = h->dk.generic;
     return in;
@@ -1061,12 +910,7 @@ static int decode_enqueue_impl(qpn_handle* h, hipStream_t stream, const DecodePl
     rc = grow(&h->d_pproj, &h->pproj_cap, (size_t)B * F * g.L * 2 * g.C); if (rc) return rc;
     rc = grow(&h->d_known, &h->known_cap, (size_t)B * n0); if (rc) return rc;
     rc = grow(&h->d_utts, &h->utts_cap, (size_t)B); if (rc) return rc;
-    if ((size_t)B > h->h_utts_cap) {
-        if (h->h_utts_pinned) (void)hipHostFree(h->h_utts_pinned);
-        h->h_utts_pinned = nullptr; h->h_utts_cap = 0;
-        QPN_HIP(hipHostMalloc((void**)&h->h_utts_pinned, (size_t)B * sizeof(UttDesc), hipHostMallocDefault));
-        h->h_utts_cap = (size_t)B;
-    }
+    rc = grow_pinned(&h->h_utts_pinned, &h->h_utts_cap, (size_t)B); if (rc) return rc;
     if (h->live_call) {
         // live output: the mirror and the counts grow like the descriptors; the counts are zeroed from the host (no kernel of this handle is
         // running: one decode in flight, and the re-run of qpn_decode_finish comes after a stream synchronisation)
@@ -1097,7 +941,7 @@ static int decode_enqueue_impl(qpn_handle* h, hipStream_t stream, const DecodePl
     QPN_HIP(hipMemsetAsync(h->d_status, 0, 64, stream));
     hipLaunchKernelGGL(k_known, dim3((unsigned)((n0 + 255) / 256), B), dim3(256), 0, stream, c.d_x, n_x, (int)n_pad, g.Q, h->d_known);
     hipLaunchKernelGGL(k_aux_project, dim3((unsigned)F, B), dim3(256), g.Ap * sizeof(float), stream, (const float4*)h->d_wpk, c.d_h, F,
-                       h->aux_woff4, h->aux_tiles, h->logRa, g.A, g.Ap, g.C, g.L, h->d_pproj);
+                       h->prog.aux_woff4, h->prog.aux_tiles, h->prog.logRa, g.A, g.Ap, g.C, g.L, h->d_pproj);
     p.wpk = (const float4*)h->d_wpk; p.flat = h->d_flat; p.qb = h->d_qb; p.tasks = h->d_tasks; p.utts = h->d_utts;
     p.status = h->d_status; p.mode = c.mode; p.seed = c.seed; p.bias_src = h->d_bias_src;
     p.inv_temp = c.inv_temp; p.top_k = c.top_k; p.top_p = c.top_p; p.min_p = c.min_p;
@@ -1216,7 +1060,7 @@ extern "C" const char* qpn_last_decode_plan(qpn_handle* h) { return h ? h->plan.
 
 extern "C" int qpn_decode_plan_query(qpn_handle* h, int n_cus, int B, int attempt, char* buf, size_t cap) {
     if (!h || !buf || cap < 1 || B < 1 || attempt < 0 || attempt > 1) { qpn_set_error("bad plan query arguments"); return QPN_EINVAL; }
-    if (!h->decode_ok) { qpn_set_error("%s", h->decode_err.c_str()); return QPN_EINVAL; }
+    if (h->prog.rc != QPN_OK) { qpn_set_error("%s", h->prog.err); return QPN_EINVAL; }
     const int pipe_rows = n_cus > 0 ? (n_cus / 40) * 8 : h->pipe_rows;
     if (n_cus <= 0) n_cus = h->n_cus;
     if (n_cus < 1) { qpn_set_error("no HIP device: the query needs n_cus"); return QPN_ENODEV; }

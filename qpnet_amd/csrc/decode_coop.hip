@@ -276,22 +276,20 @@ __global__ __launch_bounds__(COOP_NT) void k_decode_coop(DecodeParams p, FastPar
 }
 
 // ------------------------------------------------------------------------------------------ host side
-static int ilog2c(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-
 // l.rows utterances from l.first on (the kernel's b0), G workgroups each: the caller's launches hold no more than are resident together (one workgroup per CU)
 int qpn_launch_decode_coop(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, int G, hipStream_t stream) {
-    const Geom& g = h->g;
+    const Geom& g = h->g; const DecodeProgram& d = h->prog;
     const int L = g.L, C = g.C, S = g.S, Q = g.Q;
     CoopParams c; memset(&c, 0, sizeof(c));
     c.G = G; c.CB = C / G; c.SB = S / G; c.QB = Q / G; c.Sp = g.Sp;
-    c.logR = ilog2c(g.Cp / 16); c.rpt = 64 / (g.Cp / 16); c.logRs = ilog2c(g.Sp / 16); c.rpts = 64 / (g.Sp / 16);
+    c.logR = ilog2(g.Cp / 16); c.rpt = 64 / (g.Cp / 16); c.logRs = ilog2(g.Sp / 16); c.rpts = 64 / (g.Sp / 16);
     long o = 0;
-    for (int l = 0; l < L; ++l) { c.o_ring[l] = (int)o; o += (long)p.rings[l].len * C; c.w_past_il[l] = h->w_past_il[l];
-                                  c.f_resb[l] = (int)g.layers[l].resb; c.f_skipb[l] = (int)g.layers[l].skipb; }
+    for (int l = 0; l < L; ++l) { c.o_ring[l] = (int)o; o += (long)p.rings[l].len * C; c.w_past_il[l] = d.w_past_il[l];
+                                  c.f_resb[l] = d.f_resb[l]; c.f_skipb[l] = d.f_skipb[l]; }
     c.o_g = (int)o; o += (long)L * C; c.o_y1 = (int)o; o += S; c.o_y2 = (int)o; o += S; c.o_lg = (int)o; o += Q;
     o = (o + 15) & ~15L;
     if (o >= (1L << 31)) { qpn_set_error("cooperative decode: exchange block too large"); return QPN_EINVAL; }
-    c.utt_stride = o; c.f_p1b = (int)g.post1_b; c.f_p2b = (int)g.post2_b;
+    c.utt_stride = o; c.f_p1b = d.f_p1b; c.f_p2b = d.f_p2b;
     const size_t xwords = (size_t)o * l.rows + 16;
     int rc = grow_xch(h, xwords); if (rc) return rc;
     c.xch = h->d_xch + 16; c.abort = (int*)h->d_xch;          // first 128 bytes: the abort flag
@@ -301,7 +299,7 @@ int qpn_launch_decode_coop(qpn_handle* h, DecodeParams p, const DecodeLaunch& l,
     if (lds_bytes > 160 * 1024) { qpn_set_error("cooperative decode: %zu KiB of step state per workgroup exceed LDS (use more workgroups per utterance)", lds_bytes >> 10); return QPN_EINVAL; }
     QPN_HIP(hipFuncSetAttribute((const void*)k_decode_coop, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     QPN_HIP(hipMemsetAsync(h->d_xch, 0, xwords * sizeof(unsigned long long), stream));      // tags, rings, abort flag
-    hipLaunchKernelGGL(k_decode_coop, dim3(G, l.rows), dim3(COOP_NT), lds_bytes, stream, p, h->fp, c, l.first);
+    hipLaunchKernelGGL(k_decode_coop, dim3(G, l.rows), dim3(COOP_NT), lds_bytes, stream, p, d.fp, c, l.first);
     QPN_HIP(hipGetLastError());
     return QPN_OK;
 }

@@ -601,7 +601,7 @@ bool qpn_coopb_supported(const Geom& g) {
 
 // l.rows utterances on l.groups groups of C / 8 workgroups, l.per_group each (the plan has checked that 32-bit byte offsets reach: decode_coopb_fits)
 int qpn_launch_decode_coopb(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, hipStream_t stream) {
-    const Geom& g = h->g;
+    const Geom& g = h->g; const DecodeProgram& d = h->prog;
     const int B = l.rows; p.utts += l.first;
     const int L = g.L, C = g.C, S = g.S, Q = g.Q;
     CoopbParams c; memset(&c, 0, sizeof(c));
@@ -609,14 +609,14 @@ int qpn_launch_decode_coopb(qpn_handle* h, DecodeParams p, const DecodeLaunch& l
     long o = 0;
     for (int l = 0; l < L; ++l) {
         c.o_ring[l] = (int)o; o += (long)p.rings[l].len * C;
-        c.zc[l] = h->cb_zc[l]; c.zp[l] = h->cb_zp[l]; c.rs[l] = h->cb_rs[l];
-        c.f_resb[l] = (int)g.layers[l].resb; c.f_skipb[l] = (int)g.layers[l].skipb; c.adaptive[l] = g.layers[l].adaptive;
+        c.zc[l] = d.cb_zc[l]; c.zp[l] = d.cb_zp[l]; c.rs[l] = d.cb_rs[l];
+        c.f_resb[l] = d.f_resb[l]; c.f_skipb[l] = d.f_skipb[l]; c.adaptive[l] = d.fp.adaptive[l];
     }
-    c.p1 = h->cb_p1; c.p2 = h->cb_p2; c.base4 = h->cb_base4; c.per_w = h->cb_per_w;
-    c.wpk_bytes = (unsigned)(h->h_map.size() * sizeof(float));
+    c.p1 = d.cb_p1; c.p2 = d.cb_p2; c.base4 = d.cb_base4; c.per_w = d.cb_per_w;
+    c.wpk_bytes = (unsigned)(d.n_map * sizeof(float));
     c.o_g = (int)o; o += (long)L * C; c.o_y1 = (int)o; o += S; c.o_y2 = (int)o; o += S; c.o_lg = (int)o; o += Q;
     o = (o + 15) & ~15L;
-    c.utt_stride = o; c.f_p1b = (int)g.post1_b; c.f_p2b = (int)g.post2_b;
+    c.utt_stride = o; c.f_p1b = d.f_p1b; c.f_p2b = d.f_p2b;
     if (l.per_group < 1 || l.per_group > CBB_NU || l.groups * l.per_group < B) { qpn_set_error("internal: %d utterances do not fit %d batched groups of %d", B, l.groups, l.per_group); return QPN_EINVAL; }
     c.NBper = l.per_group;
     const size_t xwords = (size_t)o * B + 16;

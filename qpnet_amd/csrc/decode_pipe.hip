@@ -673,11 +673,11 @@ int qpn_pipe_rows_resident(int n_cus) {
 
 // l.rows utterances on l.groups five-role groups, as even as possible: the shortest rows share
 int qpn_launch_decode_pipe(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, hipStream_t stream) {
-    const Geom& g = h->g;
+    const DecodeProgram& d = h->prog;
     const int B = l.rows, groups = l.groups, nu = l.per_group; p.utts += l.first;
     PipeParams pp; memset(&pp, 0, sizeof(pp));
-    for (int k = 0; k < 8; ++k) { pp.w_past_il[k] = h->w_past_il[k]; pp.f_resb[k] = (int)g.layers[k].resb; pp.f_skipb[k] = (int)g.layers[k].skipb; }
-    pp.f_p1b = (int)g.post1_b; pp.f_p2b = (int)g.post2_b; pp.nutt = B;
+    for (int k = 0; k < 8; ++k) { pp.w_past_il[k] = d.w_past_il[k]; pp.f_resb[k] = d.f_resb[k]; pp.f_skipb[k] = d.f_skipb[k]; }
+    pp.f_p1b = d.f_p1b; pp.f_p2b = d.f_p2b; pp.nutt = B;
     if (groups < 1 || groups > B || nu < 1 || nu > PIPE_MAX_NU || nu * groups < B) { qpn_set_error("internal: %d utterances do not fit %d pipelined groups", B, groups); return QPN_EINVAL; }
     pp.groups = groups; pp.base = B / groups; pp.rem = B % groups;
     const size_t xwords = (size_t)PX_STRIDE * B + 16;
@@ -703,7 +703,7 @@ int qpn_launch_decode_pipe(qpn_handle* h, DecodeParams p, const DecodeLaunch& l,
     const PipeKernel kfn = kernels[draw][nu - 1];
     QPN_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));    // per device: set at every launch
     const int nchunks = (groups + 7) / 8;
-    hipLaunchKernelGGL(kfn, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, h->fp, pp);
+    hipLaunchKernelGGL(kfn, dim3(40 * nchunks), dim3(PIPE_NT), lds, stream, p, d.fp, pp);
     QPN_HIP(hipGetLastError());
     return QPN_OK;
 }

@@ -6,9 +6,7 @@
 #include <vector>
 #include "../../include/qpnet_hip.h"
 #include "qpn_geom.h"             // LayerGeom / Geom / QPN_MAX_LAYERS / qpn_build_geom / qpn_pad_k, and the declaration of qpn_set_error
-
-#define QPN_NW 16                 // waves per decode workgroup
-#define QPN_NT (QPN_NW * 64)
+#include "decode_program.h"       // QPN_NW / QPN_NT, the OP_ / TF_ constants, Task / RingDesc / FastParams / BiasDesc, and the planner of the decode program
 
 // ---------------------------------------------------------------- error plumbing
 #define QPN_HIP(call)                                                                      \
@@ -22,24 +20,6 @@
 
 // ---------------------------------------------------------------- decode program
 #define QPN_MODE_SAMPLING_CTL 2   // DecodeParams.mode only, never an ABI value: QPN_MODE_SAMPLING with a sampling control set (qpn_decode_sampling / _ex: any of the four)
-enum {
-    OP_NOP = 0, OP_PAST, OP_Z, OP_RES, OP_SKIP, OP_POST1, OP_POST2, OP_CAUSAL, OP_ARGMAX, OP_STAGE
-};
-#define TF_BARRIER 0x100      // workgroup barrier before this task
-#define TF_DRAIN   0x200      // ... and drain this wave's global stores first
-#define TF_LAST    0x400      // OP_SKIP of the last layer: also emit relu(skip total)
-#define TF_HASW    0x800      // task consumes a weight tile (prefetchable)
-
-struct Task {          // 32 bytes, wave-uniform; the table is copied to LDS at kernel start
-    int op;            // opcode | flags | (log2 R << 16)
-    int woff4;         // float4 offset of the weight tile in the packed buffer
-    int xoff;          // LDS float offset of the input vector
-    int row0;          // first row of the tile (in the matrix' packed row order)
-    int a, b, c, d;    // op specific
-};
-
-struct RingDesc { int base; int len; int mult; int adaptive; };   // base: float offset in the utterance's ring block
-
 struct UttDesc {            // offsets into the base pointers of DecodeParams (kernel-argument pointers keep
                             // the GLOBAL address space; pointers loaded from memory would become FLAT accesses)
     int64_t pproj;          // floats: [F][L][2C] per-frame aux projections
@@ -52,14 +32,6 @@ struct UttDesc {            // offsets into the base pointers of DecodeParams (k
     int n_pad, n0, n_samples, d_is_f32;
     int64_t F;
     int row, pad_;          // row of the caller's batch (the descriptors of a launch are a permuted slice of the batch): Philox key
-};
-
-// per-layer tile / bias locations for the specialised straight-line decode kernel (k_decode_fast)
-struct FastParams {
-    int w_cur[QPN_MAX_LAYERS], w_past[QPN_MAX_LAYERS], w_res[QPN_MAX_LAYERS], w_skip[QPN_MAX_LAYERS];   // float4 offsets
-    int b_res[QPN_MAX_LAYERS], b_skip[QPN_MAX_LAYERS];                                                   // LDS float offsets
-    int adaptive[QPN_MAX_LAYERS];
-    int w_p1, w_p2, b_p1, b_p2;
 };
 
 // cooperative decode (decode_coop.hip): G workgroups per utterance, each owning 1/G of every layer's output rows; full
@@ -104,3 +76,5 @@ struct DecodeParams {
     int live_every;         // a row publishes its count after every live_every samples, and after its last one
     const int* cancel;      // the host's stop request (qpn_decode_cancel): one word, non-zero once the caller asked; read at publish points and at a row's start
 };
+static_assert(sizeof(DecodeParams) == 1080 && offsetof(DecodeParams, n_slots) == 112 && offsetof(DecodeParams, o_xbuf) == 168 && offsetof(DecodeParams, o_gl) == 236 &&
+              offsetof(DecodeParams, bias_src) == 248 && offsetof(DecodeParams, rings) == 280 && offsetof(DecodeParams, live) == 1048, "kernel argument layout");

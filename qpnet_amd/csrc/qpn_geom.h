@@ -1,5 +1,6 @@
 // qpn_geom.h -- the model geometry: where every tensor lives in the flat, state_dict-ordered parameter vector.  Plain C++ (no HIP): qpn_common.h
-// includes it for the kernels' translation units, and the pure planners (train_plan.h) and their stand-alone CPU tests include it alone.
+// includes it for the kernels' translation units, and the pure planners (train_plan.h, decode_program.h) and their stand-alone CPU tests include it alone.
+// It also states, once, the flat index of every weight element (tp_*_src at the end).
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -93,3 +94,31 @@ inline int qpn_build_geom(const qpn_config* c, Geom* g) {
     for (int l = 0; l < g->L; ++l) (g->layers[l].adaptive ? g->recA : g->recF) += g->layers[l].dilation;
     return QPN_OK;
 }
+
+// ---------------------------------------------------------------- where a tensor element lives in the flat parameter vector
+// Every index expression of a tensor is stated ONCE, here: the training planner (train_plan.h: forward packs, transposes, gradient map) and the decode planner
+// (decode_program.h: every kernel family's gather map) both go through it, so decode reads the parameter training packs and reduces its gradient into.
+// gate operand B[k][n] of z = [x_cur | x_past | aux] . W1: input column k, z column n = half * C + r (half 0 sigmoid, 1 tanh); -1 behind the aux columns.
+// A fixed layer keeps both taps in one (C, C, 2) tensor (tap 1 current, tap 0 past); an adaptive one has convC / convP
+inline int64_t tp_gate_src(const LayerGeom& y, int C, int A, int k, int n) {
+    const int half = n / C, r = n % C;
+    if (k < C) return y.adaptive ? (half ? y.wT : y.wS) + (int64_t)r * C + k : (half ? y.wT : y.wS) + ((int64_t)r * C + k) * 2 + 1;
+    if (k < 2 * C) { const int kk = k - C; return y.adaptive ? (half ? y.wTP : y.wSP) + (int64_t)r * C + kk : (half ? y.wT : y.wS) + ((int64_t)r * C + kk) * 2; }
+    if (k < 2 * C + A) return (half ? y.auxT : y.auxS) + (int64_t)r * A + (k - 2 * C);
+    return -1;
+}
+// residual 1x1 B[k][n] = Wr[n][k]; skip 1x1 of all layers stacked along k (k = l * C + c); the two post-net 1x1
+inline int64_t tp_res_src(const LayerGeom& y, int C, int k, int n) { return y.res + (int64_t)n * C + k; }
+inline int64_t tp_skip_src(const Geom& g, int k, int n) { return g.layers[k / g.C].skip + (int64_t)n * g.C + (k % g.C); }
+inline int64_t tp_post1_src(const Geom& g, int k, int n) { return g.post1_w + (int64_t)n * g.S + k; }
+inline int64_t tp_post2_src(const Geom& g, int k, int n) { return g.post2_w + (int64_t)n * g.S + k; }
+// the biases that add up on gate column n (conv, aux 1x1, and the past-tap conv of an adaptive layer): they share one packed bias and one gradient
+inline int tp_gate_bias(const LayerGeom& y, int C, int n, int64_t (&out)[3]) {
+    const int half = n / C, r = n % C;
+    out[0] = (half ? y.bT : y.bS) + r; out[1] = (half ? y.auxTb : y.auxSb) + r;
+    if (!y.adaptive) return 2;
+    out[2] = (half ? y.bTP : y.bSP) + r;
+    return 3;
+}
+// THE narrowing of a flat index to the 32 bits the device maps hold (both planners refuse a geometry whose indices do not fit)
+inline int tp_idx(int64_t flat) { return (int)flat; }

@@ -3,7 +3,6 @@
 #include "qpn_common.h"
 #include "decode_plan.h"
 
-struct BiasDesc { int64_t auxb[2], convb[2], convPb[2]; int adaptive; int pad; };
 struct TrainState;
 void qpn_train_destroy(TrainState* t);
 
@@ -19,64 +18,57 @@ struct DecodeKnobs {
     bool test_pipe_gives_up;   // -DQPN_TESTING builds only (QPN_TEST_PIPE_GIVES_UP=1)
 };
 
-struct qpn_handle {
-    Geom g;
-    int device;
-    DecodeKnobs dk;
-    // decode program
-    std::vector<int> h_map;          // gather map of the packed tile buffer
-    std::vector<Task> h_tasks;
-    int n_slots;
-    int aux_woff4, aux_tiles, logRa;
-    DecodeParams dp;                 // template (pointers filled per call)
-    FastParams fp;                   // tile map of the specialised kernel
-    int* d_map; float* d_wpk; Task* d_tasks; float* d_qb; BiasDesc* d_bd; int* d_status; int* d_bias_src;
-    std::vector<int> h_bias_src;
-    const float* d_flat; bool have_weights;
+struct qpn_handle {      // every member has an initialiser: qpn_create sets only what it computes, qpn_destroy may meet a handle at any stage of it
+    Geom g = {};
+    int device = -1;
+    DecodeKnobs dk = {};
+    // decode program (decode_program.h), decided in qpn_create; its lists are uploaded by the first qpn_set_weights, which then drops the host copies
+    DecodeProgram prog;
+    DecodeParams dp = {};            // template (pointers filled per call)
+    int* d_map = nullptr; float* d_wpk = nullptr; Task* d_tasks = nullptr; float* d_qb = nullptr; BiasDesc* d_bd = nullptr; int* d_status = nullptr; int* d_bias_src = nullptr;
+    const float* d_flat = nullptr; bool have_weights = false;
     // per-call workspaces (grow only)
-    float* d_pproj; size_t pproj_cap;
-    float* d_ring; size_t ring_cap;
-    int* d_known; size_t known_cap;
-    UttDesc* d_utts; size_t utts_cap;
-    hipEvent_t ev0, ev1; float last_ms;
-    bool pending;
+    float* d_pproj = nullptr; size_t pproj_cap = 0;
+    float* d_ring = nullptr; size_t ring_cap = 0;
+    int* d_known = nullptr; size_t known_cap = 0;
+    UttDesc* d_utts = nullptr; size_t utts_cap = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr; float last_ms = 0;
+    bool pending = false;
     // device facts queried at qpn_create (nothing assumes a 256-CU chip that is all ours)
-    int n_cus;                       // hipDeviceAttributeMultiprocessorCount
-    int pipe_rows;                   // five-role groups one pipelined launch can hold resident (5 workgroups each), a multiple of 8
-    int pipe_nu;                     // utterances per group when the batch exceeds them (1..3)
+    int n_cus = 0;                   // hipDeviceAttributeMultiprocessorCount
+    int pipe_rows = 0;               // five-role groups one pipelined launch can hold resident (5 workgroups each), a multiple of 8
+    int pipe_nu = 3;                 // utterances per group when the batch exceeds them (QPN_PIPE_NU: 2..3)
     // pinned staging of the utterance descriptors (enqueue does not synchronise)
-    UttDesc* h_utts_pinned; size_t h_utts_cap;
+    UttDesc* h_utts_pinned = nullptr; size_t h_utts_cap = 0;
     // live output (qpn_decode_live / qpn_decode_poll): host-coherent pinned memory the running kernel writes and the host reads
-    int live_every;                  // 0: not armed
-    bool live_call;                  // the decode in flight was enqueued armed
-    int32_t* h_live; int32_t* d_live; size_t live_cap;                 // mirror of d_out, [B][max_n] (host address / the device's address of it)
-    long long* h_live_done; long long* d_live_done; size_t live_done_cap;   // [B] published counts
-    int64_t live_stride;             // max_n of the call in flight
-    int* h_cancel; int* d_cancel; size_t cancel_cap;   // the stop request of qpn_decode_cancel: one host-coherent word, zeroed at every armed enqueue, read by the kernels at their publish points
-    float samp_top_p, samp_min_p;          // ... and top_p / min_p (qpn_decode_sampling_ex; 1.0f / 0.0f: off)
-    float samp_inv_temp; int samp_top_k;   // sampling controls of the decode calls enqueued from now on (qpn_decode_sampling): 1 / temperature, top-k cut (0: off; k == n_quantize is stored as 0)
-    bool live_final;                 // the last decode was armed and has been finished: qpn_decode_final_counts reads its counts (until the next enqueue)
+    int live_every = 0;              // 0: not armed
+    bool live_call = false;          // the decode in flight was enqueued armed
+    int32_t* h_live = nullptr; int32_t* d_live = nullptr; size_t live_cap = 0;                     // mirror of d_out, [B][max_n] (host address / the device's address of it)
+    long long* h_live_done = nullptr; long long* d_live_done = nullptr; size_t live_done_cap = 0;   // [B] published counts
+    int64_t live_stride = 0;         // max_n of the call in flight
+    int* h_cancel = nullptr; int* d_cancel = nullptr; size_t cancel_cap = 0;   // the stop request of qpn_decode_cancel: one host-coherent word, zeroed at every armed enqueue, read by the kernels at their publish points
+    float samp_top_p = 1.0f, samp_min_p = 0.0f;      // ... and top_p / min_p (qpn_decode_sampling_ex; 1.0f / 0.0f: off)
+    float samp_inv_temp = 1.0f; int samp_top_k = 0;  // sampling controls of the decode calls enqueued from now on (qpn_decode_sampling): 1 / temperature, top-k cut (0: off; k == n_quantize is stored as 0)
+    bool live_final = false;         // the last decode was armed and has been finished: qpn_decode_final_counts reads its counts (until the next enqueue)
     std::vector<int64_t> live_seen;  // per-row high-water mark of what qpn_decode_poll has reported.  The counts restart only while qpn_decode_finish re-runs a launch that gave up,
                                      // and a handle is not thread-safe: only a caller that polls from a second thread under its own lock around finish could ever see the restart
     struct DecodeCall {              // arguments of the decode in flight: qpn_decode_finish re-runs it with the plan of decode_plan_retry when a
-        int B, n_x; int64_t F, Td;   // multi-workgroup launch gave up (peers not co-resident: masked / shared GPU)
-        const int64_t* d_x; const float* d_h; const void* d_dfac; int d_is_f32;
-        std::vector<int64_t> n_samples; int maxd, mode; uint64_t seed;
-        float inv_temp; int top_k;      // the handle's sampling controls at the enqueue: a re-run draws with the same ones
-        float top_p, min_p;
-        const int64_t* d_teacher; int64_t* d_out; float* d_logits;
-        DecodePlanIn in; DecodePlan plan;   // what was planned from, and what the launches followed
+        int B = 0, n_x = 0; int64_t F = 0, Td = 0;   // multi-workgroup launch gave up (peers not co-resident: masked / shared GPU)
+        const int64_t* d_x = nullptr; const float* d_h = nullptr; const void* d_dfac = nullptr; int d_is_f32 = 0;
+        std::vector<int64_t> n_samples; int maxd = 0, mode = 0; uint64_t seed = 0;
+        float inv_temp = 1.0f; int top_k = 0;      // the handle's sampling controls at the enqueue: a re-run draws with the same ones
+        float top_p = 1.0f, min_p = 0.0f;
+        const int64_t* d_teacher = nullptr; int64_t* d_out = nullptr; float* d_logits = nullptr;
+        DecodePlanIn in = {}; DecodePlan plan = {};   // what was planned from, and what the launches followed
     } call;
     std::string plan;                // human-readable launch plan of the last decode (qpn_last_decode_plan)
-    bool single_cu_ok;               // the step state fits one CU's LDS (decode.hip kernels); otherwise decode_coop.hip only
-    int w_past_il[QPN_MAX_LAYERS];   // channel-interleaved past-tap tiles (cooperative kernel)
-    unsigned long long* d_xch; size_t xch_cap;   // exchange granules of the cooperative kernels
-    // batched cooperative kernel (decode_coopb.hip): workgroup w's A-operand fragments are the cb_per_w float4 from cb_base4 + w * cb_per_w of the packed weights;
-    // cb_zc.. = float4 offsets of the tiles inside that block; or cb_ok = false
-    bool cb_ok; int cb_zc[QPN_MAX_LAYERS], cb_zp[QPN_MAX_LAYERS], cb_rs[QPN_MAX_LAYERS], cb_p1, cb_p2; long long cb_base4; int cb_per_w;
-    bool decode_ok; std::string decode_err;   // geometries the decode kernels do not cover still train (and report why on decode calls)
-    struct TrainState* train;        // lazily created by the training entry points (train_host.hip)
+    unsigned long long* d_xch = nullptr; size_t xch_cap = 0;   // exchange granules of the cooperative kernels
+    struct TrainState* train = nullptr;        // lazily created by the training entry points (train_host.hip)
 };
+// what the launch plan needs to know of the kernels' own limits (decode_pipe.hip, decode_coopb.hip)
+bool qpn_pipe_supported(const Geom& g);
+bool qpn_coopb_supported(const Geom& g);
+int qpn_pipe_rows_resident(int n_cus);
 // the launchers of a plan's launches: rows [l.first, l.first + l.rows) of the descriptors behind p.utts, grouped as the plan says
 int qpn_launch_decode_pipe(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, hipStream_t stream);
 int qpn_launch_decode_coop(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, int G, hipStream_t stream);

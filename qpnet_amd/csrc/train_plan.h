@@ -1,6 +1,6 @@
 // train_plan.h -- the layout of a training handle: where every weight, bias and gradient lives in the packed blocks, the gradient slabs and the per-call arena.
 // Pure host arithmetic (plain C++: no HIP, no handle, no globals): train_host.hip uploads what train_plan() returns and carves the arena where train_arena()
-// says; tests/train_plan_sweep.cpp checks the invariants of both on a CPU.  Every index expression of a tensor is stated ONCE here (the tp_*_src functions):
+// says; tests/train_plan_sweep.cpp checks the invariants of both on a CPU.  Every index expression of a tensor is stated ONCE (the tp_*_src functions of qpn_geom.h):
 // the forward packs, their transposes and the gradient map all go through it, so a gradient cannot land on another parameter than the forward read.
 #pragma once
 #include "qpn_geom.h"
@@ -50,33 +50,9 @@ struct TrainKnobs {
     bool test_stack_gives_up;         // -DQPN_TESTING builds only (QPN_TEST_STACK_GIVES_UP=1): the queue launches' published flags are made unrecognisable
 };
 
-// ---------------------------------------------------------------- where a tensor element lives in the flat parameter vector
-// gate operand B[k][n] of z = [x_cur | x_past | aux] . W1: input column k, z column n = half * C + r (half 0 sigmoid, 1 tanh); -1 behind the aux columns.
-// A fixed layer keeps both taps in one (C, C, 2) tensor (tap 1 current, tap 0 past); an adaptive one has convC / convP
-inline int64_t tp_gate_src(const LayerGeom& y, int C, int A, int k, int n) {
-    const int half = n / C, r = n % C;
-    if (k < C) return y.adaptive ? (half ? y.wT : y.wS) + (int64_t)r * C + k : (half ? y.wT : y.wS) + ((int64_t)r * C + k) * 2 + 1;
-    if (k < 2 * C) { const int kk = k - C; return y.adaptive ? (half ? y.wTP : y.wSP) + (int64_t)r * C + kk : (half ? y.wT : y.wS) + ((int64_t)r * C + kk) * 2; }
-    if (k < 2 * C + A) return (half ? y.auxT : y.auxS) + (int64_t)r * A + (k - 2 * C);
-    return -1;
-}
-// residual 1x1 B[k][n] = Wr[n][k]; skip 1x1 of all layers stacked along k (k = l * C + c); the two post-net 1x1
-inline int64_t tp_res_src(const LayerGeom& y, int C, int k, int n) { return y.res + (int64_t)n * C + k; }
-inline int64_t tp_skip_src(const Geom& g, int k, int n) { return g.layers[k / g.C].skip + (int64_t)n * g.C + (k % g.C); }
-inline int64_t tp_post1_src(const Geom& g, int k, int n) { return g.post1_w + (int64_t)n * g.S + k; }
-inline int64_t tp_post2_src(const Geom& g, int k, int n) { return g.post2_w + (int64_t)n * g.S + k; }
+// (where a tensor element lives in the flat parameter vector -- tp_gate_src .. tp_post2_src, tp_gate_bias, tp_idx: qpn_geom.h, shared with the decode planner)
 // causal conv weight (C, Q, 2)
 inline int64_t tp_causal_src(const Geom& g, int c, int q, int tap) { return g.causal_w + ((int64_t)c * g.Q + q) * 2 + tap; }
-// the biases that add up on gate column n (conv, aux 1x1, and the past-tap conv of an adaptive layer): they share one packed bias and one gradient
-inline int tp_gate_bias(const LayerGeom& y, int C, int n, int64_t (&out)[3]) {
-    const int half = n / C, r = n % C;
-    out[0] = (half ? y.bT : y.bS) + r; out[1] = (half ? y.auxTb : y.auxSb) + r;
-    if (!y.adaptive) return 2;
-    out[2] = (half ? y.bTP : y.bSP) + r;
-    return 3;
-}
-// THE narrowing of a flat index to the 32 bits the device maps hold (train_plan refuses a geometry whose indices do not fit)
-inline int tp_idx(int64_t flat) { return (int)flat; }
 inline int tp_pad_to(int v, int q) { return (v + q - 1) / q * q; }
 
 // ---------------------------------------------------------------- the two packed orders of a weight block
