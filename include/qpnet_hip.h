@@ -308,6 +308,28 @@ int qpn_adam_step_avg(qpn_handle* h, float* d_flat, const float* d_grad, float* 
                       int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                       const float* d_grad_denominator, float max_grad_norm, float* d_ema, float ema_decay, void* stream);
 
+/* Parameter groups of the optimiser step: a learning rate and a weight decay per range of the flat vector, and ranges that are not updated at all (frozen) --
+ * what torch.optim.Adam is given as several param_groups, or by leaving tensors out.  Segment s covers [h_seg_end[s-1], h_seg_end[s]) (h_seg_end[-1] = 0) and belongs
+ * to group h_seg_group[s] in [0, n_groups) or is QPN_ADAM_FROZEN.  Sticky on the handle, like qpn_decode_sampling: from this call on EVERY Adam launch of the handle
+ * (qpn_adam_step, _ex, _clip, _avg, qpn_train_step, _clip, _avg, the closing micro-step of qpn_train_step_acc) updates element i of a segment of group q with
+ * (h_lr[q], h_weight_decay[q]) -- bit for bit what the launch without groups writes there when called with those two values, data-parallel denominator and clip
+ * coefficient included; the launch's own lr / weight_decay are ignored, everything else (betas, eps, step, denominator, clipping, averaging) is the call's.  A frozen
+ * element's weight, moments and gradient are neither written nor (the averaged weights aside: they go on moving towards the weight that stays) read.  The clipping
+ * norm is that of the elements that are not frozen -- bit for bit the norm reported for the same gradient with the frozen elements set to +0, so a non-finite value in
+ * a frozen element's gradient does not skip the step.  Reports, status word, applied-update count and the skip rule are unchanged.  A launch whose n is not
+ * h_seg_end[n_seg - 1] returns QPN_EINVAL.
+ * The group values travel as kernel arguments; only the segment table (adjacent segments of one group merged, plus a pair of ints per 256 elements) lives in device memory.
+ * A call whose segment table equals the one the handle holds touches no device memory and only replaces the values: the per-step path of a learning-rate schedule.  A
+ * changed table is a set-up call: it may synchronise `stream`, and returns QPN_ESTATE while that stream is capturing.  The arrays are not referenced after return.
+ * n_groups = 0 switches groups off: the other arguments are ignored, no device is needed, and every launch is exactly what it was.
+ * Errors, checked before the device is looked at (also on a handle created without a GPU), QPN_EINVAL naming the argument: n_groups outside [0, QPN_ADAM_MAX_GROUPS];
+ * with n_groups > 0 a NULL array; an h_lr / h_weight_decay that is NaN, infinite or negative (0 is allowed, as in torch); n_seg < 1 or > 2^20; h_seg_end[0] < 1 or
+ * h_seg_end not strictly ascending; a group outside [-1, n_groups); no trainable segment.  A valid call without a GPU returns QPN_ENODEV. */
+#define QPN_ADAM_MAX_GROUPS 8
+#define QPN_ADAM_FROZEN (-1)
+int qpn_adam_groups(qpn_handle* h, int n_groups, const float* h_lr, const float* h_weight_decay,
+                    int64_t n_seg, const int64_t* h_seg_end, const int32_t* h_seg_group, void* stream);
+
 /* Adam updates APPLIED on this handle so far, counted on the device: a k_adam launch that finds the sticky status word set -- or, behind a data-parallel
  * exchange, a peer rank's flag in the trailer (d_grad_denominator[1] > 0) -- applies nothing (every rank skips a step ANY rank flagged; the others report
  * "a peer rank flagged ..." with QPN_ERANGE).  Drains `stream`.  A caller that keeps the bias correction's step number on the host (the reference:

@@ -70,6 +70,7 @@ SYMBOLS = [
     ("qpn_train_step_avg", _i, [_vp, _vp, _i, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
                                 _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _i, C.POINTER(C.c_double), C.POINTER(C.c_int),
                                 C.c_float, C.POINTER(C.c_double), _vp, C.c_float, _vp]),
+    ("qpn_adam_groups", _i, [_vp, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _i64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp]),
     ("qpn_grad_accumulate", _i, [_vp, _vp, _vp, _i64, _i, _vp]),
     ("qpn_train_step_acc", _i, [_vp, _vp, _i, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
                                 _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _i, C.POINTER(C.c_double), C.POINTER(C.c_int),

@@ -106,6 +106,44 @@ class QPNetConfig:
         return self.param_offsets()[1]
 
 
+ADAM_FROZEN = -1          # QPN_ADAM_FROZEN (include/qpnet_hip.h)
+ADAM_MAX_GROUPS = 8       # QPN_ADAM_MAX_GROUPS
+
+
+def adam_group_table(cfg: "QPNetConfig", entries, default_group: int = 0):
+    """Name patterns -> the segment table of `qpn_adam_groups` over the flat parameter vector of `cfg` (pure: no GPU, no library).
+
+    entries: [(patterns, group)] -- `patterns` one fnmatch pattern over state_dict keys or a list of them, `group` an id >= 0 or ADAM_FROZEN.  Keys
+    matched by no entry belong to `default_group`.  -> (seg_end, seg_group, key_group): one segment per run of consecutive tensors of one group
+    (the segments tile [0, n_params)), and {key: group}.  ValueError: a pattern that matches no key; a key claimed by two entries."""
+    import fnmatch
+    layout = cfg.param_layout()
+    keys = [k for k, _ in layout]
+    owner = {}                                    # key -> (entry index, the pattern that claimed it)
+    for e, (pats, group) in enumerate(entries):
+        for pat in ([pats] if isinstance(pats, str) else list(pats)):
+            hit = fnmatch.filter(keys, pat)
+            if not hit:
+                raise ValueError("parameter group pattern %r matches no parameter of the model (keys are state_dict names, e.g. %r)" % (pat, keys[0]))
+            for k in hit:
+                if k in owner and owner[k][0] != e:
+                    raise ValueError("parameter %r is claimed by two groups: pattern %r and pattern %r" % (k, owner[k][1], pat))
+                owner.setdefault(k, (e, pat))
+    seg_end, seg_group, key_group, o = [], [], {}, 0
+    for k, shp in layout:
+        n = 1
+        for s in shp:
+            n *= s
+        o += n
+        g = int(entries[owner[k][0]][1]) if k in owner else int(default_group)
+        key_group[k] = g
+        if seg_group and seg_group[-1] == g:
+            seg_end[-1] = o
+        else:
+            seg_end.append(o); seg_group.append(g)
+    return seg_end, seg_group, key_group
+
+
 # the three geometries named in SURVEY.md §8
 TINY = QPNetConfig(n_resch=32, n_skipch=32, dilationF_depth=2, dilationF_repeat=1,
                    dilationA_depth=1, dilationA_repeat=1)

@@ -657,7 +657,7 @@ void qpn_set_error(const char* fmt, ...) {
     va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof(g_err), fmt, ap); va_end(ap);
 }
 extern "C" const char* qpn_last_error(void) { return g_err; }
-extern "C" int qpn_version(void) { return 1005; }
+extern "C" int qpn_version(void) { return 1006; }
 
 extern "C" int64_t qpn_param_count(const qpn_config* cfg) {
     Geom g; if (qpn_build_geom(cfg, &g) != QPN_OK) return -1; return g.n_params;
@@ -725,7 +725,7 @@ extern "C" int qpn_create(const qpn_config* cfg, qpn_handle** out) {
 extern "C" void qpn_destroy(qpn_handle* h) {      // (every member may still be null)
     if (!h) return;
     if (h->device >= 0) {
-        void* bufs[] = {h->d_map, h->d_wpk, h->d_tasks, h->d_qb, h->d_bd, h->d_status, h->d_bias_src, h->d_pproj, h->d_ring, h->d_known, h->d_utts, h->d_xch};
+        void* bufs[] = {h->d_map, h->d_wpk, h->d_tasks, h->d_qb, h->d_bd, h->d_status, h->d_bias_src, h->d_pproj, h->d_ring, h->d_known, h->d_utts, h->d_xch, h->d_adam_table};
         for (void* b : bufs) if (b) (void)hipFree(b);
         qpn_train_destroy(h->train);
         if (h->ev0) (void)hipEventDestroy(h->ev0);

@@ -2,6 +2,7 @@
 #pragma once
 #include "qpn_common.h"
 #include "decode_plan.h"
+#include "adam_groups.h"
 
 struct TrainState;
 void qpn_train_destroy(TrainState* t);
@@ -64,6 +65,11 @@ struct qpn_handle {      // every member has an initialiser: qpn_create sets onl
     std::string plan;                // human-readable launch plan of the last decode (qpn_last_decode_plan)
     unsigned long long* d_xch = nullptr; size_t xch_cap = 0;   // exchange granules of the cooperative kernels
     struct TrainState* train = nullptr;        // lazily created by the training entry points (train_host.hip)
+    // parameter groups of the Adam launches (qpn_adam_groups, train_host.hip): on the handle, not in the training state -- qpn_adam_step works on a handle that never trained
+    int adam_n_groups = 0;                     // 0: off (the table below may stay: the same table set again costs no upload)
+    float adam_lr[QPN_ADAM_MAX_GROUPS] = {}, adam_wd[QPN_ADAM_MAX_GROUPS] = {};
+    AdamGroupTable adam_table;                 // the normalised table the device holds (adam_groups.h)
+    char* d_adam_table = nullptr;              // [seg_end int64 | block pairs 2 x int32 | seg_group int32]
 };
 // what the launch plan needs to know of the kernels' own limits (decode_pipe.hip, decode_coopb.hip)
 bool qpn_pipe_supported(const Geom& g);

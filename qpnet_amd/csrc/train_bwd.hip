@@ -10,7 +10,7 @@
 //                  weight family over (time chunk, layer), partial slabs (deterministic), bias grads = colsum(A)
 //   k_causal_bwd : the one-hot causal conv's weight grad is a histogram over sample classes -> LDS table
 //   k_up_bwd     : gradient of the (1,1,1,U) upsampling kernel and its bias
-//   k_reduce_grad: slabs -> flat gradient in state_dict order;  k_adam: torch.optim.Adam update.
+//   k_reduce_grad: slabs -> flat gradient in state_dict order;  k_adam: torch.optim.Adam update (k_adam*_grp: with parameter groups and frozen ranges).
 #include "train_common.h"
 #include "train_post.h"
 #include "qpn_handle.h"
@@ -1258,11 +1258,42 @@ __device__ __forceinline__ float adam_update(float* __restrict__ w, float* __res
 // Averaged weights (qpn_adam_step_avg): the thread that has just computed element i's new weight moves the average towards it, e += (w_new - e) * omd with
 // omd = 1 - decay formed once on the host.  EMA is a compile-time switch: the <false> bodies are k_adam / k_adam_clip as they always were (e and omd are dead there),
 // the <true> ones differ by that one read-modify-write.  A skipped update returns before it: the average is of APPLIED states.
-template <bool EMA>
+// Parameter groups (qpn_adam_groups; GROUPED, another compile-time switch: the <.., false> bodies are the kernels as they always were, G is dead there).  The block
+// reads its pair of the table's block index (adam_groups.h) -- ONE uniform 8-byte load, asked for at the top of the kernel, next to the status word's, so that it
+// puts no latency of its own in front of the loads of w, m, v, g.  In nearly every block the pair IS the lookup: the group is the same for all 256 elements, the
+// branch below is uniform and no segment is read.  Only a block that a segment boundary crosses walks: every thread forward from the block's first segment to its
+// own element.  lr / weight_decay then come out of the kernel arguments (a chain of selects over constant indices: SGPRs, no scratch).
+// -> false: the element is frozen (w, m, v, g are not touched; the caller still moves the average)
+// A workgroup of a grouped launch updates QPN_ADAM_WG_BLOCKS consecutive blocks, 256 elements at a time: the fixed cost of a workgroup (its launch, the status
+// word's and the pairs' latency, in the clipping kernels the sum of the partials) is paid once per 1024 elements, and its pairs -- the index is padded -- are one 32-byte uniform load.
+struct AdamGroupPairs { int2 p[QPN_ADAM_WG_BLOCKS]; };
+__device__ __forceinline__ AdamGroupPairs adam_group_block(const AdamGroupsArg* G) {
+    AdamGroupPairs r;
+    const int2* src = reinterpret_cast<const int2*>(G->block) + (size_t)blockIdx.x * QPN_ADAM_WG_BLOCKS;
+#pragma unroll
+    for (int k = 0; k < QPN_ADAM_WG_BLOCKS; ++k) r.p[k] = src[k];
+    return r;
+}
+__device__ __forceinline__ bool adam_group_values(const AdamGroupsArg* G, int2 blk, int64_t i, float& lr, float& wd) {
+    int q = blk.y;
+    if (q == QPN_ADAM_MIXED) {
+        int s = blk.x;
+        while (G->seg_end[s] <= i) ++s;                         // (the last end is n > i: the walk stays inside the table)
+        q = G->seg_group[s];
+    }
+    if (q < 0) return false;
+#pragma unroll
+    for (int k = 0; k < QPN_ADAM_MAX_GROUPS; ++k) if (q == k) { lr = G->lr[k]; wd = G->wd[k]; }
+    return true;
+}
+template <bool EMA, bool GROUPED>
 __device__ __forceinline__ void adam_body(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
                                           float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, const AdamReports& rep,
-                                          float* __restrict__ e, float omd) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+                                          float* __restrict__ e, float omd, const AdamGroupsArg* G) {
+    constexpr int NB = GROUPED ? QPN_ADAM_WG_BLOCKS : 1;        // 256-element blocks per workgroup
+    int64_t i = (int64_t)blockIdx.x * NB * blockDim.x + threadIdx.x;
+    AdamGroupPairs blk = {};
+    if (GROUPED) blk = adam_group_block(G);
     // The device-side status word (sticky until the host reads it: a tap / target out of range, an abandoned stack launch) flags results that must not
     // reach the parameters: the update of a flagged step -- and of the steps enqueued behind it until the host has collected the word, two steps later
     // at most -- is skipped; weights and both moments stay what the last clean step left (the host raises; the caller may drop the chunk and go on).
@@ -1279,20 +1310,38 @@ __device__ __forceinline__ void adam_body(float* __restrict__ w, const float* __
             if (!skip) atomicAdd((unsigned long long*)(status + 2), 1ull);      // updates APPLIED on this handle (qpn_train_applied_updates)
         }
     }
-    if (i >= n || skip) return;
-    float gi = g[i];
-    if (den) gi = gi / den[0];                                  // data-parallel: summed row-weighted gradients / summed row count
-    const float wn = adam_update(w, m, v, i, gi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-    if (EMA) e[i] = e[i] + (wn - e[i]) * omd;
+    if (skip) return;
+#pragma unroll
+    for (int k = 0; k < NB; ++k, i += blockDim.x) {
+        if (i >= n) return;
+        if (GROUPED && !adam_group_values(G, blk.p[k], i, lr, wd)) {      // frozen: only the average moves, towards the weight that stays
+            if (EMA) e[i] = e[i] + (w[i] - e[i]) * omd;
+            continue;
+        }
+        float gi = g[i];
+        if (den) gi = gi / den[0];                              // data-parallel: summed row-weighted gradients / summed row count
+        const float wn = adam_update(w, m, v, i, gi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        if (EMA) e[i] = e[i] + (wn - e[i]) * omd;
+    }
 }
 __global__ void k_adam(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
                        float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep) {
-    adam_body<false>(w, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, den, status, rep, nullptr, 0.f);
+    adam_body<false, false>(w, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, den, status, rep, nullptr, 0.f, nullptr);
 }
 __global__ void k_adam_ema(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
                            float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep,
                            float* __restrict__ e, float omd) {
-    adam_body<true>(w, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, den, status, rep, e, omd);
+    adam_body<true, false>(w, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, den, status, rep, e, omd, nullptr);
+}
+// ... with parameter groups: lr / weight_decay come from G, per element
+__global__ void k_adam_grp(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                           float b1, float b2, float eps, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep, AdamGroupsArg G) {
+    adam_body<false, true>(w, g, m, v, n, 0.f, b1, b2, eps, 0.f, bc1, bc2_sqrt, den, status, rep, nullptr, 0.f, &G);
+}
+__global__ void k_adam_ema_grp(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                               float b1, float b2, float eps, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep, AdamGroupsArg G,
+                               float* __restrict__ e, float omd) {
+    adam_body<true, true>(w, g, m, v, n, 0.f, b1, b2, eps, 0.f, bc1, bc2_sqrt, den, status, rep, e, omd, &G);
 }
 
 // ---- gradient-norm clipping: torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type=2) in front of the Adam update (the reference-side loop's
@@ -1331,17 +1380,72 @@ __global__ __launch_bounds__(256) void k_grad_sumsq(const float* __restrict__ g,
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
+// k_grad_sumsq over the elements that are not frozen (qpn_adam_groups): the same quads on the same threads, added in the same order, a frozen element left out --
+// bit for bit the sum k_grad_sumsq forms of the gradient with its frozen elements set to +0 (the accumulator is never -0: adding +0 changes nothing), and a frozen
+// element's gradient is not read at all.  A wave's 64 quads are the 256 elements of ONE block of the table: the lookup is one (wave-uniform) 8-byte load per quad.
+// Four quads per round, as k_grad_sumsq's unroll has them: first the four pairs, then the four gradient loads (each under its pair's verdict, none waited for), then
+// the sums in quad order -- the grid is at most TR_GN_BLOCKS blocks, so it is the loads in flight per thread that the rate lives on.  A quad of a mixed block
+// (a segment boundary inside the block) is walked element by element, in its place in that order.
+__device__ __forceinline__ void sumsq_mixed(const float* __restrict__ g, const AdamGroupsArg& G, int s, int64_t i0, int64_t i1, double& acc) {
+    for (int64_t i = i0; i < i1; ++i) {
+        while (G.seg_end[s] <= i) ++s;
+        if (G.seg_group[s] >= 0) acc += (double)g[i] * (double)g[i];
+    }
+}
+__global__ __launch_bounds__(256) void k_grad_sumsq_grp(const float* __restrict__ g, int64_t n, double* __restrict__ part, AdamGroupsArg G) {
+    __shared__ double red[4];
+    const int64_t nq = n >> 2, nthr = (int64_t)gridDim.x * 256, t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool aligned = (reinterpret_cast<uintptr_t>(g) & 15) == 0;
+    const int2* const blocks = reinterpret_cast<const int2*>(G.block);
+    double acc = 0.0;
+    for (int64_t q0 = t; q0 < nq; q0 += 4 * nthr) {
+        int2 blk[4]; float4 x[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t q = q0 + k * nthr;
+            blk[k] = q < nq ? blocks[q >> 6] : make_int2(0, QPN_ADAM_FROZEN);      // (quad q = elements 4q .. 4q + 3 of block 4q / 256; past the end: nothing to add)
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t q = q0 + k * nthr;
+            x[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (blk[k].y >= 0) {
+                if (aligned) x[k] = reinterpret_cast<const float4*>(g)[q];
+                else { x[k].x = g[4 * q]; x[k].y = g[4 * q + 1]; x[k].z = g[4 * q + 2]; x[k].w = g[4 * q + 3]; }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t q = q0 + k * nthr;
+            if (blk[k].y == QPN_ADAM_MIXED) sumsq_mixed(g, G, blk[k].x, 4 * q, 4 * q + 4, acc);
+            else if (blk[k].y >= 0) {
+                acc += (double)x[k].x * (double)x[k].x; acc += (double)x[k].y * (double)x[k].y; acc += (double)x[k].z * (double)x[k].z; acc += (double)x[k].w * (double)x[k].w;
+            }
+        }
+    }
+    if (t == nq % nthr && nq * 4 < n) {                           // the last n % 4 floats: quad nq, read one by one
+        const int2 b = blocks[nq >> 6];
+        if (b.y == QPN_ADAM_MIXED) sumsq_mixed(g, G, b.x, nq * 4, n, acc);
+        else if (b.y >= 0) for (int64_t i = nq * 4; i < n; ++i) acc += (double)g[i] * (double)g[i];
+    }
+    const double s = block_sum_f64(acc, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
 // k_adam behind k_grad_sumsq.  EVERY block adds the npart <= 256 partial sums itself, in block_sum_f64's order: all blocks of the launch (and all ranks) derive the
 // same total, hence the same coefficient and the same decision to skip, with no finalising block, counter or fence.
 //   total = sqrt(sum g^2) (/ den[0]: the norm of the AVERAGED gradient);  coef = min(1, max_norm / (total + 1e-6)) in fp64, rounded once;  g <- (g / den[0]) * coef, then weight decay.
 // The gradient buffer is left as it is.  A non-finite total skips the update like a flagged step (bit 16 of the status word, set by block 0; the blocks decide by their own total,
 // not by the word).  Block 0 leaves the total in *d_norm (and the step's pinned report slot).
-template <bool EMA>
+template <bool EMA, bool GROUPED>
 __device__ __forceinline__ void adam_clip_body(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, const AdamReports& rep,
                                                const double* __restrict__ part, int npart, float max_norm, double* __restrict__ d_norm, double* h_norm, double* red,
-                                               float* __restrict__ e, float omd) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+                                               float* __restrict__ e, float omd, const AdamGroupsArg* G) {
+    constexpr int NB = GROUPED ? QPN_ADAM_WG_BLOCKS : 1;
+    int64_t i = (int64_t)blockIdx.x * NB * blockDim.x + threadIdx.x;
+    AdamGroupPairs blk = {};
+    if (GROUPED) blk = adam_group_block(G);
     double total = sqrt(block_sum_f64((int)threadIdx.x < npart ? part[threadIdx.x] : 0.0, red));
     if (den) total = total / (double)den[0];
     const bool bad = !isfinite(total);
@@ -1361,27 +1465,49 @@ __device__ __forceinline__ void adam_clip_body(float* __restrict__ w, const floa
             }
         }
     }
-    if (i >= n || skip) return;
+    if (skip) return;
     const double c = (double)max_norm / (total + 1e-6);
     const float coef = c < 1.0 ? (float)c : 1.0f;
-    float gi = g[i];
-    if (den) gi = gi / den[0];
-    gi = __fmul_rn(gi, coef);                                   // (a product of its own: never fused into the weight-decay term, so coef == 1 leaves k_adam's bits)
-    const float wn = adam_update(w, m, v, i, gi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-    if (EMA) e[i] = e[i] + (wn - e[i]) * omd;
+#pragma unroll
+    for (int k = 0; k < NB; ++k, i += blockDim.x) {
+        if (i >= n) return;
+        if (GROUPED && !adam_group_values(G, blk.p[k], i, lr, wd)) {
+            if (EMA) e[i] = e[i] + (w[i] - e[i]) * omd;
+            continue;
+        }
+        float gi = g[i];
+        if (den) gi = gi / den[0];
+        gi = __fmul_rn(gi, coef);                               // (a product of its own: never fused into the weight-decay term, so coef == 1 leaves k_adam's bits)
+        const float wn = adam_update(w, m, v, i, gi, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        if (EMA) e[i] = e[i] + (wn - e[i]) * omd;
+    }
 }
 __global__ __launch_bounds__(256) void k_adam_clip(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                    float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep,
                                                    const double* __restrict__ part, int npart, float max_norm, double* __restrict__ d_norm, double* h_norm) {
     __shared__ double red[4];
-    adam_clip_body<false>(w, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, den, status, rep, part, npart, max_norm, d_norm, h_norm, red, nullptr, 0.f);
+    adam_clip_body<false, false>(w, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, den, status, rep, part, npart, max_norm, d_norm, h_norm, red, nullptr, 0.f, nullptr);
 }
 __global__ __launch_bounds__(256) void k_adam_clip_ema(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                        float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep,
                                                        const double* __restrict__ part, int npart, float max_norm, double* __restrict__ d_norm, double* h_norm,
                                                        float* __restrict__ e, float omd) {
     __shared__ double red[4];
-    adam_clip_body<true>(w, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, den, status, rep, part, npart, max_norm, d_norm, h_norm, red, e, omd);
+    adam_clip_body<true, false>(w, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, den, status, rep, part, npart, max_norm, d_norm, h_norm, red, e, omd, nullptr);
+}
+// ... with parameter groups (behind k_grad_sumsq_grp: the norm is that of the elements that are not frozen)
+__global__ __launch_bounds__(256) void k_adam_clip_grp(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                       float b1, float b2, float eps, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep, AdamGroupsArg G,
+                                                       const double* __restrict__ part, int npart, float max_norm, double* __restrict__ d_norm, double* h_norm) {
+    __shared__ double red[4];
+    adam_clip_body<false, true>(w, g, m, v, n, 0.f, b1, b2, eps, 0.f, bc1, bc2_sqrt, den, status, rep, part, npart, max_norm, d_norm, h_norm, red, nullptr, 0.f, &G);
+}
+__global__ __launch_bounds__(256) void k_adam_clip_ema_grp(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                           float b1, float b2, float eps, float bc1, float bc2_sqrt, const float* __restrict__ den, int* __restrict__ status, AdamReports rep, AdamGroupsArg G,
+                                                           const double* __restrict__ part, int npart, float max_norm, double* __restrict__ d_norm, double* h_norm,
+                                                           float* __restrict__ e, float omd) {
+    __shared__ double red[4];
+    adam_clip_body<true, true>(w, g, m, v, n, 0.f, b1, b2, eps, 0.f, bc1, bc2_sqrt, den, status, rep, part, npart, max_norm, d_norm, h_norm, red, e, omd, &G);
 }
 
 // ---- gradient accumulation (qpn_grad_accumulate / qpn_train_step_acc): acc <- first ? g : acc + g over cnt floats -- the row-weighted gradient of one chunk and its
@@ -1711,11 +1837,15 @@ int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k
 }
 
 // e != nullptr: the averaged weights move with the update (k_adam_ema, omd = 1 - decay); nullptr: the launch this always was
+static unsigned adam_grp_grid(int64_t n) { return (unsigned)((n + QPN_ADAM_WG_BLOCKS * 256 - 1) / (QPN_ADAM_WG_BLOCKS * 256)); }      // workgroups of a grouped launch
+// grp != nullptr: parameter groups (the _grp kernels: lr and wd are not looked at); nullptr: the launch this always was
 int qpn_launch_adam(float* w, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps, float wd, const float* den, int* status,
-                    int* h_status, double* h_loss, const double* d_loss, float* e, float omd, hipStream_t stream) {
+                    int* h_status, double* h_loss, const double* d_loss, float* e, float omd, const AdamGroupsArg* grp, hipStream_t stream) {
     const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
     AdamReports rep; rep.h_status = status ? h_status : nullptr; rep.h_loss = d_loss ? h_loss : nullptr; rep.d_loss = d_loss;
-    if (e) hipLaunchKernelGGL(k_adam_ema, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, g, m, v, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2), den, status, rep, e, omd);
+    if (grp && e) hipLaunchKernelGGL(k_adam_ema_grp, dim3(adam_grp_grid(n)), dim3(256), 0, stream, w, g, m, v, n, b1, b2, eps, (float)bc1, (float)sqrt(bc2), den, status, rep, *grp, e, omd);
+    else if (grp) hipLaunchKernelGGL(k_adam_grp, dim3(adam_grp_grid(n)), dim3(256), 0, stream, w, g, m, v, n, b1, b2, eps, (float)bc1, (float)sqrt(bc2), den, status, rep, *grp);
+    else if (e) hipLaunchKernelGGL(k_adam_ema, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, g, m, v, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2), den, status, rep, e, omd);
     else hipLaunchKernelGGL(k_adam, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, g, m, v, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2), den, status, rep);
     qpn_prof_mark(PG_ADAM, stream);
     QPN_HIP(hipGetLastError());
@@ -1724,11 +1854,22 @@ int qpn_launch_adam(float* w, const float* g, float* m, float* v, int64_t n, int
 
 // part: room for TR_GN_BLOCKS partial sums; d_norm: the handle's norm word
 int qpn_launch_adam_clip(float* w, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps, float wd, const float* den, int* status,
-                         int* h_status, double* h_loss, const double* d_loss, float max_norm, double* part, double* d_norm, double* h_norm, float* e, float omd, hipStream_t stream) {
+                         int* h_status, double* h_loss, const double* d_loss, float max_norm, double* part, double* d_norm, double* h_norm, float* e, float omd,
+                         const AdamGroupsArg* grp, hipStream_t stream) {
     const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
     AdamReports rep; rep.h_status = status ? h_status : nullptr; rep.h_loss = d_loss ? h_loss : nullptr; rep.d_loss = d_loss;
     const int64_t want = ((n >> 2) + 1 + 255) / 256;           // a thread per quad (and one for the short last quad) until the grid is full
     const int nb = want < TR_GN_BLOCKS ? (int)want : TR_GN_BLOCKS;
+    if (grp) {
+        hipLaunchKernelGGL(k_grad_sumsq_grp, dim3(nb), dim3(256), 0, stream, g, n, part, *grp);
+        if (e) hipLaunchKernelGGL(k_adam_clip_ema_grp, dim3(adam_grp_grid(n)), dim3(256), 0, stream, w, g, m, v, n, b1, b2, eps, (float)bc1, (float)sqrt(bc2), den, status, rep, *grp,
+                                  (const double*)part, nb, max_norm, d_norm, h_norm, e, omd);
+        else hipLaunchKernelGGL(k_adam_clip_grp, dim3(adam_grp_grid(n)), dim3(256), 0, stream, w, g, m, v, n, b1, b2, eps, (float)bc1, (float)sqrt(bc2), den, status, rep, *grp,
+                                (const double*)part, nb, max_norm, d_norm, h_norm);
+        qpn_prof_mark(PG_ADAM, stream);
+        QPN_HIP(hipGetLastError());
+        return QPN_OK;
+    }
     hipLaunchKernelGGL(k_grad_sumsq, dim3(nb), dim3(256), 0, stream, g, n, part);
     if (e) hipLaunchKernelGGL(k_adam_clip_ema, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, g, m, v, n, lr, b1, b2, eps, wd, (float)bc1, (float)sqrt(bc2), den, status, rep,
                               (const double*)part, nb, max_norm, d_norm, h_norm, e, omd);

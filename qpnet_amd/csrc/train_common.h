@@ -9,6 +9,7 @@
 #pragma once
 #include "qpn_common.h"
 #include "train_plan.h"      // TR_MAXL, TR_EB_SLOTS, TrainSlabs, AuxGeom, TrainGemm, TrainKnobs: the host-only layout types, and the planner that fills them
+#include "adam_groups.h"     // QPN_ADAM_MAX_GROUPS, QPN_ADAM_FROZEN, AdamGroupTable: the Adam step's parameter groups (host-only too)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -201,6 +202,13 @@ __device__ __forceinline__ void tr_queue_entry_bwd(const TrainParams& p, int pos
 int qpn_num_cus();                                   // compute units of the current device (cached per device)
 
 #define TR_GN_BLOCKS 256                             // gradient-norm clipping: the sum of squares leaves k_grad_sumsq as at most this many fp64 partial sums (one per thread of a k_adam_clip block)
+
+// parameter groups of the Adam launch (qpn_adam_groups; adam_groups.h): the segment table lives in device memory, the groups' values travel with the launch
+// as kernel arguments -- a learning-rate schedule changes them every step without touching the device
+struct AdamGroupsArg {
+    const long long* seg_end; const int* seg_group; const int* block;      // block: the pairs of AdamGroupTable::block, 8-byte aligned
+    float lr[QPN_ADAM_MAX_GROUPS], wd[QPN_ADAM_MAX_GROUPS];
+};
 
 // optional per-kernel-group timing (HIP events on the launch stream; bench.py roofline)
 // (one group per LAUNCH of the heavy kernels, so that bench.py can name the single longest kernel: PG_WGRAD = the gate contraction's weight

@@ -16,9 +16,10 @@ int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k
 int qpn_launch_fwd_gemm(const TrainParams& p, const TrainGemm& w, hipStream_t stream);
 int qpn_launch_bwd_gemm(const TrainParams& p, const TrainBwd& bw, const TrainGemm& w, hipStream_t stream);
 int qpn_launch_adam(float* w, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps, float wd, const float* den, int* status,
-                    int* h_status, double* h_loss, const double* d_loss, float* e, float omd, hipStream_t stream);
+                    int* h_status, double* h_loss, const double* d_loss, float* e, float omd, const AdamGroupsArg* grp, hipStream_t stream);
 int qpn_launch_adam_clip(float* w, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps, float wd, const float* den, int* status,
-                         int* h_status, double* h_loss, const double* d_loss, float max_norm, double* part, double* d_norm, double* h_norm, float* e, float omd, hipStream_t stream);
+                         int* h_status, double* h_loss, const double* d_loss, float max_norm, double* part, double* d_norm, double* h_norm, float* e, float omd,
+                         const AdamGroupsArg* grp, hipStream_t stream);
 int qpn_launch_grad_accum(float* acc, const float* g, int64_t cnt, int first, const int* status, int* h_status, double* h_loss, const double* d_loss, hipStream_t stream);
 
 // a pinned loss slot: the 64 partial sums, then the gradient norm of the same step (gradient-norm clipping)
@@ -662,6 +663,58 @@ static int check_ema_args(const float* d_ema, float ema_decay, float* omd) {
     return QPN_OK;
 }
 
+// ---- parameter groups (adam_groups.h).  Sticky on the handle, like qpn_decode_sampling: from the call on EVERY Adam launch of the handle (qpn_adam_step*, qpn_train_step*,
+// the closing micro-step of qpn_train_step_acc) takes lr / weight_decay per element from the table and leaves frozen elements alone; the launch's own two values
+// are ignored.  The caller's arrays are not referenced after return.  A table equal (after merging neighbours of one group) to the one the handle holds only
+// replaces the group values -- no device work: the per-step path of a learning-rate schedule.  A new table is a set-up call: it waits for `stream` (the launches
+// that read the old table) and uploads; not while that stream is capturing.  n_groups = 0: off, nothing else is looked at, no device is needed.
+extern "C" int qpn_adam_groups(qpn_handle* h, int n_groups, const float* h_lr, const float* h_weight_decay,
+                               int64_t n_seg, const int64_t* h_seg_end, const int32_t* h_seg_group, void* stream_) {
+    if (!h) { qpn_set_error("null handle"); return QPN_EINVAL; }
+    if (n_groups < 0 || n_groups > QPN_ADAM_MAX_GROUPS) { qpn_set_error("bad adam_groups arguments: n_groups must lie in [0, %d] (got %d)", QPN_ADAM_MAX_GROUPS, n_groups); return QPN_EINVAL; }
+    if (n_groups == 0) { h->adam_n_groups = 0; return QPN_OK; }
+    char why[256];
+    if (!adam_groups_check(n_groups, h_lr, h_weight_decay, n_seg, h_seg_end, h_seg_group, why, sizeof(why))) { qpn_set_error("bad adam_groups arguments: %s", why); return QPN_EINVAL; }
+    int rc = need_dev(h); if (rc) return rc;
+    if (!h->d_adam_table || !adam_groups_normalise(n_seg, h_seg_end, h_seg_group).same_segments(h->adam_table)) {
+        AdamGroupTable t = adam_groups_build(n_seg, h_seg_end, h_seg_group);
+        hipStream_t stream = (hipStream_t)stream_;
+        hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing(stream, &cap_st);
+        if (cap_st != hipStreamCaptureStatusNone) { qpn_set_error("qpn_adam_groups with a new segment table while the stream is capturing (set the table before the capture)"); return QPN_ESTATE; }
+        const size_t ns = t.seg_end.size(), nb = t.block.size();                  // [seg_end | block pairs | seg_group]: the 8-byte entries first
+        const size_t bytes = ns * sizeof(int64_t) + (ns + nb) * sizeof(int32_t);
+        char* d_new = nullptr;
+        QPN_HIP(hipStreamSynchronize(stream));
+        QPN_HIP(hipMalloc(&d_new, bytes));
+        hipError_t e = hipMemcpy(d_new, t.seg_end.data(), ns * sizeof(int64_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_new + ns * sizeof(int64_t), t.block.data(), nb * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_new + ns * sizeof(int64_t) + nb * sizeof(int32_t), t.seg_group.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(d_new); QPN_HIP(e); }
+        h->adam_n_groups = 0;                                    // (between the two tables the handle has none)
+        if (h->d_adam_table) (void)hipFree(h->d_adam_table);
+        h->d_adam_table = d_new;
+        h->adam_table = std::move(t);
+    }
+    for (int q = 0; q < QPN_ADAM_MAX_GROUPS; ++q) { h->adam_lr[q] = q < n_groups ? h_lr[q] : 0.0f; h->adam_wd[q] = q < n_groups ? h_weight_decay[q] : 0.0f; }
+    h->adam_n_groups = n_groups;
+    return QPN_OK;
+}
+
+// the groups of an Adam launch over n elements: *use = false with groups off; QPN_EINVAL when the table covers another n
+static int adam_groups_arg(const qpn_handle* h, int64_t n, AdamGroupsArg* a, bool* use) {
+    *use = h->adam_n_groups > 0;
+    if (!*use) return QPN_OK;
+    const AdamGroupTable& t = h->adam_table;
+    if (n != t.n) { qpn_set_error("bad adam_step arguments: n = %lld, the handle's parameter groups (qpn_adam_groups) cover %lld elements", (long long)n, (long long)t.n); return QPN_EINVAL; }
+    const size_t ns = t.seg_end.size();
+    a->seg_end = reinterpret_cast<const long long*>(h->d_adam_table);
+    a->block = reinterpret_cast<const int*>(h->d_adam_table + ns * sizeof(int64_t));
+    a->seg_group = a->block + t.block.size();
+    for (int q = 0; q < QPN_ADAM_MAX_GROUPS; ++q) { a->lr[q] = h->adam_lr[q]; a->wd[q] = h->adam_wd[q]; }
+    return QPN_OK;
+}
+
 // max_grad_norm > 0: torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) in front of the update (k_grad_sumsq + k_adam_clip); otherwise exactly the launch qpn_adam_step_ex always made.
 // d_ema: the averaged weights move with every APPLIED update, inside the same launch (k_adam_ema / k_adam_clip_ema); NULL with ema_decay 0: the kernels above
 extern "C" int qpn_adam_step_avg(qpn_handle* h, float* d_flat, const float* d_grad, float* d_m, float* d_v, int64_t n,
@@ -671,13 +724,16 @@ extern "C" int qpn_adam_step_avg(qpn_handle* h, float* d_flat, const float* d_gr
     int rc = check_ema_args(d_ema, ema_decay, &omd); if (rc) return rc;
     rc = need_dev(h); if (rc) return rc;
     if (!d_flat || !d_grad || !d_m || !d_v || n < 1 || step < 1 || max_grad_norm != max_grad_norm) { qpn_set_error("bad adam_step arguments"); return QPN_EINVAL; }
+    AdamGroupsArg ga; bool grouped;
+    rc = adam_groups_arg(h, n, &ga, &grouped); if (rc) return rc;
+    const AdamGroupsArg* const grp = grouped ? &ga : nullptr;
     const bool clip = max_grad_norm > 0.f;
     if (clip) { rc = train_init(h); if (rc) return rc; }                 // (the partial sums and the norm word live in the training state)
     if (h->train) { h->train->last_stream = (hipStream_t)stream_; h->train->gnorm_last = clip; }
     if (clip) return qpn_launch_adam_clip(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, d_grad_denominator, h->train->d_status, nullptr, nullptr, nullptr,
-                                          max_grad_norm, h->train->d_gnorm, h->train->d_loss + 64, nullptr, d_ema, omd, (hipStream_t)stream_);
+                                          max_grad_norm, h->train->d_gnorm, h->train->d_loss + 64, nullptr, d_ema, omd, grp, (hipStream_t)stream_);
     return qpn_launch_adam(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, d_grad_denominator, h->train ? h->train->d_status : nullptr, nullptr, nullptr, nullptr,
-                           d_ema, omd, (hipStream_t)stream_);
+                           d_ema, omd, grp, (hipStream_t)stream_);
 }
 
 // Gradient accumulation: d_acc <- first ? d_grad : d_acc + d_grad over cnt floats (k_grad_accum; callers pass n + 4: the row-weighted gradient qpn_train_backward_ex
@@ -759,6 +815,9 @@ static int train_step_impl(qpn_handle* h, float* d_flat, int B, int64_t T, int64
     const bool closing = micro == micro_count - 1;                       // ... and only its last micro-step has an Adam launch
     const bool clip = closing && max_grad_norm > 0.f;
     rc = need_dev(h); if (rc) return rc;
+    AdamGroupsArg ga; bool grouped = false;
+    if (closing) { rc = adam_groups_arg(h, n, &ga, &grouped); if (rc) return rc; }      // (before anything is enqueued: a table for another n fails the whole step)
+    const AdamGroupsArg* const grp = grouped ? &ga : nullptr;
     // a flagged word found here is cleared on THIS call's stream, in front of the step the caller runs on it next: the stream of the call before may be another
     // one, busy with work of the caller's own, and a clear queued behind that work lands after the next step's Adam launch has read the word
     if (h->train) h->train->last_stream = (hipStream_t)stream;
@@ -796,9 +855,9 @@ static int train_step_impl(qpn_handle* h, float* d_flat, int B, int64_t T, int64
                                             hl, (!closing && loss_mode == 1) ? t->d_loss : nullptr, (hipStream_t)stream); if (rc) return rc; }
     if (!closing) rc = QPN_OK;
     else if (clip) rc = qpn_launch_adam_clip(d_flat, g_adam, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, den, t->d_status, t->h_status_pinned + sslot,
-                                        hl, loss_mode == 1 ? t->d_loss : nullptr, max_grad_norm, t->d_gnorm, t->d_loss + 64, hl ? hl + 64 : nullptr, d_ema, omd, (hipStream_t)stream);
+                                        hl, loss_mode == 1 ? t->d_loss : nullptr, max_grad_norm, t->d_gnorm, t->d_loss + 64, hl ? hl + 64 : nullptr, d_ema, omd, grp, (hipStream_t)stream);
     else rc = qpn_launch_adam(d_flat, g_adam, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, den, t->d_status, t->h_status_pinned + sslot,
-                              hl, loss_mode == 1 ? t->d_loss : nullptr, d_ema, omd, (hipStream_t)stream);
+                              hl, loss_mode == 1 ? t->d_loss : nullptr, d_ema, omd, grp, (hipStream_t)stream);
     if (rc) return rc;
     QPN_HIP(hipEventRecord(t->ev_status[sslot], (hipStream_t)stream));
     t->status_pending[sslot] = true; t->status_newest = sslot;

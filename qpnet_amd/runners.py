@@ -261,6 +261,10 @@ def _train_args(update):
     p.add_argument("--max_grad_norm", default=0.0, type=float, help="clip the gradient norm inside the fused step (torch's clip_grad_norm_); 0: off")
     p.add_argument("--ema_decay", default=0.0, type=float, help="keep an exponential moving average of the weights inside the fused step, written to the checkpoints as \"ema\" (decode / validate with --ema); 0: off")
     p.add_argument("--accum_steps", default=1, type=int, help="gradient accumulation: one Adam update per K batches of the stream (an iteration is then one update: --iters, --intervals, --checkpoint_interval and the checkpoints count updates); 1: off")
+    p.add_argument("--freeze", default=None, type=str, metavar="PATTERN[,PATTERN...]",
+                   help="do not update the parameters whose state_dict names match (fnmatch), e.g. \"causal.*,dil*,res*,skip*\" adapts the conditioning path and the post-net only")
+    p.add_argument("--lr_scale", default=[], action="append", metavar="PATTERNS=SCALE",
+                   help="train the parameters whose names match PATTERN[,PATTERN...] at lr * SCALE (repeatable: a group of its own each)")
     p.add_argument("--iters", default=3000 if update else 200000, type=int)
     p.add_argument("--checkpoint_interval", default=10000, type=int)
     p.add_argument("--intervals", default=100, type=int)
@@ -269,6 +273,22 @@ def _train_args(update):
     p.add_argument("--n_gpus", default=1, type=int)
     p.add_argument("--verbose", default=1, type=int)
     return p
+
+
+def _param_groups_of(args):
+    """--freeze / --lr_scale -> FusedTrainer's param_groups (None when neither is given)"""
+    groups = []
+    if args.freeze:
+        groups.append({"params": [w for w in args.freeze.split(",") if w], "frozen": True})
+    for spec in args.lr_scale:
+        pats, sep, scale = spec.rpartition("=")
+        if not sep or not pats:
+            raise SystemExit("--lr_scale takes PATTERN[,PATTERN...]=SCALE, got %r" % spec)
+        try:
+            groups.append({"params": [w for w in pats.split(",") if w], "lr_scale": float(scale)})
+        except ValueError:
+            raise SystemExit("--lr_scale %r: %r is not a number" % (spec, scale))
+    return groups or None
 
 
 def run_train(argv=None, update=False):
@@ -294,7 +314,8 @@ def run_train(argv=None, update=False):
     from . import parallel
     model = _build_model(conf, dev).train()
     trainer = FusedTrainer(model, lr=args.lr, weight_decay=args.weight_decay, world_size=world, max_grad_norm=args.max_grad_norm, ema_decay=args.ema_decay,
-                           accum_steps=args.accum_steps)
+                           accum_steps=args.accum_steps, param_groups=_param_groups_of(args))
+    logging.info("trainable parameters = %d, frozen parameters = %d." % (trainer.n_trainable, trainer.n_frozen))
     clipping = trainer.max_grad_norm > 0.0
     K = trainer.accum_steps                    # batches per iteration: an iteration is one UPDATE (a window of K micro-steps), so checkpoints fall on window boundaries
     norm_max, n_clipped, n_seen = 0.0, 0, 0    # (clipping on) the interval's largest gradient norm, how many of its steps were clipped, how many losses it collected

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .config import ADAM_FROZEN, ADAM_MAX_GROUPS, adam_group_table
 
 
 # Walking a module tree for its parameters costs ~0.15 ms of Python per call (120 tensors, 60 sub-modules), and the reference-style
@@ -191,6 +192,7 @@ def _adam_prehook(opt, args, kwargs):
     b1, b2 = g0["betas"]
     with torch.cuda.device(dev):
         _lib.check(L.qpn_train_status_collect(hd))       # a pending forward check (no-op after a backward has collected it)
+        _groups_off(model, L, hd)                        # (a grouped FusedTrainer / FlatAdam may have stepped this module before: this optimizer has ONE group over everything)
         _lib.check(L.qpn_adam_step(hd, flat.data_ptr(), gbuf.data_ptr(), a.m.data_ptr(), a.v.data_ptr(), flat.numel(), a.steps + 1,
                                    g0["lr"], b1, b2, g0["eps"], g0["weight_decay"], torch.cuda.current_stream(dev).cuda_stream))
     a.steps += 1
@@ -542,26 +544,67 @@ def _ema_from_state_dict(model, sd):
 _ADAM_GROUP_DEFAULTS = dict(amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None)
 
 
-def adam_state_to_torch(model, m, v, steps, hyper):
+def adam_state_to_torch(model, m, v, steps, hyper, groups=None):
     """{"state": {i: {"step","exp_avg","exp_avg_sq"}}, "param_groups": [...]}: what torch.optim.Adam(model.parameters())
     .state_dict() holds after `steps` steps, built from the flat moment buffers (reference checkpoints store exactly this,
-    src/bin/qpnet_train.py:346-352), so either side can resume the other's checkpoint."""
+    src/bin/qpnet_train.py:346-352), so either side can resume the other's checkpoint.
+    groups = [(hyper of the group, [positions of its tensors in model.parameters()])]: the layout of a torch.optim.Adam built with those groups -- one entry
+    per group, "params" numbered consecutively across the groups in group order, "state" keyed by those numbers, tensors of no group (frozen) absent;
+    `hyper` is not looked at then."""
     params = list(model.parameters())
-    state, o = {}, 0
-    for i, p in enumerate(params):
-        n = p.numel()
-        if steps > 0 and m is not None:
-            state[i] = {"step": torch.tensor(float(steps)), "exp_avg": m[o:o + n].view(p.shape).clone(),
-                        "exp_avg_sq": v[o:o + n].view(p.shape).clone()}
-        o += n
-    group = dict(lr=hyper["lr"], betas=tuple(hyper["betas"]), eps=hyper["eps"], weight_decay=hyper["weight_decay"])
-    group.update(_ADAM_GROUP_DEFAULTS)
-    group["params"] = list(range(len(params)))
-    return {"state": state, "param_groups": [group]}
+    offs, o = [], 0
+    for p in params:
+        offs.append(o)
+        o += p.numel()
+    if groups is None:
+        groups = [(hyper, list(range(len(params))))]
+    state, out_groups, k = {}, [], 0
+    for hyp, positions in groups:
+        ids = []
+        for pos in positions:
+            p, o = params[pos], offs[pos]
+            n = p.numel()
+            if steps > 0 and m is not None:
+                state[k] = {"step": torch.tensor(float(steps)), "exp_avg": m[o:o + n].view(p.shape).clone(),
+                            "exp_avg_sq": v[o:o + n].view(p.shape).clone()}
+            ids.append(k)
+            k += 1
+        group = dict(lr=hyp["lr"], betas=tuple(hyp["betas"]), eps=hyp["eps"], weight_decay=hyp["weight_decay"])
+        group.update(_ADAM_GROUP_DEFAULTS)
+        group["params"] = ids
+        out_groups.append(group)
+    return {"state": state, "param_groups": out_groups}
 
 
-def adam_state_from_torch(model, sd, flat):
-    """inverse of adam_state_to_torch; also accepts the previous round's {"flat_adam": ...} format."""
+def adam_state_from_torch(model, sd, flat, groups=None):
+    """inverse of adam_state_to_torch; also accepts the previous round's {"flat_adam": ...} format.  groups = [positions of the group's tensors]: the state of an
+    optimizer with these groups -> (m, v, steps, [hyper of every group]); another number of groups, or a group of another size, raises ValueError (torch's rule)."""
+    if groups is not None:
+        sgs = sd["param_groups"]
+        if len(sgs) != len(groups):
+            raise ValueError("loaded state dict has a different number of parameter groups (%d, this optimizer has %d)" % (len(sgs), len(groups)))
+        for gi, (sg, positions) in enumerate(zip(sgs, groups)):
+            if len(sg["params"]) != len(positions):
+                raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group "
+                                 "(group %d: %d parameters, this optimizer's has %d)" % (gi, len(sg["params"]), len(positions)))
+            if sg.get("amsgrad"):
+                raise ValueError("amsgrad Adam state cannot be resumed by the fused Adam kernel")
+        params = list(model.parameters())
+        offs, o = [], 0
+        for p in params:
+            offs.append(o)
+            o += p.numel()
+        m, v = torch.zeros_like(flat), torch.zeros_like(flat)
+        steps = 0
+        for sg, positions in zip(sgs, groups):
+            for key, pos in zip(sg["params"], positions):
+                st = sd["state"].get(key)
+                if st is not None:
+                    o, n = offs[pos], params[pos].numel()
+                    m[o:o + n] = st["exp_avg"].reshape(-1).to(flat.device, torch.float32)
+                    v[o:o + n] = st["exp_avg_sq"].reshape(-1).to(flat.device, torch.float32)
+                    steps = max(steps, int(float(st["step"])))
+        return m, v, steps, [{k: sg[k] for k in ("lr", "betas", "eps", "weight_decay") if k in sg} for sg in sgs]
     if "flat_adam" in sd:
         st = sd["flat_adam"]
         return st["exp_avg"].to(flat.device).clone(), st["exp_avg_sq"].to(flat.device).clone(), int(st["step"]), dict(sd["param_groups"][0])
@@ -583,6 +626,86 @@ def adam_state_from_torch(model, sd, flat):
     return m, v, steps, hyper
 
 
+# ---------------------------------------------------------------- parameter groups (qpn_adam_groups) shared by FusedTrainer and FlatAdam
+class _AdamGroups:
+    """The segment table of a grouped optimiser over one model's flat vector, as the C ABI takes it, and which tensors every group holds.
+    seg_end / seg_group: the table; positions[g]: the positions in model.parameters() of group g's tensors, in the order state_dict() numbers them."""
+
+    def __init__(self, n_groups, seg_end, seg_group, positions, numels):
+        if n_groups > ADAM_MAX_GROUPS:
+            raise ValueError("at most %d parameter groups (got %d)" % (ADAM_MAX_GROUPS, n_groups))
+        if not any(g >= 0 for g in seg_group):
+            raise ValueError("parameter groups: every parameter is frozen (nothing to train)")
+        self.n_groups, self.positions = n_groups, positions
+        self.seg_end_list, self.seg_group_list = list(seg_end), list(seg_group)
+        self.seg_end = (C.c_int64 * len(seg_end))(*seg_end)
+        self.seg_group = (C.c_int32 * len(seg_group))(*seg_group)
+        grouped = set(pos for ps in positions for pos in ps)
+        self.n_trainable = sum(numels[pos] for pos in grouped)
+        self.n_frozen = sum(numels) - self.n_trainable
+
+    def send(self, model, L, hd, lrs, wds, stream):
+        """make the handle's Adam launches use this table with these values (the same table again: no device work, only the values change).  The groups are
+        sticky on the model's handle: the model remembers that they are on, so that an optimiser WITHOUT groups switches them off first (_groups_off)"""
+        n = self.n_groups
+        _lib.check(L.qpn_adam_groups(hd, n, (C.c_float * n)(*lrs), (C.c_float * n)(*wds), len(self.seg_end), self.seg_end, self.seg_group, stream))
+        model.__dict__["_qpn_groups_on"] = True
+
+
+def _groups_off(model, L, hd):
+    """An optimiser without parameter groups is about to launch Adam on this model's handle: groups a grouped optimiser left there (a FusedTrainer / FlatAdam that
+    froze tensors for the first N steps, say) are switched off -- its own lr / weight_decay apply to every element again.  A host-only call, made only when some
+    optimiser has switched groups on since: a model that never had groups makes exactly the calls it always made."""
+    if model.__dict__.get("_qpn_groups_on"):
+        _lib.check(L.qpn_adam_groups(hd, 0, None, None, 0, None, None, None))
+        model.__dict__["_qpn_groups_on"] = False
+
+
+def _table_of_positions(group_of, numels):
+    """group of every tensor (in model.parameters() order; -1: frozen) -> (seg_end, seg_group), a segment per run of one group"""
+    seg_end, seg_group, o = [], [], 0
+    for g, n in zip(group_of, numels):
+        o += n
+        if seg_group and seg_group[-1] == g:
+            seg_end[-1] = o
+        else:
+            seg_end.append(o); seg_group.append(g)
+    return seg_end, seg_group
+
+
+def _check_group_value(name, v):
+    v = float(v)
+    if not np.isfinite(v) or v < 0.0:
+        raise ValueError("parameter groups: %s must be a finite number >= 0, got %r" % (name, v))
+    return v
+
+
+def trainer_param_groups(model, param_groups):
+    """FusedTrainer's `param_groups` -> (_AdamGroups, [lr_scale of every group], [weight_decay of every group]).  Entries are {"params": pattern or list of
+    patterns over state_dict keys (fnmatch), "lr_scale": 1.0, "weight_decay": <the trainer's>, "frozen": False}.  Group 0 is the DEFAULT group: the parameters no
+    entry matches, at the trainer's lr and weight_decay; every entry that is not frozen is a group of its own after it, in order.  Pure: works on a CPU model."""
+    entries, scales, wds = [], [1.0], [None]
+    for e in param_groups:
+        if not isinstance(e, dict) or "params" not in e or set(e) - {"params", "lr_scale", "weight_decay", "frozen"}:
+            raise ValueError('param_groups entries are dicts {"params": pattern(s), "lr_scale": 1.0, "weight_decay": ..., "frozen": False}, got %r' % (e,))
+        if e.get("frozen", False):
+            entries.append((e["params"], ADAM_FROZEN))
+            continue
+        entries.append((e["params"], len(scales)))
+        scales.append(_check_group_value("lr_scale", e.get("lr_scale", 1.0)))
+        wds.append(None if e.get("weight_decay") is None else _check_group_value("weight_decay", e["weight_decay"]))
+    if len(scales) > ADAM_MAX_GROUPS:
+        raise ValueError("at most %d parameter groups, the default group included (got %d)" % (ADAM_MAX_GROUPS, len(scales)))
+    seg_end, seg_group, key_group = adam_group_table(model.cfg, entries, 0)
+    keys = list(key_group)                              # (layout order = state_dict order = model.parameters() order)
+    named = [k for k, _ in model.named_parameters()]
+    if named != keys:
+        raise ValueError("parameter groups: the model's parameters are not the layout of its configuration")
+    numels = [p.numel() for p in model.parameters()]
+    positions = [[i for i, k in enumerate(keys) if key_group[k] == g] for g in range(len(scales))]
+    return _AdamGroups(len(scales), seg_end, seg_group, positions, numels), scales, wds
+
+
 class FlatAdam(torch.optim.Optimizer):
     """torch.optim.Adam semantics (lr, betas, eps, weight_decay; no amsgrad) as ONE kernel over the model's flat parameter
     buffer -- a one-line swap for `torch.optim.Adam(model.parameters(), lr=...)` in the reference loop
@@ -593,17 +716,59 @@ class FlatAdam(torch.optim.Optimizer):
     max_grad_norm=c: `torch.nn.utils.clip_grad_norm_(model.parameters(), c)` in front of every step, inside the step's launches (qpn_adam_step_clip); p.grad is
     left unscaled.  A step whose gradient norm is not finite applies nothing and raises QpnError(-4) at the next status collection.
     ema_decay=d (0 < d < 1): `.ema`, a flat fp32 average of the weights seeded with them, moves inside the same launch with every APPLIED update
-    (qpn_adam_step_avg: e += (w_new - e) * (1 - d)); ema_state_dict() / load_ema() as FusedTrainer's."""
+    (qpn_adam_step_avg: e += (w_new - e) * (1 - d)); ema_state_dict() / load_ema() as FusedTrainer's.
+    params=[{"params": [tensors of this model], "lr": ..., "weight_decay": ...}, ...]: torch-style parameter groups (at most 8), each with a learning rate and a
+    weight decay of its own inside the same launch (qpn_adam_groups); parameters of the model in no group are frozen, as if they had not been passed to
+    torch.optim.Adam.  betas / eps must agree across the groups.  `param_groups` are torch's own (lr schedulers act per group: the values are sent with every
+    step), and state_dict() / load_state_dict() have the layout of a torch.optim.Adam built with the same groups."""
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, ema_decay=None):
+    def __init__(self, model, params=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, ema_decay=None):
         self.model = model
         self.max_grad_norm = _check_max_grad_norm(max_grad_norm)      # (a setting of this object, not of the checkpoint: state_dict() keeps torch.optim.Adam's layout)
         self.ema_decay = _check_ema_decay(ema_decay)
         self.ema = None
-        super().__init__(list(model.parameters()), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        super().__init__(list(model.parameters()) if params is None else params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self._groups = None if params is None else self._make_groups()
+        self._grouped = params is not None
         self._m = self._v = None
         self._steps = 0
         self._applied_base = None     # clipping on: (steps, the handle's applied-update count) at the first step (a skipped non-finite step must not advance the bias correction)
+
+    def _make_groups(self):
+        mparams = list(self.model.parameters())
+        pos_of = {id(p): i for i, p in enumerate(mparams)}
+        group_of, positions = [ADAM_FROZEN] * len(mparams), []
+        for gi, g in enumerate(self.param_groups):
+            ps = []
+            for p in g["params"]:
+                if id(p) not in pos_of:
+                    raise ValueError("FlatAdam: group %d holds a tensor that is not a parameter of this model" % gi)
+                group_of[pos_of[id(p)]] = gi
+                ps.append(pos_of[id(p)])
+            positions.append(ps)
+        self._groups_agree()
+        numels = [p.numel() for p in mparams]
+        seg_end, seg_group = _table_of_positions(group_of, numels)
+        return _AdamGroups(len(self.param_groups), seg_end, seg_group, positions, numels)
+
+    def add_param_group(self, param_group):
+        """torch's own (it also builds the groups inside __init__); on a grouped optimiser a group added later rebuilds the segment table, with every check of the
+        constructor (a tensor of this model, at most 8 groups, betas / eps in agreement).  The moments are flat over the whole model: a tensor that was frozen so
+        far starts from zero moments, at the optimiser's step count."""
+        super().add_param_group(param_group)
+        if self.__dict__.get("_grouped"):
+            try:
+                self._groups = self._make_groups()
+            except ValueError:
+                self.param_groups.pop()                 # (refused: the optimiser is what it was)
+                raise
+
+    def _groups_agree(self):
+        g0 = self.param_groups[0]
+        for gi, g in enumerate(self.param_groups):
+            if tuple(g["betas"]) != tuple(g0["betas"]) or g["eps"] != g0["eps"]:
+                raise ValueError("FlatAdam: betas / eps must agree across the parameter groups (group %d has betas=%r eps=%r, group 0 betas=%r eps=%r)"
+                                 % (gi, g["betas"], g["eps"], g0["betas"], g0["eps"]))
 
     def _applied(self, L, hd, dev):
         n = C.c_int64(0)
@@ -646,6 +811,11 @@ class FlatAdam(torch.optim.Optimizer):
         self._steps += 1
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
+            if self._groups is not None:             # (every step: a scheduler may have moved a group's lr; the same table again costs no device work)
+                self._groups_agree()
+                self._groups.send(model, L, hd, [pg["lr"] for pg in self.param_groups], [pg["weight_decay"] for pg in self.param_groups], stream)
+            else:
+                _groups_off(model, L, hd)
             if self.ema_decay > 0.0:
                 self.ema = _ema_home(self.ema, flat)
                 _lib.check(L.qpn_adam_step_avg(hd, flat.data_ptr(), g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), flat.numel(),
@@ -673,6 +843,9 @@ class FlatAdam(torch.optim.Optimizer):
         self.ema = None if sd is None else _ema_from_state_dict(self.model, sd)
 
     def state_dict(self):
+        if self._groups is not None:
+            groups = [({k: pg[k] for k in ("lr", "betas", "eps", "weight_decay")}, ps) for pg, ps in zip(self.param_groups, self._groups.positions)]
+            return adam_state_to_torch(self.model, self._m, self._v, self._steps, None, groups)
         return adam_state_to_torch(self.model, self._m, self._v, self._steps, self._hyper())
 
     def load_state_dict(self, sd):
@@ -680,6 +853,11 @@ class FlatAdam(torch.optim.Optimizer):
         flat = getattr(self.model, "_flat", None)
         if flat is None:
             flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+        if self._groups is not None:
+            self._m, self._v, self._steps, hypers = adam_state_from_torch(self.model, sd, flat, self._groups.positions)
+            for pg, hyper in zip(self.param_groups, hypers):
+                pg.update(hyper)
+            return
         self._m, self._v, self._steps, hyper = adam_state_from_torch(self.model, sd, flat)
         for k, v in hyper.items():
             if k != "params":
@@ -714,7 +892,17 @@ class FusedTrainer:
     flag in the accumulator's trailer and the closing Adam launch skips.  After a device-side status error (QpnError -4 / -2 from any call) the open window is ABANDONED:
     the next step() is micro-step 0 and overwrites the accumulator, the chunks accumulated so far are dropped as the flagged chunk itself is.  Under stream capture
     with K > 1 step() raises (one captured graph cannot hold both kinds of micro-step).  A trainer setting like max_grad_norm: not part of state_dict(), no accumulator
-    reaches a checkpoint.  K = 1 makes exactly the calls made without the option."""
+    reaches a checkpoint.  K = 1 makes exactly the calls made without the option.
+    param_groups=[{"params": pattern or list of patterns, "lr_scale": 1.0, "weight_decay": <the trainer's>, "frozen": False}, ...] (None: off): parameter groups by
+    fnmatch patterns over state_dict keys, inside the same Adam launch (qpn_adam_groups).  A frozen entry's tensors are not updated (weights and moments stay bit for
+    bit; their gradient is left out of the clipping norm); every other entry trains at lr * lr_scale (an fp32 product, formed from the current `lr` at every step)
+    with its own weight decay; parameters no entry matches form the default group at the trainer's lr and weight_decay.  At most 8 groups, the default one included.
+    Works on every host path (the one-call step, accum_steps > 1, world_size > 1 -- the groups must be the same on every rank, as the other hyper-parameters must).
+    A trainer setting like max_grad_norm; with it state_dict() / load_state_dict() have the layout of a torch.optim.Adam built with the same groups (default
+    group first when it is not empty, frozen tensors absent).  load_state_dict() with groups takes from the file: the moments and the step count; betas and eps; the
+    base `lr` (the file's lr of the first group whose lr_scale is not 0, divided by that scale); the trainer's `weight_decay` when the file has the default group.
+    lr_scale and the entries' own weight decays stay this trainer's.  `n_trainable` / `n_frozen` count the elements.  The groups are sticky on the model's native
+    handle: an optimiser without groups (a FusedTrainer / FlatAdam built later on the same model, a stock Adam stepped by the hooks) switches them off before its launch."""
 
     # The device-side status word (bad taps / targets; the reference asserts in-line, qpnet.py:294, qpnet_train.py:525) is copied to pinned
     # memory behind every step; a step starts by looking at the copy made TWO steps earlier (the previous step is still queued on the
@@ -722,8 +910,11 @@ class FusedTrainer:
     # as when the word was read every 100 steps.  check_status() collects everything outstanding.
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, process_group=None, world_size=1, max_grad_norm=None, ema_decay=None,
-                 accum_steps=1):
+                 accum_steps=1, param_groups=None):
         self.model = model
+        self._groups = self._group_scales = self._group_wds = None
+        if param_groups is not None:
+            self._groups, self._group_scales, self._group_wds = trainer_param_groups(model, param_groups)
         self.max_grad_norm = _check_max_grad_norm(max_grad_norm)
         self.ema_decay = _check_ema_decay(ema_decay)
         self.accum_steps = _check_accum_steps(accum_steps)
@@ -742,6 +933,21 @@ class FusedTrainer:
         self._two_buckets = None      # agreed over the process group at the first data-parallel step (every rank must issue the same collectives)
         if self.accum_steps > 1:
             self._two_buckets = False  # (accumulating: one exchange of the accumulator per window, on every rank)
+
+    @property
+    def n_trainable(self):
+        """elements of the flat parameter vector this trainer updates"""
+        return self._groups.n_trainable if self._groups is not None else sum(p.numel() for p in self.model.parameters())
+
+    @property
+    def n_frozen(self):
+        return self._groups.n_frozen if self._groups is not None else 0
+
+    def _group_values(self):
+        """(lr, weight_decay) of every group now: lr_g = float32(lr) * float32(lr_scale_g)"""
+        lr = np.float32(self.lr)
+        return ([float(lr * np.float32(sc)) for sc in self._group_scales],
+                [float(self.wd if wd is None else wd) for wd in self._group_wds])
 
     @property
     def micro_step(self):
@@ -791,6 +997,13 @@ class FusedTrainer:
         stream = torch.cuda.current_stream(dev).cuda_stream
         loss = C.c_double(0.0)
         multi = self.world > 1
+        if self._groups is not None:                   # (every step: lr may have moved; the same table again costs no device work)
+            lrs, wds = self._group_values()
+            with torch.cuda.device(dev):
+                self._groups.send(model, L, hd, lrs, wds, stream)
+        else:
+            with torch.cuda.device(dev):
+                _groups_off(model, L, hd)
         if self._applied_base is None and not torch.cuda.is_current_stream_capturing():
             n = C.c_int64(0)
             with torch.cuda.device(dev):
@@ -1055,7 +1268,14 @@ class FusedTrainer:
     def _hyper(self):
         return dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.wd)
 
+    def _state_groups(self):
+        """the groups state_dict() writes: the default group when it holds a tensor, then every entry that is not frozen"""
+        lrs, wds = self._group_values()
+        return [(g, dict(lr=lrs[g], betas=self.betas, eps=self.eps, weight_decay=wds[g]), ps) for g, ps in enumerate(self._groups.positions) if ps]
+
     def state_dict(self):
+        if self._groups is not None:
+            return adam_state_to_torch(self.model, self.m, self.v, self.step_count, None, [(hyp, ps) for _, hyp, ps in self._state_groups()])
         return adam_state_to_torch(self.model, self.m, self.v, self.step_count, self._hyper())
 
     def ema_state_dict(self):
@@ -1074,6 +1294,20 @@ class FusedTrainer:
         flat = getattr(self.model, "_flat", None)
         if flat is None or flat.device != params[0].device:
             flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+        if self._groups is not None:
+            # lr_scale and the entries' own weight decays are this trainer's settings.  Of the file's values: betas and eps; the base lr, from the first group
+            # whose scale is not 0 (the file holds lr * lr_scale; with every scale 0 the trainer's lr stays); the trainer's weight_decay, from the default group
+            # when the file has it (it is written first) -- as the load without groups takes lr and weight_decay from the file's one group
+            groups = self._state_groups()
+            self.m, self.v, self.step_count, hypers = adam_state_from_torch(self.model, sd, flat, [ps for _, _, ps in groups])
+            for (g, _, _), hyper in zip(groups, hypers):
+                if "lr" in hyper and self._group_scales[g] > 0.0:
+                    self.lr = hyper["lr"] if g == 0 else hyper["lr"] / self._group_scales[g]
+                    break
+            if groups[0][0] == 0:
+                self.wd = hypers[0].get("weight_decay", self.wd)
+            self.betas = tuple(hypers[0].get("betas", self.betas)); self.eps = hypers[0].get("eps", self.eps)
+            return
         self.m, self.v, self.step_count, hyper = adam_state_from_torch(self.model, sd, flat)
         self.lr = hyper.get("lr", self.lr); self.betas = tuple(hyper.get("betas", self.betas))
         self.eps = hyper.get("eps", self.eps); self.wd = hyper.get("weight_decay", self.wd)
