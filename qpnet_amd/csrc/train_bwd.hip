@@ -1707,7 +1707,9 @@ int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k
         {   // post-net: dW2[q][s] = dlogits^T relu(Y0), dW1[o][s] = dY0^T relu(S0); N split into 64-column groups
             w.nlayers = 1; w.A_lstride = w.B_lstride = 0; w.B2 = nullptr; w.bmode = 1; w.rowsA = w.rowsB = BL;
             w.row0A[0] = w.row0B[0] = 0; w.R[0] = BL; w.tap_off[0] = -1;
-            w.ncol_groups = S % 64 == 0 ? S / 64 : 1;
+            // (S no multiple of 64: as few groups as fit a kernel's tile budget -- one group of all S columns fits none from S = 144 on, with Q or S rows > 128)
+            auto post_groups = [&](int M) { return S % 64 == 0 ? S / 64 : wgrad_col_groups(M, S); };
+            w.ncol_groups = post_groups(Q);
             w.A = bw.dlogits; w.lda = Q; w.M = Q; w.B1 = p.Y0; w.ldb = S; w.N = S; w.Nvalid = S; w.ldc = S; w.goff[0] = sl.g_p2; w.gbias[0] = sl.g_bp2;
             if (Q == S && k.post_pair) {
                 // both contractions have the same shape: ONE launch with the second as "layer 1" (strides = the distance between the arrays,
@@ -1719,7 +1721,7 @@ int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k
                 ok = ok && wgrad2_any(w, nch_side_, gen, st);
             } else {
                 ok = ok && wgrad2_any(w, nch_side_, gen, st);
-                w.A = bw.DY0; w.lda = S; w.M = S; w.B1 = p.S0; w.goff[0] = sl.g_p1; w.gbias[0] = sl.g_bp1;
+                w.A = bw.DY0; w.lda = S; w.M = S; w.B1 = p.S0; w.goff[0] = sl.g_p1; w.gbias[0] = sl.g_bp1; w.ncol_groups = post_groups(S);
                 ok = ok && wgrad2_any(w, nch_side_, gen, st);
             }
             qpn_prof_mark(PG_WGRAD_POST, st);

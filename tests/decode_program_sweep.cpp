@@ -2,20 +2,23 @@
 // the gather map is decoded back through position formulas written out HERE (not the packers' loops): every 4 KiB-tile matrix and every fragment block must hold each
 // element of its tensor exactly once, at the index tp_*_src gives (what training packs and reduces into), with -1 exactly on the padding; the two families must agree;
 // the task table must cover every row of every matrix once per phase; the LDS regions must lie in the order the kernels assume.  Prints a hash of every list
-// ("GOLDEN ..." lines, compared with tests/golden/decode_program.json by tests/test_decode_program_cpu.py) and the number of programs checked.  Built with the host
-// sanitizers and run as a child process.
+// ("GOLDEN ..." lines, compared with tests/golden/decode_program.json by tests/test_decode_program_cpu.py) and the number of programs checked.  Widths that are multiples
+// of 16 but not of 32 and an acceptance sweep over n_resch, n_skipch and n_quantize run the same checks without a hash ("CHECKED ..." lines, the counts of the last line).
+// Built with the host sanitizers and run as a child process.
 #include "../qpnet_amd/csrc/qpn_geom.h"
 #include "../qpnet_amd/csrc/decode_program.h"
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <thread>
 
-static char g_err[512] = "";
+static thread_local char g_err[512] = "";      // (thread_local, atomic: the acceptance sweep checks its programs on several threads)
 void qpn_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof(g_err), fmt, ap); va_end(ap); }
 
-static std::string g_ctx;
-static long n_programs = 0;
+static thread_local std::string g_ctx;
+static std::atomic<long> n_programs(0);
 #define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "FAILED %s (line %d) -- %s\n", #cond, __LINE__, g_ctx.c_str()); exit(1); } } while (0)
 
 template <class T> static void golden(const char* name, const char* key, const T* p, size_t n) {      // 64-bit FNV-1a over the values widened to 64 bits, little endian
@@ -233,6 +236,18 @@ static void print_golden(const char* nm, const Geom& g, const DecodeProgram& d) 
     golden(nm, "biases", v.data(), v.size());
 }
 
+// ---- which widths decode, restated HERE from the kernels' tile shape and not from the planner's arithmetic: a matrix with K input columns is cut into 4 KiB tiles of
+// 64 lanes x 16 floats; K is padded to 16, 32, 64, ... so a row takes 1, 2, 4, ... lanes and a tile holds 64, 32, 16, 8, 4, 2, 1 rows.  Every matrix of the step must be a
+// whole number of tiles: the gate (2 n_resch rows), residual (n_resch) and skip (n_skipch) matrices have K = n_resch; the post-net ones (n_skipch and n_quantize rows) K =
+// n_skipch; the feature projection (2 n_resch rows) K = n_aux.  One CU's waves reduce at most 32 lanes of n_resch and 64 of the other two.
+static int rows_per_tile(int K) { return K <= 16 ? 64 : K <= 32 ? 32 : K <= 64 ? 16 : K <= 128 ? 8 : K <= 256 ? 4 : K <= 512 ? 2 : K <= 1024 ? 1 : 0; }
+static bool rule_accepts(int C, int S, int Q, int A) {
+    const int hc = rows_per_tile(C), hs = rows_per_tile(S), ha = rows_per_tile(A);
+    if (C > 512 || !hs || !ha) return false;
+    return C % hc == 0 && S % hc == 0 && S % hs == 0 && Q % hs == 0 && (2 * C) % ha == 0;
+}
+static bool names_a_quantity(const char* err) { const std::string e(err); return e.find("n_resch") != std::string::npos && e.find("n_skipch") != std::string::npos && e.find("n_quantize") != std::string::npos; }
+
 struct NG { const char* name; qpn_config c; };
 int main() {
     // {n_quantize, n_aux, n_resch, n_skipch, dilationF_depth, dilationF_repeat, dilationA_depth, dilationA_repeat, kernel_size, upsampling_factor}
@@ -282,6 +297,80 @@ int main() {
         d = decode_program(g, false);
         CHECK(d.rc == QPN_EINVAL && d.map.empty() && std::string(d.err) == "model too large for 32-bit gather map");
     }
-    printf("DECODE_PROGRAM_SWEEP_OK %ld programs\n", n_programs);
+    const long n_golden = n_programs;
+    // ---- widths that are multiples of 16 but not of 32, and the decode-only ones (tests/test_width_classes_gpu.py runs them on the kernels): the invariant checks alone.
+    // They get no golden hash -- tests/golden/decode_program.json comes from the code in front of the planner, which nobody ran at these widths -- and are printed as
+    // "CHECKED name"; the ones the planner must refuse, by the rule restated in rule_accepts, as "CHECKED name refused"
+    static const int wide[][3] = {{72, 72, 64}, {48, 80, 48}, {80, 64, 96}, {112, 144, 80}, {264, 136, 64}, {128, 112, 192}, {64, 48, 32}, {256, 256, 128},      // n_resch, n_skipch, n_quantize: the decode cases
+                                  {16, 16, 16}, {80, 48, 96}, {32, 16, 64}, {64, 16, 256}, {64, 272, 144}};                                                           // ... and the training cases that are not among them
+    for (const auto& w : wide) {
+        const qpn_config c = {w[2], 39, w[0], w[1], 2, 1, 2, 1, 2, 110};
+        Geom g;
+        CHECK(qpn_build_geom(&c, &g) == QPN_OK);
+        for (int cb = 0; cb < 2; ++cb) {
+            if (cb && (g.C % 8 || g.C < 128)) continue;
+            const std::string name = "w" + std::to_string(w[0]) + "_" + std::to_string(w[1]) + "_" + std::to_string(w[2]) + "/cb" + std::to_string(cb);
+            g_ctx = name;
+            const DecodeProgram d = decode_program(g, cb != 0);
+            if (rule_accepts(w[0], w[1], w[2], 39)) { check_program(g, cb != 0, d); printf("CHECKED %s\n", name.c_str()); }
+            else { CHECK(d.rc == QPN_EINVAL && d.map.empty() && d.tasks.empty() && names_a_quantity(d.err)); printf("CHECKED %s refused\n", name.c_str()); }
+        }
+    }
+    const long n_checked = n_programs - n_golden;
+    // ---- acceptance: a shallow 2 + 2-layer geometry with n_aux 39; every n_resch that is a multiple of 4 up to 272 (all of 8, 16, ..., 160 among them) with widths of
+    // n_skipch and n_quantize on and off every tile height.  The planner's decision is the rule's, and every program it builds passes the checks above
+    // (about a thousand programs of a million map entries each: the geometries are independent and are handed out to a few threads)
+    struct CSQ { int C, S, Q; };
+    std::vector<CSQ> combos;
+    for (int C = 4; C <= 272; C += 4) for (int S : {16, 48, 72, 80, 136, 144}) for (int Q : {16, 32, 48, 64, 80, 96, 192}) combos.push_back({C, S, Q});
+    std::atomic<size_t> next(0);
+    std::atomic<long> accepted(0);
+    auto worker = [&]() {
+        for (size_t i; (i = next.fetch_add(1)) < combos.size();) {
+            const int C = combos[i].C, S = combos[i].S, Q = combos[i].Q;
+            const qpn_config c = {Q, 39, C, S, 2, 1, 2, 1, 2, 110};
+            Geom g;
+            g_ctx = "acceptance C " + std::to_string(C) + " S " + std::to_string(S) + " Q " + std::to_string(Q);
+            CHECK(qpn_build_geom(&c, &g) == QPN_OK);
+            const DecodeProgram d = decode_program(g, false);
+            const bool want = rule_accepts(C, S, Q, 39);
+            CHECK((d.rc == QPN_OK) == want);
+            if (want) { check_program(g, false, d); ++accepted; }
+            else CHECK(d.rc == QPN_EINVAL && d.map.empty() && d.tasks.empty() && names_a_quantity(d.err));
+        }
+    };
+    {
+        const unsigned hw = std::thread::hardware_concurrency(), nthr = hw < 2 ? 1 : hw > 8 ? 8 : hw;
+        std::vector<std::thread> pool;
+        for (unsigned i = 1; i < nthr; ++i) pool.emplace_back(worker);
+        worker();
+        for (std::thread& th : pool) th.join();
+    }
+    const long n_swept = (long)combos.size(), n_accepted = accepted.load();
+    CHECK(n_accepted > 300 && n_swept - n_accepted > 300);
+    {   // where one CU stops holding the step state (n_resch in steps of 16, n_skipch = n_quantize = 64, 2 + 2 layers): the two widths test_width_classes_gpu.py decodes
+        int last_ok = 0, first_not = 0;
+        for (int C = 16; C <= 512; C += 16) {
+            const qpn_config c = {64, 39, C, 64, 2, 1, 2, 1, 2, 110};
+            Geom g;
+            g_ctx = "single_cu_ok C " + std::to_string(C);
+            CHECK(qpn_build_geom(&c, &g) == QPN_OK);
+            if (!rule_accepts(C, 64, 64, 39)) continue;
+            const DecodeProgram d = decode_program(g, false);
+            CHECK(d.rc == QPN_OK);
+            if (d.single_cu_ok) { CHECK(!first_not); last_ok = C; }      // (monotonic: no width fits again once one did not)
+            else if (!first_not) first_not = C;
+        }
+        CHECK(last_ok && first_not == last_ok + 16);
+        for (int C : {last_ok, first_not}) {
+            const qpn_config c = {64, 39, C, 64, 2, 1, 2, 1, 2, 110};
+            Geom g;
+            g_ctx = "single_cu_ok pair C " + std::to_string(C);
+            CHECK(qpn_build_geom(&c, &g) == QPN_OK);
+            check_program(g, false, decode_program(g, false));
+        }
+        printf("SINGLE_CU last %d first_not %d\n", last_ok, first_not);
+    }
+    printf("DECODE_PROGRAM_SWEEP_OK %ld programs %ld checked %ld swept %ld accepted\n", n_golden, n_checked, n_swept, n_accepted);
     return 0;
 }

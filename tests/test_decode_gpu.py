@@ -567,7 +567,8 @@ def test_batched_cooperative_decode_matches_reference_streams(case, cuda, golden
 
 
 def test_batched_cooperative_decode_other_widths_vs_oracle(cuda, oracle, monkeypatch):
-    """n_resch 256 / n_skipch 512 (16-chunk current taps, 32-chunk post-net, 128-pair gathers, 16 skip and 8 logit rows per workgroup of 32),
+    """n_resch 256 / n_skipch 256 (16-chunk current taps and post-net, 128-pair gathers, 8 skip and 8 logit rows per workgroup of 32; the batched kernel takes no
+    n_skipch above n_resch -- fewer logit rows per workgroup: tests/test_width_classes_gpu.py),
     asked for with QPN_DECODE_COOP (one CU could hold this state): three utterances, greedy and sampling, vs the oracle; and upsampling
     factor 0 on the default widths (aux features at sample rate)."""
     import dataclasses

@@ -33,7 +33,18 @@ def sweep(tmp_path_factory):
 def test_planner_invariants_sweep(sweep):
     """every plan and arena passed its checks; 13 geometries x 2 paths x 4 knob settings, five arenas each"""
     words = sweep.split("TRAIN_PLAN_SWEEP_OK")[1].split()
-    assert int(words[0]) >= 100 and int(words[2]) >= 500
+    assert int(words[0]) == len(GEOMETRIES) * 2 * 4 and int(words[2]) == len(GEOMETRIES) * 2 * 4 * 5
+
+
+def test_width_classes_pass_the_same_invariants(sweep):
+    """the nine (n_resch, n_skipch, n_quantize) of tests/test_width_classes_gpu.py -- multiples of 16, not all of 32 -- on the tile path at the four knob settings (the GEMM
+    path refuses each): the invariant checks of the named geometries, and no hash (train_plan.json comes from the code in front of the planner)"""
+    import test_width_classes_gpu as W
+    checked = [line.split()[1] for line in sweep.splitlines() if line.startswith("CHECKED ")]
+    assert checked == ["w%d_%d_%d/tile" % csq for csq in W.TRAIN_CSQ]
+    words = sweep.split("TRAIN_PLAN_SWEEP_OK")[1].split()
+    assert words[3] == "arenas" and int(words[4]) == 4 * len(W.TRAIN_CSQ) and words[5] == "checked"
+    assert {line.split()[1].split("/")[0] for line in sweep.splitlines() if line.startswith("GOLDEN ")} == set(GEOMETRIES)
 
 
 def test_maps_are_those_of_the_code_before_the_planner(sweep):

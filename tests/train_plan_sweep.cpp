@@ -1,8 +1,8 @@
 // Stand-alone sweep over the training layout planner (qpnet_amd/csrc/train_plan.h): for a list of geometries, both paths and a few knob settings, every packed block must
 // hold each element of its tensor exactly once, every transposed block must be the transpose of its forward block, the gradient map must send the gradient of an element to
 // the parameter the forward read it from, and the arena's regions must be disjoint and adjacent where the kernels rely on it.  Prints a hash of every map of the named
-// geometries ("GOLDEN ..." lines, compared with tests/golden/train_plan.json by tests/test_train_plan_cpu.py) and the number of plans checked.  Built with the host
-// sanitizers and run as a child process.
+// geometries ("GOLDEN ..." lines, compared with tests/golden/train_plan.json by tests/test_train_plan_cpu.py) and the number of plans checked.  The widths that are
+// multiples of 16 but not of 32 run the same checks without a hash ("CHECKED ..." lines).  Built with the host sanitizers and run as a child process.
 #include "../qpnet_amd/csrc/qpn_geom.h"
 #include "../qpnet_amd/csrc/train_plan.h"
 #include <algorithm>
@@ -329,10 +329,50 @@ int main() {
             golden(nm, "arena", v.data(), v.size());
         }
     }
+    // ---- widths that are multiples of 16 but not of 32 (tests/test_width_classes_gpu.py runs them on the kernels): the invariant checks alone.  They get no golden
+    // hash -- tests/golden/train_plan.json comes from the code in front of the planner, which nobody ran at these widths -- and are printed as "CHECKED name"
+    long n_checked = 0;
+    static const int wide[][3] = {{16, 16, 16}, {48, 80, 48}, {80, 48, 96}, {112, 144, 80}, {32, 16, 64}, {128, 112, 192}, {64, 48, 32}, {64, 16, 256}, {64, 272, 144}};      // n_resch, n_skipch, n_quantize
+    for (const auto& w : wide) {
+        const qpn_config c = {w[2], 39, w[0], w[1], 2, 1, 2, 1, 2, 110};
+        const std::string name = "w" + std::to_string(w[0]) + "_" + std::to_string(w[1]) + "_" + std::to_string(w[2]);
+        Geom g;
+        g_ctx = name;
+        CHECK(qpn_build_geom(&c, &g) == QPN_OK);
+        for (int knob = 0; knob < 4; ++knob) {
+            g_ctx = name + "/tile knob " + std::to_string(knob);
+            TrainKnobs kn = default_knobs();
+            if (knob == 1) kn.aux_hoist = false;
+            if (knob == 2) kn.persist_fwd = false;
+            if (knob == 3) kn.wgrad_chunks = 8;
+            const long before = n_plans;
+            const TrainPlan t = train_plan(g, kn, false);
+            check_plan(g, kn, false, t);
+            n_plans = before; ++n_checked;
+            CHECK(t.hoist == (w[0] == 64 && knob != 1 && knob != 2));      // the paper-width stacks keep the frame-rate aux path whatever S and Q are
+            // arenas: B N1 C and B BL S no multiples of 64 at the narrow widths; the smallest one is carved out of a real buffer
+            static const int grid[][3] = {{1, 40, 1}, {1, 181, 17}, {2, 500, 298}, {3, 1237, 500}};
+            const long a0 = n_arenas;
+            for (const auto& a : grid) check_arena(g, t, a[0], a[1], a[2], t.hoist ? (a[1] + g.U - 1) / g.U + 1 : 0, a[1] == 40);
+            n_arenas = a0;
+        }
+        g_ctx = name + "/gemm";      // none of them is a multiple of 32 in all three: the GEMM path refuses every one
+        CHECK(train_plan(g, default_knobs(), true).rc == QPN_EINVAL && std::string(g_err) == "the GEMM training path needs n_resch, n_skipch, n_quantize multiples of 32");
+        printf("CHECKED %s/tile\n", name.c_str());
+    }
     {   // the refusals: their codes and messages, before anything is built
         g_ctx = "refusals";
         Geom g;
-        const qpn_config c24 = {256, 39, 24, 32, 2, 1, 1, 1, 2, 110}, c48 = {256, 39, 48, 64, 2, 1, 1, 1, 2, 110}, ok = {256, 39, 32, 32, 2, 1, 1, 1, 2, 110};
+        const qpn_config c72 = {64, 39, 72, 72, 2, 1, 2, 1, 2, 110}, c144 = {64, 39, 144, 144, 2, 1, 2, 1, 2, 110};      // decode takes n_resch 72 (test_width_classes_gpu.py); 144 is a multiple of 16 and trains on the tile path only
+        CHECK(qpn_build_geom(&c72, &g) == QPN_OK);
+        CHECK(train_plan(g, default_knobs(), false).rc == QPN_EINVAL && std::string(g_err) == "training kernels need n_resch, n_skipch, n_quantize multiples of 16");
+        CHECK(qpn_build_geom(&c144, &g) == QPN_OK);
+        CHECK(train_plan(g, default_knobs(), true).rc == QPN_EINVAL && std::string(g_err) == "the GEMM training path needs n_resch, n_skipch, n_quantize multiples of 32");
+    }
+    {
+        g_ctx = "refusals (named geometries)";
+        Geom g;
+        const qpn_config c24 ={256, 39, 24, 32, 2, 1, 1, 1, 2, 110}, c48 = {256, 39, 48, 64, 2, 1, 1, 1, 2, 110}, ok = {256, 39, 32, 32, 2, 1, 1, 1, 2, 110};
         CHECK(qpn_build_geom(&c24, &g) == QPN_OK);
         CHECK(train_plan(g, default_knobs(), false).rc == QPN_EINVAL && std::string(g_err) == "training kernels need n_resch, n_skipch, n_quantize multiples of 16");
         CHECK(qpn_build_geom(&c48, &g) == QPN_OK);
@@ -343,6 +383,6 @@ int main() {
         const TrainPlan t = train_plan(g, default_knobs(), false);
         CHECK(t.rc == QPN_EINVAL && t.h_gsrc.empty() && std::string(g_err).find("32 bits") != std::string::npos);
     }
-    printf("TRAIN_PLAN_SWEEP_OK %ld plans %ld arenas\n", n_plans, n_arenas);
+    printf("TRAIN_PLAN_SWEEP_OK %ld plans %ld arenas %ld checked\n", n_plans, n_arenas, n_checked);
     return 0;
 }

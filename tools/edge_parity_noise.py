@@ -1,8 +1,8 @@
-"""The numpy oracle's own float32 noise on every input of tests/test_train_edges_gpu.py and of tests/test_aux_geometry_gpu.py (CPU only; --only edges|aux): per input, the distance between the float32 oracle and
+"""The numpy oracle's own float32 noise on every input of tests/test_train_edges_gpu.py, of tests/test_aux_geometry_gpu.py and of tests/test_width_classes_gpu.py (CPU only; --only edges|aux|widths): per input, the distance between the float32 oracle and
 the same oracle under train_oracle.precision(np.float64) evaluated on the float32 run's ReLU sides (the technique of tests/f64_child.py) -- logits, loss,
 and per gradient tensor as a fraction of that tensor's bound in util.assert_grads_match_oracle (a_scale 2e-5, a_rel 1e-4) -- and the number of post-net
 units within kink_eps = 4e-6 of a ReLU kink (at most max_units = 6 can be enumerated).  The tests' bounds must be at least 4 x these figures.
-    python tools/edge_parity_noise.py [--only edges|aux]"""
+    python tools/edge_parity_noise.py [--only edges|aux|widths]"""
 import os
 import sys
 
@@ -19,9 +19,10 @@ def main():
     import itertools
     import test_train_edges_gpu as E
     import test_aux_geometry_gpu as X
+    import test_width_classes_gpu as W
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
     worst = [0.0, 0.0, 0.0, 0]
-    for label, o in itertools.chain(E.all_cases() if only != "aux" else (), X.all_cases() if only != "edges" else ()):
+    for label, o in itertools.chain(E.all_cases() if only in (None, "edges") else (), X.all_cases() if only in (None, "aux") else (), W.all_cases() if only in (None, "widths") else ()):
         with TO.precision(np.float64):
             f64 = o.flat.astype(np.float64)
             lg64, c64 = TO.forward(o.cfg, f64, o.x, o.h.astype(np.float64), o.d, o.b)
