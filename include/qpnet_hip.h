@@ -141,6 +141,21 @@ int qpn_decode_sampling(qpn_handle* h, float temperature, int top_k);
  * QPN_ESTATE while a decode is in flight. */
 int qpn_decode_sampling_ex(qpn_handle* h, float temperature, int top_k, float top_p, float min_p);
 
+/* Per-row sampling: one record per batch row, in the caller's INPUT order (row b of d_x / d_h / h_n_samples), for the QPN_MODE_SAMPLING calls enqueued on
+ * this handle from now on (sticky, like qpn_decode_sampling; the array is copied into the handle).  The pick of row b at step i is the controlled draw
+ * above with row b's temperature / top_k / top_p / min_p and the uniform of the Philox counter (step i, h_rows[b].stream) under the key h_rows[b].seed:
+ * a row's samples depend on its own inputs and its own record only -- not on its row index, the batch size, the launch plan or the kernel (DESIGN.md
+ * section 3).  A record with the neutral values (1.0f, 0, 1.0f, 0.0f) draws the bits of the default draw, and the records {s, b, c} in every row b are
+ * the uniform call with seed s and controls c.  While records are set, the enqueue's own `seed` and the values of qpn_decode_sampling(_ex) are ignored by
+ * QPN_MODE_SAMPLING calls; QPN_MODE_ARGMAX calls ignore the records; an enqueue with B != n_rows returns QPN_EINVAL naming n_rows.  n_rows == 0
+ * switches the records off: every later call is the call of a handle that never had any (same kernels, same bytes).  The records in force at the
+ * enqueue are remembered with the call (the re-run after a launch that gave up draws with them) and reach the kernels as a small device table that is
+ * copied on the call's stream with the utterance descriptors: no host wait.  Teacher forcing, the logits output, live output and cancel compose unchanged.
+ * Checked before the device is looked at (works on a handle created without a GPU): QPN_EINVAL for n_rows < 0, a NULL array with n_rows > 0, and per
+ * record the rules and messages of qpn_decode_sampling_ex with "row <b>: " in front; QPN_ESTATE while a decode is in flight. */
+typedef struct { uint64_t seed; uint32_t stream; float temperature; int32_t top_k; float top_p, min_p; } qpn_row_draw;
+int qpn_decode_row_sampling(qpn_handle* h, int n_rows, const qpn_row_draw* h_rows);
+
 /* Non-blocking.  For the decode in flight: h_done[B] = samples of each row (input order) that are final in the mirror;
  * *h_samples / *row_stride = the mirror (int32 sample ids, row b at *h_samples + b * *row_stride; host memory owned by the
  * handle, valid until the next enqueue); *running = 0 once everything the enqueue put on the stream has completed.  The

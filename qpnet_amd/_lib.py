@@ -14,6 +14,10 @@ class QpnConfig(C.Structure):
         "dilationA_depth", "dilationA_repeat", "kernel_size", "upsampling_factor")]
 
 
+class QpnRowDraw(C.Structure):      # qpn_row_draw: one row's sampling record (qpn_decode_row_sampling)
+    _fields_ = [("seed", C.c_uint64), ("stream", C.c_uint32), ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float)]
+
+
 class QpnError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libqpnet_hip error %d: %s" % (code, msg))
@@ -36,6 +40,7 @@ SYMBOLS = [
     ("qpn_decode_live", _i, [_vp, _i]),
     ("qpn_decode_sampling", _i, [_vp, C.c_float, _i]),
     ("qpn_decode_sampling_ex", _i, [_vp, C.c_float, _i, C.c_float, C.c_float]),
+    ("qpn_decode_row_sampling", _i, [_vp, _i, C.POINTER(QpnRowDraw)]),
     ("qpn_decode_poll", _i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     ("qpn_decode_cancel", _i, [_vp]),
     ("qpn_decode_final_counts", _i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),

@@ -163,6 +163,10 @@ struct Ctx {
 
 // one slot of the per-step program for this wave; `w` holds the slot's weight tile and is refilled with
 // the tile of slot+3 as soon as it has been consumed (three tiles in flight per wave).
+// where the one-CU kernels of the calls with per-row records keep the row's record (stage_row_draw, decode_dev.h): eight LDS words behind everything else the launch
+// uses, the dev stamps included (launch_one_cu sizes the launch's LDS to match)
+__device__ __forceinline__ int one_cu_rowd(const DecodeParams& p) { return p.o_stamp + (p.stamps ? 120 * QPN_NW : 0); }
+template <bool ROW>
 __device__ __forceinline__ void run_slot(Ctx& c, int slot, int64_t t, float4 (&w)[4]) {
     const DecodeParams& p = *c.p; const UttView& u = *c.u;
     float* sm = SM; int* smi = SMI;
@@ -255,7 +259,7 @@ __device__ __forceinline__ void run_slot(Ctx& c, int slot, int64_t t, float4 (&w
         if (i >= 0 && u.logits) for (int k = lane; k < Q; k += 64) u.logits[(size_t)i * Q + k] = sm[p.o_lg + k];
         int next;
         if (i >= 0) {
-            if (p.mode != QPN_MODE_ARGMAX) bi = sample_pick(p, p.o_lg, Q, (unsigned)u.row, (unsigned)i, lane);
+            if (p.mode != QPN_MODE_ARGMAX) bi = sample_pick<ROW>(p, (unsigned)u.row, one_cu_rowd(p), p.o_lg, Q, (unsigned)i, lane);
             next = bi;
             if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
             if (lane == 0) { u.out[i] = bi; if (live_put(p, u, (int)i, bi, c.creq)) smi[p.o_samp + 2] = 1; }      // stop on request: the workgroup leaves after the next step
@@ -272,54 +276,16 @@ __device__ __forceinline__ void run_slot(Ctx& c, int slot, int64_t t, float4 (&w
     if (nopf & TF_HASW) load_tile(w, p.wpk, nwoff, lane);
 }
 
-__global__ __launch_bounds__(QPN_NT) void k_decode(DecodeParams p) {
-    float* sm = SM;
-    int* smi = SMI;
-    const UttView u = make_view(p, p.utts[blockIdx.x]);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    for (int i = tid; i < p.state_floats; i += QPN_NT) sm[i] = 0.0f;
-    for (int i = tid; i < p.n_bias; i += QPN_NT) sm[p.o_bias + i] = p.flat[p.bias_src[i]];
-    {
-        const int* src = (const int*)p.tasks;
-        for (int i = tid; i < p.n_slots * QPN_NW * 8; i += QPN_NT) smi[p.o_tasks + i] = src[i];
-    }
-    __syncthreads();
-    const int64_t Ttot = (int64_t)u.n0 + u.n_samples;
-    if (Ttot < 3) return;                                   // nothing to predict
-    if (p.cancel) {      // a row that starts after the host's stop request (qpn_decode_cancel) does not run: one lane reads the word, the workgroup leaves together
-        if (tid == 0 && cancel_requested(p)) smi[p.o_samp + 2] = 1;
-        __syncthreads();
-        if (smi[p.o_samp + 2]) return;
-    }
-    // state for the first step (t = 1): layer-0 input, aux terms; taps of step 2; pd of step 1 is all-zero
-    if (wave == 0) {
-        causal_rows(p, u, u.known[0], u.known[1], 1, lane);
-        if (lane == 0) { smi[p.o_samp] = u.known[0]; smi[p.o_samp + 1] = u.known[1]; }
-    }
-    stage_aux(p, u, 1, tid, QPN_NT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (Ttot > 3) stage_taps(p, u, 2, tid, QPN_NT, p.status);
-    __syncthreads();
-
-    Ctx c; c.p = &p; c.u = &u; c.lane = lane; c.wave = wave; c.Ttot = Ttot; c.creq = 0; c.stop = 0;
-    float4 w0[4], w1[4], w2[4];
-    {
-        const int* tk = smi + p.o_tasks + wave * 8;
-        if (tk[0] & TF_HASW) load_tile(w0, p.wpk, tk[1], lane);
-        if (tk[QPN_NW * 8] & TF_HASW) load_tile(w1, p.wpk, tk[QPN_NW * 8 + 1], lane);
-        if (tk[2 * QPN_NW * 8] & TF_HASW) load_tile(w2, p.wpk, tk[2 * QPN_NW * 8 + 1], lane);
-    }
-    for (int64_t t = 1; t + 1 < Ttot; ++t) {
-        for (int slot = 0; slot < p.n_slots; slot += 3) {
-            run_slot(c, slot, t, w0);
-            run_slot(c, slot + 1, t, w1);
-            run_slot(c, slot + 2, t, w2);
-        }
-        if (c.stop) break;      // stopped on request at the previous step's publish point (this step has drained: its pick published nothing)
-    }
-}
+#define QPN_KERNEL k_decode
+#define QPN_KERNEL_ROW false
+#include "decode_slot_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
+#define QPN_KERNEL k_decode_r      // ... of the calls with per-row records
+#define QPN_KERNEL_ROW true
+#include "decode_slot_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
 
 
 // ================================================================== specialised straight-line decode kernel
@@ -383,7 +349,7 @@ struct FastGeo {
     }
 };
 
-template <int C, int S, int Q, int NWV, bool RESL, int W0>
+template <int C, int S, int Q, int NWV, bool RESL, bool ROW, int W0>
 __device__ __forceinline__ void fast_steps(const DecodeParams& p, const FastParams& f, const UttView& u,
                                            const int wave, const int lane0, const int tid0, const int Ttot) {
     using G = FastGeo<C, S, Q, NWV>;
@@ -566,7 +532,7 @@ __device__ __forceinline__ void fast_steps(const DecodeParams& p, const FastPara
             if (i >= 0 && u.logits) for (int k = lane; k < Q; k += 64) u.logits[(size_t)i * Q + k] = sm[p.o_lg + k];
             int next;
             if (i >= 0) {
-                if (p.mode != QPN_MODE_ARGMAX) bi = sample_pick(p, p.o_lg, Q, (unsigned)u.row, (unsigned)i, lane);
+                if (p.mode != QPN_MODE_ARGMAX) bi = sample_pick<ROW>(p, (unsigned)u.row, one_cu_rowd(p), p.o_lg, Q, (unsigned)i, lane);
                 next = bi;
                 if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
                 if (lane == 0) u.out[i] = bi;
@@ -600,56 +566,30 @@ __device__ __forceinline__ void fast_steps(const DecodeParams& p, const FastPara
 #undef QPN_LAYER
 }
 
-template <int C, int S, int Q, int NWV, bool RESL, int W0>
+template <int C, int S, int Q, int NWV, bool RESL, bool ROW, int W0>
 __device__ __forceinline__ void fast_dispatch(const DecodeParams& p, const FastParams& f, const UttView& u,
                                               const int wave, const int lane, const int tid, const int Ttot) {
     constexpr int NB = FastGeo<C, S, Q, NWV>::next_boundary(W0);
-    if constexpr (NB >= NWV) fast_steps<C, S, Q, NWV, RESL, W0>(p, f, u, wave, lane, tid, Ttot);
+    if constexpr (NB >= NWV) fast_steps<C, S, Q, NWV, RESL, ROW, W0>(p, f, u, wave, lane, tid, Ttot);
     else {
-        if (wave < NB) fast_steps<C, S, Q, NWV, RESL, W0>(p, f, u, wave, lane, tid, Ttot);
-        else fast_dispatch<C, S, Q, NWV, RESL, NB>(p, f, u, wave, lane, tid, Ttot);
+        if (wave < NB) fast_steps<C, S, Q, NWV, RESL, ROW, W0>(p, f, u, wave, lane, tid, Ttot);
+        else fast_dispatch<C, S, Q, NWV, RESL, ROW, NB>(p, f, u, wave, lane, tid, Ttot);
     }
 }
 
 // RESL: the residual-1x1 tiles of layers 0..L-2 (the ones on the critical path of every R phase) live in LDS for the whole
 // launch: 16 fewer 1 KiB requests per layer through the serial vector-memory front end, and the waves that own them never
 // block on it.  The host picks RESL when the tiles fit beside the step state (paper-size: 112 KiB + 38 KiB).
-template <int C, int S, int Q, int NWV, bool RESL>
-__global__ __launch_bounds__(NWV * 64) void k_decode_fast(DecodeParams p, FastParams f) {
-    using G = FastGeo<C, S, Q, NWV>;
-    static_assert(G::R <= 8 && G::RS <= 32 && G::ZT >= 1 && G::RT >= 1, "geometry not covered by the fast kernel");
-    constexpr int NTH = NWV * 64;
-    float* sm = SM; int* smi = SMI;
-    const UttView u = make_view(p, p.utts[blockIdx.x]);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    for (int i = tid; i < p.state_floats; i += NTH) sm[i] = 0.0f;
-    for (int i = tid; i < p.n_bias; i += NTH) sm[p.o_bias + i] = p.flat[p.bias_src[i]];
-    __syncthreads();
-    const int Ttot = u.n0 + u.n_samples;
-    if (Ttot < 3) return;
-    if (p.cancel) {      // a row that starts after the host's stop request (qpn_decode_cancel) does not run: one lane reads the word, the workgroup leaves together
-        if (tid == 0 && cancel_requested(p)) smi[p.o_samp + 2] = 1;
-        __syncthreads();
-        if (smi[p.o_samp + 2]) return;
-    }
-    if (wave == 0) {
-        causal_rows(p, u, u.known[0], u.known[1], 1, lane);
-        if (lane == 0) { smi[p.o_samp] = u.known[0]; smi[p.o_samp + 1] = u.known[1]; }
-    }
-    stage_aux(p, u, 1, tid, NTH);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (Ttot > 3) stage_taps(p, u, 2, tid, NTH, p.status);
-    __syncthreads();
-    if constexpr (RESL) {
-        const int per = G::NRES * 256;                                   // float4s per layer
-        float4* dst = (float4*)(sm + p.o_wres);
-        for (int i = tid; i < (p.L - 1) * per; i += NTH) { const int l = i / per; dst[i] = p.wpk[f.w_res[l] + (i - l * per)]; }
-        __syncthreads();
-    }
-    fast_dispatch<C, S, Q, NWV, RESL, 0>(p, f, u, wave, lane, tid, Ttot);
-}
+#define QPN_KERNEL k_decode_fast
+#define QPN_KERNEL_ROW false
+#include "decode_fast_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
+#define QPN_KERNEL k_decode_fast_r      // ... of the calls with per-row records
+#define QPN_KERNEL_ROW true
+#include "decode_fast_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
 
 // ================================================================== host side
 static thread_local char g_err[512] = "";
@@ -725,12 +665,13 @@ extern "C" int qpn_create(const qpn_config* cfg, qpn_handle** out) {
 extern "C" void qpn_destroy(qpn_handle* h) {      // (every member may still be null)
     if (!h) return;
     if (h->device >= 0) {
-        void* bufs[] = {h->d_map, h->d_wpk, h->d_tasks, h->d_qb, h->d_bd, h->d_status, h->d_bias_src, h->d_pproj, h->d_ring, h->d_known, h->d_utts, h->d_xch, h->d_adam_table};
+        void* bufs[] = {h->d_map, h->d_wpk, h->d_tasks, h->d_qb, h->d_bd, h->d_status, h->d_bias_src, h->d_pproj, h->d_ring, h->d_known, h->d_utts, h->d_xch, h->d_adam_table, h->d_rows};
         for (void* b : bufs) if (b) (void)hipFree(b);
         qpn_train_destroy(h->train);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
         if (h->ev1) (void)hipEventDestroy(h->ev1);
         if (h->h_utts_pinned) (void)hipHostFree(h->h_utts_pinned);
+        if (h->h_rows_pinned) (void)hipHostFree(h->h_rows_pinned);
         if (h->h_live) (void)hipHostFree(h->h_live);
         if (h->h_live_done) (void)hipHostFree(h->h_live_done);
         if (h->h_cancel) (void)hipHostFree(h->h_cancel);
@@ -845,17 +786,24 @@ static int launch_one_cu(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, h
     const int stamp_floats = p.stamps ? 120 * QPN_NW : 0;
     const int nres_tiles = (g.C * g.C / 1024) * (g.L - 1);
     p.o_wres = (p.o_tasks + 3) & ~3;
+    const int rowd_floats = p.row_draw ? 8 : 0;      // a call with per-row records: the row's record, behind everything else (stage_row_draw, decode_dev.h)
     const bool resl = (fast64 || fast32) && g.L >= 2 && !h->dk.no_resl &&
-                      ((size_t)p.o_wres + (size_t)nres_tiles * 1024 + stamp_floats) * sizeof(float) <= 160 * 1024;
+                      ((size_t)p.o_wres + (size_t)nres_tiles * 1024 + stamp_floats + rowd_floats) * sizeof(float) <= 160 * 1024;
     const int use_floats = resl ? p.o_wres + nres_tiles * 1024 : p.lds_floats;
     p.o_stamp = use_floats;
-    const size_t lds_bytes = ((size_t)use_floats + stamp_floats) * sizeof(float);
+    const size_t lds_bytes = ((size_t)use_floats + stamp_floats + rowd_floats) * sizeof(float);
+    if (rowd_floats && lds_bytes > 160 * 1024) { qpn_set_error("per-row sampling records need 32 bytes of LDS behind the %d KiB of step state of this geometry", (int)(lds_bytes >> 10)); return QPN_EINVAL; }
     typedef void (*FastKernel)(DecodeParams, FastParams);      // the ONE choice: a straight-line kernel, or (null) the interpreter
-    const FastKernel fast = fast64 ? (resl ? k_decode_fast<64, 256, 256, 16, true> : k_decode_fast<64, 256, 256, 16, false>)
+    const bool rowk = p.mode == QPN_MODE_SAMPLING_ROW;      // per-row records: the kernels whose pick reads them (sample_pick<true>)
+    const FastKernel fast = rowk ? (fast64 ? (resl ? k_decode_fast_r<64, 256, 256, 16, true> : k_decode_fast_r<64, 256, 256, 16, false>)
+                                  : fast32 ? (resl ? k_decode_fast_r<32, 32, 256, 16, true> : k_decode_fast_r<32, 32, 256, 16, false>) : nullptr)
+                          : fast64 ? (resl ? k_decode_fast<64, 256, 256, 16, true> : k_decode_fast<64, 256, 256, 16, false>)
                           : fast32 ? (resl ? k_decode_fast<32, 32, 256, 16, true> : k_decode_fast<32, 32, 256, 16, false>) : nullptr;
-    if (lds_bytes > 48 * 1024) QPN_HIP(hipFuncSetAttribute(fast ? (const void*)fast : (const void*)k_decode, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    typedef void (*SlotKernel)(DecodeParams);
+    const SlotKernel interp = rowk ? k_decode_r : k_decode;
+    if (lds_bytes > 48 * 1024) QPN_HIP(hipFuncSetAttribute(fast ? (const void*)fast : (const void*)interp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     if (fast) hipLaunchKernelGGL(fast, dim3(n), dim3(QPN_NT), lds_bytes, stream, p, h->prog.fp);
-    else hipLaunchKernelGGL(k_decode, dim3(n), dim3(QPN_NT), lds_bytes, stream, p);
+    else hipLaunchKernelGGL(interp, dim3(n), dim3(QPN_NT), lds_bytes, stream, p);
     QPN_HIP(hipGetLastError());
     return QPN_OK;
 }
@@ -937,6 +885,13 @@ static int decode_enqueue_impl(qpn_handle* h, hipStream_t stream, const DecodePl
         u.row = b; u.pad_ = 0;
     }
     QPN_HIP(hipMemcpyAsync(h->d_utts, utts, (size_t)B * sizeof(UttDesc), hipMemcpyHostToDevice, stream));
+    const bool row_draw = c.mode == QPN_MODE_SAMPLING && !c.rows.empty();      // per-row records (qpn_decode_row_sampling): staged and copied like the descriptors, no host wait
+    if (row_draw) {
+        rc = grow(&h->d_rows, &h->rows_cap, (size_t)B); if (rc) return rc;
+        rc = grow_pinned(&h->h_rows_pinned, &h->h_rows_cap, (size_t)B); if (rc) return rc;
+        memcpy(h->h_rows_pinned, c.rows.data(), (size_t)B * sizeof(RowDraw));
+        QPN_HIP(hipMemcpyAsync(h->d_rows, h->h_rows_pinned, (size_t)B * sizeof(RowDraw), hipMemcpyHostToDevice, stream));
+    }
     if (c.plan.needs_ring) QPN_HIP(hipMemsetAsync(h->d_ring, 0, ring_floats * (size_t)B * sizeof(float), stream));
     QPN_HIP(hipMemsetAsync(h->d_status, 0, 64, stream));
     hipLaunchKernelGGL(k_known, dim3((unsigned)((n0 + 255) / 256), B), dim3(256), 0, stream, c.d_x, n_x, (int)n_pad, g.Q, h->d_known);
@@ -946,6 +901,7 @@ static int decode_enqueue_impl(qpn_handle* h, hipStream_t stream, const DecodePl
     p.status = h->d_status; p.mode = c.mode; p.seed = c.seed; p.bias_src = h->d_bias_src;
     p.inv_temp = c.inv_temp; p.top_k = c.top_k; p.top_p = c.top_p; p.min_p = c.min_p;
     if (c.mode == QPN_MODE_SAMPLING && (c.inv_temp != 1.0f || c.top_k != 0 || c.top_p != 1.0f || c.min_p != 0.0f)) p.mode = QPN_MODE_SAMPLING_CTL;
+    if (row_draw) { p.mode = QPN_MODE_SAMPLING_ROW; p.row_draw = h->d_rows; }      // the records take the place of the call's seed and of the four uniform values
     p.stamps = h->dk.stamps ? (long long*)(h->d_status + 16) : nullptr;
     p.pproj = h->d_pproj; p.dfac = c.d_dfac; p.known = h->d_known; p.teacher = d_teacher; p.out = c.d_out; p.logits = d_logits; p.ring = h->d_ring;
     QPN_HIP(hipEventRecord(h->ev0, stream));
@@ -971,10 +927,14 @@ extern "C" int qpn_decode_enqueue(qpn_handle* h, int B, int n_x, int64_t F, int6
     if (B < 1 || n_x < 1 || F < 1 || !d_x || !d_h || !d_dfac || !h_n_samples || !d_out || maxd < 1) { qpn_set_error("bad decode arguments"); return QPN_EINVAL; }
     if (mode != QPN_MODE_ARGMAX && mode != QPN_MODE_SAMPLING) { qpn_set_error("mode must be QPN_MODE_ARGMAX or QPN_MODE_SAMPLING"); return QPN_EINVAL; }
     if (mode == QPN_MODE_SAMPLING && (h->g.Q % 64 || h->g.Q > 256)) { qpn_set_error("sampling needs n_quantize in {64,128,192,256}"); return QPN_EINVAL; }
+    if (mode == QPN_MODE_SAMPLING && !h->samp_rows.empty() && (size_t)B != h->samp_rows.size()) {
+        qpn_set_error("B = %d rows, but qpn_decode_row_sampling set n_rows = %zu records (one per batch row; n_rows = 0 switches them off)", B, h->samp_rows.size()); return QPN_EINVAL;
+    }
     qpn_handle::DecodeCall& c = h->call;
     c.B = B; c.n_x = n_x; c.F = F; c.Td = Td; c.d_x = d_x; c.d_h = d_h; c.d_dfac = d_dfac; c.d_is_f32 = d_is_f32;
     c.n_samples.assign(h_n_samples, h_n_samples + B); c.maxd = maxd; c.mode = mode; c.seed = seed;
     c.inv_temp = h->samp_inv_temp; c.top_k = h->samp_top_k; c.top_p = h->samp_top_p; c.min_p = h->samp_min_p;
+    if (mode == QPN_MODE_SAMPLING) c.rows = h->samp_rows; else c.rows.clear();
     c.d_teacher = d_teacher; c.d_out = d_out; c.d_logits = d_logits;
     h->live_call = h->live_every > 0;
     h->live_final = false;
@@ -1014,6 +974,27 @@ extern "C" int qpn_decode_sampling_ex(qpn_handle* h, float temperature, int top_
     return QPN_OK;
 }
 extern "C" int qpn_decode_sampling(qpn_handle* h, float temperature, int top_k) { return qpn_decode_sampling_ex(h, temperature, top_k, 1.0f, 0.0f); }
+
+extern "C" int qpn_decode_row_sampling(qpn_handle* h, int n_rows, const qpn_row_draw* h_rows) {
+    if (!h) { qpn_set_error("null handle"); return QPN_EINVAL; }
+    if (n_rows < 0) { qpn_set_error("n_rows must be >= 0 (0: off; got %d)", n_rows); return QPN_EINVAL; }
+    if (n_rows > 0 && !h_rows) { qpn_set_error("h_rows is NULL with n_rows = %d", n_rows); return QPN_EINVAL; }
+    std::vector<RowDraw> rows((size_t)n_rows);
+    for (int b = 0; b < n_rows; ++b) {
+        const qpn_row_draw& r = h_rows[b];
+        float inv; int k;
+        if (sampling_controls(r.temperature, r.top_k, r.top_p, r.min_p, h->g.Q, &inv, &k)) {      // the rules and messages of qpn_decode_sampling_ex, with the row in front
+            const std::string why = qpn_last_error();
+            qpn_set_error("row %d: %s", b, why.c_str()); return QPN_EINVAL;
+        }
+        RowDraw& o = rows[(size_t)b];
+        o.seed_lo = (unsigned)r.seed; o.seed_hi = (unsigned)(r.seed >> 32); o.stream = r.stream;
+        o.inv_temp = inv; o.top_k = k; o.top_p = r.top_p; o.min_p = r.min_p; o.pad_ = 0;
+    }
+    if (h->pending) { qpn_set_error("a decode is in flight: call qpn_decode_finish first"); return QPN_ESTATE; }
+    h->samp_rows.swap(rows);
+    return QPN_OK;
+}
 
 extern "C" int qpn_decode_poll(qpn_handle* h, int64_t* h_done, const int32_t** h_samples, int64_t* row_stride, int* running) {
     int rc = need_device(h); if (rc) return rc;

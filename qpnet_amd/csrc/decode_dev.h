@@ -326,18 +326,10 @@ __device__ __forceinline__ int sample_wave_ctl(int o_lg, int Q, float u, float i
     const unsigned long long any = __builtin_amdgcn_ballot_w64(hi >= 0);
     return any ? __builtin_amdgcn_readlane(hi, 63 - __builtin_clzll(any)) : Q - 1;
 }
-// what the decode kernels' picks call when p.mode is not QPN_MODE_ARGMAX.  The host folds "a control is set" into the mode word the picks test anyway
-// (QPN_MODE_SAMPLING_CTL, qpn_common.h): one wave-uniform compare of a kernel argument selects the draw, a default call runs sample_wave / sample_wave_u
-// untouched, and the controls themselves (DecodeParams.inv_temp / top_k, kernel arguments too: a captured launch replays them) are read on the
-// controlled path only (top_p / min_p of qpn_decode_sampling_ex as well)
-__device__ __forceinline__ int sample_pick(const DecodeParams& p, int o_lg, int Q, unsigned row, unsigned step, int lane) {
-    if (p.mode == QPN_MODE_SAMPLING) return sample_wave(o_lg, Q, p.seed, row, step, lane);
-    return sample_wave_ctl<true>(o_lg, Q, sample_uniform(p.seed, row, step), p.inv_temp, p.top_k, p.top_p, p.min_p, lane);
-}
-
 struct UttView {            // per-utterance pointers derived from kernel-argument bases (global address space)
     const float* pproj; const void* dfac; const int* known; const int64_t* teacher; int64_t* out; float* logits; float* ring;
     int n_pad, n0, n_samples, d_is_f32, row;
+    RowDraw rd;             // the row's sampling record (qpn_decode_row_sampling), wave-uniform: filled by make_row_view only (the pipelined kernel), zeros otherwise
 };
 __device__ __forceinline__ UttView make_view(const DecodeParams& p, const UttDesc& d) {
     UttView u;
@@ -349,7 +341,52 @@ __device__ __forceinline__ UttView make_view(const DecodeParams& p, const UttDes
     u.logits = d.logits >= 0 ? p.logits + d.logits : nullptr;
     u.ring = p.ring + d.ring;
     u.n_pad = d.n_pad; u.n0 = d.n0; u.n_samples = d.n_samples; u.d_is_f32 = d.d_is_f32; u.row = d.row;
+    u.rd = RowDraw{};
     return u;
+}
+// ... and the view of the pipelined kernel's per-row instantiations (k_decode_pipe_r, decode_pipe.hip): with the row's record, one 32-byte load of the table behind
+// p.row_draw when the group takes the utterance.  Their picks read the record from the view's registers: nothing is fetched per step
+__device__ __forceinline__ UttView make_row_view(const DecodeParams& p, const UttDesc& d) {
+    UttView u = make_view(p, d);
+    if (p.row_draw) u.rd = p.row_draw[d.row];
+    return u;
+}
+__device__ __forceinline__ unsigned long long row_seed(const RowDraw& r) { return (unsigned long long)r.seed_lo | ((unsigned long long)r.seed_hi << 32); }
+// The kernels whose pick chooses its draw at run time (the one-CU kernels, decode_coop.hip, decode_coopb.hip) keep a row's record in LDS instead: eight words at SMI[o_rd],
+// copied ONCE when the workgroup takes the row (the caller passes a barrier before its first pick) and read back by the picks of the ROW instantiations (sample_pick).  Held in
+// registers for the whole launch, the seven values pushed the one-CU kernels' spilled scalars into scratch memory.
+__device__ __forceinline__ void stage_row_draw(const DecodeParams& p, int row, int o_rd, int tid) {
+    if (p.row_draw && tid < 8) SMI[o_rd + tid] = ((const int*)(p.row_draw + row))[tid];
+}
+// a record read from LDS (every lane reads the same words): back into scalar registers, so that the draw's loop bounds and compares stay wave-uniform
+__device__ __forceinline__ RowDraw row_draw_lds(int o_rd) {
+    const int* r = SMI + o_rd;
+    RowDraw o;
+    o.seed_lo = (unsigned)__builtin_amdgcn_readfirstlane(r[0]); o.seed_hi = (unsigned)__builtin_amdgcn_readfirstlane(r[1]); o.stream = (unsigned)__builtin_amdgcn_readfirstlane(r[2]);
+    o.inv_temp = __int_as_float(__builtin_amdgcn_readfirstlane(r[3])); o.top_k = __builtin_amdgcn_readfirstlane(r[4]);
+    o.top_p = __int_as_float(__builtin_amdgcn_readfirstlane(r[5])); o.min_p = __int_as_float(__builtin_amdgcn_readfirstlane(r[6]));
+    o.pad_ = 0;
+    return o;
+}
+// what the decode kernels' picks call when p.mode is not QPN_MODE_ARGMAX.  The host folds "a control is set" into the mode word the picks test anyway
+// (QPN_MODE_SAMPLING_CTL, qpn_common.h): one wave-uniform compare of a kernel argument selects the draw, a default call runs sample_wave / sample_wave_u
+// untouched, and the controls themselves (DecodeParams.inv_temp / top_k, kernel arguments too: a captured launch replays them) are read on the
+// controlled path only (top_p / min_p of qpn_decode_sampling_ex as well).
+// ROW: the kernels of the calls with per-row records (qpn_decode_row_sampling; p.mode == QPN_MODE_SAMPLING_ROW, which the launchers turn into the choice of the
+// kernel: k_decode_r, k_decode_fast_r, k_decode_coop_r, k_decode_coopb_r): the same controlled draw with its key, its counter word and its four values taken from
+// the row's record at SMI[o_rd] instead of DecodeParams and the batch row.  Kernels of their own, as k_decode_pipe_c is: compiled into the kernels of every call
+// behind one more compare, the second draw cost calls WITHOUT records 1.8 % of the batched cooperative kernel's step time (repo-default model at B = 20) and, merged
+// into one call behind selects, the one-CU kernels 68 bytes of scratch per lane.  Each kernel body is a file that its .hip includes twice (decode_*_kernel.h): with
+// ROW = false the source is what it was, and the compiled kernels have the instruction counts, scratch sizes and register figures they had.
+template <bool ROW>
+__device__ __forceinline__ int sample_pick(const DecodeParams& p, unsigned row, int o_rd, int o_lg, int Q, unsigned step, int lane) {
+    if constexpr (ROW) {
+        const RowDraw r = row_draw_lds(o_rd);
+        return sample_wave_ctl<true>(o_lg, Q, sample_uniform(row_seed(r), r.stream, step), r.inv_temp, r.top_k, r.top_p, r.min_p, lane);
+    } else {
+        if (p.mode == QPN_MODE_SAMPLING) return sample_wave(o_lg, Q, p.seed, row, step, lane);
+        return sample_wave_ctl<true>(o_lg, Q, sample_uniform(p.seed, row, step), p.inv_temp, p.top_k, p.top_p, p.min_p, lane);
+    }
 }
 
 // Live output: the lane that has just stored sample i of its row (bi) mirrors it into host memory and, every live_every samples and after the

@@ -20,6 +20,14 @@
 
 // ---------------------------------------------------------------- decode program
 #define QPN_MODE_SAMPLING_CTL 2   // DecodeParams.mode only, never an ABI value: QPN_MODE_SAMPLING with a sampling control set (qpn_decode_sampling / _ex: any of the four)
+#define QPN_MODE_SAMPLING_ROW 3   // DecodeParams.mode only, never an ABI value: QPN_MODE_SAMPLING with per-row records set (qpn_decode_row_sampling): the pick takes its key and its
+                                  // five values from DecodeParams.row_draw[UttDesc.row] instead of from DecodeParams
+struct RowDraw {            // one batch row's record as the kernels read it (32 bytes: one scalar load), indexed by UttDesc.row; the host forms 1 / temperature and folds top_k
+    unsigned seed_lo, seed_hi, stream;      // Philox key, and the counter word that a uniform call fills with the batch row
+    float inv_temp; int top_k; float top_p, min_p;
+    int pad_;
+};
+static_assert(sizeof(RowDraw) == 32, "one 32-byte record per row");
 struct UttDesc {            // offsets into the base pointers of DecodeParams (kernel-argument pointers keep
                             // the GLOBAL address space; pointers loaded from memory would become FLAT accesses)
     int64_t pproj;          // floats: [F][L][2C] per-frame aux projections
@@ -75,6 +83,7 @@ struct DecodeParams {
     long long* live_done;   // [B], indexed by UttDesc.row: samples of that row that are final in the mirror
     int live_every;         // a row publishes its count after every live_every samples, and after its last one
     const int* cancel;      // the host's stop request (qpn_decode_cancel): one word, non-zero once the caller asked; read at publish points and at a row's start
+    const RowDraw* row_draw;   // per-row sampling records (qpn_decode_row_sampling), [B] indexed by UttDesc.row; null unless mode == QPN_MODE_SAMPLING_ROW.  Loaded once when a workgroup takes a row
 };
-static_assert(sizeof(DecodeParams) == 1080 && offsetof(DecodeParams, n_slots) == 112 && offsetof(DecodeParams, o_xbuf) == 168 && offsetof(DecodeParams, o_gl) == 236 &&
+static_assert(sizeof(DecodeParams) == 1088 && offsetof(DecodeParams, n_slots) == 112 && offsetof(DecodeParams, o_xbuf) == 168 && offsetof(DecodeParams, o_gl) == 236 &&
               offsetof(DecodeParams, bias_src) == 248 && offsetof(DecodeParams, rings) == 280 && offsetof(DecodeParams, live) == 1048, "kernel argument layout");

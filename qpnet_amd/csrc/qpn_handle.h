@@ -50,6 +50,9 @@ struct qpn_handle {      // every member has an initialiser: qpn_create sets onl
     int* h_cancel = nullptr; int* d_cancel = nullptr; size_t cancel_cap = 0;   // the stop request of qpn_decode_cancel: one host-coherent word, zeroed at every armed enqueue, read by the kernels at their publish points
     float samp_top_p = 1.0f, samp_min_p = 0.0f;      // ... and top_p / min_p (qpn_decode_sampling_ex; 1.0f / 0.0f: off)
     float samp_inv_temp = 1.0f; int samp_top_k = 0;  // sampling controls of the decode calls enqueued from now on (qpn_decode_sampling): 1 / temperature, top-k cut (0: off; k == n_quantize is stored as 0)
+    std::vector<RowDraw> samp_rows;  // per-row records of the QPN_MODE_SAMPLING calls enqueued from now on (qpn_decode_row_sampling), input order, checked and converted; empty: off
+    RowDraw* h_rows_pinned = nullptr; size_t h_rows_cap = 0;      // pinned staging of the call's records (copied on the call's stream with the descriptors) ...
+    RowDraw* d_rows = nullptr; size_t rows_cap = 0;               // ... and the device table the kernels index by UttDesc.row
     bool live_final = false;         // the last decode was armed and has been finished: qpn_decode_final_counts reads its counts (until the next enqueue)
     std::vector<int64_t> live_seen;  // per-row high-water mark of what qpn_decode_poll has reported.  The counts restart only while qpn_decode_finish re-runs a launch that gave up,
                                      // and a handle is not thread-safe: only a caller that polls from a second thread under its own lock around finish could ever see the restart
@@ -59,6 +62,7 @@ struct qpn_handle {      // every member has an initialiser: qpn_create sets onl
         std::vector<int64_t> n_samples; int maxd = 0, mode = 0; uint64_t seed = 0;
         float inv_temp = 1.0f; int top_k = 0;      // the handle's sampling controls at the enqueue: a re-run draws with the same ones
         float top_p = 1.0f, min_p = 0.0f;
+        std::vector<RowDraw> rows;                 // ... and the per-row records in force at the enqueue (empty: none): the re-run draws with the same ones
         const int64_t* d_teacher = nullptr; int64_t* d_out = nullptr; float* d_logits = nullptr;
         DecodePlanIn in = {}; DecodePlan plan = {};   // what was planned from, and what the launches followed
     } call;

@@ -10,6 +10,7 @@ Same batching / chunking semantics as the reference task scripts, but over array
                        that overlap by RF, x[:-1] / x[1:] input-target shift)
   save_checkpoint / load_checkpoint <- src/bin/qpnet_train.py:338-353,481-499,557-563 ({"model","optimizer","iterations"})
 """
+import hashlib
 import logging
 import math
 import os
@@ -19,6 +20,13 @@ import torch
 
 from . import harness
 from .qpnet import encode_mu_law
+
+
+def row_seed(seed, feat_id):
+    """The Philox key of one file under run_decode --per_file_seed: the first eight bytes (little-endian) of SHA-256 of "<seed>:<feat_id>".  It depends
+    on the run's seed and the file's id alone -- not on Python's per-process hash(), the batch, the rank or the rest of the list -- so it is the same
+    in every process and on every machine."""
+    return int.from_bytes(hashlib.sha256(("%d:%s" % (seed, feat_id)).encode("utf-8")).digest()[:8], "little")
 
 
 def decode_generator(feats, fs, feat_ids=None, wav_transform=None, feat_transform=None, dense_factor=8, batch_size=32,

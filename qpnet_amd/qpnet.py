@@ -141,6 +141,7 @@ class QPNet(nn.Module):
         self.sampling_seed = None          # set to an int to pin the sampling-mode random stream
         self._n_generate_calls = 0
         self.last_sampling_seed = None
+        self.last_row_seeds = None         # the Philox key of every row (input order) of the last decode call that drew per row (per-row controls or row_seeds=); None after a uniform call
         self.last_decode_counts, self.last_decode_cancelled = None, False   # generate_live: every row's final count (input order) / whether the call stopped short on request
         self._live_first_piece_s, self._live_mirror_pieces = None, 0      # generate_live (diagnostics): enqueue return -> first piece, pieces of the last call that were read from the mirror while the call was in flight
 
@@ -216,7 +217,7 @@ class QPNet(nn.Module):
 
     # ------------------------------------------------------------------ autoregressive decode
     def batch_fast_generate(self, x, h, n_samples_list, dilated_factors,
-                            intervals=None, mode="sampling", extra_memory=False, *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0):
+                            intervals=None, mode="sampling", extra_memory=False, *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, row_seeds=None):
         """Batch fast generation (reference qpnet.py:314-559).
 
         x (B,T0) long seed, h (B,n_aux,F) float, n_samples_list list[int] (consumed exactly like
@@ -229,8 +230,15 @@ class QPNet(nn.Module):
         (qpn_decode_sampling).  min_p in [0, 1] then keeps the classes whose probability is at least min_p times the most probable class's
         (0 = off), and top_p in (0, 1] the most probable of those whose mass reaches the fraction top_p of the whole, ties with the last one
         kept (1 = off; qpn_decode_sampling_ex): two cuts that follow the width of the distribution where top_k's count
-        is fixed.  The defaults are the reference's draw.  The values hold for this call only."""
-        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature, top_k, top_p, min_p)
+        is fixed.  The defaults are the reference's draw.  The values hold for this call only.
+
+        Per row (qpn_decode_row_sampling): each of the four accepts a sequence of B values instead of a scalar (B >= 2: a batch of one row takes
+        scalars, as it always did, and a sequence there is a ValueError), and row_seeds B integers in [0, 2^64) (any B); both always refer to the
+        INPUT rows, whatever order the results come back in.  With row_seeds, row b draws from the stream
+        (seed = row_seeds[b], stream 0): its samples depend on its own inputs, values and seed only, not on its place in the batch, the batch
+        size or the launch plan.  Without row_seeds but with a per-row control, row b draws from (call seed, stream b), the stream of a uniform
+        call.  All scalars and no row_seeds is the uniform call: same kernels, same bytes.  last_row_seeds records the keys that were used."""
+        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature, top_k, top_p, min_p, row_seeds)
         L, hd, dev, B, ns, max_n, out, stream = a["L"], a["hd"], a["dev"], a["B"], a["ns"], a["max_n"], a["out"], a["stream"]
         t_start = a["t_start"]
         with torch.cuda.device(dev):
@@ -280,19 +288,59 @@ class QPNet(nn.Module):
             raise ValueError("temperature / top_k / top_p / min_p shape the draw of mode='sampling'; mode='argmax' takes none of them")
         return t, int(top_k), cuts[0], cuts[1]
 
-    def _decode_args(self, x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0):
+    def _row_controls(self, mode, B, temperature, top_k, top_p, min_p, row_seeds):
+        """The draw of a decode call, checked on the host before anything touches the device -> (the four uniform values, None) for a uniform call (all
+        scalars, no row_seeds), or ((1.0, 0, 1.0, 0.0), [(seed or None, temperature, top_k, top_p, min_p)] * B in input order) for a per-row call."""
+        vals = tuple(v.tolist() if isinstance(v, torch.Tensor) and v.dim() >= 1 else v for v in (temperature, top_k, top_p, min_p))      # (a 1-D tensor is a sequence like any other)
+        if isinstance(row_seeds, torch.Tensor):
+            row_seeds = row_seeds.tolist()
+        seq = [isinstance(v, (list, tuple, np.ndarray)) and np.ndim(v) >= 1 for v in vals]
+        if not any(seq) and row_seeds is None:
+            return self._sampling_controls(mode, temperature, top_k, top_p, min_p), None
+        if mode == "argmax":
+            raise ValueError("per-row temperature / top_k / top_p / min_p and row_seeds shape the draw of mode='sampling'; mode='argmax' takes none of them")
+        cols = []
+        for name, v, is_seq in zip(("temperature", "top_k", "top_p", "min_p"), vals, seq):
+            if is_seq:
+                if B < 2:       # a batch of one row has no rows to tell apart: its controls stay the scalars they always were, and a list there stays the error it was
+                    raise ValueError("%s must be a number for a batch of one row (a sequence gives one value per row of a batch of two or more), not %r" % (name, v))
+                v = v.tolist() if isinstance(v, np.ndarray) and v.ndim == 1 else list(v)
+                if len(v) != B:
+                    raise ValueError("%s has %d values for a batch of %d rows (one per input row, or a scalar)" % (name, len(v), B))
+                if name == "top_k" and any(isinstance(k, float) for k in v):
+                    raise ValueError("top_k must hold ints, not %r" % (v,))
+            cols.append(v if is_seq else [v] * B)
+        if row_seeds is not None:
+            seeds = row_seeds.tolist() if isinstance(row_seeds, np.ndarray) else list(row_seeds)
+            if len(seeds) != B:
+                raise ValueError("row_seeds has %d values for a batch of %d rows (one per input row)" % (len(seeds), B))
+            for b, sd in enumerate(seeds):
+                if isinstance(sd, bool) or not isinstance(sd, (int, np.integer)) or not 0 <= int(sd) < (1 << 64):
+                    raise ValueError("row %d: row_seeds must hold ints in [0, 2^64), not %r" % (b, sd))
+            seeds = [int(sd) for sd in seeds]
+        else:
+            seeds = [None] * B
+        rows = []
+        for b in range(B):
+            try:
+                rows.append((seeds[b],) + self._sampling_controls(mode, cols[0][b], cols[1][b], cols[2][b], cols[3][b]))
+            except ValueError as e:
+                raise ValueError("row %d: %s" % (b, e)) from None
+        return (1.0, 0, 1.0, 0.0), rows
+
+    def _decode_args(self, x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, row_seeds=None):
         """What batch_fast_generate and generate_live do before the library call: mode check, maxd, dtype and device moves, the
         output buffer, the sampling seed, binding the weights.  -> dict; "call" is the argument tuple of qpn_decode / qpn_decode_enqueue, the rest
         keeps the tensors behind its pointers alive."""
         if mode not in ("sampling", "argmax"):
             logging.error("mode should be sampling or argmax")
             sys.exit(1)
-        temperature, top_k, top_p, min_p = self._sampling_controls(mode, temperature, top_k, top_p, min_p)
+        B = len(n_samples_list)
+        (temperature, top_k, top_p, min_p), rows = self._row_controls(mode, B, temperature, top_k, top_p, min_p, row_seeds)
         import ctypes as C
         dev = x.device
         L, hd = self._native(dev)
         _lib.check(L.qpn_decode_sampling_ex(hd, temperature, top_k, top_p, min_p))      # this call's values, set before every enqueue: nothing is left over from the last call
-        B = len(n_samples_list)
         assert x.shape[0] == B and h.shape[0] == B
         # maxd exactly as the reference computes it (qpnet.py:347-350)
         if extra_memory:
@@ -318,6 +366,15 @@ class QPNet(nn.Module):
         seed = self.sampling_seed if self.sampling_seed is not None else (torch.initial_seed() + self._n_generate_calls) % (1 << 64)
         self._n_generate_calls += 1
         self.last_sampling_seed = seed
+        # ... and this call's per-row records, set or cleared before every enqueue for the same reason.  A row without a seed of its own draws from
+        # (call seed, stream = its input row): the stream of the uniform call
+        if rows is None:
+            _lib.check(L.qpn_decode_row_sampling(hd, 0, None))
+            self.last_row_seeds = None
+        else:
+            rec = (_lib.QpnRowDraw * B)(*[_lib.QpnRowDraw(seed if sd is None else sd, b if sd is None else 0, t, k, tp, mp) for b, (sd, t, k, tp, mp) in enumerate(rows)])
+            _lib.check(L.qpn_decode_row_sampling(hd, B, rec))
+            self.last_row_seeds = [seed if sd is None else sd for sd, _, _, _, _ in rows]
         t_start = time.time()           # (the clock of batch_fast_generate's progress lines starts here, in front of the weight binding)
         arr = (C.c_int64 * B)(*ns)
         call = (hd, B, xd.shape[1], hd_.shape[2], d_dev.shape[1], xd.data_ptr(), hd_.data_ptr(), d_dev.data_ptr(), d_is_f32,
@@ -328,7 +385,7 @@ class QPNet(nn.Module):
 
     # ------------------------------------------------------------------ live decode output
     def generate_live(self, x, h, n_samples_list, dilated_factors, intervals=None, mode="sampling",
-                      extra_memory=False, every=256, poll_s=0.001, on_close="finish", *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0):
+                      extra_memory=False, every=256, poll_s=0.001, on_close="finish", *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, row_seeds=None):
         """batch_fast_generate as a generator that hands samples over while the decode kernel runs: yields (row, start, samples)
         -- row = index in the input order, samples = a fresh int64 ndarray holding that row's samples [start, start + len) --
         as soon as a poll of the library (qpn_decode_poll) shows new finished samples of a row.  A row's pieces are contiguous
@@ -343,19 +400,19 @@ class QPNet(nn.Module):
         (`every` samples of the longest-running row each) plus the drain of the launch.  A generator that is iterated to its end
         never cancels.  After the generator has ended, either way, last_decode_counts holds every row's final count in input
         order (samples below it are valid; n_samples for a call that ran to its end) and last_decode_cancelled whether the call
-        stopped short on request.  temperature / top_k / top_p / min_p: as in batch_fast_generate."""
+        stopped short on request.  temperature / top_k / top_p / min_p / row_seeds: as in batch_fast_generate, per-row sequences included."""
         if on_close not in ("finish", "cancel"):
             raise ValueError("on_close must be 'finish' or 'cancel', not %r" % (on_close,))
         if int(every) < 1:
             raise ValueError("every must be >= 1")
         if mode in ("sampling", "argmax"):
-            self._sampling_controls(mode, temperature, top_k, top_p, min_p)          # (bad values are refused here, at the call, not at the first next())
+            self._row_controls(mode, len(n_samples_list), temperature, top_k, top_p, min_p, row_seeds)          # (bad values are refused here, at the call, not at the first next())
         self._native(x.device)          # (CPU tensors are refused here, at the call, not at the first next())
-        return self._live_pieces(x, h, list(n_samples_list), dilated_factors, intervals, mode, extra_memory, int(every), float(poll_s), on_close == "cancel", temperature, top_k, top_p, min_p)
+        return self._live_pieces(x, h, list(n_samples_list), dilated_factors, intervals, mode, extra_memory, int(every), float(poll_s), on_close == "cancel", temperature, top_k, top_p, min_p, row_seeds)
 
-    def _live_pieces(self, x, h, n_samples_list, dilated_factors, intervals, mode, extra_memory, every, poll_s, cancel_on_close, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0):
+    def _live_pieces(self, x, h, n_samples_list, dilated_factors, intervals, mode, extra_memory, every, poll_s, cancel_on_close, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, row_seeds=None):
         import ctypes as C
-        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature, top_k, top_p, min_p)
+        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature, top_k, top_p, min_p, row_seeds)
         L, hd, dev, B, ns, max_n, out, stream = a["L"], a["hd"], a["dev"], a["B"], a["ns"], a["max_n"], a["out"], a["stream"]
         done = (C.c_int64 * B)()
         mirror, stride, running = C.POINTER(C.c_int32)(), C.c_int64(), C.c_int()

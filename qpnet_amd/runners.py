@@ -501,6 +501,8 @@ def _decode_args():
     p.add_argument("--top_k", default=0, type=int, help="sampling mode: draw among the classes with the top_k largest logits only (ties kept); 0: off")
     p.add_argument("--top_p", default=1.0, type=float, help="sampling mode: draw among the most probable classes whose mass reaches this fraction (ties kept); 1: off")
     p.add_argument("--min_p", default=0.0, type=float, help="sampling mode: draw among the classes at least this fraction as probable as the most probable one; 0: off")
+    p.add_argument("--per_file_seed", action="store_true", help="sampling mode: every file draws from a stream of its own, keyed by --seed and the file's id "
+                   "(loaders.row_seed): its wav does not depend on --batch_size, --n_gpus or the other files of the list; off: the reference-like per-call stream")
     return p
 
 
@@ -534,10 +536,14 @@ def run_decode(argv=None):
                                        feat_transform=scaler, dense_factor=conf.dense_factor, batch_size=args.batch_size,
                                        upsampling_factor=conf.upsampling_factor, f0_factor=args.f0_factor,
                                        f0_dim_index=args.f0_dim_index, extra_memory=args.extra_memory, device=dev)
+        per_file = args.per_file_seed and args.mode == "sampling"      # (argmax draws nothing)
+        if per_file:
+            logging.info("per-file seeds on: every file draws from its own stream (seed %d and its id), whatever its batch." % args.seed)
         for feat_ids, bx, bh, ns, bd in gen:
             logging.info("decoding start!")
+            row_seeds = [loaders.row_seed(args.seed, i) for i in feat_ids] if per_file else None      # (input order: feat_ids lists the batch rows)
             outs = model.batch_fast_generate(bx, bh, ns, bd, intervals=args.intervals, mode=args.mode, extra_memory=args.extra_memory,
-                                             temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, min_p=args.min_p)
+                                             temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, min_p=args.min_p, row_seeds=row_seeds)
             for feat_id, samples in zip(feat_ids, outs):
                 name = args.outdir.replace("feat_id", feat_id)
                 loaders.write_wav(name, args.fs, samples, conf.n_quantize)
