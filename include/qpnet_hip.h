@@ -225,6 +225,20 @@ int qpn_train_backward(qpn_handle* h, const float* d_dlogits, float* d_flatgrad,
  * backward's own status bits too); 2: the trailer leaves with the early exchange bucket (qpn_train_early_bucket) and carries the forward's bits only. */
 int qpn_train_backward_ex(qpn_handle* h, const float* d_dlogits, float* d_flatgrad, float grad_scale, int append_scale, void* stream);
 
+/* Arm (d_dh != NULL) or disarm (NULL) the feature gradient for the NEXT backward enqueued on this handle: qpn_train_backward[_ex], or the one inside
+ * qpn_train_step* / qpn_train_step_acc.  That backward also writes d_dh[B][n_aux][F] = d(sum(dlogits * logits)) / d h of its forward (F as that forward was
+ * given it; for the fused step: d(mean CE of this chunk) / dh, not weighted by grad_scale), every element, exact zeros where no row reaches (the frames in
+ * front of the chunk's receptive field; with upsampling_factor = 0 the leading F - (rows of the chunk) columns).  One shot:
+ * consumed by that backward.  n must equal B * n_aux * F of the forward the backward belongs to, else that backward returns QPN_EINVAL naming n before
+ * it launches anything (and the arm is dropped).  Reads the weights as they are when the backward runs (before the step's Adam launch).
+ * The gradient with respect to the dilated factors is not computed: the pitch tap is a rounding, its derivative is zero almost everywhere (what the
+ * reference's autograd yields too).  Fixed summation order, no atomics of its own; where the layer backward's accumulators it reads are float atomics (the
+ * frame-rate aux path, the pitch-adaptive layers' scatter) the result is reproducible to rounding, not bit for bit.
+ * Arguments are checked before the device is looked at (works on a handle created without a GPU): QPN_EINVAL for a null handle, or n < 1 with a
+ * non-null d_dh; disarming always succeeds.  An armed backward enqueued while its stream is capturing returns QPN_ESTATE (the arm is host state that a
+ * replay would not renew) and drops the arm.  A backward that is not armed launches exactly what it always launched. */
+int qpn_train_input_grad(qpn_handle* h, float* d_dh, int64_t n);
+
 /* Number of qpn_train_forward calls on this handle so far.  The activations backward needs live in the handle's workspace
  * (one outstanding forward per handle): a caller that defers backward (torch autograd) records the value after forward and
  * compares before backward (reference: autograd keeps per-call activations, src/bin/qpnet_train.py:520-530). */

@@ -50,6 +50,7 @@ SYMBOLS = [
     ("qpn_train_forward", _i, [_vp, _vp, _i, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     ("qpn_train_backward", _i, [_vp, _vp, _vp, _vp]),
     ("qpn_train_backward_ex", _i, [_vp, _vp, _vp, C.c_float, _i, _vp]),
+    ("qpn_train_input_grad", _i, [_vp, _vp, _i64]),
     ("qpn_train_generation", _i64, [_vp]),
     ("qpn_train_status", _i, [_vp, _vp]),
     ("qpn_train_status_enqueue", _i, [_vp, _vp]),

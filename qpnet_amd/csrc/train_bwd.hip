@@ -1633,6 +1633,7 @@ int qpn_launch_grad_tail(const TrainParams& p, const TrainBwd& bw, const AuxGeom
         }
         if (p.U > 0 && !up_done && !p.hoist) launch_up_bwd(p, bw, stream);
         if (p.hoist && ag && !up_done) launch_aux_tail(p, bw, *ag, stream);      // (behind the reduction's zeroing: it adds onto the upsampling-bias entry; up_done: it ran on the side stream)
+        if (bw.dh && !up_done) qpn_launch_input_grad(p, bw, ag, stream);          // (armed only -- qpn_train_input_grad; up_done: it ran on the side stream too)
     }
     qpn_prof_mark(PG_GRAD_TAIL, stream);
     QPN_HIP(hipGetLastError());
@@ -1822,7 +1823,11 @@ int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k
         QPN_HIP(hipEventRecord(bw.ev_mid, stream));
         QPN_HIP(hipStreamWaitEvent(side, bw.ev_mid, 0));
         qpn_prof_mark(-1, side);
-        if (up_side) { if (p.hoist) launch_aux_tail(p, bw, ag, side); else launch_up_bwd(p, bw, side); qpn_prof_mark(PG_GRAD_TAIL, side); }      // (behind the early reduction's zeroing, on the same stream)
+        if (up_side) {      // (behind the early reduction's zeroing, on the same stream; the feature gradient, when armed, next to it: it reads what the layer backward left, as they do)
+            if (p.hoist) launch_aux_tail(p, bw, ag, side); else launch_up_bwd(p, bw, side);
+            if (bw.dh) qpn_launch_input_grad(p, bw, &ag, side);
+            qpn_prof_mark(PG_GRAD_TAIL, side);
+        }
         if (wr_side) { ok = ok && wgrad2_any(build_wr(), nch, gen, side); qpn_prof_mark(PG_WGRAD_WR, side); }
     }
     if (overlap) QPN_HIP(hipEventRecord(ev_join, side));

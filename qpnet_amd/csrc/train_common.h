@@ -95,7 +95,9 @@ struct TrainBwd {            // backward-only buffers / maps (see train_bwd.hip)
     const int* status;                // the handle's sticky status word (read for the trailer's flag)
     hipStream_t side; hipEvent_t ev_fork, ev_join, ev_mid;   // side stream of the weight gradients that run under the layer backward (owned by TrainState)
     hipEvent_t ev_early; int* early_recorded;                // recorded on the side stream behind the early reduction when it also wrote the trailer (qpn_train_early_bucket)
+    float* dh;                        // qpn_train_input_grad: [B][A][F] feature gradient of this backward, or nullptr (not armed: nothing extra is launched)
 };
+void qpn_launch_input_grad(const TrainParams& p, const TrainBwd& bw, const AuxGeom* ag, hipStream_t st);      // train_input_grad.hip
 
 
 // the (compact) kernel arguments of k_aux_proj / k_aux_tail (AuxGeom: train_plan.h)

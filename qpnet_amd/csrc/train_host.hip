@@ -600,12 +600,34 @@ extern "C" int qpn_train_backward(qpn_handle* h, const float* d_dlogits, float* 
     return qpn_train_backward_ex(h, d_dlogits, d_flatgrad, 1.0f, 0, stream_);
 }
 
+// The arm is host state on the handle (no device is needed to set it); the next backward takes it -- whatever that backward then returns
+extern "C" int qpn_train_input_grad(qpn_handle* h, float* d_dh, int64_t n) {
+    if (!h) { qpn_set_error("null handle"); return QPN_EINVAL; }
+    if (d_dh && n < 1) { qpn_set_error("qpn_train_input_grad: n must be >= 1 with a destination (got %lld)", (long long)n); h->in_grad = nullptr; h->in_grad_n = 0; return QPN_EINVAL; }
+    h->in_grad = d_dh; h->in_grad_n = d_dh ? n : 0;
+    return QPN_OK;
+}
+
 extern "C" int qpn_train_backward_ex(qpn_handle* h, const float* d_dlogits, float* d_flatgrad, float grad_scale, int append_scale, void* stream_) {
+    float* d_dh = nullptr; int64_t dh_n = 0;
+    if (h) { d_dh = h->in_grad; dh_n = h->in_grad_n; h->in_grad = nullptr; h->in_grad_n = 0; }      // one shot: consumed here, also by a backward that fails below
     int rc = need_dev(h); if (rc) return rc;
     if (!h->train || !h->train->fwd_valid) { qpn_set_error("qpn_train_backward needs a preceding qpn_train_forward"); return QPN_ESTATE; }
     if (!d_dlogits || !d_flatgrad) { qpn_set_error("bad train_backward arguments"); return QPN_EINVAL; }
     TrainState* t = h->train;
     TrainBwd& bw = t->bw;
+    bw.dh = nullptr;
+    if (d_dh) {
+        const int64_t want = (int64_t)t->tp.B * h->g.A * t->tp.F;
+        if (dh_n != want) {
+            qpn_set_error("qpn_train_input_grad: n = %lld, the forward of this backward has B * n_aux * F = %d * %d * %d = %lld", (long long)dh_n, t->tp.B, h->g.A, t->tp.F, (long long)want);
+            return QPN_EINVAL;
+        }
+        hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing((hipStream_t)stream_, &cap_st);
+        if (cap_st != hipStreamCaptureStatusNone) { qpn_set_error("qpn_train_input_grad: an armed backward cannot be captured (the arm is host state a replay would not renew)"); return QPN_ESTATE; }
+        bw.dh = d_dh;
+    }
     bw.dlogits = d_dlogits; bw.gflat = d_flatgrad; bw.gdst = t->d_gdst; bw.gdst_list = t->d_gdst_list; bw.gzero = t->d_gzero; bw.n_gzero = t->n_gzero;
     bw.gscale = grad_scale; bw.append_scale = append_scale; bw.status = h->train->d_status;
     bw.side = t->side; bw.ev_fork = t->ev_fork; bw.ev_join = t->ev_join; bw.ev_mid = t->ev_mid;
@@ -799,7 +821,7 @@ extern "C" int qpn_train_step_clip(qpn_handle* h, float* d_flat, int B, int64_t 
 // step's, out of the same pinned slot as its loss; mode 2: this step's; mode 0: none.  0 where that step did not clip.
 // d_ema / ema_decay: qpn_adam_step_avg's (every loss mode moves the average: it is the Adam launch's own work).
 // d_acc != NULL: micro-step `micro` of a window of micro_count > 1 chunks (qpn_train_step_acc); NULL: the plain step, launch for launch what it always was
-static int train_step_impl(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
+static int train_step_body(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
                            const int64_t* d_x, const float* d_h, const float* d_dfac, const int64_t* d_targets, int64_t tgt_stride,
                            float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
                            int step, float lr, float beta1, float beta2, float eps, float weight_decay,
@@ -868,6 +890,19 @@ static int train_step_impl(qpn_handle* h, float* d_flat, int B, int64_t T, int64
         if (h_grad_norm && t->gnorm_collected_valid) *h_grad_norm = t->gnorm_collected;
     }
     return QPN_OK;
+}
+
+// (a step that fails in front of its backward has no backward to consume an armed feature gradient: the arm is dropped with it)
+static int train_step_impl(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
+                           const int64_t* d_x, const float* d_h, const float* d_dfac, const int64_t* d_targets, int64_t tgt_stride,
+                           float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
+                           int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                           int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm,
+                           float* d_ema, float ema_decay, float* d_acc, int micro, int micro_count, void* stream) {
+    const int rc = train_step_body(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
+                                   step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, max_grad_norm, h_grad_norm, d_ema, ema_decay, d_acc, micro, micro_count, stream);
+    if (rc && h) { h->in_grad = nullptr; h->in_grad_n = 0; }
+    return rc;
 }
 
 extern "C" int qpn_train_step_avg(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,

@@ -211,7 +211,10 @@ class QPNet(nn.Module):
     # ------------------------------------------------------------------ training forward
     def forward(self, x, h, dilated_factors, blength):
         """Teacher-forced forward (reference qpnet.py:239-312): x (B,T) long, h (B,n_aux,F),
-        dilated_factors (B,T) float, blength (B) -> (B, batch_length, n_quantize) logits."""
+        dilated_factors (B,T) float, blength (B) -> (B, batch_length, n_quantize) logits.
+        Differentiable in the parameters and in `h` (h.requires_grad_(): backward fills h.grad as the reference's autograd does, exact zeros in the
+        frames in front of the chunk's receptive field); `dilated_factors` gets no gradient (the pitch tap is a rounding: zero almost everywhere,
+        in the reference too).  There is no input-only backward: with every parameter frozen the whole backward still runs."""
         from . import train   # native training path (autograd.Function over the C ABI)
         return train.qpnet_forward(self, x, h, dilated_factors, blength)
 

@@ -15,6 +15,7 @@ import ctypes as C
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .config import ADAM_FROZEN, ADAM_MAX_GROUPS, adam_group_table
@@ -334,8 +335,17 @@ def _flat_grad_of(params):
     return torch.as_strided(g0, (o,), (1,), g0.storage_offset()) if g0.untyped_storage().nbytes() >= 4 * (g0.storage_offset() + o) else None
 
 
+def _arm_input_grad(L, hd, dh):
+    """the next backward on this handle also writes dL/dh into `dh` (qpn_train_input_grad: one shot); None: nothing to arm"""
+    if dh is not None:
+        _lib.check(L.qpn_train_input_grad(hd, dh.data_ptr(), dh.numel()))
+
+
 class QPNetFunction(torch.autograd.Function):
-    """logits = QPNet.forward(x, h, d, blength); backward = hand-written HIP kernels."""
+    """logits = QPNet.forward(x, h, d, blength); backward = hand-written HIP kernels.
+    Gradients: the parameters, and the auxiliary features `h` when they require one (the same backward writes it: there is no input-only backward -- with every
+    parameter frozen the weight gradients are still computed, into a scratch buffer).  `dilated_factors` gets None: the pitch tap is a rounding of the factor, its
+    derivative is zero almost everywhere -- what the reference's autograd yields there too.  Once differentiable: the backward is not itself recorded."""
 
     @staticmethod
     def forward(ctx, model, x, h, d, BL, maxd, *params):
@@ -364,6 +374,7 @@ class QPNetFunction(torch.autograd.Function):
         return logits
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dlogits):
         model = ctx.model
         dev = dlogits.device
@@ -384,18 +395,21 @@ class QPNetFunction(torch.autograd.Function):
         flat = model._flat
         dl = dlogits.contiguous()
         stream = torch.cuda.current_stream(dev).cuda_stream
+        # the features' gradient (h.requires_grad): a fresh buffer the backward's own launches fill, every element (qpn_train_input_grad)
+        dh = torch.empty_like(ctx.keep[1]) if ctx.needs_input_grad[2] else None
         if ctx.anchored:
-            _anchored_backward(model, L, hd, dl, flat, stream, dev)
-            return (None, None, None, None, None, None, None)
+            _anchored_backward(model, L, hd, dl, flat, stream, dev, dh)
+            return (None, None, dh, None, None, None, None)
         # a FRESH buffer per backward: autograd keeps (or accumulates into) the views it is handed, so they must not
-        # alias memory a later backward writes
+        # alias memory a later backward writes (only the features want a gradient: the buffer is scratch)
         g = torch.empty_like(flat)
         with torch.cuda.device(dev):
+            _arm_input_grad(L, hd, dh)
             _lib.check(L.qpn_train_backward(hd, dl.data_ptr(), g.data_ptr(), stream))
-        return (None, None, None, None, None, None) + tuple(_split_like(model, g))
+        return (None, None, dh, None, None, None) + tuple(v if need else None for v, need in zip(_split_like(model, g), ctx.needs_input_grad[6:]))
 
 
-def _anchored_backward(model, L, hd, dl, flat, stream, dev):
+def _anchored_backward(model, L, hd, dl, flat, stream, dev, dh=None):
     """The reference loop's backward without autograd's 120-way fan-out (qpnet_train.py:527-531: zero_grad, loss.backward(), optimizer.step()).
     The graph holds ONE anchor leaf instead of the 120 parameters, and this function gives every parameter its .grad itself, with
     loss.backward()'s semantics: parameters without a gradient (after optimizer.zero_grad(), whose default sets them to None) get one, the
@@ -417,6 +431,7 @@ def _anchored_backward(model, L, hd, dl, flat, stream, dev):
         fb = _flat_grad_of(params)
         mine = fb is not None and fb.data_ptr() == gflat.data_ptr()
     with torch.cuda.device(dev):
+        _arm_input_grad(L, hd, dh)                         # (consumed by whichever of the two backward calls below runs)
         if none_yet:                                       # the usual step: the kernels write the buffer the .grad views live in
             _lib.check(L.qpn_train_backward(hd, dl.data_ptr(), gflat.data_ptr(), stream))
             for p, v in zip(params, views):
@@ -468,9 +483,9 @@ def qpnet_forward(model, x, h, dilated_factors, blength):
     d = dilated_factors.to(dev, torch.float32).contiguous()
     ensure_flat(model, dev)
     params = model_params(model)
-    # no graph will be recorded (no_grad, or no parameter wants a gradient): no backward will come to collect the status
+    # no graph will be recorded (no_grad, or neither a parameter nor the features want a gradient): no backward will come to collect the status
     wants = [p.requires_grad for p in params]
-    model._qpn_sync_status = not (torch.is_grad_enabled() and any(wants))
+    model._qpn_sync_status = not (torch.is_grad_enabled() and (any(wants) or h.requires_grad))
     if torch.is_grad_enabled() and all(wants) and os.environ.get("QPN_DROPIN_FLAT_GRAD", "1") != "0":
         # every parameter trains (the reference trainer): ONE anchor leaf stands for them in the graph, the backward assigns their gradients (_anchored_backward)
         a = model.__dict__.get("_qpn_anchor")
@@ -502,6 +517,20 @@ def _check_ema_decay(v):
     if not (0.0 < v < 1.0) or not (0.0 < float(np.float32(v)) < 1.0):
         raise ValueError("ema_decay must lie in (0, 1) (None or 0: no averaged weights), got %r" % (v,))
     return v
+
+
+def _check_h_grad(h_grad, h, dev):
+    """FusedTrainer.step's h_grad as the C ABI takes it: float32, shaped like h, contiguous, on the (CUDA) device of the step's inputs."""
+    if not isinstance(h_grad, torch.Tensor):
+        raise ValueError("h_grad must be a torch.Tensor (or None), got %r" % (type(h_grad),))
+    if h_grad.dtype != torch.float32:
+        raise ValueError("h_grad must be float32, got %s" % (h_grad.dtype,))
+    if tuple(h_grad.shape) != tuple(h.shape):
+        raise ValueError("h_grad must be shaped like h %s, got %s" % (tuple(h.shape), tuple(h_grad.shape)))
+    if not h_grad.is_contiguous():
+        raise ValueError("h_grad must be contiguous")
+    if not h_grad.is_cuda or h_grad.device != dev:
+        raise ValueError("h_grad must be a CUDA tensor on the device of the step's inputs (%s), got %s" % (dev, h_grad.device))
 
 
 def _check_accum_steps(v):
@@ -972,10 +1001,30 @@ class FusedTrainer:
     def _norm(t, dtype, dev):
         return t if (t.dtype == dtype and t.device == dev and t.is_contiguous()) else t.to(dev, dtype).contiguous()
 
-    def step(self, x, h, t, d, blength, want_loss=True, maxd=None):
+    def step(self, x, h, t, d, blength, want_loss=True, maxd=None, h_grad=None):
         """One optimisation step.  maxd = ceil(max(d)) of the chunk; a loader that built d on the host (the reference's
         train_generator does, qpnet_train.py:268-272) passes it in, otherwise it is read back from the device (one sync).
-        Inputs are normalised like QPNet.forward does (int64 samples/targets, float32 features/factors, contiguous)."""
+        Inputs are normalised like QPNet.forward does (int64 samples/targets, float32 features/factors, contiguous).
+        h_grad: an optional float32 CUDA tensor shaped like `h`, contiguous, on the inputs' device (anything else: ValueError before any device work).  The step's
+        backward fills it, stream-ordered, with d(mean CE of THIS chunk) / dh at the weights the forward saw (the Adam launch comes behind it), every element, exact
+        zeros in the frames no row of the chunk reaches.  With accum_steps > 1 every micro-step takes its own; with world_size > 1 it is the local chunk's gradient,
+        nothing is exchanged; the row-count weighting of either never enters it.  A step that is being captured raises with it; after a step whose status word
+        is set its contents are unspecified."""
+        if h_grad is None:
+            return self._step(x, h, t, d, blength, want_loss, maxd)
+        _check_h_grad(h_grad, h, x.device)
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("qpnet_amd.FusedTrainer.step(h_grad=...): a step cannot be captured into a graph with a feature gradient (the request is host "
+                               "state a replay would not renew)")
+        dev = x.device
+        L, hd = self.model._native(dev)
+        _arm_input_grad(L, hd, h_grad)
+        try:
+            return self._step(x, h, t, d, blength, want_loss, maxd)
+        finally:
+            L.qpn_train_input_grad(hd, None, 0)          # (consumed by the step's backward; a step that raised in front of it must not leave the request behind)
+
+    def _step(self, x, h, t, d, blength, want_loss, maxd):
         model = self.model
         dev = x.device
         if dev.type != "cuda":
