@@ -477,6 +477,20 @@ int qpn_sample_logits(const float* d_logits, int64_t n_rows, int Q, uint64_t see
 int qpn_sample_logits_ex(const float* d_logits, int64_t n_rows, int Q, uint64_t seed, int row, int64_t step0, float temperature, int top_k,
                          float top_p, float min_p, int64_t* d_out, void* stream);
 
+/* Teacher-forced scoring of logits the caller provides (the per-sample view of what reference src/bin/qpnet_validate.py:409-437 averages into one
+ * float per checkpoint): for every row of the (B x BL x Q) fp32 tensor d_logits and its target -- the LAST BL columns of the (B x tgt_stride) int64
+ * tensor d_targets, as in qpn_ce_loss -- one 16-byte record in d_out[B * BL]:
+ *   nll      lse - l[t] in nats, in the per-row arithmetic of qpn_ce_loss for that Q: the float64 sum of a chunk's nll over its row count IS that loss
+ *   entropy  -sum p log p in nats, a class with p == 0 contributing 0 (finite for rows that hold -inf logits)
+ *   argmax   the lowest index among the maxima (the decode kernels' rule)
+ *   rank     #{q : l[q] > l[t]}, strict, on the raw floats: top-k accuracy is rank < k
+ * A target outside [0, Q) gives nll = +inf and rank = Q (argmax and entropy stay valid): there is no handle, hence no status word.  A row with a NaN
+ * logit, or with every logit -inf, is unspecified.  One wave per row; a row of Q <= 1024 is read from memory once.  Arguments are checked before a
+ * device is looked for: QPN_EINVAL, naming the argument, for a NULL pointer, B < 1, BL < 1, Q outside 1..65536, tgt_stride < BL, B * BL >= 2^31.
+ * For scoring teacher-forced logits (qpn_train_forward, the logits output of qpn_decode).  Asynchronous on `stream`. */
+typedef struct { float nll; float entropy; int32_t argmax; int32_t rank; } qpn_score_row;
+int qpn_score_logits(const float* d_logits, const int64_t* d_targets, int64_t tgt_stride, int B, int BL, int Q, qpn_score_row* d_out, void* stream);
+
 int qpn_dilated_index_train(const float* d_d, int B, int64_t L, int dilation, int64_t* d_out, void* stream);
 int qpn_dilated_index_gen_f32(const float* d_d, int64_t n, int dilation, int64_t* d_out, void* stream);
 int qpn_dilated_index_gen_f64(const double* d_d, int64_t n, int dilation, int32_t* d_out, void* stream);

@@ -91,6 +91,7 @@ SYMBOLS = [
     ("qpn_train_profile_end", _i, [_vp, C.POINTER(C.c_float), _i, _vp]),
     ("qpn_sample_logits", _i, [_vp, _i64, _i, _u64, _i, _i64, C.c_float, _i, _vp, _vp]),
     ("qpn_sample_logits_ex", _i, [_vp, _i64, _i, _u64, _i, _i64, C.c_float, _i, C.c_float, C.c_float, _vp, _vp]),
+    ("qpn_score_logits", _i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
     ("qpn_dilated_index_train", _i, [_vp, _i, _i64, _i, _vp, _vp]),
     ("qpn_dilated_index_gen_f32", _i, [_vp, _i64, _i, _vp, _vp]),
     ("qpn_dilated_index_gen_f64", _i, [_vp, _i64, _i, _vp, _vp]),

@@ -301,6 +301,36 @@ def train_generator(utterances, model_receptiveCausal, model_receptiveF, model_r
         epoch += 1
 
 
+def score_chunks(n_frames, rf, batch_length, max_length, U):
+    """The chunk walk of per-file scoring (run_validate --per_utterance) over ONE utterance of n_frames frames (n_frames * U samples after
+    harness.validate_length) whose receptive field is rf -> [(frame0, frames, bl, keep)].
+
+    The targets scored are sample positions rf + 1 .. E, E = (n_frames - 1) * U: the first rf samples are context only (as at the head of the training
+    stream), and the last frame is not scored (a chunk carries one sample past its inputs).  A chunk starts at the frame-aligned sample a = frame0 * U,
+    has T = frames * U inputs and F = frames feature rows, and the library scores its last bl = T - rf targets -- the geometry the training generator
+    has always cut (T - bl == rf, T <= max_length).  The walk keeps `prev`, the last position already scored (rf at first): the next chunk starts at the
+    frame that holds sample prev - rf and ends at the largest frame boundary `end` <= E with end - prev <= batch_length and end - a <= max_length; of
+    its bl rows the LAST keep = end - prev are new, the at most U - 1 rows in front of them were scored by the chunk before (or are context).
+    Empty when E <= rf (nothing to score).  ValueError when no chunk can make progress: max_length < rf + 2 U, or batch_length < U."""
+    n_frames, rf, batch_length, max_length, U = int(n_frames), int(rf), int(batch_length), int(max_length), int(U)
+    if U < 1 or rf < 0:
+        raise ValueError("score_chunks: U >= 1 and rf >= 0 expected (got U = %d, rf = %d)" % (U, rf))
+    if max_length < rf + 2 * U:
+        raise ValueError("score_chunks: max_length = %d is below rf + 2 U = %d: a chunk that starts on a frame could score nothing new" % (max_length, rf + 2 * U))
+    if batch_length < U:
+        raise ValueError("score_chunks: batch_length = %d is below U = %d: no frame boundary within a chunk's reach" % (batch_length, U))
+    E = (n_frames - 1) * U
+    out = []
+    prev = rf
+    while prev < E:
+        a = ((prev - rf) // U) * U
+        end = (min(E, prev + batch_length, a + max_length) // U) * U
+        assert end > prev and end - a >= rf + 1
+        out.append((a // U, (end - a) // U, end - a - rf, end - prev))
+        prev = end
+    return out
+
+
 def mu_law_transform(n_quantize=256):
     """wav_transform of the reference scripts: encode_mu_law(x, n_quantize)."""
     return lambda x: encode_mu_law(x, n_quantize)

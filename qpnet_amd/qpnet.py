@@ -218,6 +218,19 @@ class QPNet(nn.Module):
         from . import train   # native training path (autograd.Function over the C ABI)
         return train.qpnet_forward(self, x, h, dilated_factors, blength)
 
+    def score(self, x, h, dilated_factors, blength, targets):
+        """Teacher-forced scoring: forward(x, h, dilated_factors, blength) without a graph, then one record per sample of the chunk's last `blength`
+        targets (targets (B, >= blength) long, its last columns used as the loss uses batch_t) -> train.Score(nll, entropy, argmax, rank), each
+        (B, blength).  For audio the model generated itself this is its log likelihood; see train.score_logits for the records."""
+        from . import train
+        for name, v in (("x", x), ("h", h), ("dilated_factors", dilated_factors), ("targets", targets)):
+            if v.device.type != "cuda":
+                raise RuntimeError("qpnet_amd.QPNet runs on an AMD GPU only (%s is on %s); there is no CPU fallback" % (name, v.device))
+        with torch.no_grad():
+            logits = self.forward(x, h, dilated_factors, blength)
+            train.join_staged(targets, x.device)
+            return train.score_logits(logits, targets)
+
     # ------------------------------------------------------------------ autoregressive decode
     def batch_fast_generate(self, x, h, n_samples_list, dilated_factors,
                             intervals=None, mode="sampling", extra_memory=False, *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, row_seeds=None):

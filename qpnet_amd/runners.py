@@ -12,7 +12,7 @@ communication.
 
     python -m qpnet_amd.run_train    --waveforms .. --feats .. --stats .. --expdir .. --config .. [--n_gpus N]
     python -m qpnet_amd.run_update   ... --pretrain checkpoint-final.pkl
-    python -m qpnet_amd.run_validate ... --checkpoint .. --resultdir ..
+    python -m qpnet_amd.run_validate ... --checkpoint .. --resultdir .. [--per_utterance]
     python -m qpnet_amd.run_decode   --feats .. --stats .. --config .. --checkpoint .. --outdir out/feat_id.wav
 
 With --n_gpus N > 1 and no torchrun environment the entry point re-launches itself as N ranks (before any GPU call).
@@ -439,7 +439,59 @@ def _validate_args():
     p.add_argument("--n_gpus", default=1, type=int)
     p.add_argument("--verbose", default=1, type=int)
     p.add_argument("--ema", action="store_true", help="score the checkpoint's averaged weights (a run with --ema_decay wrote them)")
+    p.add_argument("--per_utterance", action="store_true", help="after the pass above, score every file of the list on its own (batch size 1) and write per-file "
+                   "nll / bits / top-1 / top-5 / entropy to <resultdir>/validation_utterances.yml")
     return p
+
+
+def _score_entry(n, nll, ent, top1, top5):
+    """one record of validation_utterances.yml from the sums over n samples"""
+    return {"samples": int(n), "nll": float(nll / n), "bits": float(nll / n / np.log(2.0)), "top1": float(top1 / n), "top5": float(top5 / n),
+            "entropy": float(ent / n)}
+
+
+def score_utterances(args, conf, model, trainer, dev):
+    """run_validate --per_utterance: every file of the list teacher-forced on its own, chunk by chunk (loaders.score_chunks; inputs made as the training
+    generator makes them), through FusedTrainer.score -> {"total": entry, "utterances": {file id: entry}, "skipped": [file ids]}.  Of a file of n_frames
+    frames the samples rf + 1 .. (n_frames - 1) U are scored, rf the receptive field under the file's own largest dilated factor; a file too short to
+    have one is skipped.  The sums are float64 on the device: one read-back per file."""
+    wavs, feats = loaders.file_lists(args.waveforms, args.feats, conf.feature_format)
+    scaler = loaders.read_scaler_stats(args.stats, conf.feature_type)
+    wav_transform = loaders.mu_law_transform(conf.n_quantize)
+    U = int(conf.upsampling_factor)
+    from . import harness
+    utts, skipped, tot = {}, [], np.zeros(5)
+    for wav, feat in zip(wavs, feats):
+        fid = os.path.splitext(os.path.basename(wav))[0]
+        fs, x = loaders.read_wav(wav)
+        x, h = harness.validate_length(x, np.asarray(loaders.read_features(feat, conf.feature_type)), U)
+        chunks = []
+        if h.shape[0] > 0:
+            d = harness.dilated_factor(harness.batch_f0(h, args.f0_threshold), fs, conf.dense_factor)
+            rf = harness.receptive_field(model.receptiveCausal_field, model.receptiveF_field, model.receptiveA_field, d)
+            chunks = loaders.score_chunks(h.shape[0], rf, args.batch_length, args.max_length, U)
+        if not chunks:
+            logging.warning("%s: too short to score (%d frames), skipped." % (fid, h.shape[0]))
+            skipped.append(fid)
+            continue
+        xq = torch.from_numpy(np.asarray(wav_transform(x))).long()
+        hs = torch.from_numpy(np.asarray(scaler(h))).float()
+        acc = torch.zeros(5, dtype=torch.float64, device=dev)
+        for frame0, frames, bl, keep in chunks:
+            a, T = frame0 * U, frames * U
+            dc = np.repeat(d[frame0:frame0 + frames], U)
+            s = trainer.score(xq[a:a + T][None].to(dev), hs[frame0:frame0 + frames].transpose(0, 1)[None].to(dev), xq[a + 1:a + T + 1][None].to(dev),
+                              torch.from_numpy(dc).float()[None].to(dev), [bl], maxd=int(np.ceil(float(dc.max()))))
+            tg = xq[a + T + 1 - keep:a + T + 1].to(dev)
+            acc += torch.stack([s.nll[0, -keep:].double().sum(), s.entropy[0, -keep:].double().sum(), (s.argmax[0, -keep:] == tg).sum().double(),
+                                (s.rank[0, -keep:] < 5).sum().double(), torch.tensor(float(keep), dtype=torch.float64, device=dev)])
+        nll, ent, top1, top5, n = acc.tolist()
+        if not np.isfinite(nll):
+            raise ValueError("%s: a target sample lies outside [0, n_quantize = %d) (its nll is %r)" % (fid, conf.n_quantize, nll))
+        utts[fid] = _score_entry(n, nll, ent, top1, top5)
+        tot += (nll, ent, top1, top5, n)
+        logging.info("%s: %d samples, nll = %.6f, top1 = %.4f" % (fid, n, utts[fid]["nll"], utts[fid]["top1"]))
+    return {"total": _score_entry(tot[4], tot[0], tot[1], tot[2], tot[3]) if tot[4] > 0 else {"samples": 0}, "utterances": utts, "skipped": skipped}
 
 
 def run_validate(argv=None):
@@ -478,6 +530,15 @@ def run_validate(argv=None):
     os.makedirs(args.resultdir, exist_ok=True)
     with open(flossyml, "w", encoding="utf-8") as yf:
         yaml.safe_dump(results, yf)
+    if args.per_utterance:
+        futtyml = os.path.join(args.resultdir, "validation_utterances.yml")
+        per_file = {}
+        if os.path.exists(futtyml):
+            with open(futtyml, encoding="utf-8") as yf:
+                per_file = yaml.safe_load(yf) or {}
+        per_file[str(os.path.basename(args.checkpoint))] = score_utterances(args, conf, model, trainer, dev)
+        with open(futtyml, "w", encoding="utf-8") as yf:
+            yaml.safe_dump(per_file, yf)
     return 0
 
 

@@ -496,6 +496,31 @@ def qpnet_forward(model, x, h, dilated_factors, blength):
     return QPNetFunction.apply(model, x, h, d, BL, maxd, *params)
 
 
+Score = collections.namedtuple("Score", "nll entropy argmax rank")
+Score.__doc__ = """Per-sample records of score_logits, each (B, BL): nll (float32, nats; +inf where the target is outside [0, n_quantize)), entropy (float32, nats),
+argmax (int32, the lowest index among the maxima), rank (int32, the number of classes whose logit is strictly above the target's; n_quantize for a
+target out of range).  top-k accuracy is (rank < k); nll.double().mean() is the cross entropy the library reports for the same rows."""
+
+
+def score_logits(logits, targets):
+    """Teacher-forced scoring of given logits (qpn_score_logits): logits (B, BL, Q) float32 on the GPU, targets (B, >= BL) int64 whose LAST BL columns are
+    scored (batch_t[:, -batch_length:], as the loss takes them) -> Score.  The four tensors are views of one (B, BL) buffer of 16-byte records.  Runs on
+    the current stream and does not synchronise; nothing here is differentiable."""
+    dev = logits.device
+    if dev.type != "cuda" or targets.device.type != "cuda":
+        raise RuntimeError("qpnet_amd.score_logits runs on an AMD GPU only (tensors are on %s / %s); there is no CPU fallback" % (dev, targets.device))
+    if logits.dim() != 3 or targets.dim() != 2 or targets.shape[0] != logits.shape[0]:
+        raise ValueError("score_logits: logits (B, BL, Q) and targets (B, >= BL) expected, got %s and %s" % (tuple(logits.shape), tuple(targets.shape)))
+    lg = logits.detach().to(dev, torch.float32).contiguous()
+    tg = targets.to(dev, torch.int64).contiguous()
+    B, BL, Q = lg.shape
+    rec = torch.empty((B, BL, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().qpn_score_logits(lg.data_ptr(), tg.data_ptr(), tg.shape[1], B, BL, Q, rec.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    ints = rec.view(torch.int32)
+    return Score(rec[..., 0], rec[..., 1], ints[..., 2], ints[..., 3])
+
+
 def _check_max_grad_norm(v):
     """max_grad_norm as the C ABI takes it: None / 0 -> 0.0 (clipping off); a negative or non-finite value raises."""
     if v is None:
@@ -1312,6 +1337,36 @@ class FusedTrainer:
             _lib.check(L.qpn_train_loss(hd, C.byref(loss), stream))
             _lib.check(L.qpn_train_status(hd, stream))
         return loss.value
+
+    def score(self, x, h, t, d, blength, maxd=None, weights="model"):
+        """forward + per-sample records of the chunk's last `blength` targets (score_logits): arguments and checks of forward_loss, -> Score of (B, BL)
+        tensors.  A target outside [0, n_quantize) is not an error here: its record says nll = +inf, rank = n_quantize."""
+        if weights not in ("model", "ema"):
+            raise ValueError('score: weights must be "model" or "ema", got %r' % (weights,))
+        if weights == "ema" and self.ema_decay <= 0.0:
+            raise RuntimeError('score(weights="ema"): this trainer keeps no averaged weights (ema_decay is off)')
+        model = self.model
+        dev = x.device
+        L, hd = model._native(dev)
+        flat = ensure_flat(model, dev)
+        if weights == "ema":
+            self.ema = _ema_home(self.ema, flat)
+            flat = self.ema
+        join_staged(x, dev, h, t, d)
+        x = self._norm(x, torch.int64, dev); t = self._norm(t, torch.int64, dev)
+        h = self._norm(h, torch.float32, dev); d = self._norm(d, torch.float32, dev)
+        BL = int(blength[0])
+        if maxd is None:
+            maxd = int(torch.max(d.ceil()))
+        B, T = x.shape
+        logits = torch.empty((B, BL, model.n_quantize), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            _lib.check(L.qpn_train_forward(hd, flat.data_ptr(), B, T, h.shape[2], d.shape[1], BL, maxd,
+                                           x.data_ptr(), h.data_ptr(), d.data_ptr(), logits.data_ptr(), stream))
+            s = score_logits(logits, t)
+            _lib.check(L.qpn_train_status(hd, stream))
+        return s
 
     # ---- optimizer-state interface (checkpoints: loaders.save_checkpoint(dir, model, trainer, it))
     def _hyper(self):
