@@ -272,6 +272,33 @@ int qpn_train_status_poll(qpn_handle* h, int* pending);
 int qpn_ce_loss(qpn_handle* h, const float* d_logits, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
                 float* d_dlogits, double* h_loss, void* stream);
 
+/* Knowledge distillation (Hinton-style soft targets; DESIGN.md section 5, "Soft-target loss"): the counterpart of qpn_ce_loss for logits the caller
+ * provides.  Per row, with z = d_logits, t = d_teacher (both B x BL x n_quantize fp32), y the hard target (d_targets / tgt_stride as in qpn_ce_loss):
+ *   L_row = (1 - alpha) CE(z, y) + alpha T^2 KL(softmax(t / T) || softmax(z / T))
+ *   dL/dz = (1 - alpha) (softmax(z) - onehot(y)) + alpha T (softmax(z / T) - softmax(t / T))
+ * The loss is the mean of L_row over the B * BL rows and d_dlogits (optional) receives dL/dz over the row count, as qpn_ce_loss does; the CE term is that
+ * call's arithmetic, target rule included (out of range: clamped and flagged).  One kernel (k_ce_distill), fixed reduction order:
+ * d_dlogits is the same bits from run to run.  h_loss3 (optional, host; synchronises) receives {the loss, the hard CE mean, the T^2 KL mean}; without it the
+ * loss stays on the device for qpn_train_loss / qpn_train_loss_enqueue.  A NaN or an infinity in a row of d_teacher sets bit 5 (1 << 5) of the training status word:
+ * the next status report returns QPN_ERANGE ("... teacher logits ..."), an Adam launch that finds the word set skips its update as for every other bit.
+ * Arguments are checked before the device is looked at (works on a handle created without a GPU), QPN_EINVAL naming the argument: a null handle or pointer,
+ * B < 1, BL < 1, tgt_stride < BL, alpha outside (0, 1] or NaN, temperature <= 0, NaN or infinite; with n_quantize a multiple of 256 the three float
+ * buffers must be 16-byte aligned. */
+int qpn_distill_loss(qpn_handle* h, const float* d_logits, const float* d_teacher, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
+                     float alpha, float temperature, float* d_dlogits, double* h_loss3, void* stream);
+
+/* Arm (d_teacher != NULL) or disarm (NULL) the soft-target loss above for the NEXT forward-with-loss enqueued on this handle: qpn_train_forward_loss, or the
+ * one inside qpn_train_step / _clip / _avg / _acc.  That forward computes qpn_distill_loss(its logits, d_teacher, its targets, alpha, temperature) in the place
+ * of the cross entropy: its loss (qpn_train_loss, the step's h_loss) is the distillation total and its d_dlogits that loss's gradient, which the backward
+ * then takes as ever.  One shot: consumed by that forward; a plain qpn_train_forward computes no loss and leaves the arm alone.  An armed forward takes the
+ * route QPN_CE_SEPARATE=1 selects -- the forward writes the logits, k_ce_distill runs in k_ce's place, the backward computes the post-net itself -- on every
+ * training path; d_teacher is read when that kernel runs.  n must equal B * BL * n_quantize of that forward, else it returns QPN_EINVAL naming n before it
+ * launches anything (and the arm is dropped); an armed forward enqueued while its stream is capturing returns QPN_ESTATE (the arm is host state that a
+ * replay would not renew) and drops the arm.  Arguments are checked before the device is looked at (works on a handle created without a GPU), QPN_EINVAL
+ * naming the argument: a null handle, n < 1 with a non-null d_teacher, alpha outside (0, 1] or NaN, temperature <= 0, NaN or infinite, a d_teacher that is
+ * not 16-byte aligned; disarming always succeeds.  A forward that is not armed launches exactly what it always launched. */
+int qpn_train_distill(qpn_handle* h, const float* d_teacher, int64_t n, float alpha, float temperature);
+
 /* Forward + loss in one call: qpn_train_forward followed by qpn_ce_loss (reference src/bin/qpnet_train.py:520-528:
  * `batch_output = model(...)`, `criterion(batch_output[i], batch_t[i])`), with the cross entropy and its gradient computed
  * inside the post-net kernel while a tile's logits are still in LDS (paper-size stacks; wider ones run the separate kernel

@@ -62,6 +62,8 @@ SYMBOLS = [
     ("qpn_train_loss_enqueue", _i, [_vp, _vp]),
     ("qpn_train_loss_collect", _i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     ("qpn_ce_loss", _i, [_vp, _vp, _vp, _i64, _i, _i, _vp, C.POINTER(C.c_double), _vp]),
+    ("qpn_distill_loss", _i, [_vp, _vp, _vp, _vp, _i64, _i, _i, C.c_float, C.c_float, _vp, C.POINTER(C.c_double), _vp]),
+    ("qpn_train_distill", _i, [_vp, _vp, _i64, C.c_float, C.c_float]),
     ("qpn_adam_step", _i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp]),
     ("qpn_adam_step_ex", _i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]),
     ("qpn_train_step", _i, [_vp, _vp, _i, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64,

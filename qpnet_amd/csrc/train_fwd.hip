@@ -844,6 +844,132 @@ __global__ __launch_bounds__(256) void k_ce(const float* __restrict__ logits, co
     if (threadIdx.x == 0) atomicAdd(loss + (blockIdx.x & 63), (part[0] + part[1] + part[2] + part[3]) / (double)rows);
 }
 
+// knowledge distillation ("Soft-target loss"): per row  L = (1 - alpha) CE(z, y) + alpha T^2 KL(softmax(t / T) || softmax(z / T))  and
+//   dL/dz = (1 - alpha) (softmax(z) - onehot(y)) + alpha T (softmax(z / T) - softmax(t / T)),  both over the row count, z = logits, t = teacher.
+// k_ce's layout (one wave per row, rpw rows per wave, 16 rows per workgroup, the 64 double loss slots) and, for the CE term, k_ce's arithmetic operation for
+// operation; the wave reductions are tr_wave_max / tr_wave_sum in k_ce's order, so dL/dlogits is the same bits from run to run.
+//   NV > 0: Q == 256 NV.  The lane's 4 NV student and 4 NV teacher values of a row are loaded with 16-byte loads, ALL in flight before the first reduction,
+//           and stay in registers with their tempered exponentials: a row is read once (2 x 1 KB at Q = 256), nothing lives in scratch.
+//   NV == 0: any Q, k_ce's loops -- four classes per lane and pass when Q % 256 == 0, one otherwise -- over rows that are L2-hot after the first pass.
+// KL is formed from log-probabilities ((t_i - m_t) / T - log S_t minus the student's counterpart): a teacher bitwise equal to the student gives exact zeros.
+// A NaN or an infinity in a row's teacher logits sets status bit 5 (the Adam launch of the step skips: the sticky-status rule); that row's outputs are unspecified.
+// comp (may be nullptr): 2 x 64 more slots -- the hard CE mean, then the KL mean BEFORE its factor T^2 -- for qpn_distill_loss's h_loss3.
+__device__ __forceinline__ bool dk_bad(float v) { return !(fabsf(v) <= 3.402823466e+38f); }      // NaN or +-inf
+template <int NV>
+__global__ __launch_bounds__(256) void k_ce_distill(const float* __restrict__ logits, const float* __restrict__ teacher, const int64_t* __restrict__ tgt, int64_t tgt_stride,
+                                                    int BL, int Q, int64_t rows, float alpha, float temp, float* __restrict__ dlogits, double* __restrict__ loss,
+                                                    double* __restrict__ comp, int rpw, int* __restrict__ status) {
+    __shared__ double part[2][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float inv = 1.0f / (float)rows, invT = 1.0f / temp, oma = 1.0f - alpha, aT = alpha * temp;
+    double csum = 0.0, ksum = 0.0;
+    for (int it = 0; it < rpw; ++it) {
+        const int64_t row = ((int64_t)blockIdx.x * rpw + it) * 4 + wave;
+        if (row >= rows) break;
+        const float* lg = logits + (size_t)row * Q;
+        const float* tl = teacher + (size_t)row * Q;
+        const int64_t b = row / BL, t = row - b * BL;
+        int64_t tg = tgt[(size_t)b * tgt_stride + (tgt_stride - BL) + t];
+        float ce, kl;
+        bool bad = false;
+        if constexpr (NV > 0) {
+            float4 z[NV], u[NV];
+#pragma unroll
+            for (int k = 0; k < NV; ++k) { z[k] = *(const float4*)(lg + lane * 4 + 256 * k); u[k] = *(const float4*)(tl + lane * 4 + 256 * k); }
+            if (tg < 0 || tg >= Q) { if (lane == 0) atomicOr(status, 2); tg = tg < 0 ? 0 : Q - 1; }
+            const float ztg = lg[tg];
+            float mz = -INFINITY, mt = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+                mz = fmaxf(fmaxf(mz, fmaxf(z[k].x, z[k].y)), fmaxf(z[k].z, z[k].w));
+                mt = fmaxf(fmaxf(mt, fmaxf(u[k].x, u[k].y)), fmaxf(u[k].z, u[k].w));
+                bad = bad || dk_bad(u[k].x) || dk_bad(u[k].y) || dk_bad(u[k].z) || dk_bad(u[k].w);
+            }
+            mz = tr_wave_max(mz); mt = tr_wave_max(mt);
+            float se = 0.f, sz = 0.f, st = 0.f;
+            float4 ez[NV], eu[NV];
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+                se += (__expf(z[k].x - mz) + __expf(z[k].y - mz)) + (__expf(z[k].z - mz) + __expf(z[k].w - mz));
+                ez[k] = make_float4(__expf((z[k].x - mz) * invT), __expf((z[k].y - mz) * invT), __expf((z[k].z - mz) * invT), __expf((z[k].w - mz) * invT));
+                eu[k] = make_float4(__expf((u[k].x - mt) * invT), __expf((u[k].y - mt) * invT), __expf((u[k].z - mt) * invT), __expf((u[k].w - mt) * invT));
+                sz += (ez[k].x + ez[k].y) + (ez[k].z + ez[k].w);
+                st += (eu[k].x + eu[k].y) + (eu[k].z + eu[k].w);
+            }
+            se = tr_wave_sum(se); sz = tr_wave_sum(sz); st = tr_wave_sum(st);
+            const float lse = logf(se) + mz, lsz = logf(sz), lst = logf(st), rz = 1.0f / sz, rt = 1.0f / st;
+            float kq = 0.f;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+                const float4 pz = make_float4(ez[k].x * rz, ez[k].y * rz, ez[k].z * rz, ez[k].w * rz);
+                const float4 pt = make_float4(eu[k].x * rt, eu[k].y * rt, eu[k].z * rt, eu[k].w * rt);
+                kq += (pt.x * (((u[k].x - mt) * invT - lst) - ((z[k].x - mz) * invT - lsz)) + pt.y * (((u[k].y - mt) * invT - lst) - ((z[k].y - mz) * invT - lsz))) +
+                      (pt.z * (((u[k].z - mt) * invT - lst) - ((z[k].z - mz) * invT - lsz)) + pt.w * (((u[k].w - mt) * invT - lst) - ((z[k].w - mz) * invT - lsz)));
+                if (dlogits) {
+                    const int q = lane * 4 + 256 * k;
+                    float4 g = make_float4(__expf(z[k].x - lse), __expf(z[k].y - lse), __expf(z[k].z - lse), __expf(z[k].w - lse));
+                    const int dq = (int)tg - q;
+                    if (dq == 0) g.x -= 1.0f; else if (dq == 1) g.y -= 1.0f; else if (dq == 2) g.z -= 1.0f; else if (dq == 3) g.w -= 1.0f;
+                    *(float4*)(dlogits + (size_t)row * Q + q) = make_float4((oma * g.x + aT * (pz.x - pt.x)) * inv, (oma * g.y + aT * (pz.y - pt.y)) * inv,
+                                                                            (oma * g.z + aT * (pz.z - pt.z)) * inv, (oma * g.w + aT * (pz.w - pt.w)) * inv);
+                }
+            }
+            kl = tr_wave_sum(kq);
+            ce = lse - ztg;
+        } else {
+            if (tg < 0 || tg >= Q) { if (lane == 0) atomicOr(status, 2); tg = tg < 0 ? 0 : Q - 1; }
+            const bool vec = (Q & 255) == 0;
+            float mz = -INFINITY, mt = -INFINITY;
+            if (vec) for (int q = lane * 4; q < Q; q += 256) {
+                const float4 v = *(const float4*)(lg + q), w = *(const float4*)(tl + q);
+                mz = fmaxf(fmaxf(mz, fmaxf(v.x, v.y)), fmaxf(v.z, v.w)); mt = fmaxf(fmaxf(mt, fmaxf(w.x, w.y)), fmaxf(w.z, w.w));
+                bad = bad || dk_bad(w.x) || dk_bad(w.y) || dk_bad(w.z) || dk_bad(w.w);
+            } else for (int q = lane; q < Q; q += 64) { const float w = tl[q]; mz = fmaxf(mz, lg[q]); mt = fmaxf(mt, w); bad = bad || dk_bad(w); }
+            mz = tr_wave_max(mz); mt = tr_wave_max(mt);
+            float se = 0.f, sz = 0.f, st = 0.f;
+            if (vec) for (int q = lane * 4; q < Q; q += 256) {
+                const float4 v = *(const float4*)(lg + q), w = *(const float4*)(tl + q);
+                se += (__expf(v.x - mz) + __expf(v.y - mz)) + (__expf(v.z - mz) + __expf(v.w - mz));
+                sz += (__expf((v.x - mz) * invT) + __expf((v.y - mz) * invT)) + (__expf((v.z - mz) * invT) + __expf((v.w - mz) * invT));
+                st += (__expf((w.x - mt) * invT) + __expf((w.y - mt) * invT)) + (__expf((w.z - mt) * invT) + __expf((w.w - mt) * invT));
+            } else for (int q = lane; q < Q; q += 64) { se += expf(lg[q] - mz); sz += expf((lg[q] - mz) * invT); st += expf((tl[q] - mt) * invT); }
+            se = tr_wave_sum(se); sz = tr_wave_sum(sz); st = tr_wave_sum(st);
+            const float lse = logf(se) + mz, lsz = logf(sz), lst = logf(st), rz = 1.0f / sz, rt = 1.0f / st;
+            float kq = 0.f;
+            if (vec) for (int q = lane * 4; q < Q; q += 256) {
+                const float4 v = *(const float4*)(lg + q), w = *(const float4*)(tl + q);
+                const float zv[4] = {v.x, v.y, v.z, v.w}, wv[4] = {w.x, w.y, w.z, w.w};
+                float gv[4], kv[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float a = (zv[i] - mz) * invT, c = (wv[i] - mt) * invT;
+                    const float pz = __expf(a) * rz, pt = __expf(c) * rt;
+                    kv[i] = pt * ((c - lst) - (a - lsz));
+                    gv[i] = (oma * (__expf(zv[i] - lse) - (q + i == tg ? 1.0f : 0.0f)) + aT * (pz - pt)) * inv;
+                }
+                kq += (kv[0] + kv[1]) + (kv[2] + kv[3]);
+                if (dlogits) *(float4*)(dlogits + (size_t)row * Q + q) = make_float4(gv[0], gv[1], gv[2], gv[3]);
+            } else for (int q = lane; q < Q; q += 64) {
+                const float a = (lg[q] - mz) * invT, c = (tl[q] - mt) * invT;
+                const float pz = expf(a) * rz, pt = expf(c) * rt;
+                kq += pt * ((c - lst) - (a - lsz));
+                if (dlogits) dlogits[(size_t)row * Q + q] = (oma * (expf(lg[q] - lse) - (q == tg ? 1.0f : 0.0f)) + aT * (pz - pt)) * inv;
+            }
+            kl = tr_wave_sum(kq);
+            ce = lse - lg[tg];
+        }
+        if (__any(bad) && lane == 0) atomicOr(status, 32);
+        csum += (double)ce; ksum += (double)kl;
+    }
+    if (lane == 0) { part[0][wave] = csum; part[1][wave] = ksum; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double c = (part[0][0] + part[0][1] + part[0][2] + part[0][3]) / (double)rows, k = (part[1][0] + part[1][1] + part[1][2] + part[1][3]) / (double)rows;
+        atomicAdd(loss + (blockIdx.x & 63), (double)oma * c + (double)alpha * ((double)temp * (double)temp) * k);
+        if (comp) { atomicAdd(comp + (blockIdx.x & 63), c); atomicAdd(comp + 64 + (blockIdx.x & 63), k); }
+    }
+}
+
 // ------------------------------------------------------------------ host launchers (called from train_host.hip)
 void qpn_launch_prep(const TrainParams& p, const AuxGeom& ag, hipStream_t stream) {
     const long items = (long)p.N1 * (p.C / 4 + (p.hoist ? 0 : p.Ap / 4) + p.L);
@@ -958,6 +1084,30 @@ int qpn_launch_ce(const float* logits, const int64_t* tgt, int64_t tgt_stride, i
     if (!loss_cleared) QPN_HIP(hipMemsetAsync(loss, 0, 64 * sizeof(double), stream));
     const int rpw = 4;                // 16 rows per workgroup: ~1250 workgroups for a 20 k-row chunk (64 rows per workgroup left most CUs with one)
     hipLaunchKernelGGL(k_ce, dim3((unsigned)((rows + 4 * rpw - 1) / (4 * rpw))), dim3(256), 0, stream, logits, tgt, tgt_stride, BL, Q, rows, dlogits, loss, rpw, status);
+    qpn_prof_mark(PG_CE, stream);
+    QPN_HIP(hipGetLastError());
+    return QPN_OK;
+}
+
+// the soft-target loss in k_ce's place (qpn_distill_loss, an armed forward-with-loss): same accumulator rules; comp != nullptr: its 128 slots are cleared here
+int qpn_launch_ce_distill(const float* logits, const float* teacher, const int64_t* tgt, int64_t tgt_stride, int B, int BL, int Q, float alpha, float temp,
+                          float* dlogits, double* loss, double* comp, int* status, bool loss_cleared, hipStream_t stream) {
+    const int64_t rows = (int64_t)B * BL;
+    if (!loss_cleared) QPN_HIP(hipMemsetAsync(loss, 0, 64 * sizeof(double), stream));
+    if (comp) QPN_HIP(hipMemsetAsync(comp, 0, 128 * sizeof(double), stream));
+    const int rpw = 4;
+    const dim3 grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
+    // rows of up to 1024 classes in registers (16-byte loads: every base pointer must be 16-byte aligned, checked by the callers); anything else: k_ce's loops
+    const int nv = (Q % 256 == 0 && Q <= 1024) ? Q / 256 : 0;
+#define QPN_DISTILL_LAUNCH(NV) hipLaunchKernelGGL((k_ce_distill<NV>), grid, dim3(256), 0, stream, logits, teacher, tgt, tgt_stride, BL, Q, rows, alpha, temp, dlogits, loss, comp, rpw, status)
+    switch (nv) {
+        case 1: QPN_DISTILL_LAUNCH(1); break;
+        case 2: QPN_DISTILL_LAUNCH(2); break;
+        case 3: QPN_DISTILL_LAUNCH(3); break;
+        case 4: QPN_DISTILL_LAUNCH(4); break;
+        default: QPN_DISTILL_LAUNCH(0); break;
+    }
+#undef QPN_DISTILL_LAUNCH
     qpn_prof_mark(PG_CE, stream);
     QPN_HIP(hipGetLastError());
     return QPN_OK;

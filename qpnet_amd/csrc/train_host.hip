@@ -12,6 +12,8 @@ int qpn_launch_fwd(const TrainParams& p, const TrainKnobs& k, const AuxGeom& ag,
 bool qpn_step_prep_fits(const TrainParams& p);
 void qpn_stack_fill(TrainParams& p);
 int qpn_launch_ce(const float* logits, const int64_t* tgt, int64_t tgt_stride, int B, int BL, int Q, float* dlogits, double* loss, int* status, bool loss_cleared, hipStream_t stream);
+int qpn_launch_ce_distill(const float* logits, const float* teacher, const int64_t* tgt, int64_t tgt_stride, int B, int BL, int Q, float alpha, float temp,
+                          float* dlogits, double* loss, double* comp, int* status, bool loss_cleared, hipStream_t stream);
 int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k, const AuxGeom& ag, const StackQ* sq, hipStream_t stream, bool post_done);
 int qpn_launch_fwd_gemm(const TrainParams& p, const TrainGemm& w, hipStream_t stream);
 int qpn_launch_bwd_gemm(const TrainParams& p, const TrainBwd& bw, const TrainGemm& w, hipStream_t stream);
@@ -39,6 +41,7 @@ struct TrainState {
     // workspaces (grow only)
     float* d_ws = nullptr; size_t ws_cap = 0; // one arena, carved per call (train_arena)
     int* d_tap = nullptr; size_t tap_cap = 0;
+    double* d_loss3 = nullptr;                // qpn_distill_loss(h_loss3): 2 x 64 slots for the loss's two components, allocated by the first call that asks for them
     int* d_status = nullptr; double* d_loss = nullptr;   // d_status: 16 words -- [0] the sticky status word, [2..3] the count of Adam updates applied (k_adam)
     hipStream_t last_stream = nullptr;        // the stream of the latest training call (where a collected status word is cleared)
     int* h_status_pinned = nullptr; hipEvent_t ev_status[2] = {}; bool status_pending[2] = {}; int status_newest = 0;      // qpn_train_status_enqueue / _collect: the deferred check, two slots
@@ -250,7 +253,7 @@ static int train_init(qpn_handle* h) {
 
 void qpn_train_destroy(TrainState* t) {
     if (!t) return;
-    void* bufs[] = {t->d_wmap, t->d_wp, t->d_bstart, t->d_blist, t->d_bp, t->d_gdst, t->d_gdst_list, t->d_gzero, t->d_ws, t->d_tap, t->d_status, t->d_loss, t->d_gmap, t->d_gwp, t->d_ctmap, t->d_ct, t->d_sq, t->d_gnorm};
+    void* bufs[] = {t->d_wmap, t->d_wp, t->d_bstart, t->d_blist, t->d_bp, t->d_gdst, t->d_gdst_list, t->d_gzero, t->d_ws, t->d_tap, t->d_status, t->d_loss, t->d_gmap, t->d_gwp, t->d_ctmap, t->d_ct, t->d_sq, t->d_gnorm, t->d_loss3};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (t->h_status_pinned) (void)hipHostFree(t->h_status_pinned);
     if (t->h_loss_pinned) (void)hipHostFree(t->h_loss_pinned);
@@ -276,6 +279,9 @@ static int need_dev(qpn_handle* h) {
 static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
                               const int64_t* d_x, const float* d_h, const float* d_dfac, float* d_logits,
                               const int64_t* d_targets, int64_t tgt_stride, float* d_dlogits, int want_logits, void* stream_, bool fuse_bwd = false) {
+    // the soft-target arm (qpn_train_distill) belongs to the next forward that computes a loss: one shot, consumed here, also by a forward that fails below
+    const float* d_teacher = nullptr; int64_t teacher_n = 0; float ds_alpha = 0.f, ds_temp = 1.f;
+    if (h && d_targets && h->distill_t) { d_teacher = h->distill_t; teacher_n = h->distill_n; ds_alpha = h->distill_alpha; ds_temp = h->distill_temp; h->distill_t = nullptr; h->distill_n = 0; }
     int rc = need_dev(h); if (rc) return rc;
     rc = train_init(h); if (rc) return rc;
     TrainState* t = h->train;
@@ -283,6 +289,16 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
     const Geom& g = h->g;
     if (!d_flat || !d_x || !d_h || !d_dfac || !d_logits || B < 1 || BL < 1 || maxd < 1) { qpn_set_error("bad train_forward arguments"); return QPN_EINVAL; }
     if (d_targets && tgt_stride < BL) { qpn_set_error("bad train_forward_loss arguments: target rows shorter than batch_length"); return QPN_EINVAL; }
+    if (d_teacher) {
+        const int64_t want = (int64_t)B * BL * g.Q;
+        if (teacher_n != want) {
+            qpn_set_error("qpn_train_distill: n = %lld, this forward has B * BL * n_quantize = %d * %d * %d = %lld", (long long)teacher_n, B, BL, g.Q, (long long)want);
+            return QPN_EINVAL;
+        }
+        hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing(stream, &cap_st);
+        if (cap_st != hipStreamCaptureStatusNone) { qpn_set_error("qpn_train_distill: an armed forward cannot be captured (the arm is host state a replay would not renew)"); return QPN_ESTATE; }
+    }
     const int64_t N0 = (int64_t)g.recA * maxd + g.recF + 1 + BL;           // qpnet.py:254-262
     if (N0 > T || N0 - 1 > Td || N0 - 1 > (g.U > 0 ? F * g.U : F)) {
         qpn_set_error("chunk too short: need receptive field (%lld) + batch_length (%d) = %lld samples, have x:%lld d:%lld h_up:%lld",
@@ -381,7 +397,7 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
     qpn_prof_mark(PG_PREP, stream);
     t->fwd_valid = false; t->loss_clear = true;
     ++t->generation;
-    const bool fuse_ce = d_targets && !t->lay.use_gemm && g.Q <= g.S && g.Q % 256 == 0 && !t->knobs.ce_separate;
+    const bool fuse_ce = d_targets && !t->lay.use_gemm && g.Q <= g.S && g.Q % 256 == 0 && !t->knobs.ce_separate && !d_teacher;      // (armed: QPN_CE_SEPARATE's route, k_ce_distill in k_ce's place)
     p.ce_tgt = fuse_ce ? d_targets : nullptr; p.ce_stride = tgt_stride; p.ce_dlogits = d_dlogits; p.ce_loss = t->d_loss;
     if (fuse_ce && !want_logits) p.logits = nullptr;
     const bool fuse_post = fuse_bwd && fuse_ce && d_dlogits && t->knobs.post_fuse && t->knobs.post_wide && t->knobs.zero_in_post && g.S == 256 && g.Q == 256 && g.C == 64 && (p.LC == 256 || p.LC == 512);
@@ -393,7 +409,9 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
     t->fwd_valid = true;
     if (fuse_ce) { t->loss_clear = false; qpn_prof_mark(PG_CE, stream); }
     else if (d_targets) {
-        rc = qpn_launch_ce(d_logits, d_targets, tgt_stride, B, BL, g.Q, d_dlogits, t->d_loss, t->d_status, t->loss_clear, stream); if (rc) return rc;
+        rc = d_teacher ? qpn_launch_ce_distill(d_logits, d_teacher, d_targets, tgt_stride, B, BL, g.Q, ds_alpha, ds_temp, d_dlogits, t->d_loss, nullptr, t->d_status, t->loss_clear, stream)
+                       : qpn_launch_ce(d_logits, d_targets, tgt_stride, B, BL, g.Q, d_dlogits, t->d_loss, t->d_status, t->loss_clear, stream);
+        if (rc) return rc;
         t->loss_clear = false;
     }
     return QPN_OK;
@@ -472,6 +490,7 @@ static int status_to_rc(int st) {
     if (st & 1) { qpn_set_error("pitch-dependent tap outside the layer input (dilated factor > maxd or < 0; reference assert qpnet.py:294)"); return QPN_ERANGE; }
     if (st & 4) { qpn_set_error("the one-launch residual stack gave up waiting for a peer workgroup: the flagged step's results are invalid (its Adam update, and that of the steps enqueued behind it until this report, were skipped on the device: parameters and moments are those of the last clean step); the handle runs a launch per layer from here on (QPN_STACK_QUEUE=0 selects that from the start)"); return QPN_ENODEV; }
     if (st & 2) { qpn_set_error("target class outside [0, n_quantize) (reference assert qpnet_train.py:525)"); return QPN_ERANGE; }
+    if (st & 32) { qpn_set_error("a NaN or an infinity in the teacher logits of a distillation loss (qpn_distill_loss / qpn_train_distill): the step's Adam update, and that of the steps enqueued behind it until this report, were skipped on the device: parameters and moments are those of the last clean step"); return QPN_ERANGE; }
     if (st & (1 << 16)) { qpn_set_error("non-finite gradient norm (an inf or NaN in the gradient): the step's Adam update, and that of the steps enqueued behind it until this report, were skipped on the device: parameters and moments are those of the last clean step"); return QPN_ERANGE; }
     if (st & 8) { qpn_set_error("a peer rank flagged its chunk of this data-parallel step, or an earlier micro-step of this accumulation window was flagged (a tap or target out of range, or an abandoned stack launch there): every rank skipped the update, the replicas are unchanged"); return QPN_ERANGE; }
     return QPN_OK;
@@ -554,6 +573,56 @@ extern "C" int qpn_ce_loss(qpn_handle* h, const float* d_logits, const int64_t* 
         QPN_HIP(hipStreamSynchronize(stream));
         *h_loss = loss_sum(parts);
     }
+    return QPN_OK;
+}
+
+// alpha in (0, 1], temperature finite and > 0: the rules of both distillation entry points (checked without a device)
+static int check_distill_args(const char* fn, float alpha, float temperature) {
+    if (!(alpha > 0.f && alpha <= 1.f)) { qpn_set_error("%s: alpha must lie in (0, 1] (got %g)", fn, (double)alpha); return QPN_EINVAL; }
+    if (!(temperature > 0.f) || !(temperature <= 3.402823466e+38f)) { qpn_set_error("%s: temperature must be finite and > 0 (got %g)", fn, (double)temperature); return QPN_EINVAL; }
+    return QPN_OK;
+}
+
+extern "C" int qpn_distill_loss(qpn_handle* h, const float* d_logits, const float* d_teacher, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
+                                float alpha, float temperature, float* d_dlogits, double* h_loss3, void* stream_) {
+    if (!h) { qpn_set_error("qpn_distill_loss: null handle"); return QPN_EINVAL; }
+    if (!d_logits) { qpn_set_error("qpn_distill_loss: d_logits is NULL"); return QPN_EINVAL; }
+    if (!d_teacher) { qpn_set_error("qpn_distill_loss: d_teacher is NULL"); return QPN_EINVAL; }
+    if (!d_targets) { qpn_set_error("qpn_distill_loss: d_targets is NULL"); return QPN_EINVAL; }
+    if (B < 1) { qpn_set_error("qpn_distill_loss: B must be >= 1 (got %d)", B); return QPN_EINVAL; }
+    if (BL < 1) { qpn_set_error("qpn_distill_loss: BL must be >= 1 (got %d)", BL); return QPN_EINVAL; }
+    if (tgt_stride < BL) { qpn_set_error("qpn_distill_loss: tgt_stride (%lld) is shorter than BL (%d)", (long long)tgt_stride, BL); return QPN_EINVAL; }
+    int rc = check_distill_args("qpn_distill_loss", alpha, temperature); if (rc) return rc;
+    if (h->g.Q % 256 == 0 && ((((uintptr_t)d_logits) | ((uintptr_t)d_teacher) | ((uintptr_t)d_dlogits)) & 15)) {
+        qpn_set_error("qpn_distill_loss: d_logits, d_teacher and d_dlogits must be 16-byte aligned"); return QPN_EINVAL;
+    }
+    rc = need_dev(h); if (rc) return rc;
+    rc = train_init(h); if (rc) return rc;
+    TrainState* t = h->train;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (h_loss3 && !t->d_loss3) QPN_HIP(hipMalloc(&t->d_loss3, 128 * sizeof(double)));
+    rc = qpn_launch_ce_distill(d_logits, d_teacher, d_targets, tgt_stride, B, BL, h->g.Q, alpha, temperature, d_dlogits, t->d_loss, h_loss3 ? t->d_loss3 : nullptr,
+                               t->d_status, t->loss_clear, stream); if (rc) return rc;
+    t->loss_clear = false;
+    if (h_loss3) {
+        double parts[64], comp[128];
+        QPN_HIP(hipMemcpyAsync(parts, t->d_loss, sizeof(parts), hipMemcpyDeviceToHost, stream));
+        QPN_HIP(hipMemcpyAsync(comp, t->d_loss3, sizeof(comp), hipMemcpyDeviceToHost, stream));
+        QPN_HIP(hipStreamSynchronize(stream));
+        h_loss3[0] = loss_sum(parts); h_loss3[1] = loss_sum(comp); h_loss3[2] = (double)temperature * (double)temperature * loss_sum(comp + 64);
+    }
+    return QPN_OK;
+}
+
+// The arm is host state on the handle (no device is needed to set it); the next forward that computes a loss takes it -- whatever that forward then returns
+extern "C" int qpn_train_distill(qpn_handle* h, const float* d_teacher, int64_t n, float alpha, float temperature) {
+    if (!h) { qpn_set_error("qpn_train_distill: null handle"); return QPN_EINVAL; }
+    h->distill_t = nullptr; h->distill_n = 0;
+    if (!d_teacher) return QPN_OK;
+    if (n < 1) { qpn_set_error("qpn_train_distill: n must be >= 1 with teacher logits (got %lld)", (long long)n); return QPN_EINVAL; }
+    int rc = check_distill_args("qpn_train_distill", alpha, temperature); if (rc) return rc;
+    if ((uintptr_t)d_teacher & 15) { qpn_set_error("qpn_train_distill: d_teacher must be 16-byte aligned"); return QPN_EINVAL; }
+    h->distill_t = d_teacher; h->distill_n = n; h->distill_alpha = alpha; h->distill_temp = temperature;
     return QPN_OK;
 }
 
@@ -901,7 +970,7 @@ static int train_step_impl(qpn_handle* h, float* d_flat, int B, int64_t T, int64
                            float* d_ema, float ema_decay, float* d_acc, int micro, int micro_count, void* stream) {
     const int rc = train_step_body(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
                                    step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, max_grad_norm, h_grad_norm, d_ema, ema_decay, d_acc, micro, micro_count, stream);
-    if (rc && h) { h->in_grad = nullptr; h->in_grad_n = 0; }
+    if (rc && h) { h->in_grad = nullptr; h->in_grad_n = 0; h->distill_t = nullptr; h->distill_n = 0; }      // (... and no forward to consume a soft-target arm)
     return rc;
 }
 

@@ -201,8 +201,8 @@ def _utterance_loaders(wav_list, feat_list, feature_type):
     return [_FileUtterance(w, f, feature_type) for w, f in zip(wav_list, feat_list)]
 
 
-def _batches(args, conf, model, shuffle, epochs, device, rank=0, world=1):
-    """Training / validation batches on `device`.  With world > 1 rank r takes chunks r, r+N, ... of the generator's
+def _batches(args, conf, model, shuffle, epochs, device, rank=0, world=1, fields=None):
+    """Training / validation batches on `device`.  fields: (receptiveCausal_field, receptiveF_field, receptiveA_field) to cut the chunks for (None: the model's).  With world > 1 rank r takes chunks r, r+N, ... of the generator's
     stream (same seed on every rank: identical shuffles and chunk boundaries) INSIDE the generator: a rank encodes,
     scales, takes ceil(max d) of and copies to its GPU only its own chunks."""
     wavs, feats = loaders.file_lists(args.waveforms, args.feats, conf.feature_format)
@@ -210,8 +210,7 @@ def _batches(args, conf, model, shuffle, epochs, device, rank=0, world=1):
     scaler = loaders.read_scaler_stats(args.stats, conf.feature_type)
     fs = loaders.read_wav(wavs[0])[0]
     gen = loaders.train_generator(
-        _utterance_loaders(wavs, feats, conf.feature_type), model.receptiveCausal_field, model.receptiveF_field,
-        model.receptiveA_field, fs, wav_transform=loaders.mu_law_transform(conf.n_quantize), feat_transform=scaler,
+        _utterance_loaders(wavs, feats, conf.feature_type), *(fields or _fields_of(model)), fs, wav_transform=loaders.mu_law_transform(conf.n_quantize), feat_transform=scaler,
         dense_factor=conf.dense_factor, batch_length=args.batch_length, batch_size=args.batch_size, max_length=args.max_length,
         f0_threshold=args.f0_threshold, upsampling_factor=conf.upsampling_factor, shuffle=shuffle, epochs=epochs,
         shard=(rank, world) if world > 1 else None)
@@ -224,6 +223,48 @@ def _batches(args, conf, model, shuffle, epochs, device, rank=0, world=1):
             dv = stage({"x": bx, "h": bh, "t": bt, "d": bd})
             yield (dv["x"], dv["h"], dv["t"], dv["d"], bb, maxd)
     return with_maxd()
+
+
+def _fields_of(m):
+    """(receptiveCausal_field, receptiveF_field, receptiveA_field) of a model or a configuration: what train_generator sizes its chunks from"""
+    return (m.receptiveCausal_field, m.receptiveF_field, m.receptiveA_field)
+
+
+def joint_fields(a, b):
+    """the element-wise maximum of two models' receptive fields: a chunk cut for it is long enough for both (the training forward takes a chunk longer than its
+    own receptive field + batch_length, inputs aligned at the end)"""
+    return tuple(max(u, v) for u, v in zip(_fields_of(a), _fields_of(b)))
+
+
+_DISTILL_FLAGS = ("teacher", "teacher_config", "distill_alpha", "distill_temperature", "teacher_ema")
+
+
+def _distill_of(args, conf):
+    """--teacher & co. -> None (no teacher: the run is what it always was), or {"checkpoint", "conf", "alpha", "temperature", "use_ema"} with the teacher's model
+    configuration loaded and checked against the student's `conf`.  Every error is a SystemExit, before anything is trained.  The flags are taken OUT of `args`:
+    the Namespace a training run pickles as its model configuration holds what it always held."""
+    v = {k: getattr(args, k) for k in _DISTILL_FLAGS}
+    for k in _DISTILL_FLAGS:
+        delattr(args, k)
+    if not v["teacher"]:
+        if v["teacher_config"] or v["teacher_ema"]:
+            raise SystemExit("--teacher_config / --teacher_ema need --teacher CHECKPOINT")
+        return None
+    if not v["teacher_config"]:
+        raise SystemExit("--teacher %s needs --teacher_config MODEL_CONF (the teacher's geometry is not stored in its checkpoint)" % v["teacher"])
+    for path in (v["teacher"], v["teacher_config"]):
+        if not os.path.exists(path):
+            raise SystemExit("--teacher: %s does not exist" % path)
+    from .config import QPNetConfig
+    from .train import _check_distill_scalars, check_distill_geometry
+    try:
+        alpha, temp = _check_distill_scalars(v["distill_alpha"], v["distill_temperature"])
+        tconf = loaders.load_model_conf(v["teacher_config"])
+        check_distill_geometry(conf, tconf)
+        QPNetConfig(**loaders.model_kwargs(tconf))
+    except (ValueError, AttributeError) as e:
+        raise SystemExit("--teacher %s: %s" % (v["teacher"], e))
+    return {"checkpoint": v["teacher"], "conf": tconf, "alpha": alpha, "temperature": temp, "use_ema": bool(v["teacher_ema"])}
 
 
 def _build_model(conf, device):
@@ -265,6 +306,12 @@ def _train_args(update):
                    help="do not update the parameters whose state_dict names match (fnmatch), e.g. \"causal.*,dil*,res*,skip*\" adapts the conditioning path and the post-net only")
     p.add_argument("--lr_scale", default=[], action="append", metavar="PATTERNS=SCALE",
                    help="train the parameters whose names match PATTERN[,PATTERN...] at lr * SCALE (repeatable: a group of its own each)")
+    p.add_argument("--teacher", default=None, type=str, metavar="CHECKPOINT",
+                   help="knowledge distillation: train against this checkpoint's predicted distributions (the soft-target loss inside the fused step); the reported loss is then the distillation total")
+    p.add_argument("--teacher_config", default=None, type=str, metavar="MODEL_CONF", help="the teacher's model configuration (required with --teacher)")
+    p.add_argument("--distill_alpha", default=0.5, type=float, help="weight of the soft-target term, in (0, 1]; the hard cross entropy gets 1 - alpha")
+    p.add_argument("--distill_temperature", default=1.0, type=float, help="temperature both distributions are softened with, > 0")
+    p.add_argument("--teacher_ema", action="store_true", help="take the teacher checkpoint's averaged weights (a run with --ema_decay wrote them)")
     p.add_argument("--iters", default=3000 if update else 200000, type=int)
     p.add_argument("--checkpoint_interval", default=10000, type=int)
     p.add_argument("--intervals", default=100, type=int)
@@ -294,6 +341,8 @@ def _param_groups_of(args):
 def run_train(argv=None, update=False):
     argv = sys.argv[1:] if argv is None else argv
     args = _train_args(update).parse_args(argv)
+    sconf = None if not (args.teacher and args.teacher_config) else (loaders.load_model_conf(args.config) if update else argparse.Namespace(**vars(args)))
+    distill = _distill_of(args, sconf)          # (--teacher & co.: checked, and taken out of args, before any rank is launched)
     rc = launch_ranks(args.n_gpus, "qpnet_amd.run_update" if update else "qpnet_amd.run_train", argv)
     if rc is not None:
         return rc
@@ -313,8 +362,21 @@ def run_train(argv=None, update=False):
     from .train import FusedTrainer
     from . import parallel
     model = _build_model(conf, dev).train()
+    teacher = fields = None
+    if distill is not None:
+        # the teacher: built from its own configuration, loaded once, never written (no optimiser, no entry in the checkpoints: --resume needs the flags again)
+        from .qpnet import QPNet
+        teacher = QPNet(**loaders.model_kwargs(distill["conf"])).to(dev).eval()
+        loaders.load_checkpoint(distill["checkpoint"], teacher, None, use_ema=distill["use_ema"])
+        teacher.requires_grad_(False)
+        fields = joint_fields(model, teacher)           # every chunk is long enough for both models
+        logging.info("distillation: teacher %s%s, receptive fields (causal, fixed, adaptive) student %s teacher %s -> chunks cut for %s; alpha = %g, T = %g; "
+                     "the reported loss is the distillation total (1 - alpha) CE + alpha T^2 KL."
+                     % (distill["checkpoint"], " (averaged weights)" if distill["use_ema"] else "", _fields_of(model), _fields_of(teacher), fields,
+                        distill["alpha"], distill["temperature"]))
     trainer = FusedTrainer(model, lr=args.lr, weight_decay=args.weight_decay, world_size=world, max_grad_norm=args.max_grad_norm, ema_decay=args.ema_decay,
-                           accum_steps=args.accum_steps, param_groups=_param_groups_of(args))
+                           accum_steps=args.accum_steps, param_groups=_param_groups_of(args),
+                           distill=None if teacher is None else {"teacher": teacher, "alpha": distill["alpha"], "temperature": distill["temperature"]})
     logging.info("trainable parameters = %d, frozen parameters = %d." % (trainer.n_trainable, trainer.n_frozen))
     clipping = trainer.max_grad_norm > 0.0
     K = trainer.accum_steps                    # batches per iteration: an iteration is one UPDATE (a window of K micro-steps), so checkpoints fall on window boundaries
@@ -347,7 +409,7 @@ def run_train(argv=None, update=False):
         logging.info("updating based on %s." % args.pretrain)
     from .train import ensure_flat
     parallel.broadcast_parameters(ensure_flat(model, dev))
-    stream = Prefetcher(_batches(args, conf, model, True, None, dev, rank, world))      # rank r: chunks r, r+N, r+2N, ...
+    stream = Prefetcher(_batches(args, conf, model, True, None, dev, rank, world, fields=fields))      # rank r: chunks r, r+N, r+2N, ...
     loss = total = 0.0
     logging.info("training start!")
     # The reference reads loss.item() at every step (qpnet_train.py:533) and reports its average over `intervals` steps (:536-541).  Here a step

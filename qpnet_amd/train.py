@@ -558,6 +558,121 @@ def _check_h_grad(h_grad, h, dev):
         raise ValueError("h_grad must be a CUDA tensor on the device of the step's inputs (%s), got %s" % (dev, h_grad.device))
 
 
+def _check_distill_scalars(alpha, temperature):
+    """alpha / temperature of the soft-target loss as the C ABI takes them (qpn_train_distill's rules, after rounding to float32): alpha in (0, 1],
+    temperature finite and > 0 -> (float, float)"""
+    try:
+        with np.errstate(over="ignore"):                   # (a value beyond float32 rounds to inf, which the rules below refuse)
+            a, T = float(np.float32(alpha)), float(np.float32(temperature))
+    except (TypeError, ValueError):
+        raise ValueError("distill: alpha and temperature must be numbers, got %r and %r" % (alpha, temperature))
+    if not (0.0 < a <= 1.0):
+        raise ValueError("distill: alpha must lie in (0, 1] as a float32 number, got %r" % (alpha,))
+    if not (T > 0.0) or not np.isfinite(T):
+        raise ValueError("distill: temperature must be finite and > 0 as a float32 number, got %r" % (temperature,))
+    return a, T
+
+
+def check_distill_geometry(student, teacher):
+    """the two models of a distillation must agree where their inputs and their logits meet: n_quantize, n_aux and upsampling_factor (anything with these three
+    attributes: modules or configurations); raises ValueError naming the first that differs"""
+    for k in ("n_quantize", "n_aux", "upsampling_factor"):
+        if getattr(student, k) != getattr(teacher, k):
+            raise ValueError("distill: teacher and student differ in %s (%r against %r)" % (k, getattr(teacher, k), getattr(student, k)))
+
+
+def _check_distill(model, distill):
+    """FusedTrainer's distill= -> None, or (teacher or None, alpha, temperature); every error is a ValueError, raised before any device work"""
+    if distill is None:
+        return None
+    if not isinstance(distill, dict):
+        raise ValueError('distill must be None or a dict {"teacher": QPNet, "alpha": a, "temperature": T}, got %r' % (type(distill),))
+    unknown = sorted(set(distill) - {"teacher", "alpha", "temperature"})
+    if unknown:
+        raise ValueError("distill: unknown keys %s" % (unknown,))
+    if "alpha" not in distill or "temperature" not in distill:
+        raise ValueError('distill needs "alpha" and "temperature"')
+    a, T = _check_distill_scalars(distill["alpha"], distill["temperature"])
+    teacher = distill.get("teacher")
+    if teacher is not None:
+        if teacher is model:
+            raise ValueError("distill: the teacher is the student itself (one outstanding forward per model)")
+        if not all(hasattr(teacher, k) for k in ("n_quantize", "n_aux", "upsampling_factor", "_native")):
+            raise ValueError("distill: the teacher must be a qpnet_amd.QPNet, got %r" % (type(teacher),))
+        check_distill_geometry(model, teacher)
+    return teacher, a, T
+
+
+def _check_teacher_logits(tl, B, BL, Q, dev):
+    """precomputed teacher logits as the C ABI takes them: float32, (B, BL, Q), contiguous, on the (CUDA) device of the step's inputs"""
+    if not isinstance(tl, torch.Tensor):
+        raise ValueError("teacher_logits must be a torch.Tensor (or None), got %r" % (type(tl),))
+    if tl.dtype != torch.float32:
+        raise ValueError("teacher_logits must be float32, got %s" % (tl.dtype,))
+    if tuple(tl.shape) != (B, BL, Q):
+        raise ValueError("teacher_logits must have the shape (B, BL, n_quantize) = %s, got %s" % ((B, BL, Q), tuple(tl.shape)))
+    if not tl.is_contiguous():
+        raise ValueError("teacher_logits must be contiguous")
+    if not tl.is_cuda or tl.device != dev:
+        raise ValueError("teacher_logits must be a CUDA tensor on the device of the step's inputs (%s), got %s" % (dev, tl.device))
+
+
+class _DistillLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, teacher_logits, targets, alpha, temperature):
+        dev = logits.device
+        lg = logits.detach().to(dev, torch.float32).contiguous()
+        tl = teacher_logits.detach().to(dev, torch.float32).contiguous()
+        tg = targets.to(dev, torch.int64).contiguous()
+        B, BL, Q = lg.shape
+        dl = torch.empty_like(lg)
+        parts = (C.c_double * 3)()
+        with torch.cuda.device(dev):
+            hp = _loss_handle(dev, Q)
+            _lib.check(_lib.lib().qpn_distill_loss(hp, lg.data_ptr(), tl.data_ptr(), tg.data_ptr(), tg.shape[1], B, BL, alpha, temperature,
+                                                   dl.data_ptr(), parts, torch.cuda.current_stream(dev).cuda_stream))
+            _lib.check(_lib.lib().qpn_train_status(hp, torch.cuda.current_stream(dev).cuda_stream))      # (the stream has just been drained for the loss)
+        ctx.save_for_backward(dl)
+        return torch.tensor(parts[0], dtype=torch.float32, device=dev)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        dl, = ctx.saved_tensors
+        return grad_output * dl, None, None, None, None
+
+
+_LOSS_HANDLES = {}
+
+
+def _loss_handle(dev, Q):
+    """a native handle per (device, n_quantize) for the loss calls that take their class count from a handle and nothing else (qpn_distill_loss)"""
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), Q)
+    hp = _LOSS_HANDLES.get(key)
+    if hp is None:
+        import dataclasses
+        from .config import TINY
+        hp = C.c_void_p()
+        _lib.check(_lib.lib().qpn_create(C.byref(_lib.make_config(dataclasses.replace(TINY, n_quantize=Q))), C.byref(hp)))
+        _LOSS_HANDLES[key] = hp
+    return hp
+
+
+def distill_loss(logits, teacher_logits, targets, alpha, temperature):
+    """The soft-target loss of the fused step for a reference-style loop (qpn_distill_loss): logits, teacher_logits (B, BL, Q) float32 on the GPU, targets
+    (B, >= BL) int64 whose LAST BL columns are the hard targets ->  mean over rows of (1 - alpha) CE(z, y) + alpha T^2 KL(softmax(t / T) || softmax(z / T)),
+    a float32 scalar whose backward hands grad_output * dL/dlogits (computed by the same kernel launch) to `logits` only.  Once differentiable.  Reads the loss in the
+    call (one stream drain, as the reference's loss.item()); a NaN or an infinity in teacher_logits raises QpnError(-4)."""
+    dev = logits.device
+    if dev.type != "cuda" or teacher_logits.device != dev or targets.device.type != "cuda":
+        raise RuntimeError("qpnet_amd.distill_loss runs on an AMD GPU only (tensors are on %s / %s / %s); there is no CPU fallback" % (dev, teacher_logits.device, targets.device))
+    if logits.dim() != 3 or tuple(teacher_logits.shape) != tuple(logits.shape) or targets.dim() != 2 or targets.shape[0] != logits.shape[0] or targets.shape[1] < logits.shape[1]:
+        raise ValueError("distill_loss: logits and teacher_logits (B, BL, Q) and targets (B, >= BL) expected, got %s, %s and %s"
+                         % (tuple(logits.shape), tuple(teacher_logits.shape), tuple(targets.shape)))
+    a, T = _check_distill_scalars(alpha, temperature)
+    return _DistillLoss.apply(logits, teacher_logits, targets, a, T)
+
+
 def _check_accum_steps(v):
     """accum_steps as the C ABI's micro_count: a plain int >= 1 (a bool, a float or None is not one)."""
     if type(v) is not int or v < 1:
@@ -956,7 +1071,18 @@ class FusedTrainer:
     group first when it is not empty, frozen tensors absent).  load_state_dict() with groups takes from the file: the moments and the step count; betas and eps; the
     base `lr` (the file's lr of the first group whose lr_scale is not 0, divided by that scale); the trainer's `weight_decay` when the file has the default group.
     lr_scale and the entries' own weight decays stay this trainer's.  `n_trainable` / `n_frozen` count the elements.  The groups are sticky on the model's native
-    handle: an optimiser without groups (a FusedTrainer / FlatAdam built later on the same model, a stock Adam stepped by the hooks) switches them off before its launch."""
+    handle: an optimiser without groups (a FusedTrainer / FlatAdam built later on the same model, a stock Adam stepped by the hooks) switches them off before its launch.
+    distill={"teacher": QPNet, "alpha": a, "temperature": T} (None: off): knowledge distillation -- every step's loss is the soft-target loss
+    (1 - a) CE(z, y) + a T^2 KL(softmax(t / T) || softmax(z / T)), mean over the rows (qpn_train_distill), t the teacher's logits for the same chunk:
+    step() runs the teacher's teacher-forced forward on the current stream (its own native handle and flat weights, the same inputs) into a buffer it keeps, arms the
+    student's handle and runs the step it would have run, on every host path (the one-call step, every micro-step of accum_steps > 1, world_size > 1).  The armed step
+    leaves the fused post-net tile (the forward writes the logits, one kernel computes the loss and dL/dlogits, the backward computes the post-net itself:
+    profiles/distill.txt has the cost).  The teacher must share n_quantize, n_aux and upsampling_factor with the student (ValueError otherwise, as for 0 < a <= 1 and a
+    finite T > 0, both as float32 numbers); its stack may differ -- feed chunks cut for the larger receptive field (runners.joint_fields).  The teacher is never written
+    and gets no optimiser; its own status word is collected where the student's is and raises naming the teacher.  step(teacher_logits=...) takes precomputed logits
+    instead (a cached teacher, an ensemble average), the "teacher" entry may then be absent.  A NaN or an infinity among the teacher logits skips the update and raises
+    QpnError(-4) ("... teacher logits ...") like the other status errors.  step() / flush_loss() return the distillation total; forward_loss() and score() stay the
+    plain cross entropy.  A step being captured raises.  A trainer setting: not part of state_dict(), the teacher reaches no checkpoint."""
 
     # The device-side status word (bad taps / targets; the reference asserts in-line, qpnet.py:294, qpnet_train.py:525) is copied to pinned
     # memory behind every step; a step starts by looking at the copy made TWO steps earlier (the previous step is still queued on the
@@ -964,8 +1090,10 @@ class FusedTrainer:
     # as when the word was read every 100 steps.  check_status() collects everything outstanding.
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, process_group=None, world_size=1, max_grad_norm=None, ema_decay=None,
-                 accum_steps=1, param_groups=None):
+                 accum_steps=1, param_groups=None, distill=None):
         self.model = model
+        self._distill = _check_distill(model, distill)      # None, or (teacher or None, alpha, temperature)
+        self._teacher_logits = None                         # the teacher's (B, BL, Q) output, kept from step to step
         self._groups = self._group_scales = self._group_wds = None
         if param_groups is not None:
             self._groups, self._group_scales, self._group_wds = trainer_param_groups(model, param_groups)
@@ -1026,7 +1154,7 @@ class FusedTrainer:
     def _norm(t, dtype, dev):
         return t if (t.dtype == dtype and t.device == dev and t.is_contiguous()) else t.to(dev, dtype).contiguous()
 
-    def step(self, x, h, t, d, blength, want_loss=True, maxd=None, h_grad=None):
+    def step(self, x, h, t, d, blength, want_loss=True, maxd=None, h_grad=None, teacher_logits=None):
         """One optimisation step.  maxd = ceil(max(d)) of the chunk; a loader that built d on the host (the reference's
         train_generator does, qpnet_train.py:268-272) passes it in, otherwise it is read back from the device (one sync).
         Inputs are normalised like QPNet.forward does (int64 samples/targets, float32 features/factors, contiguous).
@@ -1034,7 +1162,11 @@ class FusedTrainer:
         backward fills it, stream-ordered, with d(mean CE of THIS chunk) / dh at the weights the forward saw (the Adam launch comes behind it), every element, exact
         zeros in the frames no row of the chunk reaches.  With accum_steps > 1 every micro-step takes its own; with world_size > 1 it is the local chunk's gradient,
         nothing is exchanged; the row-count weighting of either never enters it.  A step that is being captured raises with it; after a step whose status word
-        is set its contents are unspecified."""
+        is set its contents are unspecified.
+        teacher_logits: with distill= set, precomputed teacher logits for this chunk -- float32, CUDA, contiguous, (B, BL, n_quantize), on the inputs' device
+        (anything else: ValueError before any device work) -- in the place of a forward of distill["teacher"] (which may then be absent)."""
+        if self._distill is not None or teacher_logits is not None:
+            return self._distill_step(x, h, t, d, blength, want_loss, maxd, h_grad, teacher_logits)
         if h_grad is None:
             return self._step(x, h, t, d, blength, want_loss, maxd)
         _check_h_grad(h_grad, h, x.device)
@@ -1048,6 +1180,66 @@ class FusedTrainer:
             return self._step(x, h, t, d, blength, want_loss, maxd)
         finally:
             L.qpn_train_input_grad(hd, None, 0)          # (consumed by the step's backward; a step that raised in front of it must not leave the request behind)
+
+    def _distill_step(self, x, h, t, d, blength, want_loss, maxd, h_grad, teacher_logits):
+        """step() with the soft-target loss: the teacher's teacher-forced forward (or the logits handed in) on the current stream, the arm, then the step as ever --
+        its forward-with-loss consumes the arm and runs k_ce_distill where the cross entropy ran.  Every micro-step of an accumulation window is armed this way."""
+        model = self.model
+        if self._distill is None:
+            raise ValueError('step(teacher_logits=...) needs the trainer\'s distill={"alpha": a, "temperature": T}')
+        teacher, alpha, temp = self._distill
+        dev = x.device
+        BL = int(blength[0])
+        if teacher_logits is not None:
+            _check_teacher_logits(teacher_logits, x.shape[0], BL, model.n_quantize, dev)
+        elif teacher is None:
+            raise ValueError('distill without a "teacher" needs step(teacher_logits=...) at every step')
+        if h_grad is not None:
+            _check_h_grad(h_grad, h, dev)
+        if dev.type != "cuda":
+            raise RuntimeError("qpnet_amd.FusedTrainer runs on an AMD GPU only (tensors are on %s)" % dev)
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("qpnet_amd.FusedTrainer(distill=...): a step cannot be captured into a graph with the soft-target loss (the arm is host state a "
+                               "replay would not renew)")
+        L, hd = model._native(dev)
+        Lt = ht = None
+        if teacher_logits is None:
+            join_staged(x, dev, h, t, d)
+            x = self._norm(x, torch.int64, dev); h = self._norm(h, torch.float32, dev); d = self._norm(d, torch.float32, dev)
+            if maxd is None:
+                maxd = int(torch.max(d.ceil()))
+            B, T = x.shape
+            if self._teacher_logits is None or self._teacher_logits.shape != (B, BL, model.n_quantize) or self._teacher_logits.device != dev:
+                self._teacher_logits = torch.empty((B, BL, model.n_quantize), dtype=torch.float32, device=dev)
+            teacher_logits = self._teacher_logits
+            Lt, ht = teacher._native(dev)
+            tflat = ensure_flat(teacher, dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            with torch.cuda.device(dev):
+                # the teacher's own status word (a tap of ITS stack outside the layer input): collected where the student's is, at the same lag
+                self._teacher_check(Lt, Lt.qpn_train_status_collect_lagged(ht))
+                self._teacher_check(Lt, Lt.qpn_train_forward(ht, tflat.data_ptr(), B, T, h.shape[2], d.shape[1], BL, maxd,
+                                                             x.data_ptr(), h.data_ptr(), d.data_ptr(), teacher_logits.data_ptr(), stream))
+                self._teacher_check(Lt, Lt.qpn_train_status_enqueue(ht, stream))
+        try:
+            _lib.check(L.qpn_train_distill(hd, teacher_logits.data_ptr(), teacher_logits.numel(), alpha, temp))
+            _arm_input_grad(L, hd, h_grad)
+            out = self._step(x, h, t, d, blength, want_loss, maxd)
+        finally:
+            L.qpn_train_distill(hd, None, 0, 0.0, 1.0)       # (consumed by the step's forward; a step that raised in front of it must not leave the arm behind)
+            if h_grad is not None:
+                L.qpn_train_input_grad(hd, None, 0)
+        if ht is not None and want_loss and want_loss != "lagged":
+            with torch.cuda.device(dev):                     # (the stream has just been drained for the loss: in-step, like the student's own check)
+                self._teacher_check(Lt, Lt.qpn_train_status_collect(ht))
+        return out
+
+    @staticmethod
+    def _teacher_check(Lt, rc):
+        if rc != 0:
+            if rc in (-4, -2):
+                _lib.STATUS_ERRORS[0] += 1
+            raise _lib.QpnError(rc, "the distillation teacher's forward: " + Lt.qpn_last_error().decode("utf-8", "replace"))
 
     def _step(self, x, h, t, d, blength, want_loss, maxd):
         model = self.model
@@ -1298,6 +1490,10 @@ class FusedTrainer:
         updates the device actually applied (_rebase_step_count)."""
         try:
             self.model.check_status()
+            teacher = self._distill[0] if self._distill is not None else None
+            if teacher is not None and teacher._handle is not None:
+                with torch.cuda.device(teacher._handle_dev):
+                    self._teacher_check(_lib.lib(), _lib.lib().qpn_train_status_collect(teacher._handle))
         except _lib.QpnError as e:
             flat = getattr(self.model, "_flat", None)
             if e.code in (-4, -2) and flat is not None and flat.is_cuda:
