@@ -299,6 +299,50 @@ int qpn_distill_loss(qpn_handle* h, const float* d_logits, const float* d_teache
  * not 16-byte aligned; disarming always succeeds.  A forward that is not armed launches exactly what it always launched. */
 int qpn_train_distill(qpn_handle* h, const float* d_teacher, int64_t n, float alpha, float temperature);
 
+/* Loss options ("Loss options"): what a user of torch.nn.CrossEntropyLoss configures -- per-row sample weights, ignore_index,
+ * label_smoothing, and what the sum is divided by.  Per row r = (b, t) with logits z (Q = n_quantize classes) and target y:
+ *   w_r   = d_weights[r]  (1 when d_weights is NULL);   w_r = 0 when use_ignore and y == ignore_index
+ *   CE_r  = lse(z) - (1 - eps) z_y - (eps / Q) sum_q z_q                      eps = label_smoothing in [0, 1)
+ *   g_r   = softmax(z) - (1 - eps) onehot(y) - eps / Q
+ *   L     = (1 / N) sum_r w_r CE_r        dL/dz_r = (w_r / N) g_r
+ *   N     = B * BL   for norm = 0 ("rows");    N = sum_r w_r   for norm = 1 ("weights": torch's `mean` with ignore_index)
+ * CE_r is torch.nn.functional.cross_entropy(..., label_smoothing=eps, reduction="none").  A row with w_r == 0 contributes nothing: its logits are not read, its
+ * target is not range-checked (padding may hold anything), its d_dlogits row is exact +0.  A weight that is NaN, infinite or negative counts as 0 and sets
+ * value 64 (1 << 6) of the training status word: the next status report returns QPN_ERANGE ("... sample weights ..."), an Adam launch that finds the word set
+ * skips its update as for every other bit.  norm = 1 with sum_r w_r == 0: the loss is 0, d_dlogits all zeros, no flag.  With norm = 0 the per-chunk loss stays
+ * a mean over the row count, so the row-weighted combination over ranks and accumulation windows gives sum w CE / sum rows exactly; norm = 1 is for updates that
+ * one chunk forms.
+ * Bitwise: k_ce_opt keeps k_ce's arithmetic and reduction order and forms the row's scale w_r / N once, in fp32: with all weights 1, eps 0, norm 0 its d_dlogits
+ * is qpn_ce_loss's bit for bit; with a power-of-two weight a row is exactly that weight times qpn_ce_loss's row.  The effective sum of weights that norm = 1
+ * divides by is computed in fp64 in a fixed order (k_weight_mass): d_dlogits is the same bits from run to run for both norms. */
+typedef struct { const float* d_weights; int64_t n_weights; int use_ignore; int64_t ignore_index;
+                 float label_smoothing; int norm; /* 0 rows, 1 weights */ } qpn_loss_opts;
+
+/* qpn_ce_loss with the options above (one kernel, k_ce_opt; norm = 1: k_weight_mass in front of it).  d_weights: B x BL fp32, contiguous, n_weights == B * BL.
+ * h_loss2 (optional, host; synchronises) receives {the loss, the effective sum of weights}; without it the loss stays on the device for qpn_train_loss.
+ * Arguments are checked before the device is looked at (works on a handle created without a GPU), QPN_EINVAL naming the argument: a null handle or pointer
+ * (opts included), B < 1, BL < 1, tgt_stride < BL, n_weights < 1 or != B * BL with weights, label_smoothing NaN or outside [0, 1), norm outside {0, 1},
+ * d_weights not 4-byte aligned; with n_quantize a multiple of 256, d_logits and d_dlogits must be 16-byte aligned. */
+int qpn_ce_loss_opts(qpn_handle* h, const float* d_logits, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
+                     const qpn_loss_opts* opts, float* d_dlogits, double* h_loss2, void* stream);
+
+/* qpn_distill_loss with row weights and ignore_index: w_r multiplies the whole row loss, CE term and KL term alike, and N divides both.  label_smoothing > 0 is
+ * refused (QPN_EINVAL naming label_smoothing: the soft targets already smooth).  Otherwise the arguments and checks of qpn_distill_loss and qpn_ce_loss_opts.
+ * With all weights 1 and norm 0, d_dlogits is qpn_distill_loss's bit for bit; a power-of-two weight scales a row exactly.  h_loss4 (optional, host;
+ * synchronises): qpn_distill_loss's three values, then the effective sum of weights. */
+int qpn_distill_loss_opts(qpn_handle* h, const float* d_logits, const float* d_teacher, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
+                          float alpha, float temperature, const qpn_loss_opts* opts, float* d_dlogits, double* h_loss4, void* stream);
+
+/* Arm (opts != NULL) or disarm (NULL) the loss options for the NEXT forward-with-loss enqueued on this handle, by the rules of qpn_train_distill: one shot,
+ * consumed by qpn_train_forward_loss and by the forward inside qpn_train_step / _clip / _avg / _acc, left alone by a plain qpn_train_forward, dropped by a
+ * failing step.  The struct is copied; d_weights is read when the loss kernel runs.  An armed forward takes the route QPN_CE_SEPARATE=1 selects, k_ce_opt in
+ * k_ce's place, on every training path; with a distillation arm on the same forward, k_ce_distill's weighted form runs; qpn_train_input_grad composes as ever.
+ * n_weights must equal B * BL of that forward, else it returns QPN_EINVAL naming n_weights before it launches anything (and the arm is dropped); an armed
+ * forward enqueued while its stream is capturing returns QPN_ESTATE and drops the arm.  A struct that is entirely default (no weights, no ignore, eps 0,
+ * norm 0) arms nothing: the next forward launches exactly what it always launched.  Arguments are checked before the device is looked at, QPN_EINVAL naming
+ * the argument as for qpn_ce_loss_opts, and label_smoothing > 0 while a teacher is armed (or a teacher armed behind it); disarming always succeeds. */
+int qpn_train_loss_opts(qpn_handle* h, const qpn_loss_opts* opts);
+
 /* Forward + loss in one call: qpn_train_forward followed by qpn_ce_loss (reference src/bin/qpnet_train.py:520-528:
  * `batch_output = model(...)`, `criterion(batch_output[i], batch_t[i])`), with the cross entropy and its gradient computed
  * inside the post-net kernel while a tile's logits are still in LDS (paper-size stacks; wider ones run the separate kernel

@@ -18,6 +18,10 @@ class QpnRowDraw(C.Structure):      # qpn_row_draw: one row's sampling record (q
     _fields_ = [("seed", C.c_uint64), ("stream", C.c_uint32), ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float)]
 
 
+class QpnLossOpts(C.Structure):     # qpn_loss_opts: the loss options (qpn_ce_loss_opts / qpn_distill_loss_opts / qpn_train_loss_opts)
+    _fields_ = [("d_weights", C.c_void_p), ("n_weights", C.c_int64), ("use_ignore", C.c_int), ("ignore_index", C.c_int64), ("label_smoothing", C.c_float), ("norm", C.c_int)]
+
+
 class QpnError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libqpnet_hip error %d: %s" % (code, msg))
@@ -64,6 +68,9 @@ SYMBOLS = [
     ("qpn_ce_loss", _i, [_vp, _vp, _vp, _i64, _i, _i, _vp, C.POINTER(C.c_double), _vp]),
     ("qpn_distill_loss", _i, [_vp, _vp, _vp, _vp, _i64, _i, _i, C.c_float, C.c_float, _vp, C.POINTER(C.c_double), _vp]),
     ("qpn_train_distill", _i, [_vp, _vp, _i64, C.c_float, C.c_float]),
+    ("qpn_ce_loss_opts", _i, [_vp, _vp, _vp, _i64, _i, _i, C.POINTER(QpnLossOpts), _vp, C.POINTER(C.c_double), _vp]),
+    ("qpn_distill_loss_opts", _i, [_vp, _vp, _vp, _vp, _i64, _i, _i, C.c_float, C.c_float, C.POINTER(QpnLossOpts), _vp, C.POINTER(C.c_double), _vp]),
+    ("qpn_train_loss_opts", _i, [_vp, C.POINTER(QpnLossOpts)]),
     ("qpn_adam_step", _i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp]),
     ("qpn_adam_step_ex", _i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]),
     ("qpn_train_step", _i, [_vp, _vp, _i, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64,

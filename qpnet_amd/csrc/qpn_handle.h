@@ -71,6 +71,7 @@ struct qpn_handle {      // every member has an initialiser: qpn_create sets onl
     struct TrainState* train = nullptr;        // lazily created by the training entry points (train_host.hip)
     float* in_grad = nullptr; int64_t in_grad_n = 0;      // qpn_train_input_grad: where the next backward writes dL/dh (one shot; on the handle: armed before any training state exists)
     const float* distill_t = nullptr; int64_t distill_n = 0; float distill_alpha = 0.f, distill_temp = 1.f;      // qpn_train_distill: the teacher logits of the next forward-with-loss (one shot; on the handle for the same reason)
+    qpn_loss_opts loss_opts = {}; bool loss_opts_armed = false;      // qpn_train_loss_opts: the loss options of the next forward-with-loss (one shot; on the handle for the same reason)
     // parameter groups of the Adam launches (qpn_adam_groups, train_host.hip): on the handle, not in the training state -- qpn_adam_step works on a handle that never trained
     int adam_n_groups = 0;                     // 0: off (the table below may stay: the same table set again costs no upload)
     float adam_lr[QPN_ADAM_MAX_GROUPS] = {}, adam_wd[QPN_ADAM_MAX_GROUPS] = {};

@@ -844,6 +844,175 @@ __global__ __launch_bounds__(256) void k_ce(const float* __restrict__ logits, co
     if (threadIdx.x == 0) atomicAdd(loss + (blockIdx.x & 63), (part[0] + part[1] + part[2] + part[3]) / (double)rows);
 }
 
+// ---- loss options ("Loss options"): row weights, ignore_index, label smoothing, the normaliser.  Per row r with logits z, target y:
+//   w_r = weights[r] (1 without weights), 0 when y == ignore_index;   CE_r = lse(z) - (1 - eps) z_y - (eps / Q) sum_q z_q;
+//   L = (1 / N) sum_r w_r CE_r,   dL/dz_r = (w_r / N) (softmax(z) - (1 - eps) onehot(y) - eps / Q),   N = the row count, or the effective sum of weights.
+// The helpers below are shared by k_ce_opt, k_weight_mass and k_ce_distill's weighted form, so that all three agree on a row's weight.
+// A NaN, infinite or negative weight sets status value 64 (the Adam launch of the step skips: the sticky-status rule) and counts as 0.
+__device__ __forceinline__ float ce_weight_value(const CeOpts& o, int64_t row, int64_t tg, bool& bad) {
+    float w = 1.0f;
+    bad = false;
+    if (o.w) { w = o.w[row]; if (!(w >= 0.f && w <= 3.402823466e+38f)) { bad = true; w = 0.f; } }
+    if (o.use_ign && tg == (int64_t)o.ign) w = 0.f;
+    return w;
+}
+__device__ __forceinline__ float ce_row_weight(const CeOpts& o, int64_t row, int64_t tg, int lane, int* status) {
+    bool bad;
+    const float w = ce_weight_value(o, row, tg, bad);
+    if (bad && lane == 0) atomicOr(status, 64);
+    return w;
+}
+// the normaliser N as a double (1 where the effective mass is 0: every sum it divides is 0 then) and 1 / N as the fp32 factor of the gradient (0 there)
+template <bool W> __device__ __forceinline__ double ce_opt_den(const CeOpts& o, int64_t rows) {
+    if constexpr (W) { if (o.norm_mass) { const double m = *o.norm_mass; return m > 0.0 ? m : 1.0; } }
+    return (double)rows;
+}
+template <bool W> __device__ __forceinline__ float ce_opt_inv(const CeOpts& o, int64_t rows) {
+    if constexpr (W) { if (o.norm_mass) { const double m = *o.norm_mass; return m > 0.0 ? (float)(1.0 / m) : 0.f; } }
+    return 1.0f / (float)rows;
+}
+// a zero-weight row of dL/dlogits: exact +0, by the lanes that would have written the row's gradient
+template <int NV> __device__ __forceinline__ void ce_zero_row(float* __restrict__ dst, int Q, int lane) {
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (NV > 0) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) *(float4*)(dst + lane * 4 + 256 * k) = z4;
+    } else if ((Q & 255) == 0) { for (int q = lane * 4; q < Q; q += 256) *(float4*)(dst + q) = z4; }
+    else for (int q = lane; q < Q; q += 64) dst[q] = 0.f;
+}
+
+// The effective sum of weights for norm = "weights", in fp64 and in a FIXED order (one workgroup: strided partial sums, an LDS tree): the same bits from run to
+// run.  Written to the word k_ce_opt / k_ce_distill read (CeOpts::norm_mass); enqueued in front of them on the same stream.
+__global__ __launch_bounds__(1024) void k_weight_mass(const int64_t* __restrict__ tgt, int64_t tgt_stride, int BL, int64_t rows, CeOpts o, double* __restrict__ out) {
+    __shared__ double s[1024];
+    double a = 0.0;
+    // a thread's rows are threadIdx.x + 1024 j, added in the order of j; eight of them are loaded before the first is added (one workgroup: the loop lives on loads in flight)
+    for (int64_t base = threadIdx.x; base < rows; base += 8 * 1024) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int64_t row = base + 1024 * j;
+            v[j] = 0.f;
+            if (row < rows) {
+                int64_t tg = 0;
+                if (o.use_ign) { const int64_t b = row / BL, t = row - b * BL; tg = tgt[(size_t)b * tgt_stride + (tgt_stride - BL) + t]; }
+                bool bad;
+                v[j] = ce_weight_value(o, row, tg, bad);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a += (double)v[j];
+    }
+    s[threadIdx.x] = a;
+    __syncthreads();
+    for (int st = 512; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) s[threadIdx.x] += s[threadIdx.x + st];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = s[0];
+}
+
+// k_ce with the options above, in k_ce's place on an armed forward: k_ce's layout (one wave per row, rpw rows per wave, 16 rows per workgroup, the 64 double
+// loss slots) and k_ce's max / sum-exp / lse arithmetic and reduction order, operation for operation.
+//   NV > 0: Q == 256 NV.  The lane's 4 NV logits of a row are loaded with 16-byte loads, all in flight before the first reduction, and stay in registers:
+//           a row is read once.  NV == 0: any Q, k_ce's loops.
+// The row's scale w_r / N is formed once, in fp32, and multiplies the gradient: with w_r == 1, eps == 0 and N the row count the output is k_ce's bits, with a
+// power-of-two weight exactly that weight times k_ce's bits.  The row loss is formed in fp32 as k_ce forms it, widened and multiplied by (double)w_r.
+// A row of weight 0 is decided from the weight and the target BEFORE any load of its logits is issued: its logits are not read, its target is not range-checked,
+// its dL/dlogits row is exact +0.  Smoothing (eps > 0, wave-uniform) adds one tr_wave_sum of z.
+template <int NV>
+__global__ __launch_bounds__(256) void k_ce_opt(const float* __restrict__ logits, const int64_t* __restrict__ tgt, int64_t tgt_stride, int BL, int Q, int64_t rows,
+                                                float* __restrict__ dlogits, double* __restrict__ loss, int rpw, int* __restrict__ status, CeOpts o) {
+    __shared__ double part[2][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float inv = ce_opt_inv<true>(o, rows);
+    const bool smooth = o.eps > 0.f;
+    const float ome = 1.0f - o.eps, eq = o.eps / (float)Q;
+    double lsum = 0.0, msum = 0.0;
+    for (int it = 0; it < rpw; ++it) {
+        const int64_t row = ((int64_t)blockIdx.x * rpw + it) * 4 + wave;
+        if (row >= rows) break;
+        const float* lg = logits + (size_t)row * Q;
+        const int64_t b = row / BL, t = row - b * BL;
+        int64_t tg = tgt[(size_t)b * tgt_stride + (tgt_stride - BL) + t];
+        const float wr = ce_row_weight(o, row, tg, lane, status);
+        if (wr == 0.f) { if (dlogits) ce_zero_row<NV>(dlogits + (size_t)row * Q, Q, lane); continue; }
+        const float sc = wr * inv;
+        msum += (double)wr;
+        float ce;
+        if constexpr (NV > 0) {
+            float4 z[NV];
+#pragma unroll
+            for (int k = 0; k < NV; ++k) z[k] = *(const float4*)(lg + lane * 4 + 256 * k);
+            if (tg < 0 || tg >= Q) { if (lane == 0) atomicOr(status, 2); tg = tg < 0 ? 0 : Q - 1; }
+            const float ztg = lg[tg];
+            float m = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) m = fmaxf(fmaxf(m, fmaxf(z[k].x, z[k].y)), fmaxf(z[k].z, z[k].w));
+            m = tr_wave_max(m);
+            float se = 0.f;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) se += (__expf(z[k].x - m) + __expf(z[k].y - m)) + (__expf(z[k].z - m) + __expf(z[k].w - m));
+            se = tr_wave_sum(se);
+            const float lse = logf(se) + m;
+            if (dlogits) {
+#pragma unroll
+                for (int k = 0; k < NV; ++k) {
+                    const int q = lane * 4 + 256 * k;
+                    float4 g = make_float4(__expf(z[k].x - lse), __expf(z[k].y - lse), __expf(z[k].z - lse), __expf(z[k].w - lse));
+                    const int dq = (int)tg - q;
+                    if (dq == 0) g.x -= ome; else if (dq == 1) g.y -= ome; else if (dq == 2) g.z -= ome; else if (dq == 3) g.w -= ome;
+                    if (smooth) { g.x -= eq; g.y -= eq; g.z -= eq; g.w -= eq; }
+                    *(float4*)(dlogits + (size_t)row * Q + q) = make_float4(g.x * sc, g.y * sc, g.z * sc, g.w * sc);
+                }
+            }
+            ce = lse - ztg;
+            if (smooth) {
+                float sz = 0.f;
+#pragma unroll
+                for (int k = 0; k < NV; ++k) sz += (z[k].x + z[k].y) + (z[k].z + z[k].w);
+                sz = tr_wave_sum(sz);
+                ce = (lse - ome * ztg) - eq * sz;
+            }
+        } else {
+            if (tg < 0 || tg >= Q) { if (lane == 0) atomicOr(status, 2); tg = tg < 0 ? 0 : Q - 1; }
+            float m = -INFINITY;
+            const bool vec = (Q & 255) == 0;
+            if (vec) for (int q = lane * 4; q < Q; q += 256) { const float4 v = *(const float4*)(lg + q); m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w)); }
+            else for (int q = lane; q < Q; q += 64) m = fmaxf(m, lg[q]);
+            m = tr_wave_max(m);
+            float se = 0.f, sz = 0.f;
+            if (vec) for (int q = lane * 4; q < Q; q += 256) { const float4 v = *(const float4*)(lg + q); se += (__expf(v.x - m) + __expf(v.y - m)) + (__expf(v.z - m) + __expf(v.w - m)); sz += (v.x + v.y) + (v.z + v.w); }
+            else for (int q = lane; q < Q; q += 64) { se += expf(lg[q] - m); sz += lg[q]; }
+            se = tr_wave_sum(se);
+            const float lse = logf(se) + m;
+            if (dlogits) {
+                if (vec) for (int q = lane * 4; q < Q; q += 256) {
+                    const float4 v = *(const float4*)(lg + q);
+                    float4 g = make_float4(__expf(v.x - lse), __expf(v.y - lse), __expf(v.z - lse), __expf(v.w - lse));
+                    const int dq = (int)tg - q;
+                    if (dq == 0) g.x -= ome; else if (dq == 1) g.y -= ome; else if (dq == 2) g.z -= ome; else if (dq == 3) g.w -= ome;
+                    if (smooth) { g.x -= eq; g.y -= eq; g.z -= eq; g.w -= eq; }
+                    *(float4*)(dlogits + (size_t)row * Q + q) = make_float4(g.x * sc, g.y * sc, g.z * sc, g.w * sc);
+                } else for (int q = lane; q < Q; q += 64) {
+                    float g = expf(lg[q] - lse) - (q == tg ? ome : 0.0f);
+                    if (smooth) g -= eq;
+                    dlogits[(size_t)row * Q + q] = g * sc;
+                }
+            }
+            ce = lse - lg[tg];
+            if (smooth) { sz = tr_wave_sum(sz); ce = (lse - ome * lg[tg]) - eq * sz; }
+        }
+        lsum += (double)ce * (double)wr;
+    }
+    if (lane == 0) { part[0][wave] = lsum; part[1][wave] = msum; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(loss + (blockIdx.x & 63), (part[0][0] + part[0][1] + part[0][2] + part[0][3]) / ce_opt_den<true>(o, rows));
+        if (o.mass) atomicAdd(o.mass + (blockIdx.x & 63), part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+    }
+}
+
 // knowledge distillation ("Soft-target loss"): per row  L = (1 - alpha) CE(z, y) + alpha T^2 KL(softmax(t / T) || softmax(z / T))  and
 //   dL/dz = (1 - alpha) (softmax(z) - onehot(y)) + alpha T (softmax(z / T) - softmax(t / T)),  both over the row count, z = logits, t = teacher.
 // k_ce's layout (one wave per row, rpw rows per wave, 16 rows per workgroup, the 64 double loss slots) and, for the CE term, k_ce's arithmetic operation for
@@ -859,115 +1028,17 @@ template <int NV>
 __global__ __launch_bounds__(256) void k_ce_distill(const float* __restrict__ logits, const float* __restrict__ teacher, const int64_t* __restrict__ tgt, int64_t tgt_stride,
                                                     int BL, int Q, int64_t rows, float alpha, float temp, float* __restrict__ dlogits, double* __restrict__ loss,
                                                     double* __restrict__ comp, int rpw, int* __restrict__ status) {
-    __shared__ double part[2][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float inv = 1.0f / (float)rows, invT = 1.0f / temp, oma = 1.0f - alpha, aT = alpha * temp;
-    double csum = 0.0, ksum = 0.0;
-    for (int it = 0; it < rpw; ++it) {
-        const int64_t row = ((int64_t)blockIdx.x * rpw + it) * 4 + wave;
-        if (row >= rows) break;
-        const float* lg = logits + (size_t)row * Q;
-        const float* tl = teacher + (size_t)row * Q;
-        const int64_t b = row / BL, t = row - b * BL;
-        int64_t tg = tgt[(size_t)b * tgt_stride + (tgt_stride - BL) + t];
-        float ce, kl;
-        bool bad = false;
-        if constexpr (NV > 0) {
-            float4 z[NV], u[NV];
-#pragma unroll
-            for (int k = 0; k < NV; ++k) { z[k] = *(const float4*)(lg + lane * 4 + 256 * k); u[k] = *(const float4*)(tl + lane * 4 + 256 * k); }
-            if (tg < 0 || tg >= Q) { if (lane == 0) atomicOr(status, 2); tg = tg < 0 ? 0 : Q - 1; }
-            const float ztg = lg[tg];
-            float mz = -INFINITY, mt = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < NV; ++k) {
-                mz = fmaxf(fmaxf(mz, fmaxf(z[k].x, z[k].y)), fmaxf(z[k].z, z[k].w));
-                mt = fmaxf(fmaxf(mt, fmaxf(u[k].x, u[k].y)), fmaxf(u[k].z, u[k].w));
-                bad = bad || dk_bad(u[k].x) || dk_bad(u[k].y) || dk_bad(u[k].z) || dk_bad(u[k].w);
-            }
-            mz = tr_wave_max(mz); mt = tr_wave_max(mt);
-            float se = 0.f, sz = 0.f, st = 0.f;
-            float4 ez[NV], eu[NV];
-#pragma unroll
-            for (int k = 0; k < NV; ++k) {
-                se += (__expf(z[k].x - mz) + __expf(z[k].y - mz)) + (__expf(z[k].z - mz) + __expf(z[k].w - mz));
-                ez[k] = make_float4(__expf((z[k].x - mz) * invT), __expf((z[k].y - mz) * invT), __expf((z[k].z - mz) * invT), __expf((z[k].w - mz) * invT));
-                eu[k] = make_float4(__expf((u[k].x - mt) * invT), __expf((u[k].y - mt) * invT), __expf((u[k].z - mt) * invT), __expf((u[k].w - mt) * invT));
-                sz += (ez[k].x + ez[k].y) + (ez[k].z + ez[k].w);
-                st += (eu[k].x + eu[k].y) + (eu[k].z + eu[k].w);
-            }
-            se = tr_wave_sum(se); sz = tr_wave_sum(sz); st = tr_wave_sum(st);
-            const float lse = logf(se) + mz, lsz = logf(sz), lst = logf(st), rz = 1.0f / sz, rt = 1.0f / st;
-            float kq = 0.f;
-#pragma unroll
-            for (int k = 0; k < NV; ++k) {
-                const float4 pz = make_float4(ez[k].x * rz, ez[k].y * rz, ez[k].z * rz, ez[k].w * rz);
-                const float4 pt = make_float4(eu[k].x * rt, eu[k].y * rt, eu[k].z * rt, eu[k].w * rt);
-                kq += (pt.x * (((u[k].x - mt) * invT - lst) - ((z[k].x - mz) * invT - lsz)) + pt.y * (((u[k].y - mt) * invT - lst) - ((z[k].y - mz) * invT - lsz))) +
-                      (pt.z * (((u[k].z - mt) * invT - lst) - ((z[k].z - mz) * invT - lsz)) + pt.w * (((u[k].w - mt) * invT - lst) - ((z[k].w - mz) * invT - lsz)));
-                if (dlogits) {
-                    const int q = lane * 4 + 256 * k;
-                    float4 g = make_float4(__expf(z[k].x - lse), __expf(z[k].y - lse), __expf(z[k].z - lse), __expf(z[k].w - lse));
-                    const int dq = (int)tg - q;
-                    if (dq == 0) g.x -= 1.0f; else if (dq == 1) g.y -= 1.0f; else if (dq == 2) g.z -= 1.0f; else if (dq == 3) g.w -= 1.0f;
-                    *(float4*)(dlogits + (size_t)row * Q + q) = make_float4((oma * g.x + aT * (pz.x - pt.x)) * inv, (oma * g.y + aT * (pz.y - pt.y)) * inv,
-                                                                            (oma * g.z + aT * (pz.z - pt.z)) * inv, (oma * g.w + aT * (pz.w - pt.w)) * inv);
-                }
-            }
-            kl = tr_wave_sum(kq);
-            ce = lse - ztg;
-        } else {
-            if (tg < 0 || tg >= Q) { if (lane == 0) atomicOr(status, 2); tg = tg < 0 ? 0 : Q - 1; }
-            const bool vec = (Q & 255) == 0;
-            float mz = -INFINITY, mt = -INFINITY;
-            if (vec) for (int q = lane * 4; q < Q; q += 256) {
-                const float4 v = *(const float4*)(lg + q), w = *(const float4*)(tl + q);
-                mz = fmaxf(fmaxf(mz, fmaxf(v.x, v.y)), fmaxf(v.z, v.w)); mt = fmaxf(fmaxf(mt, fmaxf(w.x, w.y)), fmaxf(w.z, w.w));
-                bad = bad || dk_bad(w.x) || dk_bad(w.y) || dk_bad(w.z) || dk_bad(w.w);
-            } else for (int q = lane; q < Q; q += 64) { const float w = tl[q]; mz = fmaxf(mz, lg[q]); mt = fmaxf(mt, w); bad = bad || dk_bad(w); }
-            mz = tr_wave_max(mz); mt = tr_wave_max(mt);
-            float se = 0.f, sz = 0.f, st = 0.f;
-            if (vec) for (int q = lane * 4; q < Q; q += 256) {
-                const float4 v = *(const float4*)(lg + q), w = *(const float4*)(tl + q);
-                se += (__expf(v.x - mz) + __expf(v.y - mz)) + (__expf(v.z - mz) + __expf(v.w - mz));
-                sz += (__expf((v.x - mz) * invT) + __expf((v.y - mz) * invT)) + (__expf((v.z - mz) * invT) + __expf((v.w - mz) * invT));
-                st += (__expf((w.x - mt) * invT) + __expf((w.y - mt) * invT)) + (__expf((w.z - mt) * invT) + __expf((w.w - mt) * invT));
-            } else for (int q = lane; q < Q; q += 64) { se += expf(lg[q] - mz); sz += expf((lg[q] - mz) * invT); st += expf((tl[q] - mt) * invT); }
-            se = tr_wave_sum(se); sz = tr_wave_sum(sz); st = tr_wave_sum(st);
-            const float lse = logf(se) + mz, lsz = logf(sz), lst = logf(st), rz = 1.0f / sz, rt = 1.0f / st;
-            float kq = 0.f;
-            if (vec) for (int q = lane * 4; q < Q; q += 256) {
-                const float4 v = *(const float4*)(lg + q), w = *(const float4*)(tl + q);
-                const float zv[4] = {v.x, v.y, v.z, v.w}, wv[4] = {w.x, w.y, w.z, w.w};
-                float gv[4], kv[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float a = (zv[i] - mz) * invT, c = (wv[i] - mt) * invT;
-                    const float pz = __expf(a) * rz, pt = __expf(c) * rt;
-                    kv[i] = pt * ((c - lst) - (a - lsz));
-                    gv[i] = (oma * (__expf(zv[i] - lse) - (q + i == tg ? 1.0f : 0.0f)) + aT * (pz - pt)) * inv;
-                }
-                kq += (kv[0] + kv[1]) + (kv[2] + kv[3]);
-                if (dlogits) *(float4*)(dlogits + (size_t)row * Q + q) = make_float4(gv[0], gv[1], gv[2], gv[3]);
-            } else for (int q = lane; q < Q; q += 64) {
-                const float a = (lg[q] - mz) * invT, c = (tl[q] - mt) * invT;
-                const float pz = expf(a) * rz, pt = expf(c) * rt;
-                kq += pt * ((c - lst) - (a - lsz));
-                if (dlogits) dlogits[(size_t)row * Q + q] = (oma * (expf(lg[q] - lse) - (q == tg ? 1.0f : 0.0f)) + aT * (pz - pt)) * inv;
-            }
-            kl = tr_wave_sum(kq);
-            ce = lse - lg[tg];
-        }
-        if (__any(bad) && lane == 0) atomicOr(status, 32);
-        csum += (double)ce; ksum += (double)kl;
-    }
-    if (lane == 0) { part[0][wave] = csum; part[1][wave] = ksum; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double c = (part[0][0] + part[0][1] + part[0][2] + part[0][3]) / (double)rows, k = (part[1][0] + part[1][1] + part[1][2] + part[1][3]) / (double)rows;
-        atomicAdd(loss + (blockIdx.x & 63), (double)oma * c + (double)alpha * ((double)temp * (double)temp) * k);
-        if (comp) { atomicAdd(comp + (blockIdx.x & 63), c); atomicAdd(comp + 64 + (blockIdx.x & 63), k); }
-    }
+    constexpr bool W = false;
+    [[maybe_unused]] const CeOpts o{nullptr, 0, 0, 0.f, nullptr, nullptr};
+#include "train_ce_soft.inc.h"
+}
+// ... with row weights and ignore_index (the loss options above): instantiated apart from k_ce_distill, whose instances are what they always were
+template <int NV>
+__global__ __launch_bounds__(256) void k_ce_soft_w(const float* __restrict__ logits, const float* __restrict__ teacher, const int64_t* __restrict__ tgt, int64_t tgt_stride,
+                                                   int BL, int Q, int64_t rows, float alpha, float temp, float* __restrict__ dlogits, double* __restrict__ loss,
+                                                   double* __restrict__ comp, int rpw, int* __restrict__ status, CeOpts o) {
+    constexpr bool W = true;
+#include "train_ce_soft.inc.h"
 }
 
 // ------------------------------------------------------------------ host launchers (called from train_host.hip)
@@ -1089,9 +1160,40 @@ int qpn_launch_ce(const float* logits, const int64_t* tgt, int64_t tgt_stride, i
     return QPN_OK;
 }
 
+// what both option launchers do in front of their kernel: clear the 64 mass slots and, for norm = "weights", write the word the kernel divides by
+static int qpn_launch_ce_opt_mass(const int64_t* tgt, int64_t tgt_stride, int BL, int64_t rows, const CeOpts& o, hipStream_t stream) {
+    if (o.mass) QPN_HIP(hipMemsetAsync(o.mass, 0, 64 * sizeof(double), stream));
+    if (o.norm_mass) hipLaunchKernelGGL(k_weight_mass, dim3(1), dim3(1024), 0, stream, tgt, tgt_stride, BL, rows, o, const_cast<double*>(o.norm_mass));
+    return QPN_OK;
+}
+
+// the cross entropy with options in k_ce's place (qpn_ce_loss_opts, an armed forward-with-loss): same accumulator rules
+int qpn_launch_ce_opt(const float* logits, const int64_t* tgt, int64_t tgt_stride, int B, int BL, int Q, const CeOpts& o, float* dlogits, double* loss, int* status,
+                      bool loss_cleared, hipStream_t stream) {
+    const int64_t rows = (int64_t)B * BL;
+    if (!loss_cleared) QPN_HIP(hipMemsetAsync(loss, 0, 64 * sizeof(double), stream));
+    int rc = qpn_launch_ce_opt_mass(tgt, tgt_stride, BL, rows, o, stream); if (rc) return rc;
+    const int rpw = 4;
+    const dim3 grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
+    // rows of up to 1024 classes in registers (16-byte loads: logits and dlogits must be 16-byte aligned, checked by the callers); anything else: k_ce's loops
+    const int nv = (Q % 256 == 0 && Q <= 1024) ? Q / 256 : 0;
+#define QPN_CE_OPT_LAUNCH(NV) hipLaunchKernelGGL((k_ce_opt<NV>), grid, dim3(256), 0, stream, logits, tgt, tgt_stride, BL, Q, rows, dlogits, loss, rpw, status, o)
+    switch (nv) {
+        case 1: QPN_CE_OPT_LAUNCH(1); break;
+        case 2: QPN_CE_OPT_LAUNCH(2); break;
+        case 3: QPN_CE_OPT_LAUNCH(3); break;
+        case 4: QPN_CE_OPT_LAUNCH(4); break;
+        default: QPN_CE_OPT_LAUNCH(0); break;
+    }
+#undef QPN_CE_OPT_LAUNCH
+    qpn_prof_mark(PG_CE, stream);
+    QPN_HIP(hipGetLastError());
+    return QPN_OK;
+}
+
 // the soft-target loss in k_ce's place (qpn_distill_loss, an armed forward-with-loss): same accumulator rules; comp != nullptr: its 128 slots are cleared here
 int qpn_launch_ce_distill(const float* logits, const float* teacher, const int64_t* tgt, int64_t tgt_stride, int B, int BL, int Q, float alpha, float temp,
-                          float* dlogits, double* loss, double* comp, int* status, bool loss_cleared, hipStream_t stream) {
+                          float* dlogits, double* loss, double* comp, int* status, bool loss_cleared, hipStream_t stream, const CeOpts* opts) {
     const int64_t rows = (int64_t)B * BL;
     if (!loss_cleared) QPN_HIP(hipMemsetAsync(loss, 0, 64 * sizeof(double), stream));
     if (comp) QPN_HIP(hipMemsetAsync(comp, 0, 128 * sizeof(double), stream));
@@ -1099,7 +1201,11 @@ int qpn_launch_ce_distill(const float* logits, const float* teacher, const int64
     const dim3 grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
     // rows of up to 1024 classes in registers (16-byte loads: every base pointer must be 16-byte aligned, checked by the callers); anything else: k_ce's loops
     const int nv = (Q % 256 == 0 && Q <= 1024) ? Q / 256 : 0;
-#define QPN_DISTILL_LAUNCH(NV) hipLaunchKernelGGL((k_ce_distill<NV>), grid, dim3(256), 0, stream, logits, teacher, tgt, tgt_stride, BL, Q, rows, alpha, temp, dlogits, loss, comp, rpw, status)
+    // opts (row weights / ignore_index; nullptr: none): the weighted instances -- the unweighted ones are the kernels they always were
+    const CeOpts o = opts ? *opts : CeOpts{nullptr, 0, 0, 0.f, nullptr, nullptr};
+    if (opts) { const int rc = qpn_launch_ce_opt_mass(tgt, tgt_stride, BL, rows, o, stream); if (rc) return rc; }
+#define QPN_DISTILL_LAUNCH(NV) do { if (opts) hipLaunchKernelGGL((k_ce_soft_w<NV>), grid, dim3(256), 0, stream, logits, teacher, tgt, tgt_stride, BL, Q, rows, alpha, temp, dlogits, loss, comp, rpw, status, o); \
+                                    else hipLaunchKernelGGL((k_ce_distill<NV>), grid, dim3(256), 0, stream, logits, teacher, tgt, tgt_stride, BL, Q, rows, alpha, temp, dlogits, loss, comp, rpw, status); } while (0)
     switch (nv) {
         case 1: QPN_DISTILL_LAUNCH(1); break;
         case 2: QPN_DISTILL_LAUNCH(2); break;

@@ -13,7 +13,10 @@ bool qpn_step_prep_fits(const TrainParams& p);
 void qpn_stack_fill(TrainParams& p);
 int qpn_launch_ce(const float* logits, const int64_t* tgt, int64_t tgt_stride, int B, int BL, int Q, float* dlogits, double* loss, int* status, bool loss_cleared, hipStream_t stream);
 int qpn_launch_ce_distill(const float* logits, const float* teacher, const int64_t* tgt, int64_t tgt_stride, int B, int BL, int Q, float alpha, float temp,
-                          float* dlogits, double* loss, double* comp, int* status, bool loss_cleared, hipStream_t stream);
+                          float* dlogits, double* loss, double* comp, int* status, bool loss_cleared, hipStream_t stream, const CeOpts* opts);
+int qpn_launch_ce_opt(const float* logits, const int64_t* tgt, int64_t tgt_stride, int B, int BL, int Q, const CeOpts& o, float* dlogits, double* loss, int* status,
+                      bool loss_cleared, hipStream_t stream);
+static CeOpts ce_opts_of(const qpn_loss_opts& o, double* mass, double* d_mass);
 int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k, const AuxGeom& ag, const StackQ* sq, hipStream_t stream, bool post_done);
 int qpn_launch_fwd_gemm(const TrainParams& p, const TrainGemm& w, hipStream_t stream);
 int qpn_launch_bwd_gemm(const TrainParams& p, const TrainBwd& bw, const TrainGemm& w, hipStream_t stream);
@@ -42,6 +45,7 @@ struct TrainState {
     float* d_ws = nullptr; size_t ws_cap = 0; // one arena, carved per call (train_arena)
     int* d_tap = nullptr; size_t tap_cap = 0;
     double* d_loss3 = nullptr;                // qpn_distill_loss(h_loss3): 2 x 64 slots for the loss's two components, allocated by the first call that asks for them
+    double* d_mass = nullptr;                 // loss options: 64 slots for the effective sum of weights + [64] the word k_weight_mass writes, allocated by the first call that needs them
     int* d_status = nullptr; double* d_loss = nullptr;   // d_status: 16 words -- [0] the sticky status word, [2..3] the count of Adam updates applied (k_adam)
     hipStream_t last_stream = nullptr;        // the stream of the latest training call (where a collected status word is cleared)
     int* h_status_pinned = nullptr; hipEvent_t ev_status[2] = {}; bool status_pending[2] = {}; int status_newest = 0;      // qpn_train_status_enqueue / _collect: the deferred check, two slots
@@ -253,7 +257,7 @@ static int train_init(qpn_handle* h) {
 
 void qpn_train_destroy(TrainState* t) {
     if (!t) return;
-    void* bufs[] = {t->d_wmap, t->d_wp, t->d_bstart, t->d_blist, t->d_bp, t->d_gdst, t->d_gdst_list, t->d_gzero, t->d_ws, t->d_tap, t->d_status, t->d_loss, t->d_gmap, t->d_gwp, t->d_ctmap, t->d_ct, t->d_sq, t->d_gnorm, t->d_loss3};
+    void* bufs[] = {t->d_wmap, t->d_wp, t->d_bstart, t->d_blist, t->d_bp, t->d_gdst, t->d_gdst_list, t->d_gzero, t->d_ws, t->d_tap, t->d_status, t->d_loss, t->d_gmap, t->d_gwp, t->d_ctmap, t->d_ct, t->d_sq, t->d_gnorm, t->d_loss3, t->d_mass};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (t->h_status_pinned) (void)hipHostFree(t->h_status_pinned);
     if (t->h_loss_pinned) (void)hipHostFree(t->h_loss_pinned);
@@ -282,6 +286,9 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
     // the soft-target arm (qpn_train_distill) belongs to the next forward that computes a loss: one shot, consumed here, also by a forward that fails below
     const float* d_teacher = nullptr; int64_t teacher_n = 0; float ds_alpha = 0.f, ds_temp = 1.f;
     if (h && d_targets && h->distill_t) { d_teacher = h->distill_t; teacher_n = h->distill_n; ds_alpha = h->distill_alpha; ds_temp = h->distill_temp; h->distill_t = nullptr; h->distill_n = 0; }
+    // the loss-options arm (qpn_train_loss_opts): the same rules
+    qpn_loss_opts lo = {}; bool lo_armed = false;
+    if (h && d_targets && h->loss_opts_armed) { lo = h->loss_opts; lo_armed = true; h->loss_opts_armed = false; }
     int rc = need_dev(h); if (rc) return rc;
     rc = train_init(h); if (rc) return rc;
     TrainState* t = h->train;
@@ -298,6 +305,17 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
         hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(stream, &cap_st);
         if (cap_st != hipStreamCaptureStatusNone) { qpn_set_error("qpn_train_distill: an armed forward cannot be captured (the arm is host state a replay would not renew)"); return QPN_ESTATE; }
+    }
+    if (lo_armed) {
+        if (lo.d_weights && lo.n_weights != (int64_t)B * BL) {
+            qpn_set_error("qpn_train_loss_opts: n_weights = %lld, this forward has B * BL = %d * %d = %lld rows", (long long)lo.n_weights, B, BL, (long long)B * BL);
+            return QPN_EINVAL;
+        }
+        if (d_teacher && lo.label_smoothing > 0.f) { qpn_set_error("qpn_train_loss_opts: label_smoothing cannot be combined with a distillation teacher (the soft targets already smooth)"); return QPN_EINVAL; }
+        hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing(stream, &cap_st);
+        if (cap_st != hipStreamCaptureStatusNone) { qpn_set_error("qpn_train_loss_opts: an armed forward cannot be captured (the arm is host state a replay would not renew)"); return QPN_ESTATE; }
+        if (lo.norm == 1 && !t->d_mass) QPN_HIP(hipMalloc(&t->d_mass, 72 * sizeof(double)));
     }
     const int64_t N0 = (int64_t)g.recA * maxd + g.recF + 1 + BL;           // qpnet.py:254-262
     if (N0 > T || N0 - 1 > Td || N0 - 1 > (g.U > 0 ? F * g.U : F)) {
@@ -397,7 +415,7 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
     qpn_prof_mark(PG_PREP, stream);
     t->fwd_valid = false; t->loss_clear = true;
     ++t->generation;
-    const bool fuse_ce = d_targets && !t->lay.use_gemm && g.Q <= g.S && g.Q % 256 == 0 && !t->knobs.ce_separate && !d_teacher;      // (armed: QPN_CE_SEPARATE's route, k_ce_distill in k_ce's place)
+    const bool fuse_ce = d_targets && !t->lay.use_gemm && g.Q <= g.S && g.Q % 256 == 0 && !t->knobs.ce_separate && !d_teacher && !lo_armed;      // (armed: QPN_CE_SEPARATE's route, k_ce_distill / k_ce_opt in k_ce's place)
     p.ce_tgt = fuse_ce ? d_targets : nullptr; p.ce_stride = tgt_stride; p.ce_dlogits = d_dlogits; p.ce_loss = t->d_loss;
     if (fuse_ce && !want_logits) p.logits = nullptr;
     const bool fuse_post = fuse_bwd && fuse_ce && d_dlogits && t->knobs.post_fuse && t->knobs.post_wide && t->knobs.zero_in_post && g.S == 256 && g.Q == 256 && g.C == 64 && (p.LC == 256 || p.LC == 512);
@@ -409,7 +427,9 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
     t->fwd_valid = true;
     if (fuse_ce) { t->loss_clear = false; qpn_prof_mark(PG_CE, stream); }
     else if (d_targets) {
-        rc = d_teacher ? qpn_launch_ce_distill(d_logits, d_teacher, d_targets, tgt_stride, B, BL, g.Q, ds_alpha, ds_temp, d_dlogits, t->d_loss, nullptr, t->d_status, t->loss_clear, stream)
+        const CeOpts co = ce_opts_of(lo, nullptr, t->d_mass);
+        rc = d_teacher ? qpn_launch_ce_distill(d_logits, d_teacher, d_targets, tgt_stride, B, BL, g.Q, ds_alpha, ds_temp, d_dlogits, t->d_loss, nullptr, t->d_status, t->loss_clear, stream, lo_armed ? &co : nullptr)
+             : lo_armed ? qpn_launch_ce_opt(d_logits, d_targets, tgt_stride, B, BL, g.Q, co, d_dlogits, t->d_loss, t->d_status, t->loss_clear, stream)
                        : qpn_launch_ce(d_logits, d_targets, tgt_stride, B, BL, g.Q, d_dlogits, t->d_loss, t->d_status, t->loss_clear, stream);
         if (rc) return rc;
         t->loss_clear = false;
@@ -491,6 +511,7 @@ static int status_to_rc(int st) {
     if (st & 4) { qpn_set_error("the one-launch residual stack gave up waiting for a peer workgroup: the flagged step's results are invalid (its Adam update, and that of the steps enqueued behind it until this report, were skipped on the device: parameters and moments are those of the last clean step); the handle runs a launch per layer from here on (QPN_STACK_QUEUE=0 selects that from the start)"); return QPN_ENODEV; }
     if (st & 2) { qpn_set_error("target class outside [0, n_quantize) (reference assert qpnet_train.py:525)"); return QPN_ERANGE; }
     if (st & 32) { qpn_set_error("a NaN or an infinity in the teacher logits of a distillation loss (qpn_distill_loss / qpn_train_distill): the step's Adam update, and that of the steps enqueued behind it until this report, were skipped on the device: parameters and moments are those of the last clean step"); return QPN_ERANGE; }
+    if (st & 64) { qpn_set_error("a NaN, infinite or negative value among the sample weights of a loss with options (qpn_ce_loss_opts / qpn_distill_loss_opts / qpn_train_loss_opts; it counted as 0): the step's Adam update, and that of the steps enqueued behind it until this report, were skipped on the device: parameters and moments are those of the last clean step"); return QPN_ERANGE; }
     if (st & (1 << 16)) { qpn_set_error("non-finite gradient norm (an inf or NaN in the gradient): the step's Adam update, and that of the steps enqueued behind it until this report, were skipped on the device: parameters and moments are those of the last clean step"); return QPN_ERANGE; }
     if (st & 8) { qpn_set_error("a peer rank flagged its chunk of this data-parallel step, or an earlier micro-step of this accumulation window was flagged (a tap or target out of range, or an abandoned stack launch there): every rank skipped the update, the replicas are unchanged"); return QPN_ERANGE; }
     return QPN_OK;
@@ -602,7 +623,7 @@ extern "C" int qpn_distill_loss(qpn_handle* h, const float* d_logits, const floa
     hipStream_t stream = (hipStream_t)stream_;
     if (h_loss3 && !t->d_loss3) QPN_HIP(hipMalloc(&t->d_loss3, 128 * sizeof(double)));
     rc = qpn_launch_ce_distill(d_logits, d_teacher, d_targets, tgt_stride, B, BL, h->g.Q, alpha, temperature, d_dlogits, t->d_loss, h_loss3 ? t->d_loss3 : nullptr,
-                               t->d_status, t->loss_clear, stream); if (rc) return rc;
+                               t->d_status, t->loss_clear, stream, nullptr); if (rc) return rc;
     t->loss_clear = false;
     if (h_loss3) {
         double parts[64], comp[128];
@@ -622,7 +643,104 @@ extern "C" int qpn_train_distill(qpn_handle* h, const float* d_teacher, int64_t 
     if (n < 1) { qpn_set_error("qpn_train_distill: n must be >= 1 with teacher logits (got %lld)", (long long)n); return QPN_EINVAL; }
     int rc = check_distill_args("qpn_train_distill", alpha, temperature); if (rc) return rc;
     if ((uintptr_t)d_teacher & 15) { qpn_set_error("qpn_train_distill: d_teacher must be 16-byte aligned"); return QPN_EINVAL; }
+    if (h->loss_opts_armed && h->loss_opts.label_smoothing > 0.f) { qpn_set_error("qpn_train_distill: a teacher cannot be combined with the armed label_smoothing (qpn_train_loss_opts; the soft targets already smooth)"); return QPN_EINVAL; }
     h->distill_t = d_teacher; h->distill_n = n; h->distill_alpha = alpha; h->distill_temp = temperature;
+    return QPN_OK;
+}
+
+// ---- loss options (include/qpnet_hip.h: qpn_loss_opts).  The argument rules of all three entry points, checked without a device
+static bool loss_opts_default(const qpn_loss_opts& o) { return !o.d_weights && !o.use_ignore && o.label_smoothing == 0.f && o.norm == 0; }
+static int check_loss_opts(const char* fn, const qpn_loss_opts* o, bool with_teacher) {
+    if (!o) { qpn_set_error("%s: opts is NULL", fn); return QPN_EINVAL; }
+    if (o->d_weights && o->n_weights < 1) { qpn_set_error("%s: n_weights must be >= 1 with d_weights (got %lld)", fn, (long long)o->n_weights); return QPN_EINVAL; }
+    if (!(o->label_smoothing >= 0.f && o->label_smoothing < 1.f)) { qpn_set_error("%s: label_smoothing must lie in [0, 1) (got %g)", fn, (double)o->label_smoothing); return QPN_EINVAL; }
+    if (o->norm != 0 && o->norm != 1) { qpn_set_error("%s: norm must be 0 (rows) or 1 (weights) (got %d)", fn, o->norm); return QPN_EINVAL; }
+    if ((uintptr_t)o->d_weights & 3) { qpn_set_error("%s: d_weights must be 4-byte aligned", fn); return QPN_EINVAL; }
+    if (with_teacher && o->label_smoothing > 0.f) { qpn_set_error("%s: label_smoothing cannot be combined with a distillation teacher (the soft targets already smooth)", fn); return QPN_EINVAL; }
+    return QPN_OK;
+}
+// the kernels' view of checked options: mass -- 64 slots (or nullptr); word -- where k_weight_mass writes what norm = 1 divides by (d_mass + 64)
+static CeOpts ce_opts_of(const qpn_loss_opts& o, double* mass, double* d_mass) {
+    return CeOpts{o.d_weights, (long long)o.ignore_index, o.use_ignore ? 1 : 0, o.label_smoothing, o.norm == 1 ? d_mass + 64 : nullptr, mass};
+}
+static int loss_opts_mass(TrainState* t) {
+    if (!t->d_mass) QPN_HIP(hipMalloc(&t->d_mass, 72 * sizeof(double)));
+    return QPN_OK;
+}
+
+extern "C" int qpn_ce_loss_opts(qpn_handle* h, const float* d_logits, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
+                                const qpn_loss_opts* opts, float* d_dlogits, double* h_loss2, void* stream_) {
+    if (!h) { qpn_set_error("qpn_ce_loss_opts: null handle"); return QPN_EINVAL; }
+    if (!d_logits) { qpn_set_error("qpn_ce_loss_opts: d_logits is NULL"); return QPN_EINVAL; }
+    if (!d_targets) { qpn_set_error("qpn_ce_loss_opts: d_targets is NULL"); return QPN_EINVAL; }
+    if (B < 1) { qpn_set_error("qpn_ce_loss_opts: B must be >= 1 (got %d)", B); return QPN_EINVAL; }
+    if (BL < 1) { qpn_set_error("qpn_ce_loss_opts: BL must be >= 1 (got %d)", BL); return QPN_EINVAL; }
+    if (tgt_stride < BL) { qpn_set_error("qpn_ce_loss_opts: tgt_stride (%lld) is shorter than BL (%d)", (long long)tgt_stride, BL); return QPN_EINVAL; }
+    int rc = check_loss_opts("qpn_ce_loss_opts", opts, false); if (rc) return rc;
+    if (opts->d_weights && opts->n_weights != (int64_t)B * BL) { qpn_set_error("qpn_ce_loss_opts: n_weights = %lld, the call has B * BL = %d * %d = %lld rows", (long long)opts->n_weights, B, BL, (long long)B * BL); return QPN_EINVAL; }
+    if (h->g.Q % 256 == 0 && ((((uintptr_t)d_logits) | ((uintptr_t)d_dlogits)) & 15)) { qpn_set_error("qpn_ce_loss_opts: d_logits and d_dlogits must be 16-byte aligned"); return QPN_EINVAL; }
+    rc = need_dev(h); if (rc) return rc;
+    rc = train_init(h); if (rc) return rc;
+    TrainState* t = h->train;
+    hipStream_t stream = (hipStream_t)stream_;
+    rc = loss_opts_mass(t); if (rc) return rc;
+    rc = qpn_launch_ce_opt(d_logits, d_targets, tgt_stride, B, BL, h->g.Q, ce_opts_of(*opts, h_loss2 ? t->d_mass : nullptr, t->d_mass), d_dlogits, t->d_loss, t->d_status, t->loss_clear, stream);
+    if (rc) return rc;
+    t->loss_clear = false;
+    if (h_loss2) {
+        double parts[64], mass[64];
+        QPN_HIP(hipMemcpyAsync(parts, t->d_loss, sizeof(parts), hipMemcpyDeviceToHost, stream));
+        QPN_HIP(hipMemcpyAsync(mass, t->d_mass, sizeof(mass), hipMemcpyDeviceToHost, stream));
+        QPN_HIP(hipStreamSynchronize(stream));
+        h_loss2[0] = loss_sum(parts); h_loss2[1] = loss_sum(mass);
+    }
+    return QPN_OK;
+}
+
+extern "C" int qpn_distill_loss_opts(qpn_handle* h, const float* d_logits, const float* d_teacher, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
+                                     float alpha, float temperature, const qpn_loss_opts* opts, float* d_dlogits, double* h_loss4, void* stream_) {
+    if (!h) { qpn_set_error("qpn_distill_loss_opts: null handle"); return QPN_EINVAL; }
+    if (!d_logits) { qpn_set_error("qpn_distill_loss_opts: d_logits is NULL"); return QPN_EINVAL; }
+    if (!d_teacher) { qpn_set_error("qpn_distill_loss_opts: d_teacher is NULL"); return QPN_EINVAL; }
+    if (!d_targets) { qpn_set_error("qpn_distill_loss_opts: d_targets is NULL"); return QPN_EINVAL; }
+    if (B < 1) { qpn_set_error("qpn_distill_loss_opts: B must be >= 1 (got %d)", B); return QPN_EINVAL; }
+    if (BL < 1) { qpn_set_error("qpn_distill_loss_opts: BL must be >= 1 (got %d)", BL); return QPN_EINVAL; }
+    if (tgt_stride < BL) { qpn_set_error("qpn_distill_loss_opts: tgt_stride (%lld) is shorter than BL (%d)", (long long)tgt_stride, BL); return QPN_EINVAL; }
+    int rc = check_distill_args("qpn_distill_loss_opts", alpha, temperature); if (rc) return rc;
+    rc = check_loss_opts("qpn_distill_loss_opts", opts, true); if (rc) return rc;
+    if (opts->d_weights && opts->n_weights != (int64_t)B * BL) { qpn_set_error("qpn_distill_loss_opts: n_weights = %lld, the call has B * BL = %d * %d = %lld rows", (long long)opts->n_weights, B, BL, (long long)B * BL); return QPN_EINVAL; }
+    if (h->g.Q % 256 == 0 && ((((uintptr_t)d_logits) | ((uintptr_t)d_teacher) | ((uintptr_t)d_dlogits)) & 15)) {
+        qpn_set_error("qpn_distill_loss_opts: d_logits, d_teacher and d_dlogits must be 16-byte aligned"); return QPN_EINVAL;
+    }
+    rc = need_dev(h); if (rc) return rc;
+    rc = train_init(h); if (rc) return rc;
+    TrainState* t = h->train;
+    hipStream_t stream = (hipStream_t)stream_;
+    rc = loss_opts_mass(t); if (rc) return rc;
+    if (h_loss4 && !t->d_loss3) QPN_HIP(hipMalloc(&t->d_loss3, 128 * sizeof(double)));
+    const CeOpts co = ce_opts_of(*opts, h_loss4 ? t->d_mass : nullptr, t->d_mass);
+    rc = qpn_launch_ce_distill(d_logits, d_teacher, d_targets, tgt_stride, B, BL, h->g.Q, alpha, temperature, d_dlogits, t->d_loss, h_loss4 ? t->d_loss3 : nullptr,
+                               t->d_status, t->loss_clear, stream, &co); if (rc) return rc;
+    t->loss_clear = false;
+    if (h_loss4) {
+        double parts[64], comp[128], mass[64];
+        QPN_HIP(hipMemcpyAsync(parts, t->d_loss, sizeof(parts), hipMemcpyDeviceToHost, stream));
+        QPN_HIP(hipMemcpyAsync(comp, t->d_loss3, sizeof(comp), hipMemcpyDeviceToHost, stream));
+        QPN_HIP(hipMemcpyAsync(mass, t->d_mass, sizeof(mass), hipMemcpyDeviceToHost, stream));
+        QPN_HIP(hipStreamSynchronize(stream));
+        h_loss4[0] = loss_sum(parts); h_loss4[1] = loss_sum(comp); h_loss4[2] = (double)temperature * (double)temperature * loss_sum(comp + 64); h_loss4[3] = loss_sum(mass);
+    }
+    return QPN_OK;
+}
+
+// The arm is host state on the handle, as qpn_train_distill's is.  An options struct that is entirely default arms nothing: the next forward launches what it always launched
+extern "C" int qpn_train_loss_opts(qpn_handle* h, const qpn_loss_opts* opts) {
+    if (!h) { qpn_set_error("qpn_train_loss_opts: null handle"); return QPN_EINVAL; }
+    h->loss_opts_armed = false;
+    if (!opts) return QPN_OK;
+    int rc = check_loss_opts("qpn_train_loss_opts", opts, h->distill_t != nullptr); if (rc) return rc;
+    if (loss_opts_default(*opts)) return QPN_OK;
+    h->loss_opts = *opts; h->loss_opts_armed = true;
     return QPN_OK;
 }
 
@@ -970,7 +1088,7 @@ static int train_step_impl(qpn_handle* h, float* d_flat, int B, int64_t T, int64
                            float* d_ema, float ema_decay, float* d_acc, int micro, int micro_count, void* stream) {
     const int rc = train_step_body(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
                                    step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, max_grad_norm, h_grad_norm, d_ema, ema_decay, d_acc, micro, micro_count, stream);
-    if (rc && h) { h->in_grad = nullptr; h->in_grad_n = 0; h->distill_t = nullptr; h->distill_n = 0; }      // (... and no forward to consume a soft-target arm)
+    if (rc && h) { h->in_grad = nullptr; h->in_grad_n = 0; h->distill_t = nullptr; h->distill_n = 0; h->loss_opts_armed = false; }      // (... and no forward to consume a soft-target or loss-options arm)
     return rc;
 }
 

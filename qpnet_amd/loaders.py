@@ -560,3 +560,22 @@ def file_lists(waveforms, feats, feature_format="h5"):
         assert len(wavs) == len(fts)
         return wavs, fts
     raise FileNotFoundError("--waveforms should be directory or list: %s" % waveforms)
+
+
+def unvoiced_row_weights(batch_h, batch_length, upsampling_factor, unvoiced_weight):
+    """Per-row sample weights of a chunk from its voiced / unvoiced flag: feature column 0 is uv (1 voiced, 0 unvoiced; calc_stats keeps it at mean 0 / scale 1,
+    so the scaled feature is still 0 / 1).  batch_h: (B, n_aux, F) features as the training forward takes them -> (B, batch_length) float32, 1 for the rows of voiced
+    frames and `unvoiced_weight` for the others.  Rows are aligned as the forward aligns h with its output rows: the chunk's LAST batch_length positions of the
+    upsampled features (position p lies in frame p // upsampling_factor), or of the features themselves with upsampling_factor = 0 (one feature vector per sample)."""
+    uv = np.asarray(batch_h, dtype=np.float32)[:, 0, :]
+    BL, U, F = int(batch_length), int(upsampling_factor), uv.shape[1]
+    w = float(unvoiced_weight)
+    if not (w >= 0.0 and np.isfinite(w)):
+        raise ValueError("unvoiced_weight must be finite and >= 0, got %r" % (unvoiced_weight,))
+    n = F * U if U > 0 else F
+    if BL < 1 or BL > n:
+        raise ValueError("batch_length %d does not fit the %d positions the features cover" % (BL, n))
+    pos = np.arange(n - BL, n)
+    if U > 0:
+        pos //= U
+    return np.where(uv[:, pos] > 0.5, np.float32(1.0), np.float32(w)).astype(np.float32)

@@ -201,8 +201,9 @@ def _utterance_loaders(wav_list, feat_list, feature_type):
     return [_FileUtterance(w, f, feature_type) for w, f in zip(wav_list, feat_list)]
 
 
-def _batches(args, conf, model, shuffle, epochs, device, rank=0, world=1, fields=None):
-    """Training / validation batches on `device`.  fields: (receptiveCausal_field, receptiveF_field, receptiveA_field) to cut the chunks for (None: the model's).  With world > 1 rank r takes chunks r, r+N, ... of the generator's
+def _batches(args, conf, model, shuffle, epochs, device, rank=0, world=1, fields=None, unvoiced_weight=None):
+    """Training / validation batches on `device`.  unvoiced_weight (None: off): a seventh element, the chunk's (B, batch_length) sample weights
+    (loaders.unvoiced_row_weights), staged with the chunk.  fields: (receptiveCausal_field, receptiveF_field, receptiveA_field) to cut the chunks for (None: the model's).  With world > 1 rank r takes chunks r, r+N, ... of the generator's
     stream (same seed on every rank: identical shuffles and chunk boundaries) INSIDE the generator: a rank encodes,
     scales, takes ceil(max d) of and copies to its GPU only its own chunks."""
     wavs, feats = loaders.file_lists(args.waveforms, args.feats, conf.feature_format)
@@ -220,8 +221,13 @@ def _batches(args, conf, model, shuffle, epochs, device, rank=0, world=1, fields
     def with_maxd():            # ceil(max d) is known on the host here: the fused step then needs no device read-back
         for bx, bh, bt, bd, bb in gen:
             maxd = int(np.ceil(float(bd.max())))
-            dv = stage({"x": bx, "h": bh, "t": bt, "d": bd})
-            yield (dv["x"], dv["h"], dv["t"], dv["d"], bb, maxd)
+            if unvoiced_weight is None:
+                dv = stage({"x": bx, "h": bh, "t": bt, "d": bd})
+                yield (dv["x"], dv["h"], dv["t"], dv["d"], bb, maxd)
+            else:
+                bw = torch.from_numpy(loaders.unvoiced_row_weights(bh.numpy(), int(bb[0]), conf.upsampling_factor, unvoiced_weight))
+                dv = stage({"x": bx, "h": bh, "t": bt, "d": bd, "w": bw})
+                yield (dv["x"], dv["h"], dv["t"], dv["d"], bb, maxd, dv["w"])
     return with_maxd()
 
 
@@ -312,6 +318,9 @@ def _train_args(update):
     p.add_argument("--distill_alpha", default=0.5, type=float, help="weight of the soft-target term, in (0, 1]; the hard cross entropy gets 1 - alpha")
     p.add_argument("--distill_temperature", default=1.0, type=float, help="temperature both distributions are softened with, > 0")
     p.add_argument("--teacher_ema", action="store_true", help="take the teacher checkpoint's averaged weights (a run with --ema_decay wrote them)")
+    p.add_argument("--label_smoothing", default=0.0, type=float, metavar="EPS", help="label smoothing of the cross entropy inside the fused step, in [0, 1); 0: off")
+    p.add_argument("--unvoiced_weight", default=1.0, type=float, metavar="W",
+                   help="weight of the samples of unvoiced frames in the loss (voiced ones weigh 1; finite, >= 0; the loss stays a mean over the row count); 1: off")
     p.add_argument("--iters", default=3000 if update else 200000, type=int)
     p.add_argument("--checkpoint_interval", default=10000, type=int)
     p.add_argument("--intervals", default=100, type=int)
@@ -343,6 +352,16 @@ def run_train(argv=None, update=False):
     args = _train_args(update).parse_args(argv)
     sconf = None if not (args.teacher and args.teacher_config) else (loaders.load_model_conf(args.config) if update else argparse.Namespace(**vars(args)))
     distill = _distill_of(args, sconf)          # (--teacher & co.: checked, and taken out of args, before any rank is launched)
+    # (the loss options are taken out of args as well: args is the model configuration run_train writes)
+    label_smoothing, unvoiced_weight = args.__dict__.pop("label_smoothing"), args.__dict__.pop("unvoiced_weight")
+    if not (0.0 <= label_smoothing < 1.0):
+        raise SystemExit("--label_smoothing must lie in [0, 1), got %r" % (label_smoothing,))
+    if not (unvoiced_weight >= 0.0 and np.isfinite(unvoiced_weight)):
+        raise SystemExit("--unvoiced_weight must be finite and >= 0, got %r" % (unvoiced_weight,))
+    if label_smoothing > 0.0 and distill is not None:
+        raise SystemExit("--label_smoothing cannot be combined with --teacher (the soft targets already smooth)")
+    if unvoiced_weight == 1.0:
+        unvoiced_weight = None                  # (off: no weights are made or staged, nothing is armed)
     rc = launch_ranks(args.n_gpus, "qpnet_amd.run_update" if update else "qpnet_amd.run_train", argv)
     if rc is not None:
         return rc
@@ -376,7 +395,11 @@ def run_train(argv=None, update=False):
                         distill["alpha"], distill["temperature"]))
     trainer = FusedTrainer(model, lr=args.lr, weight_decay=args.weight_decay, world_size=world, max_grad_norm=args.max_grad_norm, ema_decay=args.ema_decay,
                            accum_steps=args.accum_steps, param_groups=_param_groups_of(args),
-                           distill=None if teacher is None else {"teacher": teacher, "alpha": distill["alpha"], "temperature": distill["temperature"]})
+                           distill=None if teacher is None else {"teacher": teacher, "alpha": distill["alpha"], "temperature": distill["temperature"]},
+                           label_smoothing=label_smoothing)
+    if label_smoothing > 0.0 or unvoiced_weight is not None:
+        logging.info("loss options: label_smoothing = %g, unvoiced_weight = %g (samples of unvoiced frames; voiced ones weigh 1); the reported loss is "
+                     "sum_r w_r CE_r over the row count." % (label_smoothing, 1.0 if unvoiced_weight is None else unvoiced_weight))
     logging.info("trainable parameters = %d, frozen parameters = %d." % (trainer.n_trainable, trainer.n_frozen))
     clipping = trainer.max_grad_norm > 0.0
     K = trainer.accum_steps                    # batches per iteration: an iteration is one UPDATE (a window of K micro-steps), so checkpoints fall on window boundaries
@@ -409,7 +432,7 @@ def run_train(argv=None, update=False):
         logging.info("updating based on %s." % args.pretrain)
     from .train import ensure_flat
     parallel.broadcast_parameters(ensure_flat(model, dev))
-    stream = Prefetcher(_batches(args, conf, model, True, None, dev, rank, world, fields=fields))      # rank r: chunks r, r+N, r+2N, ...
+    stream = Prefetcher(_batches(args, conf, model, True, None, dev, rank, world, fields=fields, unvoiced_weight=unvoiced_weight))      # rank r: chunks r, r+N, r+2N, ...
     loss = total = 0.0
     logging.info("training start!")
     # The reference reads loss.item() at every step (qpnet_train.py:533) and reports its average over `intervals` steps (:536-541).  Here a step
@@ -419,9 +442,9 @@ def run_train(argv=None, update=False):
     for i in range(iterations, args.iters):
         start = time.time()
         while True:                             # the K batches of this iteration's window (K = 1: the one batch)
-            bx, bh, bt, bd, bb, maxd = next(stream)
+            bx, bh, bt, bd, bb, maxd, *bw = next(stream)
             try:
-                batch_loss = trainer.step(bx, bh, bt, bd, bb, want_loss="lagged" if lagged else True, maxd=maxd)
+                batch_loss = trainer.step(bx, bh, bt, bd, bb, want_loss="lagged" if lagged else True, maxd=maxd, sample_weights=bw[0] if bw else None)
             except Exception as e:
                 if not (clipping and _is_non_finite_norm(e)):
                     raise

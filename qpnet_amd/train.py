@@ -619,18 +619,24 @@ def _check_teacher_logits(tl, B, BL, Q, dev):
 
 class _DistillLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, teacher_logits, targets, alpha, temperature):
+    def forward(ctx, logits, teacher_logits, targets, alpha, temperature, weights=None, ignore=None):
         dev = logits.device
         lg = logits.detach().to(dev, torch.float32).contiguous()
         tl = teacher_logits.detach().to(dev, torch.float32).contiguous()
         tg = targets.to(dev, torch.int64).contiguous()
         B, BL, Q = lg.shape
         dl = torch.empty_like(lg)
-        parts = (C.c_double * 3)()
+        parts = (C.c_double * 4)()
         with torch.cuda.device(dev):
             hp = _loss_handle(dev, Q)
-            _lib.check(_lib.lib().qpn_distill_loss(hp, lg.data_ptr(), tl.data_ptr(), tg.data_ptr(), tg.shape[1], B, BL, alpha, temperature,
-                                                   dl.data_ptr(), parts, torch.cuda.current_stream(dev).cuda_stream))
+            if weights is None and ignore is None:
+                _lib.check(_lib.lib().qpn_distill_loss(hp, lg.data_ptr(), tl.data_ptr(), tg.data_ptr(), tg.shape[1], B, BL, alpha, temperature,
+                                                       dl.data_ptr(), parts, torch.cuda.current_stream(dev).cuda_stream))
+            else:
+                wt = None if weights is None else weights.detach().to(dev, torch.float32).contiguous()
+                opts = _make_loss_opts(wt, ignore, 0.0, 0)
+                _lib.check(_lib.lib().qpn_distill_loss_opts(hp, lg.data_ptr(), tl.data_ptr(), tg.data_ptr(), tg.shape[1], B, BL, alpha, temperature, C.byref(opts),
+                                                            dl.data_ptr(), parts, torch.cuda.current_stream(dev).cuda_stream))
             _lib.check(_lib.lib().qpn_train_status(hp, torch.cuda.current_stream(dev).cuda_stream))      # (the stream has just been drained for the loss)
         ctx.save_for_backward(dl)
         return torch.tensor(parts[0], dtype=torch.float32, device=dev)
@@ -639,7 +645,7 @@ class _DistillLoss(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_output):
         dl, = ctx.saved_tensors
-        return grad_output * dl, None, None, None, None
+        return grad_output * dl, None, None, None, None, None, None
 
 
 _LOSS_HANDLES = {}
@@ -658,11 +664,16 @@ def _loss_handle(dev, Q):
     return hp
 
 
-def distill_loss(logits, teacher_logits, targets, alpha, temperature):
+def distill_loss(logits, teacher_logits, targets, alpha, temperature, sample_weights=None, ignore_index=None):
     """The soft-target loss of the fused step for a reference-style loop (qpn_distill_loss): logits, teacher_logits (B, BL, Q) float32 on the GPU, targets
     (B, >= BL) int64 whose LAST BL columns are the hard targets ->  mean over rows of (1 - alpha) CE(z, y) + alpha T^2 KL(softmax(t / T) || softmax(z / T)),
     a float32 scalar whose backward hands grad_output * dL/dlogits (computed by the same kernel launch) to `logits` only.  Once differentiable.  Reads the loss in the
-    call (one stream drain, as the reference's loss.item()); a NaN or an infinity in teacher_logits raises QpnError(-4)."""
+    call (one stream drain, as the reference's loss.item()); a NaN or an infinity in teacher_logits raises QpnError(-4).
+    sample_weights (B, BL) / ignore_index: the row weights of cross_entropy() below (qpn_distill_loss_opts): w_r multiplies the whole row loss, CE and KL term
+    alike, over the row count."""
+    ign, _, _ = _check_loss_options(ignore_index, 0.0, "rows")
+    if sample_weights is not None:
+        _check_weights_like(sample_weights, logits.shape[0] * logits.shape[1] if logits.dim() == 3 else -1)
     dev = logits.device
     if dev.type != "cuda" or teacher_logits.device != dev or targets.device.type != "cuda":
         raise RuntimeError("qpnet_amd.distill_loss runs on an AMD GPU only (tensors are on %s / %s / %s); there is no CPU fallback" % (dev, teacher_logits.device, targets.device))
@@ -670,7 +681,110 @@ def distill_loss(logits, teacher_logits, targets, alpha, temperature):
         raise ValueError("distill_loss: logits and teacher_logits (B, BL, Q) and targets (B, >= BL) expected, got %s, %s and %s"
                          % (tuple(logits.shape), tuple(teacher_logits.shape), tuple(targets.shape)))
     a, T = _check_distill_scalars(alpha, temperature)
-    return _DistillLoss.apply(logits, teacher_logits, targets, a, T)
+    return _DistillLoss.apply(logits, teacher_logits, targets, a, T, sample_weights, ign)
+
+
+_LOSS_NORMS = {"rows": 0, "weights": 1}
+
+
+def _check_loss_options(ignore_index, label_smoothing, norm):
+    """the loss options as the C ABI takes them (qpn_loss_opts' rules, eps after rounding to float32) -> (ignore_index or None, eps, norm code); every error is a
+    ValueError"""
+    if ignore_index is not None and (isinstance(ignore_index, bool) or not isinstance(ignore_index, (int, np.integer)) or not -2 ** 63 <= int(ignore_index) < 2 ** 63):
+        raise ValueError("ignore_index must be None or an int (a 64-bit one), got %r" % (ignore_index,))
+    try:
+        eps = float("nan") if isinstance(label_smoothing, (bool, str, bytes)) or label_smoothing is None else float(np.float32(label_smoothing))
+    except (TypeError, ValueError):
+        raise ValueError("label_smoothing must be a number, got %r" % (label_smoothing,))
+    if not (0.0 <= eps < 1.0):
+        raise ValueError("label_smoothing must lie in [0, 1) as a float32 number, got %r" % (label_smoothing,))
+    if not isinstance(norm, str) or norm not in _LOSS_NORMS:
+        raise ValueError('norm must be "rows" (divide by the row count) or "weights" (divide by the sum of the weights), got %r' % (norm,))
+    return (None if ignore_index is None else int(ignore_index)), eps, _LOSS_NORMS[norm]
+
+
+def _check_weights_like(w, rows):
+    if not isinstance(w, torch.Tensor):
+        raise ValueError("sample_weights must be a torch.Tensor (or None), got %r" % (type(w),))
+    if not w.is_floating_point():
+        raise ValueError("sample_weights must be a floating-point tensor, got %s" % (w.dtype,))
+    if w.numel() != rows:
+        raise ValueError("sample_weights must hold one weight per row (%d), got the shape %s" % (rows, tuple(w.shape)))
+
+
+def _check_sample_weights(w, B, BL, dev):
+    """a step's sample weights as the C ABI takes them: float32, (B, BL), contiguous, on the (CUDA) device of the step's inputs"""
+    if not isinstance(w, torch.Tensor):
+        raise ValueError("sample_weights must be a torch.Tensor (or None), got %r" % (type(w),))
+    if w.dtype != torch.float32:
+        raise ValueError("sample_weights must be float32, got %s" % (w.dtype,))
+    if tuple(w.shape) != (B, BL):
+        raise ValueError("sample_weights must have the shape (B, BL) = %s, got %s" % ((B, BL), tuple(w.shape)))
+    if not w.is_contiguous():
+        raise ValueError("sample_weights must be contiguous")
+    if not w.is_cuda or w.device != dev:
+        raise ValueError("sample_weights must be a CUDA tensor on the device of the step's inputs (%s), got %s" % (dev, w.device))
+
+
+def _make_loss_opts(weights, ignore_index, eps, norm):
+    """qpn_loss_opts from checked values (weights: a float32 contiguous CUDA tensor or None, kept alive by the caller)"""
+    return _lib.QpnLossOpts(weights.data_ptr() if weights is not None else None, weights.numel() if weights is not None else 0,
+                            0 if ignore_index is None else 1, 0 if ignore_index is None else ignore_index, eps, norm)
+
+
+class _CrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, targets, weights, ignore, eps, norm):
+        dev = logits.device
+        lg = logits.detach().to(dev, torch.float32).contiguous()
+        tg = targets.to(dev, torch.int64).contiguous()
+        if lg.dim() == 2:                                   # (rows, Q) and (rows,): the reference's criterion(output.view(-1, Q), t.view(-1))
+            lg, tg = lg[None], tg[None]
+        B, BL, Q = lg.shape
+        wt = None if weights is None else weights.detach().to(dev, torch.float32).contiguous()
+        dl = torch.empty_like(lg)
+        parts = (C.c_double * 2)()
+        opts = _make_loss_opts(wt, ignore, eps, norm)
+        with torch.cuda.device(dev):
+            hp = _loss_handle(dev, Q)
+            _lib.check(_lib.lib().qpn_ce_loss_opts(hp, lg.data_ptr(), tg.data_ptr(), tg.shape[1], B, BL, C.byref(opts), dl.data_ptr(), parts,
+                                                   torch.cuda.current_stream(dev).cuda_stream))
+            _lib.check(_lib.lib().qpn_train_status(hp, torch.cuda.current_stream(dev).cuda_stream))      # (the stream has just been drained for the loss)
+        ctx.save_for_backward(dl.view(logits.shape))
+        return torch.tensor(parts[0], dtype=torch.float32, device=dev)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        dl, = ctx.saved_tensors
+        return grad_output * dl, None, None, None, None, None
+
+
+def cross_entropy(logits, targets, sample_weights=None, ignore_index=None, label_smoothing=0.0, norm="rows"):
+    """The fused step's criterion with its options for a reference-style loop (qpn_ce_loss_opts; DESIGN.md section 5, "Loss options") -- a drop-in for
+    `criterion = torch.nn.CrossEntropyLoss()`: logits (B, BL, Q) float32 on the GPU with targets (B, >= BL) int64 whose LAST BL columns are the targets, or the
+    reference's flattened pair, logits (rows, Q) and targets (rows,).  With w_r = sample_weights[r] (one per row; 1 without), 0 where the target equals ignore_index:
+        L = (1 / N) sum_r w_r (lse(z) - (1 - eps) z_y - (eps / Q) sum_q z_q),   N = the row count (norm="rows") or sum_r w_r (norm="weights": torch's mean with
+    ignore_index), a float32 scalar whose backward hands grad_output * dL/dlogits (computed by the same kernel launch) to `logits` only.  Once differentiable.  Rows
+    of weight 0 are not read (their targets may hold anything).  Reads the loss in the call (one stream drain, as the reference's loss.item()); a NaN, infinite or
+    negative weight raises QpnError(-4), as a target outside [0, Q) in a live row does.  No CPU fallback; argument errors are ValueErrors before any device work."""
+    if not isinstance(logits, torch.Tensor) or not isinstance(targets, torch.Tensor):
+        raise ValueError("cross_entropy: logits and targets must be torch.Tensors")
+    flat = logits.dim() == 2
+    if flat:
+        ok = targets.dim() == 1 and targets.shape[0] == logits.shape[0]
+    else:
+        ok = logits.dim() == 3 and targets.dim() == 2 and targets.shape[0] == logits.shape[0] and targets.shape[1] >= logits.shape[1]
+    if not ok or logits.numel() == 0:
+        raise ValueError("cross_entropy: logits (B, BL, Q) and targets (B, >= BL), or logits (rows, Q) and targets (rows,), expected, got %s and %s"
+                         % (tuple(logits.shape), tuple(targets.shape)))
+    ign, eps, code = _check_loss_options(ignore_index, label_smoothing, norm)
+    if sample_weights is not None:
+        _check_weights_like(sample_weights, logits.numel() // logits.shape[-1])
+    dev = logits.device
+    if dev.type != "cuda" or targets.device.type != "cuda" or (sample_weights is not None and sample_weights.device.type != "cuda"):
+        raise ValueError("qpnet_amd.train.cross_entropy runs on an AMD GPU only (logits are on %s, targets on %s); there is no CPU fallback" % (dev, targets.device))
+    return _CrossEntropy.apply(logits, targets, sample_weights, ign, eps, code)
 
 
 def _check_accum_steps(v):
@@ -1082,7 +1196,16 @@ class FusedTrainer:
     and gets no optimiser; its own status word is collected where the student's is and raises naming the teacher.  step(teacher_logits=...) takes precomputed logits
     instead (a cached teacher, an ensemble average), the "teacher" entry may then be absent.  A NaN or an infinity among the teacher logits skips the update and raises
     QpnError(-4) ("... teacher logits ...") like the other status errors.  step() / flush_loss() return the distillation total; forward_loss() and score() stay the
-    plain cross entropy.  A step being captured raises.  A trainer setting: not part of state_dict(), the teacher reaches no checkpoint."""
+    plain cross entropy.  A step being captured raises.  A trainer setting: not part of state_dict(), the teacher reaches no checkpoint.
+    ignore_index=k / label_smoothing=eps / loss_norm="rows" | "weights" and step(sample_weights=w): the criterion's options (DESIGN.md section 5, "Loss options";
+    qpn_train_loss_opts) -- what torch.nn.CrossEntropyLoss(ignore_index=, label_smoothing=) or reduction="none" times a mask gives.  Per row, w_r = w[b, t] (1 without
+    weights), 0 where the target equals ignore_index; the loss is (1 / N) sum_r w_r (lse(z) - (1 - eps) z_y - (eps / Q) sum_q z_q) with N the chunk's row count
+    ("rows", the default: the row-weighted combination over ranks and accumulation windows stays exact) or sum_r w_r ("weights": torch's `mean` with ignore_index;
+    only with accum_steps=1 and world_size=1 -- ValueError otherwise, as for eps outside [0, 1) or label_smoothing together with distill=).  Rows of weight 0 are not
+    read and their targets are not range-checked.  With distill= the weights multiply the whole row loss.  A NaN, infinite or negative weight skips the update and
+    raises QpnError(-4) ("... sample weights ...").  A step with any option set leaves the fused post-net tile as a distillation step does (profiles/loss_options.txt has
+    the cost); with every option at its default the step makes exactly the calls it always made.  forward_loss() and score() stay the plain cross entropy.  A step
+    being captured raises.  Trainer settings: not part of state_dict()."""
 
     # The device-side status word (bad taps / targets; the reference asserts in-line, qpnet.py:294, qpnet_train.py:525) is copied to pinned
     # memory behind every step; a step starts by looking at the copy made TWO steps earlier (the previous step is still queued on the
@@ -1090,9 +1213,15 @@ class FusedTrainer:
     # as when the word was read every 100 steps.  check_status() collects everything outstanding.
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, process_group=None, world_size=1, max_grad_norm=None, ema_decay=None,
-                 accum_steps=1, param_groups=None, distill=None):
+                 accum_steps=1, param_groups=None, distill=None, ignore_index=None, label_smoothing=0.0, loss_norm="rows"):
         self.model = model
         self._distill = _check_distill(model, distill)      # None, or (teacher or None, alpha, temperature)
+        self._loss_ignore, self._loss_eps, self._loss_norm = _check_loss_options(ignore_index, label_smoothing, loss_norm)
+        if self._loss_eps > 0.0 and self._distill is not None:
+            raise ValueError("label_smoothing cannot be combined with distill= (the soft targets already smooth)")
+        if self._loss_norm == 1 and (_check_accum_steps(accum_steps) > 1 or world_size > 1):
+            raise ValueError('loss_norm="weights" divides by one chunk\'s sum of weights: it needs accum_steps=1 and world_size=1 (got %r and %r); "rows" combines '
+                             "exactly over ranks and accumulation windows" % (accum_steps, world_size))
         self._teacher_logits = None                         # the teacher's (B, BL, Q) output, kept from step to step
         self._groups = self._group_scales = self._group_wds = None
         if param_groups is not None:
@@ -1154,7 +1283,7 @@ class FusedTrainer:
     def _norm(t, dtype, dev):
         return t if (t.dtype == dtype and t.device == dev and t.is_contiguous()) else t.to(dev, dtype).contiguous()
 
-    def step(self, x, h, t, d, blength, want_loss=True, maxd=None, h_grad=None, teacher_logits=None):
+    def step(self, x, h, t, d, blength, want_loss=True, maxd=None, h_grad=None, teacher_logits=None, sample_weights=None):
         """One optimisation step.  maxd = ceil(max(d)) of the chunk; a loader that built d on the host (the reference's
         train_generator does, qpnet_train.py:268-272) passes it in, otherwise it is read back from the device (one sync).
         Inputs are normalised like QPNet.forward does (int64 samples/targets, float32 features/factors, contiguous).
@@ -1164,7 +1293,30 @@ class FusedTrainer:
         nothing is exchanged; the row-count weighting of either never enters it.  A step that is being captured raises with it; after a step whose status word
         is set its contents are unspecified.
         teacher_logits: with distill= set, precomputed teacher logits for this chunk -- float32, CUDA, contiguous, (B, BL, n_quantize), on the inputs' device
-        (anything else: ValueError before any device work) -- in the place of a forward of distill["teacher"] (which may then be absent)."""
+        (anything else: ValueError before any device work) -- in the place of a forward of distill["teacher"] (which may then be absent).
+        sample_weights: per-row weights of this chunk's loss -- float32, CUDA, contiguous, (B, BL), on the inputs' device (anything else: ValueError before any
+        device work); see the class docstring (ignore_index / label_smoothing / loss_norm)."""
+        if sample_weights is None and self._loss_ignore is None and self._loss_eps == 0.0 and self._loss_norm == 0:
+            return self._step_plain(x, h, t, d, blength, want_loss, maxd, h_grad, teacher_logits)
+        # loss options: arm the handle, then the step as ever -- its forward-with-loss consumes the arm and runs k_ce_opt (with distill=: k_ce_distill's weighted
+        # form) where the cross entropy ran.  Every micro-step of an accumulation window, and every host path, is armed this way.
+        dev = x.device
+        if sample_weights is not None:
+            _check_sample_weights(sample_weights, x.shape[0], int(blength[0]), dev)
+        if dev.type != "cuda":
+            raise RuntimeError("qpnet_amd.FusedTrainer runs on an AMD GPU only (tensors are on %s)" % dev)
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("qpnet_amd.FusedTrainer: a step cannot be captured into a graph with loss options (sample_weights / ignore_index / label_smoothing / "
+                               "loss_norm: the arm is host state a replay would not renew)")
+        L, hd = self.model._native(dev)
+        opts = _make_loss_opts(sample_weights, self._loss_ignore, self._loss_eps, self._loss_norm)
+        try:
+            _lib.check(L.qpn_train_loss_opts(hd, C.byref(opts)))
+            return self._step_plain(x, h, t, d, blength, want_loss, maxd, h_grad, teacher_logits)
+        finally:
+            L.qpn_train_loss_opts(hd, None)              # (consumed by the step's forward; a step that raised in front of it must not leave the arm behind)
+
+    def _step_plain(self, x, h, t, d, blength, want_loss, maxd, h_grad, teacher_logits):
         if self._distill is not None or teacher_logits is not None:
             return self._distill_step(x, h, t, d, blength, want_loss, maxd, h_grad, teacher_logits)
         if h_grad is None:
