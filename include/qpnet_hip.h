@@ -156,6 +156,26 @@ int qpn_decode_sampling_ex(qpn_handle* h, float temperature, int top_k, float to
 typedef struct { uint64_t seed; uint32_t stream; float temperature; int32_t top_k; float top_p, min_p; } qpn_row_draw;
 int qpn_decode_row_sampling(qpn_handle* h, int n_rows, const qpn_row_draw* h_rows);
 
+/* Frame-rate sampling controls: a draw track, one record per (batch row b, feature frame f), f in [0, n_frames), for the QPN_MODE_SAMPLING calls enqueued on
+ * this handle from now on (sticky, like qpn_decode_row_sampling; h_track is a host array, row-major n_rows x n_frames, rows in the caller's INPUT order, copied
+ * into the handle).  n_frames is the F of the calls that follow: the frame axis of d_h.  Generated sample i of row b is the controlled draw above with an
+ * unchanged uniform and the four values of the record of the frame whose features that step reads,
+ *     f(i) = min(F - 1, c(i) / U),  c(i) = n_x - 1 + i,  U = upsampling_factor   (U == 0: f(i) = min(F - 1, c(i))),
+ * c(i) being the reference's current_index (qpnet.py:450-451: the un-padded column of the upsampled h that the generation loop indexes; the features
+ * are upsampled at qpnet.py:343-344).  Steps over the known prefix draw nothing and use no record.  Key and counter word are those of the call
+ * without a track: (call seed, batch row), or the row's (seed, stream) when qpn_decode_row_sampling records are set -- tracks and records compose, the
+ * four values of the records are then unused.  Hence, bit for bit: a track holding one record c in every frame of row b gives row b the samples of the
+ * per-row call whose record for b holds c; and two tracks that agree on frames [0, f*) of a row give the same samples [0, i*) of it, i* the first i
+ * with f(i) >= f*, whatever they hold elsewhere.  QPN_MODE_ARGMAX calls ignore the track.  An enqueue with B != n_rows or
+ * F != n_frames returns QPN_EINVAL naming which.  n_rows == 0 switches the track off: every later call is the call of a handle that never had one
+ * (same kernels, same bytes).  The table is kept in pinned memory that this call allocates (the enqueue allocates none), reaches the kernels by a copy
+ * on the call's stream without a host wait, and stays in force for the re-run after a launch that gave up.  Teacher forcing, the logits output, live
+ * output and cancel compose unchanged.  Checked before the device is looked at (works on a handle created without a GPU): QPN_EINVAL for n_rows < 0,
+ * n_frames < 1 or a NULL array with n_rows > 0, and per record the rules and messages of qpn_decode_sampling_ex with "row <b> frame <f>: " in front;
+ * QPN_ESTATE while a decode is in flight. */
+typedef struct { float temperature; int32_t top_k; float top_p, min_p; } qpn_frame_draw;
+int qpn_decode_frame_sampling(qpn_handle* h, int n_rows, int64_t n_frames, const qpn_frame_draw* h_track);
+
 /* Non-blocking.  For the decode in flight: h_done[B] = samples of each row (input order) that are final in the mirror;
  * *h_samples / *row_stride = the mirror (int32 sample ids, row b at *h_samples + b * *row_stride; host memory owned by the
  * handle, valid until the next enqueue); *running = 0 once everything the enqueue put on the stream has completed.  The

@@ -18,6 +18,10 @@ class QpnRowDraw(C.Structure):      # qpn_row_draw: one row's sampling record (q
     _fields_ = [("seed", C.c_uint64), ("stream", C.c_uint32), ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float)]
 
 
+class QpnFrameDraw(C.Structure):    # qpn_frame_draw: one (row, frame) record of a draw track (qpn_decode_frame_sampling)
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float)]
+
+
 class QpnLossOpts(C.Structure):     # qpn_loss_opts: the loss options (qpn_ce_loss_opts / qpn_distill_loss_opts / qpn_train_loss_opts)
     _fields_ = [("d_weights", C.c_void_p), ("n_weights", C.c_int64), ("use_ignore", C.c_int), ("ignore_index", C.c_int64), ("label_smoothing", C.c_float), ("norm", C.c_int)]
 
@@ -45,6 +49,7 @@ SYMBOLS = [
     ("qpn_decode_sampling", _i, [_vp, C.c_float, _i]),
     ("qpn_decode_sampling_ex", _i, [_vp, C.c_float, _i, C.c_float, C.c_float]),
     ("qpn_decode_row_sampling", _i, [_vp, _i, C.POINTER(QpnRowDraw)]),
+    ("qpn_decode_frame_sampling", _i, [_vp, _i, _i64, C.POINTER(QpnFrameDraw)]),
     ("qpn_decode_poll", _i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     ("qpn_decode_cancel", _i, [_vp]),
     ("qpn_decode_final_counts", _i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),

@@ -166,7 +166,7 @@ struct Ctx {
 // where the one-CU kernels of the calls with per-row records keep the row's record (stage_row_draw, decode_dev.h): eight LDS words behind everything else the launch
 // uses, the dev stamps included (launch_one_cu sizes the launch's LDS to match)
 __device__ __forceinline__ int one_cu_rowd(const DecodeParams& p) { return p.o_stamp + (p.stamps ? 120 * QPN_NW : 0); }
-template <bool ROW>
+template <int ROW>
 __device__ __forceinline__ void run_slot(Ctx& c, int slot, int64_t t, float4 (&w)[4]) {
     const DecodeParams& p = *c.p; const UttView& u = *c.u;
     float* sm = SM; int* smi = SMI;
@@ -269,9 +269,12 @@ __device__ __forceinline__ void run_slot(Ctx& c, int slot, int64_t t, float4 (&w
         if (lane == 0) { smi[p.o_samp] = cur; smi[p.o_samp + 1] = next; }
     } else if (op == OP_STAGE) {    // a = first wave of the staging group, b = waves in it
         const int stid = (c.wave - ta) * 64 + lane, nst = tb * 64;
+        int fdw = 0;      // draw track: the next step's frame record, requested in front of the staging loads and stored behind them (its pick is a step away)
+        if constexpr (ROW == 2) if (t + 2 < c.Ttot) fdw = frame_draw_load(p, u, (int)t + 1, stid);
         for (int i = stid; i < p.S; i += nst) { sm[p.o_skf + i] = 0.0f; sm[p.o_ska + i] = 0.0f; }
         if (t + 2 < c.Ttot) stage_aux(p, u, t + 1, stid, nst);
         if (t + 3 < c.Ttot) stage_taps(p, u, t + 2, stid, nst, p.status);
+        if constexpr (ROW == 2) if (t + 2 < c.Ttot) frame_draw_store(u, (int)t + 1, one_cu_rowd(p), stid, fdw);
     }
     if (nopf & TF_HASW) load_tile(w, p.wpk, nwoff, lane);
 }
@@ -283,6 +286,11 @@ __device__ __forceinline__ void run_slot(Ctx& c, int slot, int64_t t, float4 (&w
 #undef QPN_KERNEL_ROW
 #define QPN_KERNEL k_decode_r      // ... of the calls with per-row records
 #define QPN_KERNEL_ROW true
+#include "decode_slot_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
+#define QPN_KERNEL k_decode_t      // ... of the calls with a draw track
+#define QPN_KERNEL_ROW 2
 #include "decode_slot_kernel.h"
 #undef QPN_KERNEL
 #undef QPN_KERNEL_ROW
@@ -349,7 +357,7 @@ struct FastGeo {
     }
 };
 
-template <int C, int S, int Q, int NWV, bool RESL, bool ROW, int W0>
+template <int C, int S, int Q, int NWV, bool RESL, int ROW, int W0>
 __device__ __forceinline__ void fast_steps(const DecodeParams& p, const FastParams& f, const UttView& u,
                                            const int wave, const int lane0, const int tid0, const int Ttot) {
     using G = FastGeo<C, S, Q, NWV>;
@@ -545,9 +553,12 @@ __device__ __forceinline__ void fast_steps(const DecodeParams& p, const FastPara
             if (i >= 0 && lane == 0 && live_put(p, u, i, bi, creq)) smi[p.o_samp + 2] = 1;
         } else {
             const int stid = (wave - 1) * 64 + lane, nst = (NWV - 1) * 64;
+            int fdw = 0;      // draw track: the next step's frame record, requested in front of the staging loads and stored behind them (its pick is a step away)
+            if constexpr (ROW == 2) if (t + 2 < Ttot) fdw = frame_draw_load(p, u, t + 1, stid);
             for (int i = stid; i < S; i += nst) { sm[p.o_skf + i] = 0.0f; sm[p.o_ska + i] = 0.0f; }
             if (t + 2 < Ttot) stage_aux(p, u, t + 1, stid, nst);
             if (t + 3 < Ttot) stage_taps(p, u, t + 2, stid, nst, p.status);
+            if constexpr (ROW == 2) if (t + 2 < Ttot) frame_draw_store(u, t + 1, one_cu_rowd(p), stid, fdw);
         }
         if (stop) break;    // stopped on request at the previous step's publish point (this step has drained: its pick published nothing)
     }
@@ -566,7 +577,7 @@ __device__ __forceinline__ void fast_steps(const DecodeParams& p, const FastPara
 #undef QPN_LAYER
 }
 
-template <int C, int S, int Q, int NWV, bool RESL, bool ROW, int W0>
+template <int C, int S, int Q, int NWV, bool RESL, int ROW, int W0>
 __device__ __forceinline__ void fast_dispatch(const DecodeParams& p, const FastParams& f, const UttView& u,
                                               const int wave, const int lane, const int tid, const int Ttot) {
     constexpr int NB = FastGeo<C, S, Q, NWV>::next_boundary(W0);
@@ -587,6 +598,11 @@ __device__ __forceinline__ void fast_dispatch(const DecodeParams& p, const FastP
 #undef QPN_KERNEL_ROW
 #define QPN_KERNEL k_decode_fast_r      // ... of the calls with per-row records
 #define QPN_KERNEL_ROW true
+#include "decode_fast_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
+#define QPN_KERNEL k_decode_fast_t      // ... of the calls with a draw track
+#define QPN_KERNEL_ROW 2
 #include "decode_fast_kernel.h"
 #undef QPN_KERNEL
 #undef QPN_KERNEL_ROW
@@ -665,13 +681,14 @@ extern "C" int qpn_create(const qpn_config* cfg, qpn_handle** out) {
 extern "C" void qpn_destroy(qpn_handle* h) {      // (every member may still be null)
     if (!h) return;
     if (h->device >= 0) {
-        void* bufs[] = {h->d_map, h->d_wpk, h->d_tasks, h->d_qb, h->d_bd, h->d_status, h->d_bias_src, h->d_pproj, h->d_ring, h->d_known, h->d_utts, h->d_xch, h->d_adam_table, h->d_rows};
+        void* bufs[] = {h->d_map, h->d_wpk, h->d_tasks, h->d_qb, h->d_bd, h->d_status, h->d_bias_src, h->d_pproj, h->d_ring, h->d_known, h->d_utts, h->d_xch, h->d_adam_table, h->d_rows, h->d_track};
         for (void* b : bufs) if (b) (void)hipFree(b);
         qpn_train_destroy(h->train);
         if (h->ev0) (void)hipEventDestroy(h->ev0);
         if (h->ev1) (void)hipEventDestroy(h->ev1);
         if (h->h_utts_pinned) (void)hipHostFree(h->h_utts_pinned);
         if (h->h_rows_pinned) (void)hipHostFree(h->h_rows_pinned);
+        if (h->h_track_pinned) (void)hipHostFree(h->h_track_pinned);
         if (h->h_live) (void)hipHostFree(h->h_live);
         if (h->h_live_done) (void)hipHostFree(h->h_live_done);
         if (h->h_cancel) (void)hipHostFree(h->h_cancel);
@@ -786,7 +803,8 @@ static int launch_one_cu(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, h
     const int stamp_floats = p.stamps ? 120 * QPN_NW : 0;
     const int nres_tiles = (g.C * g.C / 1024) * (g.L - 1);
     p.o_wres = (p.o_tasks + 3) & ~3;
-    const int rowd_floats = p.row_draw ? 8 : 0;      // a call with per-row records: the row's record, behind everything else (stage_row_draw, decode_dev.h)
+    const bool trackk = p.mode == QPN_MODE_SAMPLING_TRACK;      // a draw track: the kernels whose pick reads the step's frame record (sample_pick<2>)
+    const int rowd_floats = trackk ? 16 : p.row_draw ? 8 : 0;      // a call with per-row records: the row's record, behind everything else (stage_row_draw, decode_dev.h); a draw track: two frame records behind that
     const bool resl = (fast64 || fast32) && g.L >= 2 && !h->dk.no_resl &&
                       ((size_t)p.o_wres + (size_t)nres_tiles * 1024 + stamp_floats + rowd_floats) * sizeof(float) <= 160 * 1024;
     const int use_floats = resl ? p.o_wres + nres_tiles * 1024 : p.lds_floats;
@@ -795,12 +813,14 @@ static int launch_one_cu(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, h
     if (rowd_floats && lds_bytes > 160 * 1024) { qpn_set_error("per-row sampling records need 32 bytes of LDS behind the %d KiB of step state of this geometry", (int)(lds_bytes >> 10)); return QPN_EINVAL; }
     typedef void (*FastKernel)(DecodeParams, FastParams);      // the ONE choice: a straight-line kernel, or (null) the interpreter
     const bool rowk = p.mode == QPN_MODE_SAMPLING_ROW;      // per-row records: the kernels whose pick reads them (sample_pick<true>)
-    const FastKernel fast = rowk ? (fast64 ? (resl ? k_decode_fast_r<64, 256, 256, 16, true> : k_decode_fast_r<64, 256, 256, 16, false>)
+    const FastKernel fast = trackk ? (fast64 ? (resl ? k_decode_fast_t<64, 256, 256, 16, true> : k_decode_fast_t<64, 256, 256, 16, false>)
+                                    : fast32 ? (resl ? k_decode_fast_t<32, 32, 256, 16, true> : k_decode_fast_t<32, 32, 256, 16, false>) : nullptr)
+                          : rowk ? (fast64 ? (resl ? k_decode_fast_r<64, 256, 256, 16, true> : k_decode_fast_r<64, 256, 256, 16, false>)
                                   : fast32 ? (resl ? k_decode_fast_r<32, 32, 256, 16, true> : k_decode_fast_r<32, 32, 256, 16, false>) : nullptr)
                           : fast64 ? (resl ? k_decode_fast<64, 256, 256, 16, true> : k_decode_fast<64, 256, 256, 16, false>)
                           : fast32 ? (resl ? k_decode_fast<32, 32, 256, 16, true> : k_decode_fast<32, 32, 256, 16, false>) : nullptr;
     typedef void (*SlotKernel)(DecodeParams);
-    const SlotKernel interp = rowk ? k_decode_r : k_decode;
+    const SlotKernel interp = trackk ? k_decode_t : rowk ? k_decode_r : k_decode;
     if (lds_bytes > 48 * 1024) QPN_HIP(hipFuncSetAttribute(fast ? (const void*)fast : (const void*)interp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     if (fast) hipLaunchKernelGGL(fast, dim3(n), dim3(QPN_NT), lds_bytes, stream, p, h->prog.fp);
     else hipLaunchKernelGGL(interp, dim3(n), dim3(QPN_NT), lds_bytes, stream, p);
@@ -885,12 +905,23 @@ static int decode_enqueue_impl(qpn_handle* h, hipStream_t stream, const DecodePl
         u.row = b; u.pad_ = 0;
     }
     QPN_HIP(hipMemcpyAsync(h->d_utts, utts, (size_t)B * sizeof(UttDesc), hipMemcpyHostToDevice, stream));
-    const bool row_draw = c.mode == QPN_MODE_SAMPLING && !c.rows.empty();      // per-row records (qpn_decode_row_sampling): staged and copied like the descriptors, no host wait
+    const bool track = c.mode == QPN_MODE_SAMPLING && c.track;                 // a draw track (qpn_decode_frame_sampling): the table goes from the setter's pinned staging, no host wait
+    const bool row_draw = c.mode == QPN_MODE_SAMPLING && (!c.rows.empty() || track);      // per-row records (qpn_decode_row_sampling): staged and copied like the descriptors, no host wait
     if (row_draw) {
         rc = grow(&h->d_rows, &h->rows_cap, (size_t)B); if (rc) return rc;
-        rc = grow_pinned(&h->h_rows_pinned, &h->h_rows_cap, (size_t)B); if (rc) return rc;
-        memcpy(h->h_rows_pinned, c.rows.data(), (size_t)B * sizeof(RowDraw));
+        rc = grow_pinned(&h->h_rows_pinned, &h->h_rows_cap, (size_t)B); if (rc) return rc;      // (a track call: the setter has sized it)
+        if (!c.rows.empty()) memcpy(h->h_rows_pinned, c.rows.data(), (size_t)B * sizeof(RowDraw));
+        else for (int b = 0; b < B; ++b) {      // a track without records: key and counter word of the uniform call, (call seed, batch row); the track kernels read nothing else of it
+            RowDraw& o = h->h_rows_pinned[b];
+            o.seed_lo = (unsigned)c.seed; o.seed_hi = (unsigned)(c.seed >> 32); o.stream = (unsigned)b;
+            o.inv_temp = c.inv_temp; o.top_k = c.top_k; o.top_p = c.top_p; o.min_p = c.min_p; o.pad_ = 0;
+        }
         QPN_HIP(hipMemcpyAsync(h->d_rows, h->h_rows_pinned, (size_t)B * sizeof(RowDraw), hipMemcpyHostToDevice, stream));
+    }
+    if (track) {
+        const size_t n = (size_t)B * (size_t)F;      // (the enqueue has checked B and F against the table)
+        rc = grow(&h->d_track, &h->track_cap, n); if (rc) return rc;
+        QPN_HIP(hipMemcpyAsync(h->d_track, h->h_track_pinned, n * sizeof(FrameDraw), hipMemcpyHostToDevice, stream));
     }
     if (c.plan.needs_ring) QPN_HIP(hipMemsetAsync(h->d_ring, 0, ring_floats * (size_t)B * sizeof(float), stream));
     QPN_HIP(hipMemsetAsync(h->d_status, 0, 64, stream));
@@ -902,6 +933,7 @@ static int decode_enqueue_impl(qpn_handle* h, hipStream_t stream, const DecodePl
     p.inv_temp = c.inv_temp; p.top_k = c.top_k; p.top_p = c.top_p; p.min_p = c.min_p;
     if (c.mode == QPN_MODE_SAMPLING && (c.inv_temp != 1.0f || c.top_k != 0 || c.top_p != 1.0f || c.min_p != 0.0f)) p.mode = QPN_MODE_SAMPLING_CTL;
     if (row_draw) { p.mode = QPN_MODE_SAMPLING_ROW; p.row_draw = h->d_rows; }      // the records take the place of the call's seed and of the four uniform values
+    if (track) { p.mode = QPN_MODE_SAMPLING_TRACK; p.frame_draw = h->d_track; p.n_frames = F; }      // ... and the track's frame records the place of the four values
     p.stamps = h->dk.stamps ? (long long*)(h->d_status + 16) : nullptr;
     p.pproj = h->d_pproj; p.dfac = c.d_dfac; p.known = h->d_known; p.teacher = d_teacher; p.out = c.d_out; p.logits = d_logits; p.ring = h->d_ring;
     QPN_HIP(hipEventRecord(h->ev0, stream));
@@ -930,11 +962,16 @@ extern "C" int qpn_decode_enqueue(qpn_handle* h, int B, int n_x, int64_t F, int6
     if (mode == QPN_MODE_SAMPLING && !h->samp_rows.empty() && (size_t)B != h->samp_rows.size()) {
         qpn_set_error("B = %d rows, but qpn_decode_row_sampling set n_rows = %zu records (one per batch row; n_rows = 0 switches them off)", B, h->samp_rows.size()); return QPN_EINVAL;
     }
+    if (mode == QPN_MODE_SAMPLING && h->track_rows > 0) {
+        if (B != h->track_rows) { qpn_set_error("B = %d rows, but qpn_decode_frame_sampling set n_rows = %d (one track per batch row; n_rows = 0 switches the track off)", B, h->track_rows); return QPN_EINVAL; }
+        if (F != h->track_frames) { qpn_set_error("F = %lld frames, but qpn_decode_frame_sampling set n_frames = %lld (one record per feature frame of h)", (long long)F, (long long)h->track_frames); return QPN_EINVAL; }
+    }
     qpn_handle::DecodeCall& c = h->call;
     c.B = B; c.n_x = n_x; c.F = F; c.Td = Td; c.d_x = d_x; c.d_h = d_h; c.d_dfac = d_dfac; c.d_is_f32 = d_is_f32;
     c.n_samples.assign(h_n_samples, h_n_samples + B); c.maxd = maxd; c.mode = mode; c.seed = seed;
     c.inv_temp = h->samp_inv_temp; c.top_k = h->samp_top_k; c.top_p = h->samp_top_p; c.min_p = h->samp_min_p;
     if (mode == QPN_MODE_SAMPLING) c.rows = h->samp_rows; else c.rows.clear();
+    c.track = mode == QPN_MODE_SAMPLING && h->track_rows > 0;
     c.d_teacher = d_teacher; c.d_out = d_out; c.d_logits = d_logits;
     h->live_call = h->live_every > 0;
     h->live_final = false;
@@ -993,6 +1030,34 @@ extern "C" int qpn_decode_row_sampling(qpn_handle* h, int n_rows, const qpn_row_
     }
     if (h->pending) { qpn_set_error("a decode is in flight: call qpn_decode_finish first"); return QPN_ESTATE; }
     h->samp_rows.swap(rows);
+    return QPN_OK;
+}
+
+extern "C" int qpn_decode_frame_sampling(qpn_handle* h, int n_rows, int64_t n_frames, const qpn_frame_draw* h_track) {
+    if (!h) { qpn_set_error("null handle"); return QPN_EINVAL; }
+    if (n_rows < 0) { qpn_set_error("n_rows must be >= 0 (0: off; got %d)", n_rows); return QPN_EINVAL; }
+    if (n_rows > 0 && n_frames < 1) { qpn_set_error("n_frames must be >= 1 (got %lld)", (long long)n_frames); return QPN_EINVAL; }
+    if (n_rows > 0 && !h_track) { qpn_set_error("h_track is NULL with n_rows = %d", n_rows); return QPN_EINVAL; }
+    if (n_rows > 0 && n_frames > (int64_t)(((size_t)1 << 40) / (size_t)n_rows)) { qpn_set_error("a track of %d x %lld records is too large", n_rows, (long long)n_frames); return QPN_EINVAL; }
+    const size_t n = n_rows > 0 ? (size_t)n_rows * (size_t)n_frames : 0;
+    std::vector<FrameDraw> track(n);
+    for (size_t i = 0; i < n; ++i) {
+        const qpn_frame_draw& r = h_track[i];
+        float inv; int k;
+        if (sampling_controls(r.temperature, r.top_k, r.top_p, r.min_p, h->g.Q, &inv, &k)) {      // the rules and messages of qpn_decode_sampling_ex, with the row and the frame in front
+            const std::string why = qpn_last_error();
+            qpn_set_error("row %d frame %lld: %s", (int)(i / (size_t)n_frames), (long long)(i % (size_t)n_frames), why.c_str()); return QPN_EINVAL;
+        }
+        FrameDraw& o = track[i];
+        o.inv_temp = inv; o.top_k = k; o.top_p = r.top_p; o.min_p = r.min_p;
+    }
+    if (h->pending) { qpn_set_error("a decode is in flight: call qpn_decode_finish first"); return QPN_ESTATE; }
+    if (n && h->device >= 0) {      // the pinned staging the enqueue copies from (and that of the records it makes for a call without any): allocated here, so that the enqueue allocates nothing on the host
+        int rc = grow_pinned(&h->h_track_pinned, &h->h_track_cap, n); if (rc) return rc;
+        rc = grow_pinned(&h->h_rows_pinned, &h->h_rows_cap, (size_t)n_rows); if (rc) return rc;
+        memcpy(h->h_track_pinned, track.data(), n * sizeof(FrameDraw));
+    }
+    h->track_rows = n_rows; h->track_frames = n_rows > 0 ? n_frames : 0;
     return QPN_OK;
 }
 

@@ -71,6 +71,11 @@ __device__ __forceinline__ void gather_vec(const u64* src, int n, unsigned tag, 
 #include "decode_coop_kernel.h"
 #undef QPN_KERNEL
 #undef QPN_KERNEL_ROW
+#define QPN_KERNEL k_decode_coop_t      // ... of the calls with a draw track
+#define QPN_KERNEL_ROW 2
+#include "decode_coop_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
 
 // ------------------------------------------------------------------------------------------ host side
 // l.rows utterances from l.first on (the kernel's b0), G workgroups each: the caller's launches hold no more than are resident together (one workgroup per CU)
@@ -93,10 +98,11 @@ int qpn_launch_decode_coop(qpn_handle* h, DecodeParams p, const DecodeLaunch& l,
     // LDS of the kernel
     int lds = 2 * g.Cp + L * g.Cp + g.Cp + 2 * g.Sp + ((Q + 3) & ~3) + ((2 * c.SB + 3) & ~3) + L * 2 * c.CB + 4 + L * (c.CB + c.SB) + c.SB + c.QB;
     if (p.mode == QPN_MODE_SAMPLING_ROW) lds += 8;      // a call with per-row records: the row's record, eight words behind the rest (o_rd of coop_body<true>)
+    if (p.mode == QPN_MODE_SAMPLING_TRACK) lds += 16;   // a call with a draw track: the record and two frame records (sample_pick<2>, decode_dev.h)
     const size_t lds_bytes = (size_t)lds * sizeof(float);
     if (lds_bytes > 160 * 1024) { qpn_set_error("cooperative decode: %zu KiB of step state per workgroup exceed LDS (use more workgroups per utterance)", lds_bytes >> 10); return QPN_EINVAL; }
     typedef void (*CoopKernel)(DecodeParams, FastParams, CoopParams, int);
-    const CoopKernel kfn = p.mode == QPN_MODE_SAMPLING_ROW ? k_decode_coop_r : k_decode_coop;
+    const CoopKernel kfn = p.mode == QPN_MODE_SAMPLING_TRACK ? k_decode_coop_t : p.mode == QPN_MODE_SAMPLING_ROW ? k_decode_coop_r : k_decode_coop;
     QPN_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     QPN_HIP(hipMemsetAsync(h->d_xch, 0, xwords * sizeof(unsigned long long), stream));      // tags, rings, abort flag
     hipLaunchKernelGGL(kfn, dim3(G, l.rows), dim3(COOP_NT), lds_bytes, stream, p, d.fp, c, l.first);

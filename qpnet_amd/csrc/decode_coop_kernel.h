@@ -1,7 +1,7 @@
 // decode_coop_kernel.h -- the body of the per-utterance cooperative decode kernel, included twice by decode_coop.hip: as k_decode_coop (QPN_KERNEL_ROW false) and as
 // k_decode_coop_r, the kernel of the calls with per-row sampling records (QPN_KERNEL_ROW true).  Textual inclusion for the reason given in decode_coopb_kernel.h.
 __global__ __launch_bounds__(COOP_NT) void QPN_KERNEL(DecodeParams p, FastParams f, CoopParams c, int b0) {
-    constexpr bool ROW = QPN_KERNEL_ROW;
+    constexpr int ROW = QPN_KERNEL_ROW;      // (false, true, or 2: the kernel of the calls with a draw track -- sample_pick, decode_dev.h)
     float* sm = SM; int* smi = SMI;
     const int gidx = blockIdx.x, b = b0 + blockIdx.y;
     const UttView u = make_view(p, p.utts[b]);
@@ -57,6 +57,7 @@ __global__ __launch_bounds__(COOP_NT) void QPN_KERNEL(DecodeParams p, FastParams
             else { fr = ut; j = 0; }
             const float wj = p.U > 0 ? p.flat[p.up_w + j] : 1.0f;
             const float* pf = u.pproj + (size_t)fr * L * 2 * C;
+            if constexpr (ROW == 2) stage_frame_draw(p, u, t, o_rd, tid);      // draw track: this step's frame record, beside its aux terms
             for (int i = tid; i < n_aux; i += COOP_NT) {
                 const int l = i / (2 * CB), r = i - l * 2 * CB, half = r / CB, nat = half * C + c0 + (r - half * CB);
                 sm[o_aux + i] = __builtin_fmaf(wj, pf[l * 2 * C + nat], p.qb[l * 2 * C + nat]);

@@ -203,6 +203,11 @@ __device__ __forceinline__ float close_elem(const float* P, int r, int n) {
 #include "decode_coopb_kernel.h"
 #undef QPN_KERNEL
 #undef QPN_KERNEL_ROW
+#define QPN_KERNEL k_decode_coopb_t      // ... of the calls with a draw track
+#define QPN_KERNEL_ROW 2
+#include "decode_coopb_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
 
 // ------------------------------------------------------------------------------------------ host side
 // geometries this kernel takes: 8 channels per workgroup make the gate tile; S / G and Q / G rows fit their tiles; K = 256 or 512 chunks trees
@@ -240,8 +245,9 @@ int qpn_launch_decode_coopb(qpn_handle* h, DecodeParams p, const DecodeLaunch& l
     int rc = grow_xch(h, xwords); if (rc) return rc;
     c.xch = h->d_xch + 16; c.abort = (int*)h->d_xch;
     const bool rowk = p.mode == QPN_MODE_SAMPLING_ROW;      // per-row records: the kernel whose pick reads them (sample_pick<true>), and 16 records of LDS behind the rest
-    const size_t lds_bytes = ((size_t)cbb_lds_floats(C, L) + (rowk ? CBB_NU * 8 : 0)) * sizeof(float);
-    if (lds_bytes > 160 * 1024) { qpn_set_error("per-row sampling records need 512 bytes of LDS behind the %d KiB of this geometry's batched cooperative kernel", (int)(lds_bytes >> 10)); return QPN_EINVAL; }
+    const bool trackk = p.mode == QPN_MODE_SAMPLING_TRACK;  // a draw track: its kernel (sample_pick<2>), and two frame records more per utterance
+    const size_t lds_bytes = ((size_t)cbb_lds_floats(C, L) + (trackk ? CBB_NU * 16 : rowk ? CBB_NU * 8 : 0)) * sizeof(float);
+    if (lds_bytes > 160 * 1024) { qpn_set_error("per-row sampling records need 512 (a draw track: 1024) bytes of LDS behind the %d KiB of this geometry's batched cooperative kernel", (int)(lds_bytes >> 10)); return QPN_EINVAL; }
     // first poll of an edge's gather: 8 / 4 x 128 clocks after the exchange waves reach it (QPN_COOPB_DELAY_G / _X / _T, dev).  Polls sent before anything can have been
     // published return stale a round trip later and load the memory side the publishes go through: B = 20: 151 -> 113 us per step, B = 4: 98.6 -> 91.3, B = 64: 220 -> 189
     // (tools/coopb_delay_sweep.py, profiles/r06_coopb_poll_delay.txt)
@@ -250,7 +256,7 @@ int qpn_launch_decode_coopb(qpn_handle* h, DecodeParams p, const DecodeLaunch& l
     c.dev_nostream = getenv("QPN_COOPB_NOSTREAM") ? 1 : 0; c.dev_nocheck = getenv("QPN_COOPB_NOCHECK") ? 1 : 0;
 #endif
     typedef void (*CoopbKernel)(const DecodeParams, const CoopbParams);
-    const CoopbKernel kfn = rowk ? k_decode_coopb_r : k_decode_coopb;
+    const CoopbKernel kfn = trackk ? k_decode_coopb_t : rowk ? k_decode_coopb_r : k_decode_coopb;
     QPN_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     QPN_HIP(hipMemsetAsync(h->d_xch, 0, xwords * sizeof(unsigned long long), stream));      // tags, rings, abort flag
 #ifdef QPN_TESTING

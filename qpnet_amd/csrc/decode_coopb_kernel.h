@@ -3,7 +3,7 @@
 // template behind two one-line kernels: inlined through such a wrapper the same source compiled to other machine code (fewer instructions, another register
 // allocation) and default calls ran 0.65 % slower; included, k_decode_coopb is instruction for instruction the kernel it was before the second one existed.
 __global__ __launch_bounds__(CBB_NT) void QPN_KERNEL(const DecodeParams p, const CoopbParams c) {
-    constexpr bool ROW = QPN_KERNEL_ROW;
+    constexpr int ROW = QPN_KERNEL_ROW;      // (false, true, or 2: the kernel of the calls with a draw track -- sample_pick, decode_dev.h)
     float* sm = SM; int* smi = SMI;
     const int w = blockIdx.x, grp = blockIdx.y;
     const int wblk = (int)(c.base4 + (long long)w * c.per_w);    // float4 offset of my fragments (relative to the buffer descriptor's base)
@@ -42,7 +42,8 @@ __global__ __launch_bounds__(CBB_NT) void QPN_KERNEL(const DecodeParams p, const
     const int o_ctl = o; o += 4;
     const int o_prof = o; o += 32;                            // (dev: phase times, -DQPN_ENABLE_STAMPS builds)
     const int o_ud = (o + 1) & ~1; o = o_ud + CBB_NU * 22;                     // the group's utterance descriptors (UttDesc, 88 bytes each): read every step, a dependent global load otherwise
-    const int o_rd = o; if constexpr (ROW) o += CBB_NU * 8;   // ... and, in the kernel of the calls with per-row records (qpn_decode_row_sampling), their sampling records (RowDraw, 32 bytes each), copied once for the same reason
+    constexpr int RDW = ROW == 2 ? 16 : 8;                    // words of an utterance's block at o_rd: with a draw track, two frame records behind the RowDraw (sample_pick<2>, decode_dev.h)
+    const int o_rd = o; if constexpr (ROW) o += CBB_NU * RDW;   // ... and, in the kernel of the calls with per-row records (qpn_decode_row_sampling), their sampling records (RowDraw, 32 bytes each), copied once for the same reason
     const int o_lg = o_x;                                     // logits [nb][Q] (the images are free by then)
     for (int i = tid; i < o; i += CBB_NT) sm[i] = 0.0f;
     __syncthreads();
@@ -57,7 +58,8 @@ __global__ __launch_bounds__(CBB_NT) void QPN_KERNEL(const DecodeParams p, const
     static_assert(sizeof(UttDesc) == 88, "the LDS copy of the descriptors assumes 22 ints");
     for (int i = tid; i < nb * 22; i += CBB_NT) smi[o_ud + i] = ((const int*)(p.utts + b0))[i];
     const UttDesc* const uds = (const UttDesc*)(smi + o_ud);
-    if constexpr (ROW) for (int i = tid; i < nb * 8; i += CBB_NT) smi[o_rd + i] = ((const int*)(p.row_draw + p.utts[b0 + (i >> 3)].row))[i & 7];
+    if constexpr (ROW == 2) { for (int i = tid; i < nb * 8; i += CBB_NT) smi[o_rd + (i >> 3) * RDW + (i & 7)] = ((const int*)(p.row_draw + p.utts[b0 + (i >> 3)].row))[i & 7]; }
+    else if constexpr (ROW) for (int i = tid; i < nb * 8; i += CBB_NT) smi[o_rd + i] = ((const int*)(p.row_draw + p.utts[b0 + (i >> 3)].row))[i & 7];
     int Tmax = 0;
     for (int k = 0; k < nb; ++k) { const UttDesc ud = p.utts[b0 + k]; const int tt = ud.n0 + ud.n_samples; Tmax = tt > Tmax ? tt : Tmax; }
     if (tid < nb) { const UttView u = make_view(p, p.utts[b0 + tid]); smi[o_samp + 2 * tid] = u.known[0]; smi[o_samp + 2 * tid + 1] = u.n0 + u.n_samples >= 3 ? u.known[1] : 0; }
@@ -106,6 +108,7 @@ __global__ __launch_bounds__(CBB_NT) void QPN_KERNEL(const DecodeParams p, const
                     int f = 0;
                     if (ut >= 0) f = p.U > 0 ? (int)((unsigned)ut / (unsigned)p.U) : ut;
                     fr = (int)(ud.pproj / (2 * C)) + f * L;
+                    if constexpr (ROW == 2) stage_frame_draw(p, u, ts, o_rd + RDW * k, tid >> 4);      // draw track: the step's frame record of every utterance, a step ahead like the rest of this state (threads 0..63: word tid >> 4)
                     const int widx = ts < u.n0 - 1 ? ts - (u.n0 - 1) : 0;
                     for (int l = tid >> 4; l < L; l += 16) {
                         const int* e = smi + o_lt + l * CBB_LT;
@@ -146,7 +149,7 @@ __global__ __launch_bounds__(CBB_NT) void QPN_KERNEL(const DecodeParams p, const
             if (i >= 0 && u.logits && w == 0) for (int q = lane; q < Q; q += 64) u.logits[(size_t)i * Q + q] = sm[o_lg + k * Q + q];
             int next;
             if (i >= 0) {
-                if (p.mode != QPN_MODE_ARGMAX) bi = sample_pick<ROW>(p, (unsigned)u.row, o_rd + 8 * k, o_lg + k * Q, Q, (unsigned)i, lane);
+                if (p.mode != QPN_MODE_ARGMAX) bi = sample_pick<ROW>(p, (unsigned)u.row, o_rd + RDW * k, o_lg + k * Q, Q, (unsigned)i, lane);
                 next = bi;
                 if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
                 if (lane == 0 && w == 0) {

@@ -378,9 +378,45 @@ __device__ __forceinline__ RowDraw row_draw_lds(int o_rd) {
 // behind one more compare, the second draw cost calls WITHOUT records 1.8 % of the batched cooperative kernel's step time (repo-default model at B = 20) and, merged
 // into one call behind selects, the one-CU kernels 68 bytes of scratch per lane.  Each kernel body is a file that its .hip includes twice (decode_*_kernel.h): with
 // ROW = false the source is what it was, and the compiled kernels have the instruction counts, scratch sizes and register figures they had.
-template <bool ROW>
+//
+// ROW == 2: the kernels of the calls with a draw track (qpn_decode_frame_sampling; p.mode == QPN_MODE_SAMPLING_TRACK: k_decode_t, k_decode_fast_t, k_decode_coop_t, k_decode_coopb_t),
+// the third inclusion of the same bodies.  Key and counter word come from the row's record as above; the four values are those of the feature frame the step reads,
+//     f(i) = min(F - 1, (n_x - 1 + i) / U)        (U == 0: min(F - 1, n_x - 1 + i); the un-padded time aux_time() returns for generation step i, reference qpnet.py:450-451).
+// A row's block at SMI[o_rd] is 16 words here: the RowDraw, then two frame records, of the even and of the odd generation steps.  The record's address depends on i only, so
+// it is fetched where the kernel stages step i's aux features -- in the one-CU kernels that is during the pick of step i - 1, hence the two slots -- by four lanes, one word
+// each, and a workgroup barrier lies between that store and the pick that reads it: the load is never on the pick's dependent chain.
+__device__ __forceinline__ const int* frame_draw_record(const DecodeParams& p, int row, int ut) {      // ut: the un-padded time of a generation step (>= 0)
+    int64_t f = p.U > 0 ? (int64_t)((unsigned)ut / (unsigned)p.U) : (int64_t)ut;
+    f = f < p.n_frames - 1 ? f : p.n_frames - 1;
+    return (const int*)(p.frame_draw + ((size_t)row * (size_t)p.n_frames + (size_t)(f > 0 ? f : 0)));
+}
+// step t's record, one word in each of the lanes that call with word = 0..3 (0 elsewhere, and for the steps of the warm-up, which draw nothing)
+__device__ __forceinline__ int frame_draw_load(const DecodeParams& p, const UttView& u, int t, int word) {
+    const int i = t - (u.n0 - 1);
+    return (i >= 0 && word < 4) ? frame_draw_record(p, u.row, t - u.n_pad)[word] : 0;
+}
+__device__ __forceinline__ void frame_draw_store(const UttView& u, int t, int o_rd, int word, int v) {
+    const int i = t - (u.n0 - 1);
+    if (i >= 0 && word < 4) SMI[o_rd + 8 + 4 * (i & 1) + word] = v;
+}
+__device__ __forceinline__ void stage_frame_draw(const DecodeParams& p, const UttView& u, int t, int o_rd, int word) {
+    frame_draw_store(u, t, o_rd, word, frame_draw_load(p, u, t, word));
+}
+// the frame record of generation step `step` read from LDS (every lane reads the same words): back into scalar registers, as row_draw_lds does
+__device__ __forceinline__ FrameDraw frame_draw_lds(int o_rd, unsigned step) {
+    const int* r = SMI + o_rd + 8 + 4 * (int)(step & 1u);
+    FrameDraw o;
+    o.inv_temp = __int_as_float(__builtin_amdgcn_readfirstlane(r[0])); o.top_k = __builtin_amdgcn_readfirstlane(r[1]);
+    o.top_p = __int_as_float(__builtin_amdgcn_readfirstlane(r[2])); o.min_p = __int_as_float(__builtin_amdgcn_readfirstlane(r[3]));
+    return o;
+}
+template <int ROW>
 __device__ __forceinline__ int sample_pick(const DecodeParams& p, unsigned row, int o_rd, int o_lg, int Q, unsigned step, int lane) {
-    if constexpr (ROW) {
+    if constexpr (ROW == 2) {
+        const RowDraw r = row_draw_lds(o_rd);
+        const FrameDraw d = frame_draw_lds(o_rd, step);
+        return sample_wave_ctl<true>(o_lg, Q, sample_uniform(row_seed(r), r.stream, step), d.inv_temp, d.top_k, d.top_p, d.min_p, lane);
+    } else if constexpr (ROW == 1) {
         const RowDraw r = row_draw_lds(o_rd);
         return sample_wave_ctl<true>(o_lg, Q, sample_uniform(row_seed(r), r.stream, step), r.inv_temp, r.top_k, r.top_p, r.min_p, lane);
     } else {

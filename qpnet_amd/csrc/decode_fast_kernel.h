@@ -2,7 +2,7 @@
 // k_decode_fast_r<...>, the kernels of the calls with per-row sampling records (QPN_KERNEL_ROW true).  Textual inclusion for the reason given in decode_coopb_kernel.h.
 template <int C, int S, int Q, int NWV, bool RESL>
 __global__ __launch_bounds__(NWV * 64) void QPN_KERNEL(DecodeParams p, FastParams f) {
-    constexpr bool ROW = QPN_KERNEL_ROW;
+    constexpr int ROW = QPN_KERNEL_ROW;      // (false, true, or 2: the kernel of the calls with a draw track -- sample_pick, decode_dev.h)
     using G = FastGeo<C, S, Q, NWV>;
     static_assert(G::R <= 8 && G::RS <= 32 && G::ZT >= 1 && G::RT >= 1, "geometry not covered by the fast kernel");
     constexpr int NTH = NWV * 64;
@@ -26,6 +26,7 @@ __global__ __launch_bounds__(NWV * 64) void QPN_KERNEL(DecodeParams p, FastParam
         if (lane == 0) { smi[p.o_samp] = u.known[0]; smi[p.o_samp + 1] = u.known[1]; }
     }
     stage_aux(p, u, 1, tid, NTH);
+    if constexpr (ROW == 2) stage_frame_draw(p, u, 1, one_cu_rowd(p), tid);      // (the first step's frame record; later ones: beside the pick, a step ahead)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (Ttot > 3) stage_taps(p, u, 2, tid, NTH, p.status);

@@ -452,7 +452,8 @@ __device__ __forceinline__ void skip_fixed_role(const DecodeParams& p, const Fas
 
 // ------------------------------------------------------------------------------------------------ P: post 1x1 #2, pick, causal rows
 template <int NU, int CTL>       // CTL: the launch draws with a sampling control set (QPN_MODE_SAMPLING_CTL: sample_wave_ctl; 2: with the top_p / min_p cut; 3: per-row records,
-                                 // QPN_MODE_SAMPLING_ROW: key, counter word and values from the utterance's record in its view); kernels of their own, see k_decode_pipe_c / k_decode_pipe_r
+                                 // QPN_MODE_SAMPLING_ROW: key, counter word and values from the utterance's record in its view; 4: a draw track, QPN_MODE_SAMPLING_TRACK: key and counter
+                                 // word from that record, the four values from the record of the step's feature frame); kernels of their own, see k_decode_pipe_c / k_decode_pipe_r / k_decode_pipe_t
 __device__ __forceinline__ void post2_pick_role(const DecodeParams& p, const FastParams& f, const PipeParams& pp, const PipeUtt (&cx)[NU]) {
     constexpr int C = 64;
     float* sm = SM; int* smi = SMI;
@@ -505,7 +506,10 @@ __device__ __forceinline__ void post2_pick_role(const DecodeParams& p, const Fas
             const int vb = v * o_ublk;
             const int i = t - (u.n0 - 1);
             float uni = 0.0f;
-            if constexpr (CTL == 3) { if (wave == 0) uni = sample_uniform(row_seed(u.rd), u.rd.stream, (unsigned)i); }      // (the row's own key: a group that alternates utterances draws each with its record)
+            int fdw = 0;      // draw track: the step's frame record, word `lane` in lanes 0..3 of the picking wave.  Its address depends on (utterance, i) only: requested here, ahead of the
+                              // wait for the logits' inputs, and read at the pick -- every utterance of a group that alternates has its own, nothing is kept from step to step
+            if constexpr (CTL == 4) { if (wave == 0) fdw = frame_draw_load(p, u, t, lane); }
+            if constexpr (CTL == 3 || CTL == 4) { if (wave == 0) uni = sample_uniform(row_seed(u.rd), u.rd.stream, (unsigned)i); }      // (the row's own key: a group that alternates utterances draws each with its record)
             else if (sampling && wave == 0) uni = sample_uniform(p.seed, (unsigned)u.row, (unsigned)i);   // ahead of the wait: independent of the logits
             if (wave == 0) {      // ONE wave gathers all 256 granules, four per lane in one poll loop: four waves polling on their own each
                                   // sample their granules once per L2 round trip, and the barrier waited for the unluckiest phase
@@ -546,7 +550,9 @@ __device__ __forceinline__ void post2_pick_role(const DecodeParams& p, const Fas
             wg_barrier();                                         // LDS only (the polls' / hand-offs' global traffic is not waited for)
             if (wave == 0) {
                 int bi;
-                if constexpr (CTL == 3) bi = sample_wave_ctl<true>(vb + o_lg, Q, uni, u.rd.inv_temp, u.rd.top_k, u.rd.top_p, u.rd.min_p, lane);
+                if constexpr (CTL == 4) bi = sample_wave_ctl<true>(vb + o_lg, Q, uni, __int_as_float(__builtin_amdgcn_readlane(fdw, 0)), __builtin_amdgcn_readlane(fdw, 1),
+                                                                   __int_as_float(__builtin_amdgcn_readlane(fdw, 2)), __int_as_float(__builtin_amdgcn_readlane(fdw, 3)), lane);
+                else if constexpr (CTL == 3) bi = sample_wave_ctl<true>(vb + o_lg, Q, uni, u.rd.inv_temp, u.rd.top_k, u.rd.top_p, u.rd.min_p, lane);
                 else if constexpr (CTL != 0) bi = sample_wave_ctl<CTL == 2>(vb + o_lg, Q, uni, p.inv_temp, p.top_k, p.top_p, p.min_p, lane);
                 else if (sampling) bi = sample_wave_u(vb + o_lg, Q, uni, lane);
                 else {
@@ -599,7 +605,7 @@ __device__ __forceinline__ void pipe_group(const DecodeParams& p, const FastPara
     for (int v = 0; v < NU; ++v) {
         const bool on = v < n_active && row0 + v < pp.nutt;
         const int row = on ? row0 + v : row0;                          // (a switched-off slot repeats the first utterance's descriptors and never runs)
-        if constexpr (CTL == 3) cx[v].u = make_row_view(p, p.utts[row]); else cx[v].u = make_view(p, p.utts[row]);
+        if constexpr (CTL == 3 || CTL == 4) cx[v].u = make_row_view(p, p.utts[row]); else cx[v].u = make_view(p, p.utts[row]);
         cx[v].X = pp.xch + (size_t)row * PX_STRIDE;
         cx[v].Ttot = on ? cx[v].u.n0 + cx[v].u.n_samples : 0;
     }
@@ -664,6 +670,22 @@ __global__ __launch_bounds__(PIPE_NT) void k_decode_pipe_r(DecodeParams p, FastP
     }
 }
 
+// ... and the launches of a call with a draw track (qpn_decode_frame_sampling; p.mode == QPN_MODE_SAMPLING_TRACK): k_decode_pipe_r's draw with the four values taken from the
+// record of the frame the step reads (post2_pick_role, CTL == 4).  Kernels of their own for the reasons above.
+template <int NU>
+__global__ __launch_bounds__(PIPE_NT) void k_decode_pipe_t(DecodeParams p, FastParams f, PipeParams pp) {
+    const int chunk = blockIdx.x / 40, within = blockIdx.x - chunk * 40, role = within >> 3, gi = chunk * 8 + (within & 7);
+    if constexpr (NU == 1) {
+        if (gi >= pp.nutt) return;
+        pipe_group<1, 4>(p, f, pp, role, gi, 1);
+    } else {
+        if (gi >= pp.groups) return;
+        const int first_big = pp.groups - pp.rem;
+        const int row0 = gi * pp.base + (gi > first_big ? gi - first_big : 0), cnt = pp.base + (gi >= first_big ? 1 : 0);
+        pipe_group<NU, 4>(p, f, pp, role, row0, cnt);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 bool qpn_pipe_supported(const Geom& g) {
     if (g.C != 64 || g.S != 256 || g.Q != 256 || g.LF != 4 || g.LA != 4 || g.L != 8) return false;
@@ -714,12 +736,13 @@ int qpn_launch_decode_pipe(qpn_handle* h, DecodeParams p, const DecodeLaunch& l,
 #endif
     const size_t lds = pipe_lds_bytes(nu);
     typedef void (*PipeKernel)(DecodeParams, FastParams, PipeParams);
-    static const PipeKernel kernels[4][3] = {       // [0: default draw or argmax, 1: a sampling control set, 2: top_p or min_p among them, 3: per-row records][nu - 1]
+    static const PipeKernel kernels[5][3] = {       // [0: default draw or argmax, 1: a sampling control set, 2: top_p or min_p among them, 3: per-row records, 4: a draw track][nu - 1]
         { k_decode_pipe, k_decode_pipe_n<2>, k_decode_pipe_n<3> },
         { k_decode_pipe_c<1, false>, k_decode_pipe_c<2, false>, k_decode_pipe_c<3, false> },
         { k_decode_pipe_c<1, true>, k_decode_pipe_c<2, true>, k_decode_pipe_c<3, true> },
-        { k_decode_pipe_r<1>, k_decode_pipe_r<2>, k_decode_pipe_r<3> } };
-    const int draw = p.mode == QPN_MODE_SAMPLING_ROW ? 3 : p.mode != QPN_MODE_SAMPLING_CTL ? 0 : (p.top_p != 1.0f || p.min_p != 0.0f) ? 2 : 1;
+        { k_decode_pipe_r<1>, k_decode_pipe_r<2>, k_decode_pipe_r<3> },
+        { k_decode_pipe_t<1>, k_decode_pipe_t<2>, k_decode_pipe_t<3> } };
+    const int draw = p.mode == QPN_MODE_SAMPLING_TRACK ? 4 : p.mode == QPN_MODE_SAMPLING_ROW ? 3 : p.mode != QPN_MODE_SAMPLING_CTL ? 0 : (p.top_p != 1.0f || p.min_p != 0.0f) ? 2 : 1;
     const PipeKernel kfn = kernels[draw][nu - 1];
     QPN_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));    // per device: set at every launch
     const int nchunks = (groups + 7) / 8;

@@ -1,7 +1,7 @@
 // decode_slot_kernel.h -- the body of the task-table interpreter, included twice by decode.hip: as k_decode (QPN_KERNEL_ROW false) and as k_decode_r, the kernel of the
 // calls with per-row sampling records (QPN_KERNEL_ROW true).  Textual inclusion for the reason given in decode_coopb_kernel.h.
 __global__ __launch_bounds__(QPN_NT) void QPN_KERNEL(DecodeParams p) {
-    constexpr bool ROW = QPN_KERNEL_ROW;
+    constexpr int ROW = QPN_KERNEL_ROW;      // (false, true, or 2: the kernel of the calls with a draw track -- sample_pick, decode_dev.h)
     float* sm = SM;
     int* smi = SMI;
     const UttView u = make_view(p, p.utts[blockIdx.x]);
@@ -28,6 +28,7 @@ __global__ __launch_bounds__(QPN_NT) void QPN_KERNEL(DecodeParams p) {
         if (lane == 0) { smi[p.o_samp] = u.known[0]; smi[p.o_samp + 1] = u.known[1]; }
     }
     stage_aux(p, u, 1, tid, QPN_NT);
+    if constexpr (ROW == 2) stage_frame_draw(p, u, 1, one_cu_rowd(p), tid);      // (the first step's frame record; later ones: OP_STAGE, a step ahead)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (Ttot > 3) stage_taps(p, u, 2, tid, QPN_NT, p.status);

@@ -22,6 +22,13 @@
 #define QPN_MODE_SAMPLING_CTL 2   // DecodeParams.mode only, never an ABI value: QPN_MODE_SAMPLING with a sampling control set (qpn_decode_sampling / _ex: any of the four)
 #define QPN_MODE_SAMPLING_ROW 3   // DecodeParams.mode only, never an ABI value: QPN_MODE_SAMPLING with per-row records set (qpn_decode_row_sampling): the pick takes its key and its
                                   // five values from DecodeParams.row_draw[UttDesc.row] instead of from DecodeParams
+#define QPN_MODE_SAMPLING_TRACK 4 // DecodeParams.mode only, never an ABI value: QPN_MODE_SAMPLING with a draw track set (qpn_decode_frame_sampling): key and counter word from
+                                  // DecodeParams.row_draw[UttDesc.row] as above (the host fills in {call seed, row} where the call has no records), the four values from the
+                                  // record of the step's feature frame, DecodeParams.frame_draw[UttDesc.row * n_frames + f]
+struct FrameDraw {          // one (batch row, feature frame) record of a draw track as the kernels read it (16 bytes); the host forms 1 / temperature and folds top_k
+    float inv_temp; int top_k; float top_p, min_p;
+};
+static_assert(sizeof(FrameDraw) == 16, "one 16-byte record per frame");
 struct RowDraw {            // one batch row's record as the kernels read it (32 bytes: one scalar load), indexed by UttDesc.row; the host forms 1 / temperature and folds top_k
     unsigned seed_lo, seed_hi, stream;      // Philox key, and the counter word that a uniform call fills with the batch row
     float inv_temp; int top_k; float top_p, min_p;
@@ -84,6 +91,8 @@ struct DecodeParams {
     int live_every;         // a row publishes its count after every live_every samples, and after its last one
     const int* cancel;      // the host's stop request (qpn_decode_cancel): one word, non-zero once the caller asked; read at publish points and at a row's start
     const RowDraw* row_draw;   // per-row sampling records (qpn_decode_row_sampling), [B] indexed by UttDesc.row; null unless mode == QPN_MODE_SAMPLING_ROW.  Loaded once when a workgroup takes a row
+    const FrameDraw* frame_draw;   // draw track (qpn_decode_frame_sampling), [B][n_frames] with rows indexed by UttDesc.row; null unless mode == QPN_MODE_SAMPLING_TRACK.  One record per step,
+    int64_t n_frames;              // fetched a step ahead of the pick that uses it (stage_frame_draw / frame_draw_word, decode_dev.h)
 };
-static_assert(sizeof(DecodeParams) == 1088 && offsetof(DecodeParams, n_slots) == 112 && offsetof(DecodeParams, o_xbuf) == 168 && offsetof(DecodeParams, o_gl) == 236 &&
+static_assert(sizeof(DecodeParams) == 1104 && offsetof(DecodeParams, n_slots) == 112 && offsetof(DecodeParams, o_xbuf) == 168 && offsetof(DecodeParams, o_gl) == 236 &&
               offsetof(DecodeParams, bias_src) == 248 && offsetof(DecodeParams, rings) == 280 && offsetof(DecodeParams, live) == 1048, "kernel argument layout");

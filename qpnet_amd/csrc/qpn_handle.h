@@ -53,6 +53,12 @@ struct qpn_handle {      // every member has an initialiser: qpn_create sets onl
     std::vector<RowDraw> samp_rows;  // per-row records of the QPN_MODE_SAMPLING calls enqueued from now on (qpn_decode_row_sampling), input order, checked and converted; empty: off
     RowDraw* h_rows_pinned = nullptr; size_t h_rows_cap = 0;      // pinned staging of the call's records (copied on the call's stream with the descriptors) ...
     RowDraw* d_rows = nullptr; size_t rows_cap = 0;               // ... and the device table the kernels index by UttDesc.row
+    // draw track of the QPN_MODE_SAMPLING calls enqueued from now on (qpn_decode_frame_sampling): [track_rows][track_frames], input order, checked and converted; track_rows == 0: off.
+    // The table lives in h_track_pinned, allocated and filled by the setter (never by the enqueue; a handle without a device keeps the shape only).  The setter is refused while a
+    // decode is in flight, so the staging holds the table of the call in flight until qpn_decode_finish has run: the re-run after a give-up copies it again
+    int track_rows = 0; int64_t track_frames = 0;
+    FrameDraw* h_track_pinned = nullptr; size_t h_track_cap = 0;
+    FrameDraw* d_track = nullptr; size_t track_cap = 0;           // ... and the device table the kernels index by (UttDesc.row, frame)
     bool live_final = false;         // the last decode was armed and has been finished: qpn_decode_final_counts reads its counts (until the next enqueue)
     std::vector<int64_t> live_seen;  // per-row high-water mark of what qpn_decode_poll has reported.  The counts restart only while qpn_decode_finish re-runs a launch that gave up,
                                      // and a handle is not thread-safe: only a caller that polls from a second thread under its own lock around finish could ever see the restart
@@ -63,6 +69,7 @@ struct qpn_handle {      // every member has an initialiser: qpn_create sets onl
         float inv_temp = 1.0f; int top_k = 0;      // the handle's sampling controls at the enqueue: a re-run draws with the same ones
         float top_p = 1.0f, min_p = 0.0f;
         std::vector<RowDraw> rows;                 // ... and the per-row records in force at the enqueue (empty: none): the re-run draws with the same ones
+        bool track = false;                        // ... and whether the handle's draw track was in force (it cannot change before qpn_decode_finish: see h_track_pinned)
         const int64_t* d_teacher = nullptr; int64_t* d_out = nullptr; float* d_logits = nullptr;
         DecodePlanIn in = {}; DecodePlan plan = {};   // what was planned from, and what the launches followed
     } call;

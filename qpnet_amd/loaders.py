@@ -579,3 +579,21 @@ def unvoiced_row_weights(batch_h, batch_length, upsampling_factor, unvoiced_weig
     if U > 0:
         pos //= U
     return np.where(uv[:, pos] > 0.5, np.float32(1.0), np.float32(w)).astype(np.float32)
+
+
+def uv_draw_track(batch_h, voiced, unvoiced):
+    """A voiced / unvoiced draw track for QPNet.batch_fast_generate(draw_track=...) from the features' flag, under the convention of unvoiced_row_weights: feature
+    column 0 is uv (1 voiced, 0 unvoiced; calc_stats keeps it at mean 0 / scale 1, so the scaled feature is still 0 / 1), and > 0.5 is voiced.  batch_h: (B, n_aux, F)
+    features as the decode call takes them (array or tensor); voiced, unvoiced: dicts with the same keys among "temperature", "top_k", "top_p", "min_p" -> {key: (B, F)
+    array} holding voiced[key] in the voiced frames and unvoiced[key] in the others (int32 for top_k, float32 otherwise).  Frames are the features' own: the decode
+    kernels look a sample's frame up themselves."""
+    if hasattr(batch_h, "detach"):
+        batch_h = batch_h.detach().cpu().numpy()
+    h = np.asarray(batch_h, dtype=np.float32)
+    if h.ndim != 3 or h.shape[1] < 1:
+        raise ValueError("batch_h must be (B, n_aux, F) features, got shape %r" % (h.shape,))
+    keys = ("temperature", "top_k", "top_p", "min_p")
+    if set(voiced) != set(unvoiced) or not set(voiced) <= set(keys):
+        raise ValueError("voiced and unvoiced must hold the same keys among %s, got %r and %r" % (", ".join(keys), sorted(voiced), sorted(unvoiced)))
+    is_voiced = h[:, 0, :] > 0.5
+    return {k: np.where(is_voiced, voiced[k], unvoiced[k]).astype(np.int32 if k == "top_k" else np.float32) for k in keys if k in voiced}

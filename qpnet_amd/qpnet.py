@@ -233,7 +233,7 @@ class QPNet(nn.Module):
 
     # ------------------------------------------------------------------ autoregressive decode
     def batch_fast_generate(self, x, h, n_samples_list, dilated_factors,
-                            intervals=None, mode="sampling", extra_memory=False, *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, row_seeds=None):
+                            intervals=None, mode="sampling", extra_memory=False, *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, row_seeds=None, draw_track=None):
         """Batch fast generation (reference qpnet.py:314-559).
 
         x (B,T0) long seed, h (B,n_aux,F) float, n_samples_list list[int] (consumed exactly like
@@ -253,12 +253,23 @@ class QPNet(nn.Module):
         INPUT rows, whatever order the results come back in.  With row_seeds, row b draws from the stream
         (seed = row_seeds[b], stream 0): its samples depend on its own inputs, values and seed only, not on its place in the batch, the batch
         size or the launch plan.  Without row_seeds but with a per-row control, row b draws from (call seed, stream b), the stream of a uniform
-        call.  All scalars and no row_seeds is the uniform call: same kernels, same bytes.  last_row_seeds records the keys that were used."""
-        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature, top_k, top_p, min_p, row_seeds)
+        call.  All scalars and no row_seeds is the uniform call: same kernels, same bytes.  last_row_seeds records the keys that were used.
+
+        At frame rate (qpn_decode_frame_sampling): draw_track is a dict with any of the keys "temperature", "top_k", "top_p", "min_p", each an array or tensor
+        of shape (B, F) -- rows in INPUT order, F = h.shape[2] -- or (F,), which every row shares.  Generated sample i of a row is drawn with the values of the
+        frame whose features that step reads, f(i) = min(F - 1, (x.shape[1] - 1 + i) // upsampling_factor) (upsampling_factor 0: min(F - 1, x.shape[1] - 1 + i));
+        the uniforms are those of the same call without a track.  A key the dict does not hold takes the call's scalar or per-row value of that name; a key given
+        both ways is a ValueError.  A track whose rows are constant gives the samples of the per-row call with those constants, bit for bit, and what a track
+        holds from frame f on cannot change a sample drawn before the row reaches f.  loaders.uv_draw_track builds a voiced / unvoiced one."""
+        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature, top_k, top_p, min_p, row_seeds, draw_track)
         L, hd, dev, B, ns, max_n, out, stream = a["L"], a["hd"], a["dev"], a["B"], a["ns"], a["max_n"], a["out"], a["stream"]
         t_start = a["t_start"]
         with torch.cuda.device(dev):
-            _lib.check(L.qpn_decode(*a["call"]))
+            try:
+                _lib.check(L.qpn_decode(*a["call"]))
+            finally:
+                if a["track"]:
+                    L.qpn_decode_frame_sampling(hd, 0, 0, None)      # this call's track goes with it: nothing is left over for a caller of the C interface either
             self.last_decode_kernel_ms = float(L.qpn_last_decode_kernel_ms(hd))
             self.last_decode_plan = L.qpn_last_decode_plan(hd).decode("utf-8", "replace")
         out_np = out.cpu().numpy()
@@ -344,7 +355,62 @@ class QPNet(nn.Module):
                 raise ValueError("row %d: %s" % (b, e)) from None
         return (1.0, 0, 1.0, 0.0), rows
 
-    def _decode_args(self, x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, row_seeds=None):
+    _TRACK_KEYS = ("temperature", "top_k", "top_p", "min_p")
+    _TRACK_DEFAULTS = {"temperature": 1.0, "top_k": 0, "top_p": 1.0, "min_p": 0.0}
+
+    def _track_controls(self, mode, B, F, draw_track, temperature, top_k, top_p, min_p):
+        """draw_track of a decode call, checked on the host before anything touches the device -> None (no track), or {key: (B, F) ndarray, float32 or int32}
+        holding the keys the dict gave.  The four arguments are the call's own values of those names: a key given both ways is refused."""
+        if draw_track is None:
+            return None
+        if not isinstance(draw_track, dict):
+            raise ValueError("draw_track must be a dict with any of the keys %s, not %r" % (", ".join(self._TRACK_KEYS), type(draw_track).__name__))
+        unknown = [k for k in draw_track if k not in self._TRACK_KEYS]
+        if unknown:
+            raise ValueError("draw_track has no key %r (its keys: %s)" % (unknown[0], ", ".join(self._TRACK_KEYS)))
+        if mode == "argmax":
+            raise ValueError("temperature / top_k / top_p / min_p shape the draw of mode='sampling'; mode='argmax' takes none of them")
+        out = {}
+        for name, arg in zip(self._TRACK_KEYS, (temperature, top_k, top_p, min_p)):
+            if name not in draw_track:
+                continue
+            if not (isinstance(arg, (int, float, np.integer, np.floating)) and arg == self._TRACK_DEFAULTS[name]):
+                raise ValueError("%s is given twice: in draw_track and as the argument %s=%r (one of them only)" % (name, name, arg))
+            src = draw_track[name]
+            src = src.detach().cpu().numpy() if isinstance(src, torch.Tensor) else np.asarray(src)
+            if src.dtype.kind not in "iuf":
+                raise ValueError("draw_track[%r] must hold numbers, not dtype %s" % (name, src.dtype))
+            if src.shape == (F,):
+                v = np.broadcast_to(src, (B, F))
+            elif src.shape == (B, F):
+                v = src
+            else:
+                raise ValueError("draw_track[%r] has shape %r: expected (B, F) = (%d, %d), or (F,) = (%d,) for every row (F: the frames of h)" % (name, tuple(src.shape), B, F, F))
+            with np.errstate(all="ignore"):
+                if name == "top_k":
+                    if v.dtype.kind == "f":
+                        raise ValueError("draw_track['top_k'] must hold ints, not dtype %s" % v.dtype)
+                    bad = (v < 0) | (v > self.n_quantize)
+                    rule = "must be an int in 0..n_quantize = %d (0: off)" % self.n_quantize
+                    v = np.where(bad, 0, v).astype(np.int32)
+                else:
+                    v = v.astype(np.float32)      # (what the library sees: the rounded value is what is checked)
+                    if name == "temperature":
+                        bad = ~(np.isfinite(v) & (v > 0) & np.isfinite(np.float32(1.0) / v))
+                        rule = "must be a finite float32 > 0 whose reciprocal is finite"
+                    elif name == "top_p":
+                        bad = ~((v > 0) & (v <= 1))
+                        rule = "must be a float32 in (0, 1] (1: off)"
+                    else:
+                        bad = ~((v >= 0) & (v <= 1))
+                        rule = "must be a float32 in [0, 1] (0: off)"
+            if bad.any():
+                b, fr = (int(i) for i in np.argwhere(bad)[0])
+                raise ValueError("draw_track[%r] row %d frame %d: %s, not %r" % (name, b, fr, rule, src[fr] if src.ndim == 1 else src[b, fr]))
+            out[name] = np.ascontiguousarray(v)
+        return out
+
+    def _decode_args(self, x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, row_seeds=None, draw_track=None):
         """What batch_fast_generate and generate_live do before the library call: mode check, maxd, dtype and device moves, the
         output buffer, the sampling seed, binding the weights.  -> dict; "call" is the argument tuple of qpn_decode / qpn_decode_enqueue, the rest
         keeps the tensors behind its pointers alive."""
@@ -352,6 +418,7 @@ class QPNet(nn.Module):
             logging.error("mode should be sampling or argmax")
             sys.exit(1)
         B = len(n_samples_list)
+        track = self._track_controls(mode, B, int(h.shape[2]), draw_track, temperature, top_k, top_p, min_p)
         (temperature, top_k, top_p, min_p), rows = self._row_controls(mode, B, temperature, top_k, top_p, min_p, row_seeds)
         import ctypes as C
         dev = x.device
@@ -391,17 +458,32 @@ class QPNet(nn.Module):
             rec = (_lib.QpnRowDraw * B)(*[_lib.QpnRowDraw(seed if sd is None else sd, b if sd is None else 0, t, k, tp, mp) for b, (sd, t, k, tp, mp) in enumerate(rows)])
             _lib.check(L.qpn_decode_row_sampling(hd, B, rec))
             self.last_row_seeds = [seed if sd is None else sd for sd, _, _, _, _ in rows]
+        # ... and this call's draw track, likewise.  A key the dict does not hold is filled with the call's own value of that name: the row's, or the scalar
+        rec_t = None
+        if track is None:
+            _lib.check(L.qpn_decode_frame_sampling(hd, 0, 0, None))
+        else:
+            F = int(h.shape[2])
+            rec_t = np.empty((B, F), dtype=np.dtype([("temperature", "<f4"), ("top_k", "<i4"), ("top_p", "<f4"), ("min_p", "<f4")]))
+            for j, (name, scalar) in enumerate(zip(self._TRACK_KEYS, (temperature, top_k, top_p, min_p))):
+                if name in track:
+                    rec_t[name] = track[name]
+                elif rows is not None:
+                    rec_t[name] = np.asarray([r[1 + j] for r in rows])[:, None]
+                else:
+                    rec_t[name] = scalar
+            _lib.check(L.qpn_decode_frame_sampling(hd, B, F, rec_t.ctypes.data_as(C.POINTER(_lib.QpnFrameDraw))))
         t_start = time.time()           # (the clock of batch_fast_generate's progress lines starts here, in front of the weight binding)
         arr = (C.c_int64 * B)(*ns)
         call = (hd, B, xd.shape[1], hd_.shape[2], d_dev.shape[1], xd.data_ptr(), hd_.data_ptr(), d_dev.data_ptr(), d_is_f32,
                 arr, maxd, 1 if mode == "sampling" else 0, seed, None, out.data_ptr(), None, stream)
         with torch.cuda.device(dev):
             flat = self._bind_decode_weights(L, hd, dev, stream)
-        return dict(L=L, hd=hd, dev=dev, B=B, ns=ns, max_n=max_n, out=out, stream=stream, call=call, t_start=t_start, keep=(xd, hd_, d_dev, arr, flat))
+        return dict(L=L, hd=hd, dev=dev, B=B, ns=ns, max_n=max_n, out=out, stream=stream, call=call, t_start=t_start, track=track is not None, keep=(xd, hd_, d_dev, arr, flat, rec_t))
 
     # ------------------------------------------------------------------ live decode output
     def generate_live(self, x, h, n_samples_list, dilated_factors, intervals=None, mode="sampling",
-                      extra_memory=False, every=256, poll_s=0.001, on_close="finish", *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, row_seeds=None):
+                      extra_memory=False, every=256, poll_s=0.001, on_close="finish", *, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, row_seeds=None, draw_track=None):
         """batch_fast_generate as a generator that hands samples over while the decode kernel runs: yields (row, start, samples)
         -- row = index in the input order, samples = a fresh int64 ndarray holding that row's samples [start, start + len) --
         as soon as a poll of the library (qpn_decode_poll) shows new finished samples of a row.  A row's pieces are contiguous
@@ -416,19 +498,21 @@ class QPNet(nn.Module):
         (`every` samples of the longest-running row each) plus the drain of the launch.  A generator that is iterated to its end
         never cancels.  After the generator has ended, either way, last_decode_counts holds every row's final count in input
         order (samples below it are valid; n_samples for a call that ran to its end) and last_decode_cancelled whether the call
-        stopped short on request.  temperature / top_k / top_p / min_p / row_seeds: as in batch_fast_generate, per-row sequences included."""
+        stopped short on request.  temperature / top_k / top_p / min_p / row_seeds / draw_track: as in batch_fast_generate, per-row sequences included."""
         if on_close not in ("finish", "cancel"):
             raise ValueError("on_close must be 'finish' or 'cancel', not %r" % (on_close,))
         if int(every) < 1:
             raise ValueError("every must be >= 1")
         if mode in ("sampling", "argmax"):
+            self._track_controls(mode, len(n_samples_list), int(h.shape[2]), draw_track, temperature, top_k, top_p, min_p)
             self._row_controls(mode, len(n_samples_list), temperature, top_k, top_p, min_p, row_seeds)          # (bad values are refused here, at the call, not at the first next())
         self._native(x.device)          # (CPU tensors are refused here, at the call, not at the first next())
-        return self._live_pieces(x, h, list(n_samples_list), dilated_factors, intervals, mode, extra_memory, int(every), float(poll_s), on_close == "cancel", temperature, top_k, top_p, min_p, row_seeds)
+        return self._live_pieces(x, h, list(n_samples_list), dilated_factors, intervals, mode, extra_memory, int(every), float(poll_s), on_close == "cancel", temperature, top_k, top_p, min_p, row_seeds, draw_track)
 
-    def _live_pieces(self, x, h, n_samples_list, dilated_factors, intervals, mode, extra_memory, every, poll_s, cancel_on_close, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, row_seeds=None):
+    def _live_pieces(self, x, h, n_samples_list, dilated_factors, intervals, mode, extra_memory, every, poll_s, cancel_on_close, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, row_seeds=None,
+                     draw_track=None):
         import ctypes as C
-        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature, top_k, top_p, min_p, row_seeds)
+        a = self._decode_args(x, h, n_samples_list, dilated_factors, mode, extra_memory, temperature, top_k, top_p, min_p, row_seeds, draw_track)
         L, hd, dev, B, ns, max_n, out, stream = a["L"], a["hd"], a["dev"], a["B"], a["ns"], a["max_n"], a["out"], a["stream"]
         done = (C.c_int64 * B)()
         mirror, stride, running = C.POINTER(C.c_int32)(), C.c_int64(), C.c_int()
@@ -492,6 +576,8 @@ class QPNet(nn.Module):
                     if L.qpn_decode_final_counts(hd, done, C.byref(cancelled)) == 0:
                         self.last_decode_counts, self.last_decode_cancelled = [int(done[b]) for b in range(B)], bool(cancelled.value)
                 L.qpn_decode_live(hd, 0)
+                if a["track"]:
+                    L.qpn_decode_frame_sampling(hd, 0, 0, None)      # (the call is finished by now: this call's track goes with it)
 
     # test/diagnostic helper (not part of the reference surface): teacher-forced streaming logits
     def _stream_logits(self, x, h, dilated_factors, teacher, n_samples):

@@ -647,9 +647,28 @@ def _decode_args():
     p.add_argument("--top_k", default=0, type=int, help="sampling mode: draw among the classes with the top_k largest logits only (ties kept); 0: off")
     p.add_argument("--top_p", default=1.0, type=float, help="sampling mode: draw among the most probable classes whose mass reaches this fraction (ties kept); 1: off")
     p.add_argument("--min_p", default=0.0, type=float, help="sampling mode: draw among the classes at least this fraction as probable as the most probable one; 0: off")
+    for name, typ in (("temperature", float), ("top_k", int), ("top_p", float), ("min_p", float)):
+        for part in ("voiced", "unvoiced"):      # unset: the plain flag's value.  With none of the eight set the call is the one it always was
+            p.add_argument("--%s_%s" % (name, part), default=None, type=typ, help="sampling mode: --%s of the samples whose feature frame is %s (feature column 0, the "
+                           "uv flag; loaders.uv_draw_track); unset: the value of --%s" % (name, part, name))
     p.add_argument("--per_file_seed", action="store_true", help="sampling mode: every file draws from a stream of its own, keyed by --seed and the file's id "
                    "(loaders.row_seed): its wav does not depend on --batch_size, --n_gpus or the other files of the list; off: the reference-like per-call stream")
     return p
+
+
+def uv_decode_controls(args):
+    """run_decode's draw flags -> (plain, voiced, unvoiced): the keyword arguments of the four plain controls, and the two dicts of loaders.uv_draw_track for the
+    controls that have a --<name>_voiced or --<name>_unvoiced flag set (the side left unset takes the plain flag's value; the plain keyword is then left at its default,
+    the track carries the value).  None set: both dicts empty, and the call is the one the plain flags make."""
+    plain, voiced, unvoiced = {}, {}, {}
+    for name in ("temperature", "top_k", "top_p", "min_p"):
+        v, u, base = getattr(args, name + "_voiced"), getattr(args, name + "_unvoiced"), getattr(args, name)
+        if v is None and u is None:
+            plain[name] = base
+        else:
+            voiced[name] = base if v is None else v
+            unvoiced[name] = base if u is None else u
+    return plain, voiced, unvoiced
 
 
 def run_decode(argv=None):
@@ -685,11 +704,14 @@ def run_decode(argv=None):
         per_file = args.per_file_seed and args.mode == "sampling"      # (argmax draws nothing)
         if per_file:
             logging.info("per-file seeds on: every file draws from its own stream (seed %d and its id), whatever its batch." % args.seed)
+        plain, voiced, unvoiced = uv_decode_controls(args)
+        if voiced:
+            logging.info("voiced / unvoiced sampling on: %s in voiced frames, %s in unvoiced ones." % (voiced, unvoiced))
         for feat_ids, bx, bh, ns, bd in gen:
             logging.info("decoding start!")
             row_seeds = [loaders.row_seed(args.seed, i) for i in feat_ids] if per_file else None      # (input order: feat_ids lists the batch rows)
-            outs = model.batch_fast_generate(bx, bh, ns, bd, intervals=args.intervals, mode=args.mode, extra_memory=args.extra_memory,
-                                             temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, min_p=args.min_p, row_seeds=row_seeds)
+            track = loaders.uv_draw_track(bh, voiced, unvoiced) if voiced else None
+            outs = model.batch_fast_generate(bx, bh, ns, bd, intervals=args.intervals, mode=args.mode, extra_memory=args.extra_memory, row_seeds=row_seeds, draw_track=track, **plain)
             for feat_id, samples in zip(feat_ids, outs):
                 name = args.outdir.replace("feat_id", feat_id)
                 loaders.write_wav(name, args.fs, samples, conf.n_quantize)
