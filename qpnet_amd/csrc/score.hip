@@ -1,8 +1,8 @@
 // score.hip -- teacher-forced scoring of given logits: per row the negative log likelihood of the target, the entropy of the distribution,
 // the argmax and the target's rank (qpn_score_logits; reference src/bin/qpnet_validate.py:409-437 keeps only the mean of the first).
 //
-// One wave per row, four waves per workgroup, SC_RPW rows per wave (the row-to-wave map of k_ce, train_fwd.hip).  A row of up to 1024 classes is read
-// from global memory ONCE into registers; larger rows are read twice.  The log-sum-exp is k_ce's arithmetic for that Q, operation for operation: the
+// One wave per row, four waves per workgroup, SC_RPW rows per wave (the row-to-wave map of k_ce_hard, train_loss.hip).  A row of up to 1024 classes is read
+// from global memory ONCE into registers; larger rows are read twice.  The log-sum-exp is k_ce_hard's arithmetic for that Q, operation for operation: the
 // lane that owns a class, the order in which a lane adds its terms, tr_wave_max / tr_wave_sum, logf(se) + m -- so the float64 sum of a chunk's nll
 // over its row count is the loss qpn_ce_loss reports.  That fixes which lane holds which class:
 //   Q % 256 == 0: lane owns classes 4 lane + 256 p .. + 3 of pass p (one float4 per pass), __expf, terms added as (e0 + e1) + (e2 + e3) per pass
@@ -10,7 +10,7 @@
 #include "train_common.h"
 #include <type_traits>
 
-#define SC_RPW 4              // rows per wave (16 rows per workgroup, as k_ce)
+#define SC_RPW 4              // rows per wave (16 rows per workgroup, as k_ce_hard)
 #define SC_IDX_NONE 65536     // above every class index (Q <= 65536)
 #define SC_FLT_MAX 3.402823466e38f
 
@@ -21,7 +21,7 @@ __device__ __forceinline__ void score_store(qpn_score_row* __restrict__ out, int
     se = tr_wave_sum(se);
     s2 = tr_wave_sum(s2);
     const float lg_se = logf(se);
-    const float lse = lg_se + m;                                          // k_ce: logf(se) + m
+    const float lse = lg_se + m;                                          // k_ce_hard: logf(se) + m
     qpn_score_row r;
     r.nll = in_range ? lse - lt : INFINITY;
     r.entropy = lg_se + s2 / se;                                          // -sum p log p = log se + sum (e / se)(m - l): every term >= 0
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void k_score(const float* __restrict__ logits,
                                                qpn_score_row* __restrict__ out) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (wave-uniform: rows, targets and their addresses stay in scalar registers)
     if constexpr (NP > 0) {
-        const int64_t first = (int64_t)blockIdx.x * SC_RPW * 4 + wave;   // the wave's rows: first + 4 it (k_ce's map)
+        const int64_t first = (int64_t)blockIdx.x * SC_RPW * 4 + wave;   // the wave's rows: first + 4 it (k_ce_hard's map)
         if (first >= rows) return;
         typename std::conditional<VEC, float4, float>::type v[SC_RPW][VEC ? NP : 4 * NP];
         int64_t tg[SC_RPW]; float lt[SC_RPW];

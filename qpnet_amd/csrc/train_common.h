@@ -116,11 +116,19 @@ static inline AuxArgs tr_aux_args(const TrainParams& p, const TrainBwd* bw, cons
 // their map, the packed biases through their CSR lists (into TrainParams::bp); `loss`: the 64 partial sums of the coming step's loss, cleared
 struct RefreshArgs { const int* wmap; float* wout; int64_t nw; const int* bstart; const int* blist; int nb; double* loss; };
 void qpn_train_knobs_parse(TrainKnobs& k);
-// The loss options of k_ce_opt / k_ce_distill's weighted form (qpn_loss_opts after the host's checks; DESIGN.md section 5, "Loss options"):
+// The loss options of k_ce_hard<NV, true> / k_ce_soft<NV, true> (qpn_loss_opts after the host's checks; DESIGN.md section 5, "Loss options"):
 //   w: B x BL row weights or nullptr (all 1); use_ign / ign: rows whose target equals ign weigh 0; eps: label smoothing;
 //   norm_mass: nullptr -- the loss and its gradient are over the row count -- or the device word k_weight_mass wrote (over the effective sum of weights);
 //   mass: 64 slots that receive the effective sum of weights (or nullptr)
 struct CeOpts { const float* w; long long ign; int use_ign; float eps; const double* norm_mass; double* mass; };
+// One stand-alone loss launch (train_loss.hip): B x BL rows of Q logits, the targets the last BL entries of each tgt_stride.
+//   teacher: nullptr -- the cross entropy (k_ce_hard) -- or the soft-target loss with alpha, temp (k_ce_soft);  opts: nullptr -- the unweighted instances;
+//   loss: 64 slots, cleared by the launcher unless loss_cleared;  comp: nullptr, or 2 x 64 slots for the soft loss's two components (cleared by the launcher)
+struct LossCall {
+    const float* logits; const float* teacher; const int64_t* targets; int64_t tgt_stride; int B, BL, Q; float alpha, temp; const CeOpts* opts;
+    float* dlogits; double* loss; double* comp; int* status; bool loss_cleared;
+};
+int qpn_launch_loss(const LossCall& c, hipStream_t stream);
 
 #define TR_QHEAD_STRIDE 1056   // words between sub-queue heads (4224 bytes: different memory channels)
 #define TR_QHDR_WORDS 17920    // control block: [1] abort, counters [4..6] forward, [8..10] backward, [1024 + (8 dir + q) * TR_QHEAD_STRIDE]: sub-queue heads

@@ -753,7 +753,7 @@ __global__ __launch_bounds__(512) void k_post_fwd(TrainParams p) {
     }
     if (!p.ce_tgt) return;
     // ---------- fused torch.nn.CrossEntropyLoss() (mean) and its gradient on the tile's rows while the logits are in LDS
-    // (same arithmetic as k_ce: one wave per row, four classes per lane; reference qpnet_train.py:430,526-528)
+    // (same arithmetic as k_ce_hard: one wave per row, four classes per lane; reference qpnet_train.py:430,526-528)
     __syncthreads();
     {
         const int64_t rows = (int64_t)p.B * p.BL;
@@ -798,247 +798,6 @@ __global__ __launch_bounds__(512) void k_post_fwd_w(TrainParams p) {
     extern __shared__ float sm[];
     unsigned long long mS, mY; float4 bq[2];
     post_fwd_w_tile<MT, false>(p, sm, mS, mY, bq);
-}
-
-// mean cross entropy + its gradient, one wave per row, rpw rows per wave (reference qpnet_train.py:430,526-528)
-__global__ __launch_bounds__(256) void k_ce(const float* __restrict__ logits, const int64_t* __restrict__ tgt, int64_t tgt_stride,
-                                            int BL, int Q, int64_t rows, float* __restrict__ dlogits, double* __restrict__ loss, int rpw, int* __restrict__ status) {
-    __shared__ double part[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float inv = 1.0f / (float)rows;
-    double lsum = 0.0;
-    for (int it = 0; it < rpw; ++it) {
-        const int64_t row = ((int64_t)blockIdx.x * rpw + it) * 4 + wave;
-        if (row >= rows) break;
-        const float* lg = logits + (size_t)row * Q;
-        const int64_t b = row / BL, t = row - b * BL;
-        int64_t tg = tgt[(size_t)b * tgt_stride + (tgt_stride - BL) + t];
-        if (tg < 0 || tg >= Q) { if (lane == 0) atomicOr(status, 2); tg = tg < 0 ? 0 : Q - 1; }     // reference: assert max(batch_t) < n_quantize
-        float m = -INFINITY;
-        const bool vec = (Q & 255) == 0;             // 4 contiguous logits per lane per pass (16-byte accesses)
-        if (vec) for (int q = lane * 4; q < Q; q += 256) { const float4 v = *(const float4*)(lg + q); m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w)); }
-        else for (int q = lane; q < Q; q += 64) m = fmaxf(m, lg[q]);
-        m = tr_wave_max(m);
-        float se = 0.f;
-        if (vec) for (int q = lane * 4; q < Q; q += 256) { const float4 v = *(const float4*)(lg + q); se += (__expf(v.x - m) + __expf(v.y - m)) + (__expf(v.z - m) + __expf(v.w - m)); }
-        else for (int q = lane; q < Q; q += 64) se += expf(lg[q] - m);
-        se = tr_wave_sum(se);
-        const float lse = logf(se) + m;
-        if (dlogits) {
-            if (vec) for (int q = lane * 4; q < Q; q += 256) {
-                const float4 v = *(const float4*)(lg + q);
-                float4 g = make_float4(__expf(v.x - lse), __expf(v.y - lse), __expf(v.z - lse), __expf(v.w - lse));
-                const int dq = (int)tg - q;
-                if (dq == 0) g.x -= 1.0f; else if (dq == 1) g.y -= 1.0f; else if (dq == 2) g.z -= 1.0f; else if (dq == 3) g.w -= 1.0f;
-                *(float4*)(dlogits + (size_t)row * Q + q) = make_float4(g.x * inv, g.y * inv, g.z * inv, g.w * inv);
-            } else for (int q = lane; q < Q; q += 64) {
-                const float pr = expf(lg[q] - lse);
-                dlogits[(size_t)row * Q + q] = (pr - (q == tg ? 1.0f : 0.0f)) * inv;
-            }
-        }
-        lsum += (double)(lse - lg[tg]);
-    }
-    if (lane == 0) part[wave] = lsum;
-    __syncthreads();
-    // 64 accumulator slots (summed by the reader): one double atomic per workgroup on ONE address serialises at the memory side
-    if (threadIdx.x == 0) atomicAdd(loss + (blockIdx.x & 63), (part[0] + part[1] + part[2] + part[3]) / (double)rows);
-}
-
-// ---- loss options ("Loss options"): row weights, ignore_index, label smoothing, the normaliser.  Per row r with logits z, target y:
-//   w_r = weights[r] (1 without weights), 0 when y == ignore_index;   CE_r = lse(z) - (1 - eps) z_y - (eps / Q) sum_q z_q;
-//   L = (1 / N) sum_r w_r CE_r,   dL/dz_r = (w_r / N) (softmax(z) - (1 - eps) onehot(y) - eps / Q),   N = the row count, or the effective sum of weights.
-// The helpers below are shared by k_ce_opt, k_weight_mass and k_ce_distill's weighted form, so that all three agree on a row's weight.
-// A NaN, infinite or negative weight sets status value 64 (the Adam launch of the step skips: the sticky-status rule) and counts as 0.
-__device__ __forceinline__ float ce_weight_value(const CeOpts& o, int64_t row, int64_t tg, bool& bad) {
-    float w = 1.0f;
-    bad = false;
-    if (o.w) { w = o.w[row]; if (!(w >= 0.f && w <= 3.402823466e+38f)) { bad = true; w = 0.f; } }
-    if (o.use_ign && tg == (int64_t)o.ign) w = 0.f;
-    return w;
-}
-__device__ __forceinline__ float ce_row_weight(const CeOpts& o, int64_t row, int64_t tg, int lane, int* status) {
-    bool bad;
-    const float w = ce_weight_value(o, row, tg, bad);
-    if (bad && lane == 0) atomicOr(status, 64);
-    return w;
-}
-// the normaliser N as a double (1 where the effective mass is 0: every sum it divides is 0 then) and 1 / N as the fp32 factor of the gradient (0 there)
-template <bool W> __device__ __forceinline__ double ce_opt_den(const CeOpts& o, int64_t rows) {
-    if constexpr (W) { if (o.norm_mass) { const double m = *o.norm_mass; return m > 0.0 ? m : 1.0; } }
-    return (double)rows;
-}
-template <bool W> __device__ __forceinline__ float ce_opt_inv(const CeOpts& o, int64_t rows) {
-    if constexpr (W) { if (o.norm_mass) { const double m = *o.norm_mass; return m > 0.0 ? (float)(1.0 / m) : 0.f; } }
-    return 1.0f / (float)rows;
-}
-// a zero-weight row of dL/dlogits: exact +0, by the lanes that would have written the row's gradient
-template <int NV> __device__ __forceinline__ void ce_zero_row(float* __restrict__ dst, int Q, int lane) {
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (NV > 0) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) *(float4*)(dst + lane * 4 + 256 * k) = z4;
-    } else if ((Q & 255) == 0) { for (int q = lane * 4; q < Q; q += 256) *(float4*)(dst + q) = z4; }
-    else for (int q = lane; q < Q; q += 64) dst[q] = 0.f;
-}
-
-// The effective sum of weights for norm = "weights", in fp64 and in a FIXED order (one workgroup: strided partial sums, an LDS tree): the same bits from run to
-// run.  Written to the word k_ce_opt / k_ce_distill read (CeOpts::norm_mass); enqueued in front of them on the same stream.
-__global__ __launch_bounds__(1024) void k_weight_mass(const int64_t* __restrict__ tgt, int64_t tgt_stride, int BL, int64_t rows, CeOpts o, double* __restrict__ out) {
-    __shared__ double s[1024];
-    double a = 0.0;
-    // a thread's rows are threadIdx.x + 1024 j, added in the order of j; eight of them are loaded before the first is added (one workgroup: the loop lives on loads in flight)
-    for (int64_t base = threadIdx.x; base < rows; base += 8 * 1024) {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int64_t row = base + 1024 * j;
-            v[j] = 0.f;
-            if (row < rows) {
-                int64_t tg = 0;
-                if (o.use_ign) { const int64_t b = row / BL, t = row - b * BL; tg = tgt[(size_t)b * tgt_stride + (tgt_stride - BL) + t]; }
-                bool bad;
-                v[j] = ce_weight_value(o, row, tg, bad);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a += (double)v[j];
-    }
-    s[threadIdx.x] = a;
-    __syncthreads();
-    for (int st = 512; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) s[threadIdx.x] += s[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = s[0];
-}
-
-// k_ce with the options above, in k_ce's place on an armed forward: k_ce's layout (one wave per row, rpw rows per wave, 16 rows per workgroup, the 64 double
-// loss slots) and k_ce's max / sum-exp / lse arithmetic and reduction order, operation for operation.
-//   NV > 0: Q == 256 NV.  The lane's 4 NV logits of a row are loaded with 16-byte loads, all in flight before the first reduction, and stay in registers:
-//           a row is read once.  NV == 0: any Q, k_ce's loops.
-// The row's scale w_r / N is formed once, in fp32, and multiplies the gradient: with w_r == 1, eps == 0 and N the row count the output is k_ce's bits, with a
-// power-of-two weight exactly that weight times k_ce's bits.  The row loss is formed in fp32 as k_ce forms it, widened and multiplied by (double)w_r.
-// A row of weight 0 is decided from the weight and the target BEFORE any load of its logits is issued: its logits are not read, its target is not range-checked,
-// its dL/dlogits row is exact +0.  Smoothing (eps > 0, wave-uniform) adds one tr_wave_sum of z.
-template <int NV>
-__global__ __launch_bounds__(256) void k_ce_opt(const float* __restrict__ logits, const int64_t* __restrict__ tgt, int64_t tgt_stride, int BL, int Q, int64_t rows,
-                                                float* __restrict__ dlogits, double* __restrict__ loss, int rpw, int* __restrict__ status, CeOpts o) {
-    __shared__ double part[2][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float inv = ce_opt_inv<true>(o, rows);
-    const bool smooth = o.eps > 0.f;
-    const float ome = 1.0f - o.eps, eq = o.eps / (float)Q;
-    double lsum = 0.0, msum = 0.0;
-    for (int it = 0; it < rpw; ++it) {
-        const int64_t row = ((int64_t)blockIdx.x * rpw + it) * 4 + wave;
-        if (row >= rows) break;
-        const float* lg = logits + (size_t)row * Q;
-        const int64_t b = row / BL, t = row - b * BL;
-        int64_t tg = tgt[(size_t)b * tgt_stride + (tgt_stride - BL) + t];
-        const float wr = ce_row_weight(o, row, tg, lane, status);
-        if (wr == 0.f) { if (dlogits) ce_zero_row<NV>(dlogits + (size_t)row * Q, Q, lane); continue; }
-        const float sc = wr * inv;
-        msum += (double)wr;
-        float ce;
-        if constexpr (NV > 0) {
-            float4 z[NV];
-#pragma unroll
-            for (int k = 0; k < NV; ++k) z[k] = *(const float4*)(lg + lane * 4 + 256 * k);
-            if (tg < 0 || tg >= Q) { if (lane == 0) atomicOr(status, 2); tg = tg < 0 ? 0 : Q - 1; }
-            const float ztg = lg[tg];
-            float m = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < NV; ++k) m = fmaxf(fmaxf(m, fmaxf(z[k].x, z[k].y)), fmaxf(z[k].z, z[k].w));
-            m = tr_wave_max(m);
-            float se = 0.f;
-#pragma unroll
-            for (int k = 0; k < NV; ++k) se += (__expf(z[k].x - m) + __expf(z[k].y - m)) + (__expf(z[k].z - m) + __expf(z[k].w - m));
-            se = tr_wave_sum(se);
-            const float lse = logf(se) + m;
-            if (dlogits) {
-#pragma unroll
-                for (int k = 0; k < NV; ++k) {
-                    const int q = lane * 4 + 256 * k;
-                    float4 g = make_float4(__expf(z[k].x - lse), __expf(z[k].y - lse), __expf(z[k].z - lse), __expf(z[k].w - lse));
-                    const int dq = (int)tg - q;
-                    if (dq == 0) g.x -= ome; else if (dq == 1) g.y -= ome; else if (dq == 2) g.z -= ome; else if (dq == 3) g.w -= ome;
-                    if (smooth) { g.x -= eq; g.y -= eq; g.z -= eq; g.w -= eq; }
-                    *(float4*)(dlogits + (size_t)row * Q + q) = make_float4(g.x * sc, g.y * sc, g.z * sc, g.w * sc);
-                }
-            }
-            ce = lse - ztg;
-            if (smooth) {
-                float sz = 0.f;
-#pragma unroll
-                for (int k = 0; k < NV; ++k) sz += (z[k].x + z[k].y) + (z[k].z + z[k].w);
-                sz = tr_wave_sum(sz);
-                ce = (lse - ome * ztg) - eq * sz;
-            }
-        } else {
-            if (tg < 0 || tg >= Q) { if (lane == 0) atomicOr(status, 2); tg = tg < 0 ? 0 : Q - 1; }
-            float m = -INFINITY;
-            const bool vec = (Q & 255) == 0;
-            if (vec) for (int q = lane * 4; q < Q; q += 256) { const float4 v = *(const float4*)(lg + q); m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w)); }
-            else for (int q = lane; q < Q; q += 64) m = fmaxf(m, lg[q]);
-            m = tr_wave_max(m);
-            float se = 0.f, sz = 0.f;
-            if (vec) for (int q = lane * 4; q < Q; q += 256) { const float4 v = *(const float4*)(lg + q); se += (__expf(v.x - m) + __expf(v.y - m)) + (__expf(v.z - m) + __expf(v.w - m)); sz += (v.x + v.y) + (v.z + v.w); }
-            else for (int q = lane; q < Q; q += 64) { se += expf(lg[q] - m); sz += lg[q]; }
-            se = tr_wave_sum(se);
-            const float lse = logf(se) + m;
-            if (dlogits) {
-                if (vec) for (int q = lane * 4; q < Q; q += 256) {
-                    const float4 v = *(const float4*)(lg + q);
-                    float4 g = make_float4(__expf(v.x - lse), __expf(v.y - lse), __expf(v.z - lse), __expf(v.w - lse));
-                    const int dq = (int)tg - q;
-                    if (dq == 0) g.x -= ome; else if (dq == 1) g.y -= ome; else if (dq == 2) g.z -= ome; else if (dq == 3) g.w -= ome;
-                    if (smooth) { g.x -= eq; g.y -= eq; g.z -= eq; g.w -= eq; }
-                    *(float4*)(dlogits + (size_t)row * Q + q) = make_float4(g.x * sc, g.y * sc, g.z * sc, g.w * sc);
-                } else for (int q = lane; q < Q; q += 64) {
-                    float g = expf(lg[q] - lse) - (q == tg ? ome : 0.0f);
-                    if (smooth) g -= eq;
-                    dlogits[(size_t)row * Q + q] = g * sc;
-                }
-            }
-            ce = lse - lg[tg];
-            if (smooth) { sz = tr_wave_sum(sz); ce = (lse - ome * lg[tg]) - eq * sz; }
-        }
-        lsum += (double)ce * (double)wr;
-    }
-    if (lane == 0) { part[0][wave] = lsum; part[1][wave] = msum; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicAdd(loss + (blockIdx.x & 63), (part[0][0] + part[0][1] + part[0][2] + part[0][3]) / ce_opt_den<true>(o, rows));
-        if (o.mass) atomicAdd(o.mass + (blockIdx.x & 63), part[1][0] + part[1][1] + part[1][2] + part[1][3]);
-    }
-}
-
-// knowledge distillation ("Soft-target loss"): per row  L = (1 - alpha) CE(z, y) + alpha T^2 KL(softmax(t / T) || softmax(z / T))  and
-//   dL/dz = (1 - alpha) (softmax(z) - onehot(y)) + alpha T (softmax(z / T) - softmax(t / T)),  both over the row count, z = logits, t = teacher.
-// k_ce's layout (one wave per row, rpw rows per wave, 16 rows per workgroup, the 64 double loss slots) and, for the CE term, k_ce's arithmetic operation for
-// operation; the wave reductions are tr_wave_max / tr_wave_sum in k_ce's order, so dL/dlogits is the same bits from run to run.
-//   NV > 0: Q == 256 NV.  The lane's 4 NV student and 4 NV teacher values of a row are loaded with 16-byte loads, ALL in flight before the first reduction,
-//           and stay in registers with their tempered exponentials: a row is read once (2 x 1 KB at Q = 256), nothing lives in scratch.
-//   NV == 0: any Q, k_ce's loops -- four classes per lane and pass when Q % 256 == 0, one otherwise -- over rows that are L2-hot after the first pass.
-// KL is formed from log-probabilities ((t_i - m_t) / T - log S_t minus the student's counterpart): a teacher bitwise equal to the student gives exact zeros.
-// A NaN or an infinity in a row's teacher logits sets status bit 5 (the Adam launch of the step skips: the sticky-status rule); that row's outputs are unspecified.
-// comp (may be nullptr): 2 x 64 more slots -- the hard CE mean, then the KL mean BEFORE its factor T^2 -- for qpn_distill_loss's h_loss3.
-__device__ __forceinline__ bool dk_bad(float v) { return !(fabsf(v) <= 3.402823466e+38f); }      // NaN or +-inf
-template <int NV>
-__global__ __launch_bounds__(256) void k_ce_distill(const float* __restrict__ logits, const float* __restrict__ teacher, const int64_t* __restrict__ tgt, int64_t tgt_stride,
-                                                    int BL, int Q, int64_t rows, float alpha, float temp, float* __restrict__ dlogits, double* __restrict__ loss,
-                                                    double* __restrict__ comp, int rpw, int* __restrict__ status) {
-    constexpr bool W = false;
-    [[maybe_unused]] const CeOpts o{nullptr, 0, 0, 0.f, nullptr, nullptr};
-#include "train_ce_soft.inc.h"
-}
-// ... with row weights and ignore_index (the loss options above): instantiated apart from k_ce_distill, whose instances are what they always were
-template <int NV>
-__global__ __launch_bounds__(256) void k_ce_soft_w(const float* __restrict__ logits, const float* __restrict__ teacher, const int64_t* __restrict__ tgt, int64_t tgt_stride,
-                                                   int BL, int Q, int64_t rows, float alpha, float temp, float* __restrict__ dlogits, double* __restrict__ loss,
-                                                   double* __restrict__ comp, int rpw, int* __restrict__ status, CeOpts o) {
-    constexpr bool W = true;
-#include "train_ce_soft.inc.h"
 }
 
 // ------------------------------------------------------------------ host launchers (called from train_host.hip)
@@ -1145,76 +904,6 @@ int qpn_launch_fwd(const TrainParams& p, const TrainKnobs& k, const AuxGeom& ag,
         hipLaunchKernelGGL((k_post_fwd<1>), dim3((p.BL + 15) / 16, p.B), dim3(512), lds_post, stream, p);
     }
     qpn_prof_mark(PG_POST_FWD, stream);
-    QPN_HIP(hipGetLastError());
-    return QPN_OK;
-}
-
-int qpn_launch_ce(const float* logits, const int64_t* tgt, int64_t tgt_stride, int B, int BL, int Q, float* dlogits, double* loss, int* status, bool loss_cleared, hipStream_t stream) {
-    const int64_t rows = (int64_t)B * BL;
-    // (the loss accumulator was cleared by this step's k_refresh; a CE call without a forward in front clears it itself)
-    if (!loss_cleared) QPN_HIP(hipMemsetAsync(loss, 0, 64 * sizeof(double), stream));
-    const int rpw = 4;                // 16 rows per workgroup: ~1250 workgroups for a 20 k-row chunk (64 rows per workgroup left most CUs with one)
-    hipLaunchKernelGGL(k_ce, dim3((unsigned)((rows + 4 * rpw - 1) / (4 * rpw))), dim3(256), 0, stream, logits, tgt, tgt_stride, BL, Q, rows, dlogits, loss, rpw, status);
-    qpn_prof_mark(PG_CE, stream);
-    QPN_HIP(hipGetLastError());
-    return QPN_OK;
-}
-
-// what both option launchers do in front of their kernel: clear the 64 mass slots and, for norm = "weights", write the word the kernel divides by
-static int qpn_launch_ce_opt_mass(const int64_t* tgt, int64_t tgt_stride, int BL, int64_t rows, const CeOpts& o, hipStream_t stream) {
-    if (o.mass) QPN_HIP(hipMemsetAsync(o.mass, 0, 64 * sizeof(double), stream));
-    if (o.norm_mass) hipLaunchKernelGGL(k_weight_mass, dim3(1), dim3(1024), 0, stream, tgt, tgt_stride, BL, rows, o, const_cast<double*>(o.norm_mass));
-    return QPN_OK;
-}
-
-// the cross entropy with options in k_ce's place (qpn_ce_loss_opts, an armed forward-with-loss): same accumulator rules
-int qpn_launch_ce_opt(const float* logits, const int64_t* tgt, int64_t tgt_stride, int B, int BL, int Q, const CeOpts& o, float* dlogits, double* loss, int* status,
-                      bool loss_cleared, hipStream_t stream) {
-    const int64_t rows = (int64_t)B * BL;
-    if (!loss_cleared) QPN_HIP(hipMemsetAsync(loss, 0, 64 * sizeof(double), stream));
-    int rc = qpn_launch_ce_opt_mass(tgt, tgt_stride, BL, rows, o, stream); if (rc) return rc;
-    const int rpw = 4;
-    const dim3 grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
-    // rows of up to 1024 classes in registers (16-byte loads: logits and dlogits must be 16-byte aligned, checked by the callers); anything else: k_ce's loops
-    const int nv = (Q % 256 == 0 && Q <= 1024) ? Q / 256 : 0;
-#define QPN_CE_OPT_LAUNCH(NV) hipLaunchKernelGGL((k_ce_opt<NV>), grid, dim3(256), 0, stream, logits, tgt, tgt_stride, BL, Q, rows, dlogits, loss, rpw, status, o)
-    switch (nv) {
-        case 1: QPN_CE_OPT_LAUNCH(1); break;
-        case 2: QPN_CE_OPT_LAUNCH(2); break;
-        case 3: QPN_CE_OPT_LAUNCH(3); break;
-        case 4: QPN_CE_OPT_LAUNCH(4); break;
-        default: QPN_CE_OPT_LAUNCH(0); break;
-    }
-#undef QPN_CE_OPT_LAUNCH
-    qpn_prof_mark(PG_CE, stream);
-    QPN_HIP(hipGetLastError());
-    return QPN_OK;
-}
-
-// the soft-target loss in k_ce's place (qpn_distill_loss, an armed forward-with-loss): same accumulator rules; comp != nullptr: its 128 slots are cleared here
-int qpn_launch_ce_distill(const float* logits, const float* teacher, const int64_t* tgt, int64_t tgt_stride, int B, int BL, int Q, float alpha, float temp,
-                          float* dlogits, double* loss, double* comp, int* status, bool loss_cleared, hipStream_t stream, const CeOpts* opts) {
-    const int64_t rows = (int64_t)B * BL;
-    if (!loss_cleared) QPN_HIP(hipMemsetAsync(loss, 0, 64 * sizeof(double), stream));
-    if (comp) QPN_HIP(hipMemsetAsync(comp, 0, 128 * sizeof(double), stream));
-    const int rpw = 4;
-    const dim3 grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
-    // rows of up to 1024 classes in registers (16-byte loads: every base pointer must be 16-byte aligned, checked by the callers); anything else: k_ce's loops
-    const int nv = (Q % 256 == 0 && Q <= 1024) ? Q / 256 : 0;
-    // opts (row weights / ignore_index; nullptr: none): the weighted instances -- the unweighted ones are the kernels they always were
-    const CeOpts o = opts ? *opts : CeOpts{nullptr, 0, 0, 0.f, nullptr, nullptr};
-    if (opts) { const int rc = qpn_launch_ce_opt_mass(tgt, tgt_stride, BL, rows, o, stream); if (rc) return rc; }
-#define QPN_DISTILL_LAUNCH(NV) do { if (opts) hipLaunchKernelGGL((k_ce_soft_w<NV>), grid, dim3(256), 0, stream, logits, teacher, tgt, tgt_stride, BL, Q, rows, alpha, temp, dlogits, loss, comp, rpw, status, o); \
-                                    else hipLaunchKernelGGL((k_ce_distill<NV>), grid, dim3(256), 0, stream, logits, teacher, tgt, tgt_stride, BL, Q, rows, alpha, temp, dlogits, loss, comp, rpw, status); } while (0)
-    switch (nv) {
-        case 1: QPN_DISTILL_LAUNCH(1); break;
-        case 2: QPN_DISTILL_LAUNCH(2); break;
-        case 3: QPN_DISTILL_LAUNCH(3); break;
-        case 4: QPN_DISTILL_LAUNCH(4); break;
-        default: QPN_DISTILL_LAUNCH(0); break;
-    }
-#undef QPN_DISTILL_LAUNCH
-    qpn_prof_mark(PG_CE, stream);
     QPN_HIP(hipGetLastError());
     return QPN_OK;
 }

@@ -11,11 +11,6 @@
 int qpn_launch_fwd(const TrainParams& p, const TrainKnobs& k, const AuxGeom& ag, const StackQ* sq, hipStream_t stream, const TrainBwd* fuse_post_bwd, const RefreshArgs* rf);
 bool qpn_step_prep_fits(const TrainParams& p);
 void qpn_stack_fill(TrainParams& p);
-int qpn_launch_ce(const float* logits, const int64_t* tgt, int64_t tgt_stride, int B, int BL, int Q, float* dlogits, double* loss, int* status, bool loss_cleared, hipStream_t stream);
-int qpn_launch_ce_distill(const float* logits, const float* teacher, const int64_t* tgt, int64_t tgt_stride, int B, int BL, int Q, float alpha, float temp,
-                          float* dlogits, double* loss, double* comp, int* status, bool loss_cleared, hipStream_t stream, const CeOpts* opts);
-int qpn_launch_ce_opt(const float* logits, const int64_t* tgt, int64_t tgt_stride, int B, int BL, int Q, const CeOpts& o, float* dlogits, double* loss, int* status,
-                      bool loss_cleared, hipStream_t stream);
 static CeOpts ce_opts_of(const qpn_loss_opts& o, double* mass, double* d_mass);
 int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k, const AuxGeom& ag, const StackQ* sq, hipStream_t stream, bool post_done);
 int qpn_launch_fwd_gemm(const TrainParams& p, const TrainGemm& w, hipStream_t stream);
@@ -278,7 +273,7 @@ static int need_dev(qpn_handle* h) {
 }
 
 // targets == nullptr: plain forward.  Otherwise the mean cross entropy (and d_dlogits) is computed too: inside the post-net kernel
-// when the tile path can hold a row of logits in LDS, by a k_ce launch behind the forward otherwise.
+// when the tile path can hold a row of logits in LDS, by a k_ce_hard launch (train_loss.hip) behind the forward otherwise.
 // fuse_bwd: the caller runs this forward's backward next, with the same d_dlogits, whatever the loss is (qpn_train_step): the post-net's backward may run inside the forward's launch
 static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
                               const int64_t* d_x, const float* d_h, const float* d_dfac, float* d_logits,
@@ -415,7 +410,7 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
     qpn_prof_mark(PG_PREP, stream);
     t->fwd_valid = false; t->loss_clear = true;
     ++t->generation;
-    const bool fuse_ce = d_targets && !t->lay.use_gemm && g.Q <= g.S && g.Q % 256 == 0 && !t->knobs.ce_separate && !d_teacher && !lo_armed;      // (armed: QPN_CE_SEPARATE's route, k_ce_distill / k_ce_opt in k_ce's place)
+    const bool fuse_ce = d_targets && !t->lay.use_gemm && g.Q <= g.S && g.Q % 256 == 0 && !t->knobs.ce_separate && !d_teacher && !lo_armed;      // (armed: QPN_CE_SEPARATE's route, k_ce_soft / k_ce_hard<NV, true> in the plain kernel's place)
     p.ce_tgt = fuse_ce ? d_targets : nullptr; p.ce_stride = tgt_stride; p.ce_dlogits = d_dlogits; p.ce_loss = t->d_loss;
     if (fuse_ce && !want_logits) p.logits = nullptr;
     const bool fuse_post = fuse_bwd && fuse_ce && d_dlogits && t->knobs.post_fuse && t->knobs.post_wide && t->knobs.zero_in_post && g.S == 256 && g.Q == 256 && g.C == 64 && (p.LC == 256 || p.LC == 512);
@@ -428,9 +423,8 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
     if (fuse_ce) { t->loss_clear = false; qpn_prof_mark(PG_CE, stream); }
     else if (d_targets) {
         const CeOpts co = ce_opts_of(lo, nullptr, t->d_mass);
-        rc = d_teacher ? qpn_launch_ce_distill(d_logits, d_teacher, d_targets, tgt_stride, B, BL, g.Q, ds_alpha, ds_temp, d_dlogits, t->d_loss, nullptr, t->d_status, t->loss_clear, stream, lo_armed ? &co : nullptr)
-             : lo_armed ? qpn_launch_ce_opt(d_logits, d_targets, tgt_stride, B, BL, g.Q, co, d_dlogits, t->d_loss, t->d_status, t->loss_clear, stream)
-                       : qpn_launch_ce(d_logits, d_targets, tgt_stride, B, BL, g.Q, d_dlogits, t->d_loss, t->d_status, t->loss_clear, stream);
+        const LossCall lc = {d_logits, d_teacher, d_targets, tgt_stride, B, BL, g.Q, ds_alpha, ds_temp, lo_armed ? &co : nullptr, d_dlogits, t->d_loss, nullptr, t->d_status, t->loss_clear};
+        rc = qpn_launch_loss(lc, stream);
         if (rc) return rc;
         t->loss_clear = false;
     }
@@ -580,58 +574,10 @@ extern "C" int qpn_train_status_collect_lagged(qpn_handle* h) {
     return status_collect_slot(h->train, h->train->status_newest ^ 1);
 }
 
-extern "C" int qpn_ce_loss(qpn_handle* h, const float* d_logits, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
-                           float* d_dlogits, double* h_loss, void* stream_) {
-    int rc = need_dev(h); if (rc) return rc;
-    rc = train_init(h); if (rc) return rc;
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!d_logits || !d_targets || B < 1 || BL < 1 || tgt_stride < BL) { qpn_set_error("bad ce_loss arguments"); return QPN_EINVAL; }
-    rc = qpn_launch_ce(d_logits, d_targets, tgt_stride, B, BL, h->g.Q, d_dlogits, h->train->d_loss, h->train->d_status, h->train->loss_clear, stream); if (rc) return rc;
-    h->train->loss_clear = false;
-    if (h_loss) {
-        double parts[64];
-        QPN_HIP(hipMemcpyAsync(parts, h->train->d_loss, sizeof(parts), hipMemcpyDeviceToHost, stream));
-        QPN_HIP(hipStreamSynchronize(stream));
-        *h_loss = loss_sum(parts);
-    }
-    return QPN_OK;
-}
-
 // alpha in (0, 1], temperature finite and > 0: the rules of both distillation entry points (checked without a device)
 static int check_distill_args(const char* fn, float alpha, float temperature) {
     if (!(alpha > 0.f && alpha <= 1.f)) { qpn_set_error("%s: alpha must lie in (0, 1] (got %g)", fn, (double)alpha); return QPN_EINVAL; }
     if (!(temperature > 0.f) || !(temperature <= 3.402823466e+38f)) { qpn_set_error("%s: temperature must be finite and > 0 (got %g)", fn, (double)temperature); return QPN_EINVAL; }
-    return QPN_OK;
-}
-
-extern "C" int qpn_distill_loss(qpn_handle* h, const float* d_logits, const float* d_teacher, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
-                                float alpha, float temperature, float* d_dlogits, double* h_loss3, void* stream_) {
-    if (!h) { qpn_set_error("qpn_distill_loss: null handle"); return QPN_EINVAL; }
-    if (!d_logits) { qpn_set_error("qpn_distill_loss: d_logits is NULL"); return QPN_EINVAL; }
-    if (!d_teacher) { qpn_set_error("qpn_distill_loss: d_teacher is NULL"); return QPN_EINVAL; }
-    if (!d_targets) { qpn_set_error("qpn_distill_loss: d_targets is NULL"); return QPN_EINVAL; }
-    if (B < 1) { qpn_set_error("qpn_distill_loss: B must be >= 1 (got %d)", B); return QPN_EINVAL; }
-    if (BL < 1) { qpn_set_error("qpn_distill_loss: BL must be >= 1 (got %d)", BL); return QPN_EINVAL; }
-    if (tgt_stride < BL) { qpn_set_error("qpn_distill_loss: tgt_stride (%lld) is shorter than BL (%d)", (long long)tgt_stride, BL); return QPN_EINVAL; }
-    int rc = check_distill_args("qpn_distill_loss", alpha, temperature); if (rc) return rc;
-    if (h->g.Q % 256 == 0 && ((((uintptr_t)d_logits) | ((uintptr_t)d_teacher) | ((uintptr_t)d_dlogits)) & 15)) {
-        qpn_set_error("qpn_distill_loss: d_logits, d_teacher and d_dlogits must be 16-byte aligned"); return QPN_EINVAL;
-    }
-    rc = need_dev(h); if (rc) return rc;
-    rc = train_init(h); if (rc) return rc;
-    TrainState* t = h->train;
-    hipStream_t stream = (hipStream_t)stream_;
-    if (h_loss3 && !t->d_loss3) QPN_HIP(hipMalloc(&t->d_loss3, 128 * sizeof(double)));
-    rc = qpn_launch_ce_distill(d_logits, d_teacher, d_targets, tgt_stride, B, BL, h->g.Q, alpha, temperature, d_dlogits, t->d_loss, h_loss3 ? t->d_loss3 : nullptr,
-                               t->d_status, t->loss_clear, stream, nullptr); if (rc) return rc;
-    t->loss_clear = false;
-    if (h_loss3) {
-        double parts[64], comp[128];
-        QPN_HIP(hipMemcpyAsync(parts, t->d_loss, sizeof(parts), hipMemcpyDeviceToHost, stream));
-        QPN_HIP(hipMemcpyAsync(comp, t->d_loss3, sizeof(comp), hipMemcpyDeviceToHost, stream));
-        QPN_HIP(hipStreamSynchronize(stream));
-        h_loss3[0] = loss_sum(parts); h_loss3[1] = loss_sum(comp); h_loss3[2] = (double)temperature * (double)temperature * loss_sum(comp + 64);
-    }
     return QPN_OK;
 }
 
@@ -663,74 +609,72 @@ static int check_loss_opts(const char* fn, const qpn_loss_opts* o, bool with_tea
 static CeOpts ce_opts_of(const qpn_loss_opts& o, double* mass, double* d_mass) {
     return CeOpts{o.d_weights, (long long)o.ignore_index, o.use_ignore ? 1 : 0, o.label_smoothing, o.norm == 1 ? d_mass + 64 : nullptr, mass};
 }
-static int loss_opts_mass(TrainState* t) {
-    if (!t->d_mass) QPN_HIP(hipMalloc(&t->d_mass, 72 * sizeof(double)));
-    return QPN_OK;
-}
-
-extern "C" int qpn_ce_loss_opts(qpn_handle* h, const float* d_logits, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
-                                const qpn_loss_opts* opts, float* d_dlogits, double* h_loss2, void* stream_) {
-    if (!h) { qpn_set_error("qpn_ce_loss_opts: null handle"); return QPN_EINVAL; }
-    if (!d_logits) { qpn_set_error("qpn_ce_loss_opts: d_logits is NULL"); return QPN_EINVAL; }
-    if (!d_targets) { qpn_set_error("qpn_ce_loss_opts: d_targets is NULL"); return QPN_EINVAL; }
-    if (B < 1) { qpn_set_error("qpn_ce_loss_opts: B must be >= 1 (got %d)", B); return QPN_EINVAL; }
-    if (BL < 1) { qpn_set_error("qpn_ce_loss_opts: BL must be >= 1 (got %d)", BL); return QPN_EINVAL; }
-    if (tgt_stride < BL) { qpn_set_error("qpn_ce_loss_opts: tgt_stride (%lld) is shorter than BL (%d)", (long long)tgt_stride, BL); return QPN_EINVAL; }
-    int rc = check_loss_opts("qpn_ce_loss_opts", opts, false); if (rc) return rc;
-    if (opts->d_weights && opts->n_weights != (int64_t)B * BL) { qpn_set_error("qpn_ce_loss_opts: n_weights = %lld, the call has B * BL = %d * %d = %lld rows", (long long)opts->n_weights, B, BL, (long long)B * BL); return QPN_EINVAL; }
-    if (h->g.Q % 256 == 0 && ((((uintptr_t)d_logits) | ((uintptr_t)d_dlogits)) & 15)) { qpn_set_error("qpn_ce_loss_opts: d_logits and d_dlogits must be 16-byte aligned"); return QPN_EINVAL; }
-    rc = need_dev(h); if (rc) return rc;
-    rc = train_init(h); if (rc) return rc;
-    TrainState* t = h->train;
-    hipStream_t stream = (hipStream_t)stream_;
-    rc = loss_opts_mass(t); if (rc) return rc;
-    rc = qpn_launch_ce_opt(d_logits, d_targets, tgt_stride, B, BL, h->g.Q, ce_opts_of(*opts, h_loss2 ? t->d_mass : nullptr, t->d_mass), d_dlogits, t->d_loss, t->d_status, t->loss_clear, stream);
-    if (rc) return rc;
-    t->loss_clear = false;
-    if (h_loss2) {
-        double parts[64], mass[64];
-        QPN_HIP(hipMemcpyAsync(parts, t->d_loss, sizeof(parts), hipMemcpyDeviceToHost, stream));
-        QPN_HIP(hipMemcpyAsync(mass, t->d_mass, sizeof(mass), hipMemcpyDeviceToHost, stream));
-        QPN_HIP(hipStreamSynchronize(stream));
-        h_loss2[0] = loss_sum(parts); h_loss2[1] = loss_sum(mass);
-    }
-    return QPN_OK;
-}
-
-extern "C" int qpn_distill_loss_opts(qpn_handle* h, const float* d_logits, const float* d_teacher, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
-                                     float alpha, float temperature, const qpn_loss_opts* opts, float* d_dlogits, double* h_loss4, void* stream_) {
-    if (!h) { qpn_set_error("qpn_distill_loss_opts: null handle"); return QPN_EINVAL; }
-    if (!d_logits) { qpn_set_error("qpn_distill_loss_opts: d_logits is NULL"); return QPN_EINVAL; }
-    if (!d_teacher) { qpn_set_error("qpn_distill_loss_opts: d_teacher is NULL"); return QPN_EINVAL; }
-    if (!d_targets) { qpn_set_error("qpn_distill_loss_opts: d_targets is NULL"); return QPN_EINVAL; }
-    if (B < 1) { qpn_set_error("qpn_distill_loss_opts: B must be >= 1 (got %d)", B); return QPN_EINVAL; }
-    if (BL < 1) { qpn_set_error("qpn_distill_loss_opts: BL must be >= 1 (got %d)", BL); return QPN_EINVAL; }
-    if (tgt_stride < BL) { qpn_set_error("qpn_distill_loss_opts: tgt_stride (%lld) is shorter than BL (%d)", (long long)tgt_stride, BL); return QPN_EINVAL; }
-    int rc = check_distill_args("qpn_distill_loss_opts", alpha, temperature); if (rc) return rc;
-    rc = check_loss_opts("qpn_distill_loss_opts", opts, true); if (rc) return rc;
-    if (opts->d_weights && opts->n_weights != (int64_t)B * BL) { qpn_set_error("qpn_distill_loss_opts: n_weights = %lld, the call has B * BL = %d * %d = %lld rows", (long long)opts->n_weights, B, BL, (long long)B * BL); return QPN_EINVAL; }
-    if (h->g.Q % 256 == 0 && ((((uintptr_t)d_logits) | ((uintptr_t)d_teacher) | ((uintptr_t)d_dlogits)) & 15)) {
-        qpn_set_error("qpn_distill_loss_opts: d_logits, d_teacher and d_dlogits must be 16-byte aligned"); return QPN_EINVAL;
+// The four stand-alone loss entry points below are this one function.  fn: the entry's name for its messages (nullptr: qpn_ce_loss, which has made its one
+// terse check, behind need_dev / train_init); soft / with_opts: the entry takes a teacher / options.  Argument errors are reported before any device is needed.
+// h_out (may be NULL: nothing is read back and the call does not synchronise): [0] the loss; soft: then the hard CE mean and T^2 KL; with_opts: then the
+// effective sum of weights
+static int loss_entry(const char* fn, qpn_handle* h, const float* d_logits, bool soft, const float* d_teacher, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
+                      float alpha, float temperature, bool with_opts, const qpn_loss_opts* opts, float* d_dlogits, double* h_out, void* stream_) {
+    int rc;
+    if (fn) {
+        if (!h) { qpn_set_error("%s: null handle", fn); return QPN_EINVAL; }
+        if (!d_logits) { qpn_set_error("%s: d_logits is NULL", fn); return QPN_EINVAL; }
+        if (soft && !d_teacher) { qpn_set_error("%s: d_teacher is NULL", fn); return QPN_EINVAL; }
+        if (!d_targets) { qpn_set_error("%s: d_targets is NULL", fn); return QPN_EINVAL; }
+        if (B < 1) { qpn_set_error("%s: B must be >= 1 (got %d)", fn, B); return QPN_EINVAL; }
+        if (BL < 1) { qpn_set_error("%s: BL must be >= 1 (got %d)", fn, BL); return QPN_EINVAL; }
+        if (tgt_stride < BL) { qpn_set_error("%s: tgt_stride (%lld) is shorter than BL (%d)", fn, (long long)tgt_stride, BL); return QPN_EINVAL; }
+        if (soft) { rc = check_distill_args(fn, alpha, temperature); if (rc) return rc; }
+        if (with_opts) {
+            rc = check_loss_opts(fn, opts, soft); if (rc) return rc;
+            if (opts->d_weights && opts->n_weights != (int64_t)B * BL) { qpn_set_error("%s: n_weights = %lld, the call has B * BL = %d * %d = %lld rows", fn, (long long)opts->n_weights, B, BL, (long long)B * BL); return QPN_EINVAL; }
+        }
+        if (h->g.Q % 256 == 0 && ((((uintptr_t)d_logits) | (soft ? (uintptr_t)d_teacher : 0) | ((uintptr_t)d_dlogits)) & 15)) {
+            qpn_set_error(soft ? "%s: d_logits, d_teacher and d_dlogits must be 16-byte aligned" : "%s: d_logits and d_dlogits must be 16-byte aligned", fn); return QPN_EINVAL;
+        }
     }
     rc = need_dev(h); if (rc) return rc;
     rc = train_init(h); if (rc) return rc;
     TrainState* t = h->train;
     hipStream_t stream = (hipStream_t)stream_;
-    rc = loss_opts_mass(t); if (rc) return rc;
-    if (h_loss4 && !t->d_loss3) QPN_HIP(hipMalloc(&t->d_loss3, 128 * sizeof(double)));
-    const CeOpts co = ce_opts_of(*opts, h_loss4 ? t->d_mass : nullptr, t->d_mass);
-    rc = qpn_launch_ce_distill(d_logits, d_teacher, d_targets, tgt_stride, B, BL, h->g.Q, alpha, temperature, d_dlogits, t->d_loss, h_loss4 ? t->d_loss3 : nullptr,
-                               t->d_status, t->loss_clear, stream, &co); if (rc) return rc;
+    if (with_opts && !t->d_mass) QPN_HIP(hipMalloc(&t->d_mass, 72 * sizeof(double)));
+    if (soft && h_out && !t->d_loss3) QPN_HIP(hipMalloc(&t->d_loss3, 128 * sizeof(double)));
+    const CeOpts co = with_opts ? ce_opts_of(*opts, h_out ? t->d_mass : nullptr, t->d_mass) : CeOpts{};
+    const LossCall lc = {d_logits, soft ? d_teacher : nullptr, d_targets, tgt_stride, B, BL, h->g.Q, alpha, temperature, with_opts ? &co : nullptr,
+                         d_dlogits, t->d_loss, soft && h_out ? t->d_loss3 : nullptr, t->d_status, t->loss_clear};
+    rc = qpn_launch_loss(lc, stream); if (rc) return rc;
     t->loss_clear = false;
-    if (h_loss4) {
+    if (h_out) {
         double parts[64], comp[128], mass[64];
         QPN_HIP(hipMemcpyAsync(parts, t->d_loss, sizeof(parts), hipMemcpyDeviceToHost, stream));
-        QPN_HIP(hipMemcpyAsync(comp, t->d_loss3, sizeof(comp), hipMemcpyDeviceToHost, stream));
-        QPN_HIP(hipMemcpyAsync(mass, t->d_mass, sizeof(mass), hipMemcpyDeviceToHost, stream));
+        if (soft) QPN_HIP(hipMemcpyAsync(comp, t->d_loss3, sizeof(comp), hipMemcpyDeviceToHost, stream));
+        if (with_opts) QPN_HIP(hipMemcpyAsync(mass, t->d_mass, sizeof(mass), hipMemcpyDeviceToHost, stream));
         QPN_HIP(hipStreamSynchronize(stream));
-        h_loss4[0] = loss_sum(parts); h_loss4[1] = loss_sum(comp); h_loss4[2] = (double)temperature * (double)temperature * loss_sum(comp + 64); h_loss4[3] = loss_sum(mass);
+        *h_out++ = loss_sum(parts);
+        if (soft) { *h_out++ = loss_sum(comp); *h_out++ = (double)temperature * (double)temperature * loss_sum(comp + 64); }
+        if (with_opts) *h_out++ = loss_sum(mass);
     }
     return QPN_OK;
+}
+
+extern "C" int qpn_ce_loss(qpn_handle* h, const float* d_logits, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
+                           float* d_dlogits, double* h_loss, void* stream_) {
+    int rc = need_dev(h); if (rc) return rc;
+    rc = train_init(h); if (rc) return rc;
+    if (!d_logits || !d_targets || B < 1 || BL < 1 || tgt_stride < BL) { qpn_set_error("bad ce_loss arguments"); return QPN_EINVAL; }
+    return loss_entry(nullptr, h, d_logits, false, nullptr, d_targets, tgt_stride, B, BL, 0.f, 0.f, false, nullptr, d_dlogits, h_loss, stream_);
+}
+extern "C" int qpn_distill_loss(qpn_handle* h, const float* d_logits, const float* d_teacher, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
+                                float alpha, float temperature, float* d_dlogits, double* h_loss3, void* stream_) {
+    return loss_entry("qpn_distill_loss", h, d_logits, true, d_teacher, d_targets, tgt_stride, B, BL, alpha, temperature, false, nullptr, d_dlogits, h_loss3, stream_);
+}
+extern "C" int qpn_ce_loss_opts(qpn_handle* h, const float* d_logits, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
+                                const qpn_loss_opts* opts, float* d_dlogits, double* h_loss2, void* stream_) {
+    return loss_entry("qpn_ce_loss_opts", h, d_logits, false, nullptr, d_targets, tgt_stride, B, BL, 0.f, 0.f, true, opts, d_dlogits, h_loss2, stream_);
+}
+extern "C" int qpn_distill_loss_opts(qpn_handle* h, const float* d_logits, const float* d_teacher, const int64_t* d_targets, int64_t tgt_stride, int B, int BL,
+                                     float alpha, float temperature, const qpn_loss_opts* opts, float* d_dlogits, double* h_loss4, void* stream_) {
+    return loss_entry("qpn_distill_loss_opts", h, d_logits, true, d_teacher, d_targets, tgt_stride, B, BL, alpha, temperature, true, opts, d_dlogits, h_loss4, stream_);
 }
 
 // The arm is host state on the handle, as qpn_train_distill's is.  An options struct that is entirely default arms nothing: the next forward launches what it always launched

@@ -135,7 +135,7 @@ __device__ __forceinline__ void post_fwd_w_tile(const TrainParams& p, float* sm,
             if (t0 + r < p.BL) *(float2*)(p.logits + ((size_t)b * p.BL + t0 + r) * Q + kk) = *(const float2*)(T + (size_t)r * lds + kk);
         }
     if (!p.ce_tgt) return;
-    // ---------- fused torch.nn.CrossEntropyLoss() (mean) and its gradient while the logits are in LDS (same arithmetic as k_ce)
+    // ---------- fused torch.nn.CrossEntropyLoss() (mean) and its gradient while the logits are in LDS (same arithmetic as k_ce_hard)
     {
         const int64_t rows = (int64_t)p.B * p.BL;
         const float inv = 1.0f / (float)rows;
@@ -161,7 +161,7 @@ __device__ __forceinline__ void post_fwd_w_tile(const TrainParams& p, float* sm,
             const bool in = t0 + r < p.BL;
             const int64_t row = (int64_t)b * p.BL + t0 + r;
             const int q = lane * 4;
-            // (the wave reductions are k_ce's: DPP inside the 16-lane rows + v_readlane across them, same order, bit-identical dL/dlogits; as six
+            // (the wave reductions are k_ce_hard's: DPP inside the 16-lane rows + v_readlane across them, same order, bit-identical dL/dlogits; as six
             //  dependent ds_bpermute each they made the cross entropy 25 k of the tile's 232 k cycles: profiles/r05_post_fwd_stamps.txt)
             const float m = tr_wave_max(fmaxf(fmaxf(lv[k][0], lv[k][1]), fmaxf(lv[k][2], lv[k][3])));
             const float se = tr_wave_sum((__expf(lv[k][0] - m) + __expf(lv[k][1] - m)) + (__expf(lv[k][2] - m) + __expf(lv[k][3] - m)));

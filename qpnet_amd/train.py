@@ -603,49 +603,19 @@ def _check_distill(model, distill):
     return teacher, a, T
 
 
-def _check_teacher_logits(tl, B, BL, Q, dev):
-    """precomputed teacher logits as the C ABI takes them: float32, (B, BL, Q), contiguous, on the (CUDA) device of the step's inputs"""
-    if not isinstance(tl, torch.Tensor):
-        raise ValueError("teacher_logits must be a torch.Tensor (or None), got %r" % (type(tl),))
-    if tl.dtype != torch.float32:
-        raise ValueError("teacher_logits must be float32, got %s" % (tl.dtype,))
-    if tuple(tl.shape) != (B, BL, Q):
-        raise ValueError("teacher_logits must have the shape (B, BL, n_quantize) = %s, got %s" % ((B, BL, Q), tuple(tl.shape)))
-    if not tl.is_contiguous():
-        raise ValueError("teacher_logits must be contiguous")
-    if not tl.is_cuda or tl.device != dev:
-        raise ValueError("teacher_logits must be a CUDA tensor on the device of the step's inputs (%s), got %s" % (dev, tl.device))
-
-
-class _DistillLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, teacher_logits, targets, alpha, temperature, weights=None, ignore=None):
-        dev = logits.device
-        lg = logits.detach().to(dev, torch.float32).contiguous()
-        tl = teacher_logits.detach().to(dev, torch.float32).contiguous()
-        tg = targets.to(dev, torch.int64).contiguous()
-        B, BL, Q = lg.shape
-        dl = torch.empty_like(lg)
-        parts = (C.c_double * 4)()
-        with torch.cuda.device(dev):
-            hp = _loss_handle(dev, Q)
-            if weights is None and ignore is None:
-                _lib.check(_lib.lib().qpn_distill_loss(hp, lg.data_ptr(), tl.data_ptr(), tg.data_ptr(), tg.shape[1], B, BL, alpha, temperature,
-                                                       dl.data_ptr(), parts, torch.cuda.current_stream(dev).cuda_stream))
-            else:
-                wt = None if weights is None else weights.detach().to(dev, torch.float32).contiguous()
-                opts = _make_loss_opts(wt, ignore, 0.0, 0)
-                _lib.check(_lib.lib().qpn_distill_loss_opts(hp, lg.data_ptr(), tl.data_ptr(), tg.data_ptr(), tg.shape[1], B, BL, alpha, temperature, C.byref(opts),
-                                                            dl.data_ptr(), parts, torch.cuda.current_stream(dev).cuda_stream))
-            _lib.check(_lib.lib().qpn_train_status(hp, torch.cuda.current_stream(dev).cuda_stream))      # (the stream has just been drained for the loss)
-        ctx.save_for_backward(dl)
-        return torch.tensor(parts[0], dtype=torch.float32, device=dev)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_output):
-        dl, = ctx.saved_tensors
-        return grad_output * dl, None, None, None, None, None, None
+def _check_step_tensor(name, label, v, shape, dev):
+    """a step's precomputed teacher logits or sample weights as the C ABI takes them: float32, `shape` (named `label` in the message), contiguous, on the (CUDA)
+    device of the step's inputs"""
+    if not isinstance(v, torch.Tensor):
+        raise ValueError("%s must be a torch.Tensor (or None), got %r" % (name, type(v)))
+    if v.dtype != torch.float32:
+        raise ValueError("%s must be float32, got %s" % (name, v.dtype))
+    if tuple(v.shape) != shape:
+        raise ValueError("%s must have the shape %s = %s, got %s" % (name, label, shape, tuple(v.shape)))
+    if not v.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+    if not v.is_cuda or v.device != dev:
+        raise ValueError("%s must be a CUDA tensor on the device of the step's inputs (%s), got %s" % (name, dev, v.device))
 
 
 _LOSS_HANDLES = {}
@@ -681,7 +651,7 @@ def distill_loss(logits, teacher_logits, targets, alpha, temperature, sample_wei
         raise ValueError("distill_loss: logits and teacher_logits (B, BL, Q) and targets (B, >= BL) expected, got %s, %s and %s"
                          % (tuple(logits.shape), tuple(teacher_logits.shape), tuple(targets.shape)))
     a, T = _check_distill_scalars(alpha, temperature)
-    return _DistillLoss.apply(logits, teacher_logits, targets, a, T, sample_weights, ign)
+    return _NativeLoss.apply(logits, targets, teacher_logits, a, T, sample_weights, ign, 0.0, 0)
 
 
 _LOSS_NORMS = {"rows": 0, "weights": 1}
@@ -712,29 +682,16 @@ def _check_weights_like(w, rows):
         raise ValueError("sample_weights must hold one weight per row (%d), got the shape %s" % (rows, tuple(w.shape)))
 
 
-def _check_sample_weights(w, B, BL, dev):
-    """a step's sample weights as the C ABI takes them: float32, (B, BL), contiguous, on the (CUDA) device of the step's inputs"""
-    if not isinstance(w, torch.Tensor):
-        raise ValueError("sample_weights must be a torch.Tensor (or None), got %r" % (type(w),))
-    if w.dtype != torch.float32:
-        raise ValueError("sample_weights must be float32, got %s" % (w.dtype,))
-    if tuple(w.shape) != (B, BL):
-        raise ValueError("sample_weights must have the shape (B, BL) = %s, got %s" % ((B, BL), tuple(w.shape)))
-    if not w.is_contiguous():
-        raise ValueError("sample_weights must be contiguous")
-    if not w.is_cuda or w.device != dev:
-        raise ValueError("sample_weights must be a CUDA tensor on the device of the step's inputs (%s), got %s" % (dev, w.device))
-
-
 def _make_loss_opts(weights, ignore_index, eps, norm):
     """qpn_loss_opts from checked values (weights: a float32 contiguous CUDA tensor or None, kept alive by the caller)"""
     return _lib.QpnLossOpts(weights.data_ptr() if weights is not None else None, weights.numel() if weights is not None else 0,
                             0 if ignore_index is None else 1, 0 if ignore_index is None else ignore_index, eps, norm)
 
 
-class _CrossEntropy(torch.autograd.Function):
+class _NativeLoss(torch.autograd.Function):
+    """cross_entropy() (teacher_logits None) and distill_loss(): one launch computes the loss and dL/dlogits, backward scales the saved dL/dlogits"""
     @staticmethod
-    def forward(ctx, logits, targets, weights, ignore, eps, norm):
+    def forward(ctx, logits, targets, teacher_logits, alpha, temperature, weights, ignore, eps, norm):
         dev = logits.device
         lg = logits.detach().to(dev, torch.float32).contiguous()
         tg = targets.to(dev, torch.int64).contiguous()
@@ -743,13 +700,23 @@ class _CrossEntropy(torch.autograd.Function):
         B, BL, Q = lg.shape
         wt = None if weights is None else weights.detach().to(dev, torch.float32).contiguous()
         dl = torch.empty_like(lg)
-        parts = (C.c_double * 2)()
+        parts = (C.c_double * 4)()
         opts = _make_loss_opts(wt, ignore, eps, norm)
+        L = _lib.lib()
         with torch.cuda.device(dev):
             hp = _loss_handle(dev, Q)
-            _lib.check(_lib.lib().qpn_ce_loss_opts(hp, lg.data_ptr(), tg.data_ptr(), tg.shape[1], B, BL, C.byref(opts), dl.data_ptr(), parts,
-                                                   torch.cuda.current_stream(dev).cuda_stream))
-            _lib.check(_lib.lib().qpn_train_status(hp, torch.cuda.current_stream(dev).cuda_stream))      # (the stream has just been drained for the loss)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if teacher_logits is None:
+                rc = L.qpn_ce_loss_opts(hp, lg.data_ptr(), tg.data_ptr(), tg.shape[1], B, BL, C.byref(opts), dl.data_ptr(), parts, stream)
+            else:
+                tl = teacher_logits.detach().to(dev, torch.float32).contiguous()
+                head = (hp, lg.data_ptr(), tl.data_ptr(), tg.data_ptr(), tg.shape[1], B, BL, alpha, temperature)
+                if weights is None and ignore is None:      # the entry point without options: its kernels are instances of their own
+                    rc = L.qpn_distill_loss(*head, dl.data_ptr(), parts, stream)
+                else:
+                    rc = L.qpn_distill_loss_opts(*head, C.byref(opts), dl.data_ptr(), parts, stream)
+            _lib.check(rc)
+            _lib.check(L.qpn_train_status(hp, stream))      # (the stream has just been drained for the loss)
         ctx.save_for_backward(dl.view(logits.shape))
         return torch.tensor(parts[0], dtype=torch.float32, device=dev)
 
@@ -757,7 +724,7 @@ class _CrossEntropy(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_output):
         dl, = ctx.saved_tensors
-        return grad_output * dl, None, None, None, None, None
+        return (grad_output * dl,) + (None,) * 8
 
 
 def cross_entropy(logits, targets, sample_weights=None, ignore_index=None, label_smoothing=0.0, norm="rows"):
@@ -784,7 +751,7 @@ def cross_entropy(logits, targets, sample_weights=None, ignore_index=None, label
     dev = logits.device
     if dev.type != "cuda" or targets.device.type != "cuda" or (sample_weights is not None and sample_weights.device.type != "cuda"):
         raise ValueError("qpnet_amd.train.cross_entropy runs on an AMD GPU only (logits are on %s, targets on %s); there is no CPU fallback" % (dev, targets.device))
-    return _CrossEntropy.apply(logits, targets, sample_weights, ign, eps, code)
+    return _NativeLoss.apply(logits, targets, None, 0.0, 0.0, sample_weights, ign, eps, code)
 
 
 def _check_accum_steps(v):
@@ -1298,11 +1265,11 @@ class FusedTrainer:
         device work); see the class docstring (ignore_index / label_smoothing / loss_norm)."""
         if sample_weights is None and self._loss_ignore is None and self._loss_eps == 0.0 and self._loss_norm == 0:
             return self._step_plain(x, h, t, d, blength, want_loss, maxd, h_grad, teacher_logits)
-        # loss options: arm the handle, then the step as ever -- its forward-with-loss consumes the arm and runs k_ce_opt (with distill=: k_ce_distill's weighted
-        # form) where the cross entropy ran.  Every micro-step of an accumulation window, and every host path, is armed this way.
+        # loss options: arm the handle, then the step as ever -- its forward-with-loss consumes the arm and runs k_ce_hard<NV, true> (with distill=:
+        # k_ce_soft<NV, true>) where the cross entropy ran.  Every micro-step of an accumulation window, and every host path, is armed this way.
         dev = x.device
         if sample_weights is not None:
-            _check_sample_weights(sample_weights, x.shape[0], int(blength[0]), dev)
+            _check_step_tensor("sample_weights", "(B, BL)", sample_weights, (x.shape[0], int(blength[0])), dev)
         if dev.type != "cuda":
             raise RuntimeError("qpnet_amd.FusedTrainer runs on an AMD GPU only (tensors are on %s)" % dev)
         if torch.cuda.is_current_stream_capturing():
@@ -1335,7 +1302,7 @@ class FusedTrainer:
 
     def _distill_step(self, x, h, t, d, blength, want_loss, maxd, h_grad, teacher_logits):
         """step() with the soft-target loss: the teacher's teacher-forced forward (or the logits handed in) on the current stream, the arm, then the step as ever --
-        its forward-with-loss consumes the arm and runs k_ce_distill where the cross entropy ran.  Every micro-step of an accumulation window is armed this way."""
+        its forward-with-loss consumes the arm and runs k_ce_soft where the cross entropy ran.  Every micro-step of an accumulation window is armed this way."""
         model = self.model
         if self._distill is None:
             raise ValueError('step(teacher_logits=...) needs the trainer\'s distill={"alpha": a, "temperature": T}')
@@ -1343,7 +1310,7 @@ class FusedTrainer:
         dev = x.device
         BL = int(blength[0])
         if teacher_logits is not None:
-            _check_teacher_logits(teacher_logits, x.shape[0], BL, model.n_quantize, dev)
+            _check_step_tensor("teacher_logits", "(B, BL, n_quantize)", teacher_logits, (x.shape[0], BL, model.n_quantize), dev)
         elif teacher is None:
             raise ValueError('distill without a "teacher" needs step(teacher_logits=...) at every step')
         if h_grad is not None:

@@ -1,11 +1,9 @@
 """Knowledge distillation without a GPU: the argument checks of qpn_distill_loss / qpn_train_distill on a handle created without a device, the ValueErrors of
 FusedTrainer(distill=...) and step(teacher_logits=...), the runner's --teacher flags, the chunks train_generator cuts for two models at once, and the
-register report of k_ce_distill (no scratch memory)."""
+register report of k_ce_soft's unweighted instances (no scratch memory)."""
 import argparse
 import ctypes as C
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,6 +11,7 @@ import pytest
 from cases import generator_corpus
 from qpnet_amd import _lib, harness, loaders, synth
 from qpnet_amd.config import TINY, PAPER, DEFAULT
+import test_kernel_resources
 import util
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -229,27 +228,15 @@ def test_chunks_cut_for_the_joint_fields_are_long_enough_for_both_models(pair):
 
 
 def test_distill_kernel_keeps_everything_in_registers():
-    """hipcc's resource report of every instance of k_ce_distill (rows of 256 .. 1024 classes in registers, and the looping one): 0 bytes of scratch memory, and
-    at least three waves per SIMD -- a streaming kernel lives on loads in flight"""
+    """hipcc's resource report of every unweighted instance of k_ce_soft (rows of 256 .. 1024 classes in registers, and the looping one): 0 bytes of scratch
+    memory, and at least three waves per SIMD -- a streaming kernel lives on loads in flight"""
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not installed")
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-c",
-                          os.path.join(ROOT, "qpnet_amd", "csrc", "train_fwd.hip"), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1); kernels[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\d+)", line)
-        if m and cur:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    hits = {k: v for k, v in kernels.items() if "k_ce_distill" in k}
+    kernels = test_kernel_resources._report("train_loss.hip")
+    hits = {k: v for k, v in kernels.items() if any("k_ce_softILi%dELb0E" % nv in k for nv in range(5))}          # (k_ce_soft<NV, false>, as mangled)
     assert len(hits) == 5, sorted(kernels)
     for name, r in sorted(hits.items()):
-        print("K_CE_DISTILL %s: %d VGPRs, %d bytes of scratch per lane, %d waves per SIMD"
+        print("K_CE_SOFT %s: %d VGPRs, %d bytes of scratch per lane, %d waves per SIMD"
               % (name, r.get("VGPRs", -1), r.get("ScratchSize [bytes/lane]", -1), r.get("Occupancy [waves/SIMD]", -1)))
         assert r.get("ScratchSize [bytes/lane]", -1) == 0, name
         assert r.get("Occupancy [waves/SIMD]", -1) >= 3, name

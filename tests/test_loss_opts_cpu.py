@@ -4,7 +4,6 @@ mapping against a per-row loop, the float64 spec against torch, and the register
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import pytest
 from qpnet_amd import _lib, loaders, synth
 from qpnet_amd.config import TINY
 import loss_opts_spec as spec
+import test_kernel_resources
 import util
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -273,27 +273,18 @@ def test_spec_equals_torch_cross_entropy_in_float64(eps):
 
 
 def test_new_loss_kernels_keep_everything_in_registers():
-    """hipcc's resource report of every instance of k_ce_opt and k_ce_soft_w and of k_weight_mass: 0 bytes of scratch memory; k_ce_distill's own instances stay five"""
+    """hipcc's resource report of every instance of k_ce_hard<NV, true> and k_ce_soft<NV, true> and of k_weight_mass: 0 bytes of scratch memory; k_ce_soft's
+    unweighted instances stay five; the plain criterion k_ce_hard<0, false> keeps its 8 waves per SIMD"""
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not installed")
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-c",
-                          os.path.join(ROOT, "qpnet_amd", "csrc", "train_fwd.hip"), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1); kernels[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\d+)", line)
-        if m and cur:
-            kernels[cur][m.group(1).strip()] = int(m.group(2))
-    for stem, count in (("k_ce_opt", 5), ("k_ce_soft_w", 5), ("k_weight_mass", 1), ("k_ce_distill", 5)):
-        hits = {k: v for k, v in kernels.items() if stem in k}
+    kernels = test_kernel_resources._report("train_loss.hip")
+    for stem, count, min_occ in (("k_ce_hardILi%dELb1E", 5, 3), ("k_ce_softILi%dELb1E", 5, 3), ("k_weight_mass", 1, 3), ("k_ce_softILi%dELb0E", 5, 3), ("k_ce_hardILi0ELb0E", 1, 8)):
+        frags = tuple(stem % nv for nv in range(5)) if "%d" in stem else (stem,)
+        hits = {k: v for k, v in kernels.items() if any(f in k for f in frags)}
         assert len(hits) == count, (stem, sorted(kernels))
         for name, r in sorted(hits.items()):
             print("LOSS_OPTS_KERNEL %s: %d VGPRs, %d bytes of scratch per lane, %d waves per SIMD"
                   % (name, r.get("VGPRs", -1), r.get("ScratchSize [bytes/lane]", -1), r.get("Occupancy [waves/SIMD]", -1)))
             assert r.get("ScratchSize [bytes/lane]", -1) == 0, name
-            assert r.get("Occupancy [waves/SIMD]", -1) >= 3, name          # (a streaming kernel lives on loads in flight: k_ce_distill's rule)
+            assert r.get("Occupancy [waves/SIMD]", -1) >= min_occ, name          # (a streaming kernel lives on loads in flight: k_ce_soft's rule)
+    assert sum("k_ce_hard" in k for k in kernels) == 6 and sum("k_ce_soft" in k for k in kernels) == 10, sorted(kernels)

@@ -1,4 +1,4 @@
-"""GPU: the loss options -- k_ce_opt / k_weight_mass / k_ce_soft_w (qpn_ce_loss_opts, qpn_distill_loss_opts) bit for bit against qpn_ce_loss / qpn_distill_loss
+"""GPU: the loss options -- k_ce_hard<NV, true> / k_weight_mass / k_ce_soft<NV, true> (qpn_ce_loss_opts, qpn_distill_loss_opts) bit for bit against qpn_ce_loss / qpn_distill_loss
 where the options are neutral or powers of two, and against the float64 spec (tests/loss_opts_spec.py) elsewhere; the armed forward-with-loss
 (qpn_train_loss_opts) against its pieces; FusedTrainer(ignore_index=, label_smoothing=, loss_norm=).step(sample_weights=) against a loop of forward,
 train.cross_entropy and backward; the compositions (accumulation, world_size 2, distillation, h_grad, a non-blocking stream); run_train's two flags.
@@ -36,7 +36,8 @@ def _opts(w=None, ign=None, eps=0.0, norm=0):
     return _lib.QpnLossOpts(w.data_ptr() if w is not None else None, w.numel() if w is not None else 0, 0 if ign is None else 1, 0 if ign is None else ign, eps, norm)
 
 
-@pytest.fixture(scope="module", params=[256, 512, 96], ids=["Q256-NV1", "Q512-NV2", "Q96-scalar"])
+# every instance family of train_loss.hip: the register forms NV = 1 .. 4 (Q = 256 NV), the float4 loop form (Q % 256 == 0, Q > 1024) and the scalar loop form
+@pytest.fixture(scope="module", params=[256, 512, 96, 768, 1024, 1280], ids=["Q256-NV1", "Q512-NV2", "Q96-scalar", "Q768-NV3", "Q1024-NV4", "Q1280-vecloop"])
 def case(request):
     """one handle and one set of inputs per class count, shared by the kernel tests (and left unchanged by them): random logits with |z| <= 10, one peaked row;
     the plain kernels' outputs, computed once"""

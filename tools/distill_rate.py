@@ -1,9 +1,9 @@
 """What the soft-target loss costs in the fused step: FusedTrainer.step on the paper-size bench chunk, in ONE process, the variants interleaved block by block:
 
     fused        the step as it is (cross entropy inside the post-net tile, the post-net's backward in the same launch)
-    ce_separate  the same step under QPN_CE_SEPARATE=1 -- the route an armed step takes (the forward writes the logits, k_ce behind it, the backward computes the
+    ce_separate  the same step under QPN_CE_SEPARATE=1 -- the route an armed step takes (the forward writes the logits, k_ce_hard<0, false> behind it, the backward computes the
                  post-net itself): what leaving the fused tile costs, without the soft-target term
-    armed        FusedTrainer(distill={"alpha", "temperature"}).step(teacher_logits=...) with precomputed teacher logits: k_ce_distill in k_ce's place
+    armed        FusedTrainer(distill={"alpha", "temperature"}).step(teacher_logits=...) with precomputed teacher logits: k_ce_soft in the plain kernel's place
     teacher      (--teacher, default on) FusedTrainer(distill={"teacher": a second paper-size model, ...}): the armed step plus the teacher's forward
 
 Each variant has a trainer and a model of its own (the launch-plan knobs are read when a model's training state is created), all from the same weights, stepping

@@ -1,13 +1,13 @@
 """What the loss options cost in the fused step: FusedTrainer.step on the paper-size bench chunk, in ONE process, the variants interleaved block by block:
 
     fused          the step as it is (cross entropy inside the post-net tile, the post-net's backward in the same launch)
-    ce_separate    the same step under QPN_CE_SEPARATE=1 -- the route an armed step takes (the forward writes the logits, k_ce behind it, the backward computes the
+    ce_separate    the same step under QPN_CE_SEPARATE=1 -- the route an armed step takes (the forward writes the logits, k_ce_hard<0, false> behind it, the backward computes the
                    post-net itself): what leaving the fused tile costs, without any option
-    weights        step(sample_weights=w), w uniform in [0, 2): k_ce_opt in k_ce's place
+    weights        step(sample_weights=w), w uniform in [0, 2): k_ce_hard<NV, true> in the plain kernel's place
     weights_half   the same with half the rows at weight 0 (alternating blocks of 64 rows: whole workgroups skip their logits)
-    smoothing      FusedTrainer(label_smoothing=0.1): k_ce_opt with its extra wave sum
-    norm_weights   FusedTrainer(loss_norm="weights").step(sample_weights=w): k_weight_mass in front of k_ce_opt
-    weights_distill  distill= with precomputed teacher logits plus sample_weights: k_ce_soft_w in k_ce_distill's place
+    smoothing      FusedTrainer(label_smoothing=0.1): k_ce_hard<NV, true> with its extra wave sum
+    norm_weights   FusedTrainer(loss_norm="weights").step(sample_weights=w): k_weight_mass in front of k_ce_hard<NV, true>
+    weights_distill  distill= with precomputed teacher logits plus sample_weights: k_ce_soft<NV, true> in k_ce_soft<NV, false>'s place
 
 `fused` and `ce_separate` have a model of their own (the launch-plan knobs are read when a model's training state is created); the armed variants are trainers of their
 own on ONE more model, all from the same weights, stepping through the same chunks.  Three training states, not seven: every training state owns a side stream for the
