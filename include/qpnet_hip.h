@@ -582,6 +582,30 @@ int qpn_sample_logits_ex(const float* d_logits, int64_t n_rows, int Q, uint64_t 
 typedef struct { float nll; float entropy; int32_t argmax; int32_t rank; } qpn_score_row;
 int qpn_score_logits(const float* d_logits, const int64_t* d_targets, int64_t tgt_stride, int B, int BL, int Q, qpn_score_row* d_out, void* stream);
 
+/* Cut one training batch out of a device-resident corpus (what the reference's generator, src/bin/qpnet_train.py:200-335, assembles on the host for
+ * every step; the reference has no device counterpart).  The corpus is three arenas, utterances back to back: d_samples, int16 mu-law class indices
+ * [n_samples]; d_feats, fp32 scaled features [n_frames][n_aux] row-major; d_factors, fp32 dilated factors [n_frames], one per frame.  Row b of the batch is
+ * the concatenation of the segments row_first[b] .. row_first[b + 1] - 1 of the table (row_first[0] = 0, row_first[B] = n_segs): n_samples samples from
+ * sample0, n_frames feature rows from frame0, and for its samples the factors of the frames from factor0 on (sample s of the segment takes factor0 + s / U).
+ * A segment may hold samples and no feature row.  A row's segments together hold T + 1 = frames * U + 1 samples and exactly `frames` feature rows.  Outputs,
+ * every element written exactly once by ONE launch on `stream`, no host synchronisation:
+ *   d_x int64 (B x T)               the row's samples [0, T)
+ *   d_t int64 (B x T)               the row's samples [1, T + 1)
+ *   d_h fp32  (B x n_aux x frames)  the row's feature rows, transposed
+ *   d_d fp32  (B x T)               sample s gets the factor of the row's frame s / U
+ *   d_w fp32  (B x bl), or NULL     1 where feature column 0 of the frame at position p / U is above 0.5, else unvoiced_weight; p runs over the last bl of
+ *                                   the row's T positions
+ * d_x, d_t, d_d and d_w must be 16-byte aligned.  The table is given twice: h_segs / h_row_first on the host, checked here before anything is launched, and
+ * d_segs / d_row_first, a device copy of the same bytes that the caller has enqueued on `stream` and that the kernel reads.  A table that fails the check
+ * returns QPN_ERANGE (a segment leaves an arena) or QPN_EINVAL (a negative count, a row whose sums are not T + 1 samples and `frames` rows, row_first not
+ * monotone, U < 1, n_aux < 1, bl outside 1..T) with a message that names the row and the segment; nothing is launched then, so the kernel is never handed an
+ * index outside the arenas and there is no status word.  No handle.  Arguments are checked before a device is looked for. */
+typedef struct { int64_t sample0; int64_t frame0; int64_t factor0; int32_t n_samples; int32_t n_frames; } qpn_corpus_seg;
+int qpn_cut_chunks(const int16_t* d_samples, int64_t n_samples, const float* d_feats, const float* d_factors, int64_t n_frames, int n_aux,
+                   const qpn_corpus_seg* h_segs, const int32_t* h_row_first, const qpn_corpus_seg* d_segs, const int32_t* d_row_first, int64_t n_segs,
+                   int B, int frames, int U, int bl, float unvoiced_weight,
+                   int64_t* d_x, int64_t* d_t, float* d_h, float* d_d, float* d_w, void* stream);
+
 int qpn_dilated_index_train(const float* d_d, int B, int64_t L, int dilation, int64_t* d_out, void* stream);
 int qpn_dilated_index_gen_f32(const float* d_d, int64_t n, int dilation, int64_t* d_out, void* stream);
 int qpn_dilated_index_gen_f64(const double* d_d, int64_t n, int dilation, int32_t* d_out, void* stream);

@@ -26,6 +26,10 @@ class QpnLossOpts(C.Structure):     # qpn_loss_opts: the loss options (qpn_ce_lo
     _fields_ = [("d_weights", C.c_void_p), ("n_weights", C.c_int64), ("use_ignore", C.c_int), ("ignore_index", C.c_int64), ("label_smoothing", C.c_float), ("norm", C.c_int)]
 
 
+class QpnCorpusSeg(C.Structure):    # qpn_corpus_seg: one segment of a batch row (qpn_cut_chunks); loaders.CORPUS_SEG_DTYPE is the same 32 bytes for numpy
+    _fields_ = [("sample0", C.c_int64), ("frame0", C.c_int64), ("factor0", C.c_int64), ("n_samples", C.c_int32), ("n_frames", C.c_int32)]
+
+
 class QpnError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libqpnet_hip error %d: %s" % (code, msg))
@@ -106,6 +110,7 @@ SYMBOLS = [
     ("qpn_sample_logits", _i, [_vp, _i64, _i, _u64, _i, _i64, C.c_float, _i, _vp, _vp]),
     ("qpn_sample_logits_ex", _i, [_vp, _i64, _i, _u64, _i, _i64, C.c_float, _i, C.c_float, C.c_float, _vp, _vp]),
     ("qpn_score_logits", _i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
+    ("qpn_cut_chunks", _i, [_vp, _i64, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("qpn_dilated_index_train", _i, [_vp, _i, _i64, _i, _vp, _vp]),
     ("qpn_dilated_index_gen_f32", _i, [_vp, _i64, _i, _vp, _vp]),
     ("qpn_dilated_index_gen_f64", _i, [_vp, _i64, _i, _vp, _vp]),

@@ -8,6 +8,8 @@ Same batching / chunking semantics as the reference task scripts, but over array
   train_generator   <- src/bin/qpnet_train.py:200-335   (running x/h/d buffers over utterances, receptive field from the
                        buffer's max d, batch_length shrunk to max_length and to a multiple of U, chunks of RF+BL samples
                        that overlap by RF, x[:-1] / x[1:] input-target shift)
+  DeviceCorpus / plan_device_batches / device_train_generator: train_generator's stream cut on the GPU out of a corpus that is encoded, scaled and
+                       uploaded once (no counterpart in the reference; csrc/corpus.hip)
   save_checkpoint / load_checkpoint <- src/bin/qpnet_train.py:338-353,481-499,557-563 ({"model","optimizer","iterations"})
 """
 import hashlib
@@ -299,6 +301,261 @@ def train_generator(utterances, model_receptiveCausal, model_receptiveF, model_r
         if shuffle:
             order = order[np.random.permutation(n_files)]      # the reference re-shuffles the ALREADY shuffled list (:331-335)
         epoch += 1
+
+
+# ---------------------------------------------------------------- device-resident corpus (no counterpart in the reference; its generator is qpnet_train.py:200-335)
+# one segment of a batch row as qpn_cut_chunks reads it (qpn_corpus_seg, include/qpnet_hip.h): 32 bytes
+CORPUS_SEG_DTYPE = np.dtype([("sample0", "<i8"), ("frame0", "<i8"), ("factor0", "<i8"), ("n_samples", "<i4"), ("n_frames", "<i4")])
+_UPLOAD_PIECE = 32 << 20                               # bytes of the pinned buffer the corpus goes to the device through
+
+
+class DeviceCorpus:
+    """The whole training corpus, encoded and scaled ONCE, in three device arenas with the utterances back to back:
+        samples  int16   (n_samples,)        wav_transform of the waveform (mu-law class indices), cast as train_generator's .long() casts it
+        feats    float32 (n_frames, n_aux)   feat_transform of the features, cast as train_generator's .float() casts it
+        factors  float32 (n_frames,)         harness.dilated_factor(harness.batch_f0(h, f0_threshold), fs, dense_factor), one per frame
+    utterances: the items train_generator takes, (x, h) pairs or zero-argument callables returning one.  Each is loaded once, trimmed by
+    harness.validate_length and transformed whole: both transforms are element-wise, so any slice of the arenas is bit for bit what train_generator makes of
+    that slice.  Kept on the host: what plan_device_batches needs and no more -- per utterance its frame count, its arena offsets, its float64 factors and
+    their suffix maxima (a few KB each); no memory map or file handle outlives the packing of its utterance.  A corpus larger than max_bytes (default: half
+    of the device memory free at construction) is a ValueError before anything is allocated on the device; it is raised as soon as the utterances packed so
+    far exceed the bound.  With data-parallel ranks every rank holds the whole corpus.  device: a cuda device, or the CPU (plan_device_batches and host
+    copies of the arenas for tests; device_train_generator needs the GPU: there is no CPU fallback for the cut)."""
+
+    def __init__(self, utterances, upsampling_factor, fs, dense_factor, f0_threshold=0, wav_transform=None, feat_transform=None, device=None, max_bytes=None):
+        U = int(upsampling_factor)
+        if U < 1:
+            raise ValueError("DeviceCorpus needs upsampling_factor >= 1, got %d (one feature vector per sample has no frame grid to cut chunks on)" % U)
+        self.U, self.fs, self.dense_factor, self.f0_threshold = U, fs, dense_factor, f0_threshold
+        self.device = torch.device("cpu" if device is None else device)
+        if max_bytes is None and self.device.type == "cuda":
+            max_bytes = torch.cuda.mem_get_info(self.device)[0] // 2
+        self.max_bytes = max_bytes
+        xs, hs, ds = [], [], []
+        self.meta = []                                  # per utterance: (frames, first arena sample, first arena frame, float64 factors, their suffix maxima)
+        n_samples = n_frames = 0
+        self.n_aux = None
+        for item in utterances:
+            x, h = item() if callable(item) else item
+            x, h = harness.validate_length(np.array(x, dtype=np.float32), np.asarray(h), U)
+            frames = h.shape[0]
+            d = np.asarray(harness.dilated_factor(harness.batch_f0(h, f0_threshold), fs, dense_factor), dtype=np.float64)
+            self.meta.append((frames, n_samples, n_frames, d, np.fmax.accumulate(d[::-1])[::-1] if frames else d))
+            if frames == 0:
+                continue
+            xq = wav_transform(x) if wav_transform is not None else x
+            xq = torch.from_numpy(np.ascontiguousarray(xq)).long().numpy()
+            if xq.min() < 0 or xq.max() > 32767:
+                raise ValueError("utterance %d: sample value %d does not fit the int16 arena (class indices in [0, 32767] expected)"
+                                 % (len(self.meta) - 1, int(xq.min() if xq.min() < 0 else xq.max())))
+            hq = h.astype(np.result_type(np.float32, h.dtype), copy=False)
+            if feat_transform is not None:
+                hq = feat_transform(hq)
+            hq = torch.from_numpy(np.ascontiguousarray(hq)).float().numpy()
+            if self.n_aux is None:
+                self.n_aux = hq.shape[1]
+            elif hq.shape[1] != self.n_aux:
+                raise ValueError("utterance %d has %d features per frame, the ones before it %d" % (len(self.meta) - 1, hq.shape[1], self.n_aux))
+            xs.append(xq.astype(np.int16)); hs.append(hq); ds.append(d.astype(np.float32))
+            n_samples += frames * U
+            n_frames += frames
+            nbytes = 2 * n_samples + 4 * n_frames * (self.n_aux + 1)
+            if max_bytes is not None and nbytes > max_bytes:
+                raise ValueError("the corpus needs more than %d bytes on the device (%d after %d of %d utterances), above max_bytes = %d"
+                                 % (nbytes, nbytes, len(self.meta), len(utterances), max_bytes))
+        if n_frames == 0:
+            raise ValueError("the corpus holds no frame")
+        self.n_utterances, self.n_frames, self.n_samples = len(self.meta), n_frames, n_samples
+        self.nbytes = 2 * n_samples + 4 * n_frames * (self.n_aux + 1)
+        self.samples = self._upload(xs, np.int16, (n_samples,))
+        self.feats = self._upload(hs, np.float32, (n_frames, self.n_aux))
+        self.factors = self._upload(ds, np.float32, (n_frames,))
+
+    def _upload(self, parts, dtype, shape):
+        """the concatenation of `parts` as one device tensor; to a GPU it goes in pieces of at most _UPLOAD_PIECE bytes through two pinned buffers"""
+        tdtype = {np.int16: torch.int16, np.float32: torch.float32}[dtype]
+        out = torch.empty(shape, dtype=tdtype, device=self.device)
+        flat = out.view(-1)
+        if self.device.type != "cuda":
+            pos = 0
+            for a in parts:
+                flat[pos:pos + a.size] = torch.from_numpy(a.reshape(-1))
+                pos += a.size
+            parts.clear()
+            return out
+        per = _UPLOAD_PIECE // np.dtype(dtype).itemsize
+        pins = [torch.empty(per, dtype=tdtype).pin_memory() for _ in range(2)]
+        events = [None, None]
+        pos = fill = k = 0
+
+        def flush():
+            nonlocal pos, fill, k
+            if fill:
+                flat[pos:pos + fill].copy_(pins[k][:fill], non_blocking=True)
+                events[k] = torch.cuda.Event()
+                events[k].record(torch.cuda.current_stream(self.device))
+                pos += fill
+                fill, k = 0, 1 - k
+                if events[k] is not None:
+                    events[k].synchronize()            # the copy that last read the buffer about to be filled is done
+        for a in parts:
+            a = torch.from_numpy(a.reshape(-1))
+            done = 0
+            while done < a.numel():
+                n = min(per - fill, a.numel() - done)
+                pins[k][fill:fill + n] = a[done:done + n]
+                fill += n; done += n
+                if fill == per:
+                    flush()
+        flush()
+        torch.cuda.current_stream(self.device).synchronize()
+        parts.clear()
+        return out
+
+
+def plan_device_batches(corpus, model_receptiveCausal, model_receptiveF, model_receptiveA, batch_length=20000, batch_size=1, max_length=23070,
+                        shuffle=True, epochs=None, shard=None):
+    """The window walk of train_generator over a DeviceCorpus, as a plan: no sample or feature is touched.  Same np.random.permutation calls in the same order,
+    the window survives epoch boundaries, the receptive field is re-evaluated after every append from the suffix maxima, harness.chunk_plan and the same
+    `while` condition decide where chunks are cut, and the window advances by bl // U frames.  Yields one tuple per batch of the stream, over all ranks:
+        (rows, frames, bl, mine, maxd)
+    mine: the batch is this rank's (shard = (rank, world); always True without).  For a foreign batch the window only advances: rows is None and maxd 0.
+    rows: per batch row a list of segments (sample0, n_samples, frame0, n_frames, factor0) in ARENA terms (the fields of qpn_corpus_seg), together
+    frames * U + 1 samples and `frames` feature rows.  maxd: ceil of the largest float32 factor among the frames the batch covers (what runners._batches
+    takes from the chunk's tensor).  The rows of a batch are always cut under one receptive field: the `while` condition asks for more than slots_left chunks'
+    worth of frames and a chunk advances the window by less than its length, so a batch that is begun is completed before the next utterance is appended."""
+    import collections
+    U = corpus.U
+    rank, world = (0, 1) if shard is None else (int(shard[0]), int(shard[1]))
+    n_files = len(corpus.meta)
+    order = np.random.permutation(n_files) if shuffle else np.arange(n_files)
+    win = collections.deque()                           # utterances with live frames, oldest first
+    first, live = 0, 0                                  # frames of win[0] already consumed; live frames in the window
+    n_batches = epoch = 0
+
+    def front(frames):
+        segs, need_s, need_f, off, dmax = [], frames * U + 1, frames, first, 0.0
+        for i in win:
+            if need_s <= 0:
+                break
+            nfr, s0, f0, d = corpus.meta[i][:4]
+            take_s = min(need_s, (nfr - off) * U)
+            take_f = min(need_f, nfr - off) if need_f > 0 else 0
+            segs.append((s0 + off * U, take_s, f0 + off, take_f, f0 + off))
+            if take_f > 0:
+                dmax = max(dmax, float(d[off:off + take_f].max()))
+            need_s -= take_s; need_f -= take_f; off = 0
+        assert need_s == 0 and need_f == 0
+        return segs, dmax
+    while epochs is None or epoch < epochs:
+        rows, dmaxs = [], []
+        slots_left = batch_size
+        for i in order:
+            i = int(i)
+            if corpus.meta[i][0] > 0:
+                win.append(i)
+                live += corpus.meta[i][0]
+            m = np.nan                                  # (fmax: as _SampleWindow.max_factor)
+            for k, j in enumerate(win):
+                m = np.fmax(m, corpus.meta[j][4][first if k == 0 else 0])
+            rf = harness.receptive_field(model_receptiveCausal, model_receptiveF, model_receptiveA, float(m))
+            bl, frames, samples = harness.chunk_plan(rf, batch_length, max_length, U)
+            hop_frames = bl // U
+            while live > slots_left * frames and live * U > slots_left * samples:
+                mine = n_batches % world == rank
+                if mine:
+                    segs, dmax = front(frames)
+                    rows.append(segs); dmaxs.append(dmax)
+                slots_left -= 1
+                live -= hop_frames
+                first += hop_frames
+                while win and first >= corpus.meta[win[0]][0]:
+                    first -= corpus.meta[win.popleft()][0]
+                if slots_left == 0:
+                    if mine:
+                        yield rows, frames, bl, True, int(np.ceil(float(np.float32(max(dmaxs)))))
+                    else:
+                        yield None, frames, bl, False, 0
+                    rows, dmaxs, slots_left = [], [], batch_size
+                    n_batches += 1
+        if shuffle:
+            order = order[np.random.permutation(n_files)]
+        epoch += 1
+
+
+def corpus_segment_table(rows, frames, U):
+    """The rows of one batch (lists of (sample0, n_samples, frame0, n_frames, factor0), as plan_device_batches yields them) -> (records, row_first): the
+    CORPUS_SEG_DTYPE array and the int32 index qpn_cut_chunks takes.  Rows of unequal length -- any row that does not hold frames * U + 1 samples and `frames`
+    feature rows, where train_generator would fail in torch.stack -- raise ValueError, before anything is launched."""
+    T = int(frames) * int(U)
+    for b, r in enumerate(rows):
+        ns, nf = sum(s[1] for s in r), sum(s[3] for s in r)
+        if ns != T + 1 or nf != frames:
+            raise ValueError("the rows of a batch must have equal length: row %d holds %d samples and %d feature rows, %d and %d expected" % (b, ns, nf, T + 1, frames))
+    recs = np.array([(s0, f0, fd0, ns, nf) for r in rows for (s0, ns, f0, nf, fd0) in r], dtype=CORPUS_SEG_DTYPE)
+    return recs, np.cumsum([0] + [len(r) for r in rows]).astype(np.int32)
+
+
+def device_train_generator(corpus, model_receptiveCausal, model_receptiveF, model_receptiveA, batch_length=20000, batch_size=1, max_length=23070,
+                           shuffle=True, epochs=None, shard=None, unvoiced_weight=None):
+    """train_generator's stream (same seed, same chunks, same order) cut on the GPU out of a DeviceCorpus: per batch the host sends the segment table (a few
+    dozen bytes) and qpn_cut_chunks writes the tensors.  Yields (batch_x, batch_h, batch_t, batch_d, batch_b, maxd[, batch_w]) for this rank's batches:
+    batch_b is the CPU tensor train_generator yields, maxd what runners._batches adds, batch_w (with unvoiced_weight) unvoiced_row_weights; the others are
+    views of ONE device buffer, bit for bit train_generator's tensors moved to the device.  The work is enqueued on a stream of the generator's own (it runs
+    on the prefetch thread): the table goes through a small ring of pinned buffers (an event per slot, as runners.PinnedStager), the launch follows it on that
+    stream, and the outputs carry `_qpn_staged` = (event, buffer): the consumer joins them through train.join_staged like any staged copy."""
+    import ctypes as C
+    from . import _lib
+    if corpus.device.type != "cuda":
+        raise RuntimeError("device_train_generator needs the corpus on an AMD GPU: there is no CPU fallback for the cut")
+    if unvoiced_weight is not None and not (float(unvoiced_weight) >= 0.0 and np.isfinite(float(unvoiced_weight))):
+        raise ValueError("unvoiced_weight must be finite and >= 0, got %r" % (unvoiced_weight,))
+    L = _lib.lib()
+    dev, U, n_aux = corpus.device, corpus.U, corpus.n_aux
+    stream = torch.cuda.Stream(dev)
+    depth = 4
+    pins, events, slot = [None] * depth, [None] * depth, 0
+    pad = lambda n: (n + 255) // 256 * 256              # noqa: E731
+    for rows, frames, bl, mine, maxd in plan_device_batches(corpus, model_receptiveCausal, model_receptiveF, model_receptiveA, batch_length, batch_size,
+                                                            max_length, shuffle, epochs, shard):
+        if not mine:
+            continue
+        B, T = len(rows), frames * U
+        recs, row_first = corpus_segment_table(rows, frames, U)
+        n_segs = len(recs)
+        o_first = n_segs * CORPUS_SEG_DTYPE.itemsize    # the table: n_segs records, then row_first[B + 1]
+        n_table = o_first + 4 * (B + 1)
+        if events[slot] is not None:
+            events[slot].synchronize()                  # the copy that last read this slot is done
+        pin = pins[slot]
+        if pin is None or pin.numel() < n_table:
+            pin = pins[slot] = torch.empty(max(2 * n_table, 4096), dtype=torch.uint8).pin_memory()
+        host = pin.numpy()
+        host[:o_first].view(CORPUS_SEG_DTYPE)[:] = recs
+        host[o_first:n_table].view(np.int32)[:] = row_first
+        offs, total = {}, 0
+        for name, n in (("x", 8 * B * T), ("t", 8 * B * T), ("d", 4 * B * T), ("h", 4 * B * n_aux * frames)) + ((("w", 4 * B * bl),) if unvoiced_weight is not None else ()):
+            offs[name] = (total, n)
+            total += pad(n)
+        with torch.cuda.stream(stream):
+            table = pin[:n_table].to(dev, non_blocking=True)
+            buf = torch.empty(total, dtype=torch.uint8, device=dev)
+            ptr = lambda name: buf.data_ptr() + offs[name][0]      # noqa: E731
+            _lib.check(L.qpn_cut_chunks(corpus.samples.data_ptr(), corpus.n_samples, corpus.feats.data_ptr(), corpus.factors.data_ptr(), corpus.n_frames, n_aux,
+                                        pin.data_ptr(), pin.data_ptr() + o_first, table.data_ptr(), table.data_ptr() + o_first, n_segs,
+                                        B, frames, U, bl, C.c_float(0.0 if unvoiced_weight is None else float(unvoiced_weight)),
+                                        ptr("x"), ptr("t"), ptr("h"), ptr("d"), ptr("w") if unvoiced_weight is not None else None, stream.cuda_stream))
+            ev = torch.cuda.Event()
+            ev.record(stream)
+        events[slot] = ev
+        slot = (slot + 1) % depth
+        view = lambda name, dtype, shape: buf[offs[name][0]:offs[name][0] + offs[name][1]].view(dtype).view(shape)      # noqa: E731
+        out = [view("x", torch.int64, (B, T)), view("h", torch.float32, (B, n_aux, frames)), view("t", torch.int64, (B, T)), view("d", torch.float32, (B, T))]
+        if unvoiced_weight is not None:
+            out.append(view("w", torch.float32, (B, bl)))
+        for t in out:
+            t.__dict__["_qpn_staged"] = (ev, buf)
+        yield tuple(out[:4]) + (torch.tensor([bl] * B), maxd) + tuple(out[4:])
 
 
 def score_chunks(n_frames, rf, batch_length, max_length, U):

@@ -201,15 +201,25 @@ def _utterance_loaders(wav_list, feat_list, feature_type):
     return [_FileUtterance(w, f, feature_type) for w, f in zip(wav_list, feat_list)]
 
 
-def _batches(args, conf, model, shuffle, epochs, device, rank=0, world=1, fields=None, unvoiced_weight=None):
+def _batches(args, conf, model, shuffle, epochs, device, rank=0, world=1, fields=None, unvoiced_weight=None, device_corpus=None):
     """Training / validation batches on `device`.  unvoiced_weight (None: off): a seventh element, the chunk's (B, batch_length) sample weights
     (loaders.unvoiced_row_weights), staged with the chunk.  fields: (receptiveCausal_field, receptiveF_field, receptiveA_field) to cut the chunks for (None: the model's).  With world > 1 rank r takes chunks r, r+N, ... of the generator's
     stream (same seed on every rank: identical shuffles and chunk boundaries) INSIDE the generator: a rank encodes,
-    scales, takes ceil(max d) of and copies to its GPU only its own chunks."""
+    scales, takes ceil(max d) of and copies to its GPU only its own chunks.  device_corpus ({"max_bytes": bound or None}; None: off): the corpus is encoded,
+    scaled and uploaded once (loaders.DeviceCorpus, every rank the whole of it) and the same stream of batches is cut on the GPU (loaders.device_train_generator)."""
     wavs, feats = loaders.file_lists(args.waveforms, args.feats, conf.feature_format)
     logging.info("number of utterances = %d." % len(wavs))
     scaler = loaders.read_scaler_stats(args.stats, conf.feature_type)
     fs = loaders.read_wav(wavs[0])[0]
+    if device_corpus is not None:
+        t0 = time.time()
+        # (plain loads, not _FileUtterance's maps: nothing of a file stays open once its utterance is packed)
+        utts = [lambda w=w, f=f: (loaders.read_wav(w)[1], loaders.read_features(f, conf.feature_type)) for w, f in zip(wavs, feats)]
+        corpus = loaders.DeviceCorpus(utts, conf.upsampling_factor, fs, conf.dense_factor, args.f0_threshold, loaders.mu_law_transform(conf.n_quantize), scaler,
+                                      device, device_corpus.get("max_bytes"))
+        logging.info("device corpus: %d utterances, %d frames, %d bytes on %s, built in %.2f s." % (corpus.n_utterances, corpus.n_frames, corpus.nbytes, device, time.time() - t0))
+        return loaders.device_train_generator(corpus, *(fields or _fields_of(model)), args.batch_length, args.batch_size, args.max_length, shuffle, epochs,
+                                              (rank, world) if world > 1 else None, unvoiced_weight)
     gen = loaders.train_generator(
         _utterance_loaders(wavs, feats, conf.feature_type), *(fields or _fields_of(model)), fs, wav_transform=loaders.mu_law_transform(conf.n_quantize), feat_transform=scaler,
         dense_factor=conf.dense_factor, batch_length=args.batch_length, batch_size=args.batch_size, max_length=args.max_length,
@@ -321,6 +331,9 @@ def _train_args(update):
     p.add_argument("--label_smoothing", default=0.0, type=float, metavar="EPS", help="label smoothing of the cross entropy inside the fused step, in [0, 1); 0: off")
     p.add_argument("--unvoiced_weight", default=1.0, type=float, metavar="W",
                    help="weight of the samples of unvoiced frames in the loss (voiced ones weigh 1; finite, >= 0; the loss stays a mean over the row count); 1: off")
+    p.add_argument("--device_corpus", action="store_true", help="keep the encoded, scaled corpus on the GPU and cut every chunk there (the same stream of batches; "
+                   "every rank holds the whole corpus); off: the host loader")
+    p.add_argument("--device_corpus_max_gb", default=None, type=float, metavar="G", help="with --device_corpus: refuse a corpus above G GB on the device (default: half of the free device memory)")
     p.add_argument("--iters", default=3000 if update else 200000, type=int)
     p.add_argument("--checkpoint_interval", default=10000, type=int)
     p.add_argument("--intervals", default=100, type=int)
@@ -354,6 +367,13 @@ def run_train(argv=None, update=False):
     distill = _distill_of(args, sconf)          # (--teacher & co.: checked, and taken out of args, before any rank is launched)
     # (the loss options are taken out of args as well: args is the model configuration run_train writes)
     label_smoothing, unvoiced_weight = args.__dict__.pop("label_smoothing"), args.__dict__.pop("unvoiced_weight")
+    # (... and the loader's: --device_corpus changes where the batches are made, not the model)
+    device_corpus, max_gb = args.__dict__.pop("device_corpus"), args.__dict__.pop("device_corpus_max_gb")
+    if max_gb is not None and not device_corpus:
+        raise SystemExit("--device_corpus_max_gb needs --device_corpus")
+    if max_gb is not None and not (max_gb > 0.0 and np.isfinite(max_gb)):
+        raise SystemExit("--device_corpus_max_gb must be finite and > 0, got %r" % (max_gb,))
+    device_corpus = {"max_bytes": None if max_gb is None else int(max_gb * 1e9)} if device_corpus else None
     if not (0.0 <= label_smoothing < 1.0):
         raise SystemExit("--label_smoothing must lie in [0, 1), got %r" % (label_smoothing,))
     if not (unvoiced_weight >= 0.0 and np.isfinite(unvoiced_weight)):
@@ -432,7 +452,7 @@ def run_train(argv=None, update=False):
         logging.info("updating based on %s." % args.pretrain)
     from .train import ensure_flat
     parallel.broadcast_parameters(ensure_flat(model, dev))
-    stream = Prefetcher(_batches(args, conf, model, True, None, dev, rank, world, fields=fields, unvoiced_weight=unvoiced_weight))      # rank r: chunks r, r+N, r+2N, ...
+    stream = Prefetcher(_batches(args, conf, model, True, None, dev, rank, world, fields=fields, unvoiced_weight=unvoiced_weight, device_corpus=device_corpus))      # rank r: chunks r, r+N, r+2N, ...
     loss = total = 0.0
     logging.info("training start!")
     # The reference reads loss.item() at every step (qpnet_train.py:533) and reports its average over `intervals` steps (:536-541).  Here a step

@@ -1,5 +1,6 @@
 """Dev: where an iteration of the run_train loop (bench.py runner_loop_rate) spends its host time -- waiting for the loader thread's batch vs inside FusedTrainer.step --
-and what the box is (CPU model, clock, cores).   python tools/runner_loop_split.py"""
+and what the box is (CPU model, clock, cores).   python tools/runner_loop_split.py [--device_corpus]
+--device_corpus: the same loop fed by loaders.device_train_generator (the corpus resident on the GPU, every chunk cut there)."""
 import os
 import sys
 import time
@@ -43,9 +44,20 @@ def main():
                                   batch_length=20000, max_length=30000, upsampling_factor=U, shuffle=True)
     stage = PinnedStager(dev)
     tgen = [0.0, 0.0, 0]
+    corpus = None
+    if "--device_corpus" in sys.argv:
+        t0 = time.perf_counter()
+        corpus = loaders.DeviceCorpus(utts, U, 22050, 8, 0, loaders.mu_law_transform(cfg.n_quantize), lambda h: (h - mean) / scale, dev)
+        print("device corpus: %d utterances, %d frames, %d bytes, built in %.3f s" % (corpus.n_utterances, corpus.n_frames, corpus.nbytes, time.perf_counter() - t0))
+        gen = loaders.device_train_generator(corpus, cfg.receptiveCausal_field, cfg.receptiveF_field, cfg.receptiveA_field, 20000, 1, 30000, True, None, None)
 
     def batches():
         it = iter(gen)
+        while corpus is not None:                       # (the generator's batches are on the device already: no stager)
+            t0 = time.perf_counter()
+            b = next(it)
+            tgen[0] += time.perf_counter() - t0; tgen[2] += 1
+            yield b
         while True:
             t0 = time.perf_counter()
             bx, bh, bt, bd, bb = next(it)
