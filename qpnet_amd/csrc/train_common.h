@@ -216,7 +216,7 @@ __device__ __forceinline__ void tr_queue_entry_bwd(const TrainParams& p, int pos
 
 int qpn_num_cus();                                   // compute units of the current device (cached per device)
 
-#define TR_GN_BLOCKS 256                             // gradient-norm clipping: the sum of squares leaves k_grad_sumsq as at most this many fp64 partial sums (one per thread of a k_adam_clip block)
+#define TR_GN_BLOCKS 256                             // gradient-norm clipping: the sum of squares leaves k_grad_sumsq as at most this many fp64 partial sums (one per thread of a clipping k_adam block)
 
 // parameter groups of the Adam launch (qpn_adam_groups; adam_groups.h): the segment table lives in device memory, the groups' values travel with the launch
 // as kernel arguments -- a learning-rate schedule changes them every step without touching the device
@@ -224,6 +224,22 @@ struct AdamGroupsArg {
     const long long* seg_end; const int* seg_group; const int* block;      // block: the pairs of AdamGroupTable::block, 8-byte aligned
     float lr[QPN_ADAM_MAX_GROUPS], wd[QPN_ADAM_MAX_GROUPS];
 };
+// One Adam launch (train_adam.hip): n floats of w, g, m, v; `step` is the bias corrections' exponent.
+//   den: nullptr, or the trailer {summed row count, summed flags} of a data-parallel / accumulated gradient;  status: the handle's status word (may be nullptr)
+//   h_status, h_loss, d_loss: the reports the kernel's block 0 writes into pinned memory (each nullptr: not made)
+//   max_norm <= 0: no clipping; otherwise part (room for TR_GN_BLOCKS partial sums) and d_norm (the handle's norm word) are needed, h_norm (pinned) may be nullptr
+//   ema: nullptr, or the averaged weights with omd = 1 - decay;  grp: nullptr, or the parameter groups (lr and wd are then not looked at)
+struct AdamCall {
+    float* w; const float* g; float* m; float* v; int64_t n;
+    int step; float lr, b1, b2, eps, wd;
+    const float* den; int* status;
+    int* h_status; double* h_loss; const double* d_loss;
+    float max_norm; double* part; double* d_norm; double* h_norm;
+    float* ema; float omd;
+    const AdamGroupsArg* grp;
+};
+int qpn_launch_adam(const AdamCall& c, hipStream_t stream);
+int qpn_launch_grad_accum(float* acc, const float* g, int64_t cnt, int first, const int* status, int* h_status, double* h_loss, const double* d_loss, hipStream_t stream);
 
 // optional per-kernel-group timing (HIP events on the launch stream; bench.py roofline)
 // (one group per LAUNCH of the heavy kernels, so that bench.py can name the single longest kernel: PG_WGRAD = the gate contraction's weight

@@ -15,12 +15,6 @@ static CeOpts ce_opts_of(const qpn_loss_opts& o, double* mass, double* d_mass);
 int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k, const AuxGeom& ag, const StackQ* sq, hipStream_t stream, bool post_done);
 int qpn_launch_fwd_gemm(const TrainParams& p, const TrainGemm& w, hipStream_t stream);
 int qpn_launch_bwd_gemm(const TrainParams& p, const TrainBwd& bw, const TrainGemm& w, hipStream_t stream);
-int qpn_launch_adam(float* w, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps, float wd, const float* den, int* status,
-                    int* h_status, double* h_loss, const double* d_loss, float* e, float omd, const AdamGroupsArg* grp, hipStream_t stream);
-int qpn_launch_adam_clip(float* w, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps, float wd, const float* den, int* status,
-                         int* h_status, double* h_loss, const double* d_loss, float max_norm, double* part, double* d_norm, double* h_norm, float* e, float omd,
-                         const AdamGroupsArg* grp, hipStream_t stream);
-int qpn_launch_grad_accum(float* acc, const float* g, int64_t cnt, int first, const int* status, int* h_status, double* h_loss, const double* d_loss, hipStream_t stream);
 
 // a pinned loss slot: the 64 partial sums, then the gradient norm of the same step (gradient-norm clipping)
 #define LOSS_SLOT 72
@@ -45,7 +39,7 @@ struct TrainState {
     hipStream_t last_stream = nullptr;        // the stream of the latest training call (where a collected status word is cleared)
     int* h_status_pinned = nullptr; hipEvent_t ev_status[2] = {}; bool status_pending[2] = {}; int status_newest = 0;      // qpn_train_status_enqueue / _collect: the deferred check, two slots
     double* h_loss_pinned = nullptr; hipEvent_t ev_loss[2] = {}; bool loss_pending[2] = {}; int loss_newest = 0;            // qpn_train_loss_enqueue / _collect: the loss read one step late, two slots of LOSS_SLOT doubles
-    // gradient-norm clipping (qpn_adam_step_clip): d_gnorm = TR_GN_BLOCKS partial sums of squares; the norm word k_adam_clip leaves is d_loss[64] (one copy takes both out)
+    // gradient-norm clipping (qpn_adam_step_clip): d_gnorm = TR_GN_BLOCKS partial sums of squares; the norm word a clipping k_adam leaves is d_loss[64] (one copy takes both out)
     double* d_gnorm = nullptr; bool gnorm_last = false;      // gnorm_last: the latest Adam launch on this handle clipped (the norm word is that launch's)
     bool gnorm_slot[2] = {};                  // loss slot i carries a norm
     double gnorm_collected = 0.0; bool gnorm_collected_valid = false;      // the norm that came with the loss the last qpn_train_loss_collect returned
@@ -868,8 +862,8 @@ static int adam_groups_arg(const qpn_handle* h, int64_t n, AdamGroupsArg* a, boo
     return QPN_OK;
 }
 
-// max_grad_norm > 0: torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) in front of the update (k_grad_sumsq + k_adam_clip); otherwise exactly the launch qpn_adam_step_ex always made.
-// d_ema: the averaged weights move with every APPLIED update, inside the same launch (k_adam_ema / k_adam_clip_ema); NULL with ema_decay 0: the kernels above
+// max_grad_norm > 0: torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) in front of the update (k_grad_sumsq + k_adam<true, ..>); otherwise exactly the launch qpn_adam_step_ex always made.
+// d_ema: the averaged weights move with every APPLIED update, inside the same launch (k_adam<.., true, ..>); NULL with ema_decay 0: the instances without it
 extern "C" int qpn_adam_step_avg(qpn_handle* h, float* d_flat, const float* d_grad, float* d_m, float* d_v, int64_t n,
                                  int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                                  const float* d_grad_denominator, float max_grad_norm, float* d_ema, float ema_decay, void* stream_) {
@@ -879,14 +873,13 @@ extern "C" int qpn_adam_step_avg(qpn_handle* h, float* d_flat, const float* d_gr
     if (!d_flat || !d_grad || !d_m || !d_v || n < 1 || step < 1 || max_grad_norm != max_grad_norm) { qpn_set_error("bad adam_step arguments"); return QPN_EINVAL; }
     AdamGroupsArg ga; bool grouped;
     rc = adam_groups_arg(h, n, &ga, &grouped); if (rc) return rc;
-    const AdamGroupsArg* const grp = grouped ? &ga : nullptr;
     const bool clip = max_grad_norm > 0.f;
     if (clip) { rc = train_init(h); if (rc) return rc; }                 // (the partial sums and the norm word live in the training state)
-    if (h->train) { h->train->last_stream = (hipStream_t)stream_; h->train->gnorm_last = clip; }
-    if (clip) return qpn_launch_adam_clip(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, d_grad_denominator, h->train->d_status, nullptr, nullptr, nullptr,
-                                          max_grad_norm, h->train->d_gnorm, h->train->d_loss + 64, nullptr, d_ema, omd, grp, (hipStream_t)stream_);
-    return qpn_launch_adam(d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, d_grad_denominator, h->train ? h->train->d_status : nullptr, nullptr, nullptr, nullptr,
-                           d_ema, omd, grp, (hipStream_t)stream_);
+    TrainState* const t = h->train;
+    if (t) { t->last_stream = (hipStream_t)stream_; t->gnorm_last = clip; }
+    const AdamCall c = {d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, d_grad_denominator, t ? t->d_status : nullptr, nullptr, nullptr, nullptr,
+                        max_grad_norm, clip ? t->d_gnorm : nullptr, clip ? t->d_loss + 64 : nullptr, nullptr, d_ema, omd, grouped ? &ga : nullptr};
+    return qpn_launch_adam(c, (hipStream_t)stream_);
 }
 
 // Gradient accumulation: d_acc <- first ? d_grad : d_acc + d_grad over cnt floats (k_grad_accum; callers pass n + 4: the row-weighted gradient qpn_train_backward_ex
@@ -930,13 +923,101 @@ extern "C" int qpn_train_grad_norm_lagged(qpn_handle* h, double* h_norm, int* h_
 //   step or right behind a flush: qpn_train_loss_collect(newest = 1) fetches the last one), the stream is never drained;  2: this step's loss, read in the call
 //   (drains the stream, as the reference's loss.item() does).
 // The device-side status word is handled as FusedTrainer.step documents: collected two steps late at most (mode 0 / 1), in the call (mode 2).
+// The arguments of a step, in the order of the widest entry point (qpn_train_step_acc); the narrower ones leave the tail at "off":
+// max_grad_norm > 0: the step clips (qpn_adam_step_clip), and *h_grad_norm (may be NULL) receives the norm of the step whose loss *h_loss is -- mode 1: the previous
+// step's, out of the same pinned slot as its loss; mode 2: this step's; mode 0: none.  0 where that step did not clip.
+// d_ema / ema_decay: qpn_adam_step_avg's (every loss mode moves the average: it is the Adam launch's own work).
+// d_acc != NULL: micro-step `micro` of a window of micro_count > 1 chunks (qpn_train_step_acc); NULL: the plain step, launch for launch what it always was
+struct TrainStepArgs {
+    float* d_flat; int B; int64_t T, F, Td; int BL, maxd;
+    const int64_t* d_x; const float* d_h; const float* d_dfac; const int64_t* d_targets; int64_t tgt_stride;
+    float* d_logits; float* d_dlogits; float* d_grad; float* d_m; float* d_v; int64_t n;
+    int step; float lr, beta1, beta2, eps, weight_decay;
+    int loss_mode; double* h_loss; int* h_valid; float max_grad_norm; double* h_grad_norm;
+    float* d_ema; float ema_decay; float* d_acc; int micro, micro_count; void* stream;
+};
+
+static int train_step_body(qpn_handle* h, const TrainStepArgs& a) {
+    if (a.h_valid) *a.h_valid = 0;
+    if (a.h_loss) *a.h_loss = 0.0;
+    if (a.h_grad_norm) *a.h_grad_norm = 0.0;
+    float omd;
+    int rc = check_ema_args(a.d_ema, a.ema_decay, &omd); if (rc) return rc;
+    const int loss_mode = a.loss_mode;
+    if (loss_mode < 0 || loss_mode > 2 || (loss_mode && (!a.h_loss || !a.h_valid)) || a.max_grad_norm != a.max_grad_norm) { qpn_set_error("bad train_step arguments"); return QPN_EINVAL; }
+    const bool accum = a.d_acc != nullptr;                               // a window of several chunks: the gradient goes through the accumulator ...
+    const bool closing = a.micro == a.micro_count - 1;                   // ... and only its last micro-step has an Adam launch
+    const bool clip = closing && a.max_grad_norm > 0.f;
+    rc = need_dev(h); if (rc) return rc;
+    AdamGroupsArg ga; bool grouped = false;
+    if (closing) { rc = adam_groups_arg(h, a.n, &ga, &grouped); if (rc) return rc; }      // (before anything is enqueued: a table for another n fails the whole step)
+    // a flagged word found here is cleared on THIS call's stream, in front of the step the caller runs on it next: the stream of the call before may be another
+    // one, busy with work of the caller's own, and a clear queued behind that work lands after the next step's Adam launch has read the word
+    const hipStream_t stream = (hipStream_t)a.stream;
+    if (h->train) h->train->last_stream = stream;
+    rc = qpn_train_status_collect_lagged(h); if (rc) return rc;          // the check of the step before the previous one (never waits for queued work)
+    if (!a.d_targets || !a.d_dlogits) { qpn_set_error("qpn_train_forward_loss needs targets and a dlogits buffer"); return QPN_EINVAL; }
+    if (accum && (!a.d_grad || a.n < 1)) { qpn_set_error("bad train_step arguments: d_grad / n"); return QPN_EINVAL; }
+    rc = train_forward_impl(h, a.d_flat, a.B, a.T, a.F, a.Td, a.BL, a.maxd, a.d_x, a.d_h, a.d_dfac, a.d_logits, a.d_targets, a.tgt_stride, a.d_dlogits, 0, a.stream, true); if (rc) return rc;
+    // accumulating: d_grad <- n_r * g_r with the trailer {n_r, flagged_r, 0, 0} behind it, exactly what a data-parallel rank hands to the exchange -- the window is that
+    // sum taken over time; Adam then reads the accumulator and divides by its trailer (a flag in it skips the update, as a peer rank's does)
+    rc = accum ? qpn_train_backward_ex(h, a.d_dlogits, a.d_grad, (float)((int64_t)a.B * a.BL), 1, a.stream) : qpn_train_backward(h, a.d_dlogits, a.d_grad, a.stream); if (rc) return rc;
+    TrainState* t = h->train;
+    const float* const g_adam = accum ? a.d_acc : a.d_grad;
+    const float* const den = accum ? a.d_acc + a.n : nullptr;
+    if (loss_mode == 2) {
+        if (accum) { rc = qpn_launch_grad_accum(a.d_acc, a.d_grad, a.n + 4, a.micro == 0, nullptr, nullptr, nullptr, nullptr, stream); if (rc) return rc; }
+        if (closing) { rc = qpn_adam_step_avg(h, a.d_flat, g_adam, a.d_m, a.d_v, a.n, a.step, a.lr, a.beta1, a.beta2, a.eps, a.weight_decay, den, a.max_grad_norm, a.d_ema, a.ema_decay, a.stream); if (rc) return rc; }
+        else { t->last_stream = stream; t->gnorm_last = false; }                                       // (no Adam launch: this micro-step has no norm)
+        rc = qpn_train_loss(h, a.h_loss, a.stream); if (rc) return rc;
+        *a.h_valid = 1;
+        if (clip && a.h_grad_norm) { int nv = 0; rc = qpn_train_grad_norm(h, a.h_grad_norm, &nv, a.stream); if (rc) return rc; }      // (the stream has just been drained)
+        return qpn_train_status(h, a.stream);
+    }
+    // modes 0 / 1: the Adam kernel -- the step's last -- writes the status word (and the loss partials) into the pinned slots itself: what
+    // qpn_train_status_enqueue / qpn_train_loss_enqueue do with a copy each, without the two copy-engine launches behind the step
+    if (!a.d_flat || !a.d_grad || !a.d_m || !a.d_v || a.n < 1 || a.step < 1) { qpn_set_error("bad adam_step arguments"); return QPN_EINVAL; }
+    const int sslot = t->status_newest ^ 1;
+    rc = status_collect_slot(t, sslot); if (rc) return rc;               // (two enqueues old: long done)
+    const int lslot = t->loss_newest ^ 1;
+    if (loss_mode == 1 && t->loss_pending[lslot]) QPN_HIP(hipEventSynchronize(t->ev_loss[lslot]));      // (an uncollected copy of two calls ago: dropped)
+    double* const hl = loss_mode == 1 ? t->h_loss_pinned + LOSS_SLOT * lslot : nullptr;
+    t->gnorm_last = clip;
+    t->last_stream = stream;
+    // (the micro-steps in front of the closing one end in the accumulate kernel: it carries the reports; in the closing one the Adam launch does, as ever)
+    if (accum) { rc = qpn_launch_grad_accum(a.d_acc, a.d_grad, a.n + 4, a.micro == 0, closing ? nullptr : t->d_status, t->h_status_pinned + sslot,
+                                            hl, (!closing && loss_mode == 1) ? t->d_loss : nullptr, stream); if (rc) return rc; }
+    if (closing) {
+        const AdamCall c = {a.d_flat, g_adam, a.d_m, a.d_v, a.n, a.step, a.lr, a.beta1, a.beta2, a.eps, a.weight_decay, den, t->d_status,
+                            t->h_status_pinned + sslot, hl, loss_mode == 1 ? t->d_loss : nullptr,
+                            a.max_grad_norm, t->d_gnorm, t->d_loss + 64, hl ? hl + 64 : nullptr, a.d_ema, omd, grouped ? &ga : nullptr};
+        rc = qpn_launch_adam(c, stream); if (rc) return rc;
+    }
+    QPN_HIP(hipEventRecord(t->ev_status[sslot], stream));
+    t->status_pending[sslot] = true; t->status_newest = sslot;
+    if (loss_mode == 1) {
+        QPN_HIP(hipEventRecord(t->ev_loss[lslot], stream));
+        t->loss_pending[lslot] = true; t->loss_newest = lslot; t->gnorm_slot[lslot] = clip;
+        rc = qpn_train_loss_collect(h, 0, a.h_loss, a.h_valid); if (rc) return rc;
+        if (a.h_grad_norm && t->gnorm_collected_valid) *a.h_grad_norm = t->gnorm_collected;
+    }
+    return QPN_OK;
+}
+
+// (a step that fails in front of its backward has no backward to consume an armed feature gradient: the arm is dropped with it)
+static int train_step_impl(qpn_handle* h, const TrainStepArgs& a) {
+    const int rc = train_step_body(h, a);
+    if (rc && h) { h->in_grad = nullptr; h->in_grad_n = 0; h->distill_t = nullptr; h->distill_n = 0; h->loss_opts_armed = false; }      // (... and no forward to consume a soft-target or loss-options arm)
+    return rc;
+}
+
 extern "C" int qpn_train_step(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
                               const int64_t* d_x, const float* d_h, const float* d_dfac, const int64_t* d_targets, int64_t tgt_stride,
                               float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
                               int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                               int loss_mode, double* h_loss, int* h_valid, void* stream) {
-    return qpn_train_step_clip(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
-                               step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, 0.0f, nullptr, stream);
+    return train_step_impl(h, {d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
+                               step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, 0.0f, nullptr, nullptr, 0.0f, nullptr, 0, 1, stream});
 }
 
 extern "C" int qpn_train_step_clip(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
@@ -944,96 +1025,8 @@ extern "C" int qpn_train_step_clip(qpn_handle* h, float* d_flat, int B, int64_t 
                                    float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
                                    int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                                    int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm, void* stream) {
-    return qpn_train_step_avg(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
-                              step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, max_grad_norm, h_grad_norm, nullptr, 0.0f, stream);
-}
-
-// max_grad_norm > 0: the step clips (qpn_adam_step_clip), and *h_grad_norm (may be NULL) receives the norm of the step whose loss *h_loss is -- mode 1: the previous
-// step's, out of the same pinned slot as its loss; mode 2: this step's; mode 0: none.  0 where that step did not clip.
-// d_ema / ema_decay: qpn_adam_step_avg's (every loss mode moves the average: it is the Adam launch's own work).
-// d_acc != NULL: micro-step `micro` of a window of micro_count > 1 chunks (qpn_train_step_acc); NULL: the plain step, launch for launch what it always was
-static int train_step_body(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
-                           const int64_t* d_x, const float* d_h, const float* d_dfac, const int64_t* d_targets, int64_t tgt_stride,
-                           float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
-                           int step, float lr, float beta1, float beta2, float eps, float weight_decay,
-                           int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm,
-                           float* d_ema, float ema_decay, float* d_acc, int micro, int micro_count, void* stream) {
-    if (h_valid) *h_valid = 0;
-    if (h_loss) *h_loss = 0.0;
-    if (h_grad_norm) *h_grad_norm = 0.0;
-    float omd;
-    int rc = check_ema_args(d_ema, ema_decay, &omd); if (rc) return rc;
-    if (loss_mode < 0 || loss_mode > 2 || (loss_mode && (!h_loss || !h_valid)) || max_grad_norm != max_grad_norm) { qpn_set_error("bad train_step arguments"); return QPN_EINVAL; }
-    const bool accum = d_acc != nullptr;                                 // a window of several chunks: the gradient goes through the accumulator ...
-    const bool closing = micro == micro_count - 1;                       // ... and only its last micro-step has an Adam launch
-    const bool clip = closing && max_grad_norm > 0.f;
-    rc = need_dev(h); if (rc) return rc;
-    AdamGroupsArg ga; bool grouped = false;
-    if (closing) { rc = adam_groups_arg(h, n, &ga, &grouped); if (rc) return rc; }      // (before anything is enqueued: a table for another n fails the whole step)
-    const AdamGroupsArg* const grp = grouped ? &ga : nullptr;
-    // a flagged word found here is cleared on THIS call's stream, in front of the step the caller runs on it next: the stream of the call before may be another
-    // one, busy with work of the caller's own, and a clear queued behind that work lands after the next step's Adam launch has read the word
-    if (h->train) h->train->last_stream = (hipStream_t)stream;
-    rc = qpn_train_status_collect_lagged(h); if (rc) return rc;          // the check of the step before the previous one (never waits for queued work)
-    if (!d_targets || !d_dlogits) { qpn_set_error("qpn_train_forward_loss needs targets and a dlogits buffer"); return QPN_EINVAL; }
-    if (accum && (!d_grad || n < 1)) { qpn_set_error("bad train_step arguments: d_grad / n"); return QPN_EINVAL; }
-    rc = train_forward_impl(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_logits, d_targets, tgt_stride, d_dlogits, 0, stream, true); if (rc) return rc;
-    // accumulating: d_grad <- n_r * g_r with the trailer {n_r, flagged_r, 0, 0} behind it, exactly what a data-parallel rank hands to the exchange -- the window is that
-    // sum taken over time; Adam then reads the accumulator and divides by its trailer (a flag in it skips the update, as a peer rank's does)
-    rc = accum ? qpn_train_backward_ex(h, d_dlogits, d_grad, (float)((int64_t)B * BL), 1, stream) : qpn_train_backward(h, d_dlogits, d_grad, stream); if (rc) return rc;
-    TrainState* t = h->train;
-    const float* const g_adam = accum ? d_acc : d_grad;
-    const float* const den = accum ? d_acc + n : nullptr;
-    if (loss_mode == 2) {
-        if (accum) { rc = qpn_launch_grad_accum(d_acc, d_grad, n + 4, micro == 0, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream); if (rc) return rc; }
-        if (closing) { rc = qpn_adam_step_avg(h, d_flat, g_adam, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, den, max_grad_norm, d_ema, ema_decay, stream); if (rc) return rc; }
-        else { t->last_stream = (hipStream_t)stream; t->gnorm_last = false; }                         // (no Adam launch: this micro-step has no norm)
-        rc = qpn_train_loss(h, h_loss, stream); if (rc) return rc;
-        *h_valid = 1;
-        if (clip && h_grad_norm) { int nv = 0; rc = qpn_train_grad_norm(h, h_grad_norm, &nv, stream); if (rc) return rc; }      // (the stream has just been drained)
-        return qpn_train_status(h, stream);
-    }
-    // modes 0 / 1: the Adam kernel -- the step's last -- writes the status word (and the loss partials) into the pinned slots itself: what
-    // qpn_train_status_enqueue / qpn_train_loss_enqueue do with a copy each, without the two copy-engine launches behind the step
-    if (!d_flat || !d_grad || !d_m || !d_v || n < 1 || step < 1) { qpn_set_error("bad adam_step arguments"); return QPN_EINVAL; }
-    const int sslot = t->status_newest ^ 1;
-    rc = status_collect_slot(t, sslot); if (rc) return rc;               // (two enqueues old: long done)
-    const int lslot = t->loss_newest ^ 1;
-    if (loss_mode == 1 && t->loss_pending[lslot]) QPN_HIP(hipEventSynchronize(t->ev_loss[lslot]));      // (an uncollected copy of two calls ago: dropped)
-    double* const hl = loss_mode == 1 ? t->h_loss_pinned + LOSS_SLOT * lslot : nullptr;
-    t->gnorm_last = clip;
-    t->last_stream = (hipStream_t)stream;
-    // (the micro-steps in front of the closing one end in the accumulate kernel: it carries the reports; in the closing one the Adam launch does, as ever)
-    if (accum) { rc = qpn_launch_grad_accum(d_acc, d_grad, n + 4, micro == 0, closing ? nullptr : t->d_status, t->h_status_pinned + sslot,
-                                            hl, (!closing && loss_mode == 1) ? t->d_loss : nullptr, (hipStream_t)stream); if (rc) return rc; }
-    if (!closing) rc = QPN_OK;
-    else if (clip) rc = qpn_launch_adam_clip(d_flat, g_adam, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, den, t->d_status, t->h_status_pinned + sslot,
-                                        hl, loss_mode == 1 ? t->d_loss : nullptr, max_grad_norm, t->d_gnorm, t->d_loss + 64, hl ? hl + 64 : nullptr, d_ema, omd, grp, (hipStream_t)stream);
-    else rc = qpn_launch_adam(d_flat, g_adam, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, den, t->d_status, t->h_status_pinned + sslot,
-                              hl, loss_mode == 1 ? t->d_loss : nullptr, d_ema, omd, grp, (hipStream_t)stream);
-    if (rc) return rc;
-    QPN_HIP(hipEventRecord(t->ev_status[sslot], (hipStream_t)stream));
-    t->status_pending[sslot] = true; t->status_newest = sslot;
-    if (loss_mode == 1) {
-        QPN_HIP(hipEventRecord(t->ev_loss[lslot], (hipStream_t)stream));
-        t->loss_pending[lslot] = true; t->loss_newest = lslot; t->gnorm_slot[lslot] = clip;
-        rc = qpn_train_loss_collect(h, 0, h_loss, h_valid); if (rc) return rc;
-        if (h_grad_norm && t->gnorm_collected_valid) *h_grad_norm = t->gnorm_collected;
-    }
-    return QPN_OK;
-}
-
-// (a step that fails in front of its backward has no backward to consume an armed feature gradient: the arm is dropped with it)
-static int train_step_impl(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
-                           const int64_t* d_x, const float* d_h, const float* d_dfac, const int64_t* d_targets, int64_t tgt_stride,
-                           float* d_logits, float* d_dlogits, float* d_grad, float* d_m, float* d_v, int64_t n,
-                           int step, float lr, float beta1, float beta2, float eps, float weight_decay,
-                           int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm,
-                           float* d_ema, float ema_decay, float* d_acc, int micro, int micro_count, void* stream) {
-    const int rc = train_step_body(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
-                                   step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, max_grad_norm, h_grad_norm, d_ema, ema_decay, d_acc, micro, micro_count, stream);
-    if (rc && h) { h->in_grad = nullptr; h->in_grad_n = 0; h->distill_t = nullptr; h->distill_n = 0; h->loss_opts_armed = false; }      // (... and no forward to consume a soft-target or loss-options arm)
-    return rc;
+    return train_step_impl(h, {d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
+                               step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, max_grad_norm, h_grad_norm, nullptr, 0.0f, nullptr, 0, 1, stream});
 }
 
 extern "C" int qpn_train_step_avg(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F, int64_t Td, int BL, int maxd,
@@ -1042,8 +1035,8 @@ extern "C" int qpn_train_step_avg(qpn_handle* h, float* d_flat, int B, int64_t T
                                   int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                                   int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm,
                                   float* d_ema, float ema_decay, void* stream) {
-    return train_step_impl(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
-                           step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, max_grad_norm, h_grad_norm, d_ema, ema_decay, nullptr, 0, 1, stream);
+    return train_step_impl(h, {d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
+                               step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, max_grad_norm, h_grad_norm, d_ema, ema_decay, nullptr, 0, 1, stream});
 }
 
 // Gradient accumulation: the step above as micro-step `micro` of a window of micro_count chunks.  Every micro-step runs forward + loss, the row-weighted backward
@@ -1064,7 +1057,7 @@ extern "C" int qpn_train_step_acc(qpn_handle* h, float* d_flat, int B, int64_t T
     if (micro < 0 || micro >= micro_count) { qpn_set_error("bad train_step_acc arguments: micro must lie in [0, micro_count)"); return QPN_EINVAL; }
     if (!d_acc && micro_count > 1) { qpn_set_error("bad train_step_acc arguments: d_acc is NULL with micro_count > 1"); return QPN_EINVAL; }
     if (d_acc && d_acc == d_grad) { qpn_set_error("bad train_step_acc arguments: d_acc is d_grad (the accumulator must be a buffer of its own)"); return QPN_EINVAL; }
-    return train_step_impl(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
-                           step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, max_grad_norm, h_grad_norm, d_ema, ema_decay,
-                           micro_count > 1 ? d_acc : nullptr, micro, micro_count, stream);
+    return train_step_impl(h, {d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_targets, tgt_stride, d_logits, d_dlogits, d_grad, d_m, d_v, n,
+                               step, lr, beta1, beta2, eps, weight_decay, loss_mode, h_loss, h_valid, max_grad_norm, h_grad_norm, d_ema, ema_decay,
+                               micro_count > 1 ? d_acc : nullptr, micro, micro_count, stream});
 }

@@ -1066,15 +1066,12 @@ class FlatAdam(torch.optim.Optimizer):
                 self._groups.send(model, L, hd, [pg["lr"] for pg in self.param_groups], [pg["weight_decay"] for pg in self.param_groups], stream)
             else:
                 _groups_off(model, L, hd)
-            if self.ema_decay > 0.0:
+            averaging = self.ema_decay > 0.0
+            if averaging:
                 self.ema = _ema_home(self.ema, flat)
-                _lib.check(L.qpn_adam_step_avg(hd, flat.data_ptr(), g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), flat.numel(),
-                                               self._steps, grp["lr"], grp["betas"][0], grp["betas"][1], grp["eps"], grp["weight_decay"], None,
-                                               self.max_grad_norm, self.ema.data_ptr(), self.ema_decay, stream))
-            else:
-                _lib.check(L.qpn_adam_step_clip(hd, flat.data_ptr(), g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), flat.numel(),
-                                                self._steps, grp["lr"], grp["betas"][0], grp["betas"][1], grp["eps"], grp["weight_decay"], None,
-                                                self.max_grad_norm, stream))
+            _lib.check(L.qpn_adam_step_avg(hd, flat.data_ptr(), g.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), flat.numel(),
+                                           self._steps, grp["lr"], grp["betas"][0], grp["betas"][1], grp["eps"], grp["weight_decay"], None,
+                                           self.max_grad_norm, self.ema.data_ptr() if averaging else None, self.ema_decay if averaging else 0.0, stream))
             if clipping:
                 _lib.check(L.qpn_train_status_enqueue(hd, stream))      # (a non-finite norm is this launch's own finding: the next collection reports it)
         return loss
@@ -1400,45 +1397,8 @@ class FusedTrainer:
         if capturing and self.accum_steps > 1:
             raise RuntimeError("qpnet_amd.FusedTrainer(accum_steps=%d): a step cannot be captured into a graph while accumulating (the micro-steps of a window "
                                "do not make the same launches)" % self.accum_steps)
-        if not multi and not capturing and self.accum_steps > 1:
-            return self._micro_step_call(L, hd, dev, flat, stream, x, h, t, d, B, T, BL, maxd, want_loss, loss)
         if not multi and not capturing:
-            # the whole step behind ONE foreign call (qpn_train_step: the same calls in the same order as below): while it runs, the interpreter is free
-            # for the loader thread -- the runner loop was bound by the two threads' interleaved Python, not by the device
-            self.step_count += 1
-            valid = C.c_int(0)
-            mode = 1 if want_loss == "lagged" else (2 if want_loss else 0)
-            clip = self.max_grad_norm
-            with torch.cuda.device(dev):
-                if clip > 0.0 or self.ema is not None:
-                    norm = C.c_double(0.0)
-                    if self.ema is not None:
-                        rc = L.qpn_train_step_avg(hd, flat.data_ptr(), B, T, h.shape[2], d.shape[1], BL, maxd, x.data_ptr(), h.data_ptr(), d.data_ptr(),
-                                                  t.data_ptr(), t.shape[1], self._logits.data_ptr(), self._dlogits.data_ptr(), self.g.data_ptr(),
-                                                  self.m.data_ptr(), self.v.data_ptr(), flat.numel(), self.step_count, self.lr, self.betas[0], self.betas[1],
-                                                  self.eps, self.wd, mode, C.byref(loss), C.byref(valid), clip, C.byref(norm),
-                                                  self.ema.data_ptr(), self.ema_decay, stream)
-                    else:
-                        rc = L.qpn_train_step_clip(hd, flat.data_ptr(), B, T, h.shape[2], d.shape[1], BL, maxd, x.data_ptr(), h.data_ptr(), d.data_ptr(),
-                                                   t.data_ptr(), t.shape[1], self._logits.data_ptr(), self._dlogits.data_ptr(), self.g.data_ptr(),
-                                                   self.m.data_ptr(), self.v.data_ptr(), flat.numel(), self.step_count, self.lr, self.betas[0], self.betas[1],
-                                                   self.eps, self.wd, mode, C.byref(loss), C.byref(valid), clip, C.byref(norm), stream)
-                    if clip <= 0.0:
-                        pass                                         # (averaging without clipping: there is no norm)
-                    elif not valid.value:
-                        self.last_grad_norm = None
-                    elif mode == 1:
-                        self.last_grad_norm = self._collected_norm(L, hd)      # (None where the step that loss belongs to ran unclipped: the C call hands back 0.0 there)
-                    else:
-                        self.last_grad_norm = norm.value
-                else:
-                    rc = L.qpn_train_step(hd, flat.data_ptr(), B, T, h.shape[2], d.shape[1], BL, maxd, x.data_ptr(), h.data_ptr(), d.data_ptr(),
-                                          t.data_ptr(), t.shape[1], self._logits.data_ptr(), self._dlogits.data_ptr(), self.g.data_ptr(),
-                                          self.m.data_ptr(), self.v.data_ptr(), flat.numel(), self.step_count, self.lr, self.betas[0], self.betas[1],
-                                          self.eps, self.wd, mode, C.byref(loss), C.byref(valid), stream)
-            if rc:
-                self._rebase_step_count(L, hd, dev, stream, rc)
-            return loss.value if valid.value else None
+            return self._step_call(L, hd, dev, flat, stream, x, h, t, d, B, T, BL, maxd, want_loss, loss)
         self.last_grad_norm = None
         try:
             return self._step_calls(L, hd, dev, flat, stream, x, h, t, d, B, T, BL, maxd, want_loss, multi, capturing, loss)
@@ -1448,9 +1408,11 @@ class FusedTrainer:
                 self._rebase_step_count(L, hd, dev, stream, 0)
             raise
 
-    def _micro_step_call(self, L, hd, dev, flat, stream, x, h, t, d, B, T, BL, maxd, want_loss, loss):
-        """accum_steps > 1 on one rank: the micro-step behind ONE foreign call (qpn_train_step_acc).  The update number it passes is the same for every micro-step
-        of a window; step_count moves when the window closes."""
+    def _step_call(self, L, hd, dev, flat, stream, x, h, t, d, B, T, BL, maxd, want_loss, loss):
+        """One rank, not capturing: the whole step -- or, with accum_steps > 1, the micro-step -- behind ONE foreign call (qpn_train_step_acc: the calls of
+        _step_calls in their order; averaging, clipping and the window are its arguments, None / 0 where off).  While it runs the interpreter is free for the
+        loader thread: the runner loop was bound by the two threads' interleaved Python, not by the device.  The update number it passes is the same for every
+        micro-step of a window; step_count moves when the window closes."""
         K, micro = self.accum_steps, self._micro
         closing = micro == K - 1
         valid, norm = C.c_int(0), C.c_double(0.0)
@@ -1462,8 +1424,8 @@ class FusedTrainer:
                                       self.m.data_ptr(), self.v.data_ptr(), flat.numel(), self.step_count + 1, self.lr, self.betas[0], self.betas[1],
                                       self.eps, self.wd, mode, C.byref(loss), C.byref(valid), clip, C.byref(norm),
                                       self.ema.data_ptr() if self.ema is not None else None, self.ema_decay if self.ema is not None else 0.0,
-                                      self.acc.data_ptr(), micro, K, stream)
-        if rc in (-4, -2):
+                                      self.acc.data_ptr() if K > 1 else None, micro, K, stream)
+        if K > 1 and rc in (-4, -2):
             self._micro = 0                            # a device-side status error: the open window is abandoned, the next step() overwrites the accumulator
         elif closing:
             self._micro = 0
@@ -1471,11 +1433,11 @@ class FusedTrainer:
         else:
             self._micro = micro + 1
         if clip <= 0.0:
-            pass
+            pass                                       # (no clipping: there is no norm, last_grad_norm is left alone)
         elif not valid.value:
             self.last_grad_norm = None
         elif mode == 1:
-            self.last_grad_norm = self._collected_norm(L, hd)      # (None where the micro-step that loss belongs to did not close a window)
+            self.last_grad_norm = self._collected_norm(L, hd)      # (None where the step that loss belongs to ran unclipped or did not close a window: the C call hands back 0.0 there)
         else:
             self.last_grad_norm = norm.value if closing else None
         if rc:
@@ -1547,15 +1509,11 @@ class FusedTrainer:
             den = gbuf.data_ptr() + 4 * flat.numel() if (multi or accum) else None
             if not closing:
                 self._micro += 1                       # (no Adam launch: the window stays open)
-            elif self.ema is not None:
-                self.step_count += 1; self._micro = 0
-                _lib.check(L.qpn_adam_step_avg(hd, flat.data_ptr(), gbuf.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), flat.numel(),
-                                               self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                                               den, clip, self.ema.data_ptr(), self.ema_decay, stream))
             else:
                 self.step_count += 1; self._micro = 0
-                _lib.check(L.qpn_adam_step_clip(hd, flat.data_ptr(), gbuf.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), flat.numel(),
-                                                self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, den, clip, stream))
+                _lib.check(L.qpn_adam_step_avg(hd, flat.data_ptr(), gbuf.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), flat.numel(),
+                                               self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, den, clip,
+                                               self.ema.data_ptr() if self.ema is not None else None, self.ema_decay if self.ema is not None else 0.0, stream))
             if want_loss == "lagged":
                 # this step's loss is copied out behind its kernels; what comes back is the PREVIOUS step's (None at the first step, or right after
                 # flush_loss()): the stream is never drained, and a caller that sums losses over an interval and calls flush_loss() at its end has the same sum

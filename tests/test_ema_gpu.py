@@ -281,7 +281,7 @@ def test_world2_identity_exchange_moves_the_average(cuda):
 
 @pytest.mark.parametrize("kw", [{}, {"world_size": 2}])
 def test_clipped_steps_move_the_average(kw, cuda):
-    """max_grad_norm = the median of the five unclipped norms: k_adam_clip's averaging instantiation runs, with clipped and unclipped steps"""
+    """max_grad_norm = the median of the five unclipped norms: the clipping and averaging instance of k_adam runs, with clipped and unclipped steps"""
     norms = _five_steps(cuda, True, max_grad_norm=1e30)[4]
     c = float(np.median(norms))
     assert sum(v > c for v in norms) == 2 and sum(v < c for v in norms) == 2, norms

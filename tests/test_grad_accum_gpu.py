@@ -249,6 +249,95 @@ def test_null_accumulator_with_a_window_of_one_is_the_plain_step(cuda, handle):
     util.assert_grads_match_oracle(TO, TINY, w0, og["caches"], og["dl"], g[:N], og=og["g"])
 
 
+@pytest.mark.parametrize("want_loss", [True, "lagged", False])
+def test_the_trainers_one_call_site_is_the_avg_step(want_loss, cuda, handle, ref):
+    """FusedTrainer(max_grad_norm, ema_decay) with accum_steps = 1 steps through qpn_train_step_acc(d_acc = NULL, 0, 1); three steps of it against three calls of
+    qpn_train_step_avg over the C ABI from the same weights on the same chunks, clipping at half the first chunk's oracle norm, decay 0.9.
+    Two runs of one forward + backward differ in the order of their float atomics (the upsampling bias, the adaptive blocks' scatter; tests/test_train_gpu.py holds
+    such runs to 2e-6 on the weights), so the two sequences are compared in two parts.  What a step does with ITS gradient is bit for bit: after every trainer step
+    qpn_adam_step_avg -- the Adam launch of qpn_train_step_avg -- on copies of the state the step started from, given the gradient buffer the step left, the step's
+    number, clip and decay, yields torch.equal weights, moments and average, and the same norm (the bit pattern of last_grad_norm where the step reports one).
+    Across the two runs: step_count and which steps return a loss / a norm are the same; losses and norms agree to 1e-6 relative, weights, moments and average
+    to test_train_gpu.py's bounds for two runs of the same steps.  (Measured: the two runs' weights differ by up to 1.5e-8 and are not bit-equal in any of the
+    three modes -- nor are two runs of the parent commit's library, profiles/adam_step.txt --, their norms by 1e-11 relative, their losses not at all.)"""
+    import torch
+    from qpnet_amd.train import FusedTrainer
+    L, hp = handle
+    w0 = synth.make_weights(TINY, WSEED)
+    clip = 0.5 * float(np.sqrt((ref[0]["per"][0]["g"].astype(np.float64) ** 2).sum()))
+    mode = 1 if want_loss == "lagged" else (2 if want_loss else 0)
+    # the C ABI's sequence
+    bufs = _Bufs(cuda, w0)
+    c_out = []
+    for k in range(3):
+        x, h, t, d, b = _chunk_np(k)
+        xt, ht, tt, dt = _to(cuda, x, h, t, d)
+        B, BL = x.shape[0], int(b[0])
+        logits = torch.empty((B, BL, TINY.n_quantize), dtype=torch.float32, device=cuda)
+        dlogits = torch.empty_like(logits)
+        loss, valid, norm = C.c_double(0.0), C.c_int(0), C.c_double(0.0)
+        _lib.check(L.qpn_train_step_avg(hp, bufs.flat.data_ptr(), B, x.shape[1], ht.shape[2], dt.shape[1], BL, int(np.ceil(d).max()), xt.data_ptr(), ht.data_ptr(),
+                                        dt.data_ptr(), tt.data_ptr(), tt.shape[1], logits.data_ptr(), dlogits.data_ptr(), bufs.g.data_ptr(), bufs.m.data_ptr(),
+                                        bufs.v.data_ptr(), N, k + 1, LR, 0.9, 0.999, 1e-8, 0.0, mode, C.byref(loss), C.byref(valid), clip, C.byref(norm),
+                                        bufs.ema.data_ptr(), 0.9, _stream()))
+        c_out.append((loss.value if valid.value else None, norm.value if valid.value else None))
+    if mode == 1:
+        loss, valid, norm, nv = C.c_double(0.0), C.c_int(0), C.c_double(0.0), C.c_int(0)
+        _lib.check(L.qpn_train_loss_collect(hp, 1, C.byref(loss), C.byref(valid)))
+        _lib.check(L.qpn_train_grad_norm_lagged(hp, C.byref(norm), C.byref(nv)))
+        assert valid.value == 1 and nv.value == 1
+        c_out.append((loss.value, norm.value))
+    assert L.qpn_train_status(hp, _stream()) == 0
+    # the trainer's
+    m = util.build_model(TINY, w0, cuda).train()
+    tr = FusedTrainer(m, lr=LR, max_grad_norm=clip, ema_decay=0.9)
+    assert tr.last_grad_norm is None
+    t_out = []
+    state = [torch.from_numpy(w0.copy()).to(cuda), torch.zeros(N, device=cuda), torch.zeros(N, device=cuda), torch.from_numpy(w0.copy()).to(cuda)]
+    for k in range(3):
+        loss = tr.step(*_chunk(cuda, k), want_loss=want_loss)
+        assert tr.step_count == k + 1 and tr.micro_step == 0 and tr.acc is None
+        t_out.append((loss, tr.last_grad_norm))
+        # this step's Adam launch, replayed on the state it started from
+        _lib.check(L.qpn_adam_step_avg(hp, state[0].data_ptr(), tr.g.data_ptr(), state[1].data_ptr(), state[2].data_ptr(), N, k + 1, LR, 0.9, 0.999, 1e-8, 0.0,
+                                       None, clip, state[3].data_ptr(), 0.9, _stream()))
+        replay, nv = C.c_double(0.0), C.c_int(0)
+        _lib.check(L.qpn_train_grad_norm(hp, C.byref(replay), C.byref(nv), _stream()))
+        assert nv.value == 1 and replay.value > clip
+        for what, a, r in zip(("w", "m", "v", "ema"), (m.flat_parameters(), tr.m, tr.v, tr.ema), state):
+            assert torch.equal(a, r), "step %d: %s differs from qpn_adam_step_avg on the step's own gradient" % (k, what)
+        if mode == 2:
+            assert np.float64(tr.last_grad_norm).tobytes() == np.float64(replay.value).tobytes()
+        t_norm_of_step = replay.value
+        if mode == 1 and k > 0:
+            assert np.float64(tr.last_grad_norm).tobytes() == np.float64(prev_norm).tobytes()      # (the norm that came with the previous step's loss)
+        prev_norm = t_norm_of_step
+    if mode == 1:
+        loss = tr.flush_loss()
+        assert np.float64(tr.last_grad_norm).tobytes() == np.float64(prev_norm).tobytes()
+        t_out.append((loss, tr.last_grad_norm))
+    tr.check_status()
+    assert tr.step_count == 3 and tr.state_dict()["state"][0]["step"] == 3
+    # the two sequences next to each other
+    print("C ABI:", c_out, "\ntrainer:", t_out)
+    assert [(o[0] is None, o[1] is None) for o in t_out] == [(o[0] is None, o[1] is None) for o in c_out]
+    if mode == 0:
+        assert all(o == (None, None) for o in t_out)
+    for tv, cv in zip(t_out, c_out):
+        for a, r in zip(tv, cv):
+            if r is not None:
+                np.testing.assert_allclose(a, r, rtol=1e-6, atol=0)
+    got = [t.cpu().numpy() for t in (m.flat_parameters(), tr.m, tr.v, tr.ema)]
+    want = [t.cpu().numpy() for t in (bufs.flat, bufs.m, bufs.v, bufs.ema)]
+    print("bit-equal across the two runs (w, m, v, ema):", [bool(np.array_equal(a, r)) for a, r in zip(got, want)],
+          "max |dw| %.2e" % np.abs(got[0] - want[0]).max())
+    np.testing.assert_allclose(got[0], want[0], rtol=0, atol=2e-6)
+    np.testing.assert_allclose(got[3], want[3], rtol=0, atol=2e-6)
+    np.testing.assert_allclose(got[1], want[1], rtol=0, atol=1e-5 * np.abs(want[1]).max())
+    np.testing.assert_allclose(got[2], want[2], rtol=0, atol=4e-5 * np.abs(want[2]).max())
+    assert not np.array_equal(got[0], w0) and not np.array_equal(got[3], w0)
+
+
 def test_a_flag_of_an_earlier_micro_step_skips_the_closing_update(cuda, handle):
     """the C ABI alone, loss_mode 2 (the status is read, and cleared, in every call): micro-step 0 carries a target equal to n_quantize -- clamped and flagged, the
     call reports QPN_ERANGE -- and a caller that goes on with the window anyway finds the flag in the accumulator's trailer: the closing call applies nothing and

@@ -40,6 +40,9 @@ BUDGET = {
     "k_wgrad3ILi0ELi1ELi4ELb0ELi1EE": ("train_bwd.hip", 0, 4),      # residual 1x1: one A array (dXout summed in place), one B array (the gate product); memory-bound: occupancy is what it lives on
     "k_wgrad3ILi0ELi1ELi4ELb1ELi1EE": ("train_bwd.hip", 0, 4),      # ... with the two-part dXout of the per-layer backward launches
     "k_up_bwd": ("train_bwd.hip", 0, 2),                               # a row's 16 float4 words in registers at once, still nothing in scratch
+    "k_adamILb": ("train_adam.hip", 0, 8),                             # all 8 instances of the optimiser step (clip x averaged weights x groups): memory-bound, full occupancy
+    "k_grad_sumsq": ("train_adam.hip", 0, 8),                          # ... the norm's partial sums, without and with groups
+    "k_grad_accum": ("train_adam.hip", 0, 8),
     "k_gemm_nnILi0ELi1E": ("train_gemm.hip", 0, 3),
     "k_gemm_nnILi1ELi4E": ("train_gemm.hip", 0, 3),
     "k_gemm_tnILi3E": ("train_gemm.hip", 0, 3),

@@ -1,7 +1,7 @@
 """What gradient-norm clipping costs in the fused step: FusedTrainer.step on the bench chunk with and without max_grad_norm, in ONE process, the two
 variants interleaved block by block (the same trainer, weights and buffers: only `max_grad_norm` changes between blocks), for the paper-size geometry
 (bench.py's headline workload) and the repo-default one.  Prints steps/s of both and their ratio per geometry; with --profile it then runs itself once
-more under `rocprofv3 --kernel-trace --stats` (a fresh child process, clipping on) and prints the durations of k_grad_sumsq, k_adam_clip and k_adam.
+more under `rocprofv3 --kernel-trace --stats` (a fresh child process, clipping on) and prints the durations of k_grad_sumsq, k_adam<clip> and k_adam<no clip>.
 
     python tools/clip_step_rate.py [--geometry paper,default] [--rounds 5] [--profile] [--out DIR]
 
@@ -95,11 +95,12 @@ def profile(name, out):
     total = sum(float(x["TotalDurationNs"]) for x in rows)
     res = {"geometry": name, "all_kernels_us_per_step": None, "kernels": {}}
     for x in rows:
-        for k in ("k_grad_sumsq", "k_adam_clip", "k_adam("):
-            if k in x["Name"]:
-                res["kernels"][k.rstrip("(")] = {"calls": int(x["Calls"]), "average_us": float(x["AverageNs"]) / 1e3, "min_us": float(x["MinNs"]) / 1e3,
-                                                 "max_us": float(x["MaxNs"]) / 1e3, "share_of_kernel_time_pct": 100.0 * float(x["TotalDurationNs"]) / total}
-    calls = res["kernels"].get("k_adam_clip", {}).get("calls")
+        # (the Adam kernel is one template, reported as `void k_adam<CLIP, EMA, GROUPED>(...)`: its first argument tells the clipping instance from the plain one)
+        for k, label in (("k_grad_sumsq", "k_grad_sumsq"), ("k_adam<true", "k_adam<clip>"), ("k_adam<false", "k_adam<no clip>")):
+            if k in x["Name"].replace(" ", ""):
+                res["kernels"][label] = {"calls": int(x["Calls"]), "average_us": float(x["AverageNs"]) / 1e3, "min_us": float(x["MinNs"]) / 1e3,
+                                         "max_us": float(x["MaxNs"]) / 1e3, "share_of_kernel_time_pct": 100.0 * float(x["TotalDurationNs"]) / total}
+    calls = res["kernels"].get("k_adam<clip>", {}).get("calls")
     if calls:
         res["all_kernels_us_per_step"] = total / calls / 1e3
     return res
