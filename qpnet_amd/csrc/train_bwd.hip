@@ -6,8 +6,8 @@
 //                  x_cur part (+ residual) is stored at its own row; the x_past part is the backward of
 //                  the pitch-dependent gather = scatter-add to row tap[n] (float atomics only for the
 //                  adaptive blocks; fixed blocks have a unique writer per row)
-//   k_wgrad2     : every weight gradient is a time-contraction dW[m][n] = sum_t A[t][m] B[t][n]; one launch per
-//                  weight family over (time chunk, layer), partial slabs (deterministic), bias grads = colsum(A)
+//   (the weight gradients -- every one a time contraction dW[m][n] = sum_t A[t][m] B[t][n] into partial slabs -- are train_wgrad.hip;
+//    their records and which kernel instance each gets: train_wgrad_plan.h.  qpn_launch_bwd below places their launches.)
 //   k_causal_bwd : the one-hot causal conv's weight grad is a histogram over sample classes -> LDS table
 //   k_up_bwd     : gradient of the (1,1,1,U) upsampling kernel and its bias
 //   k_reduce_grad: slabs -> flat gradient in state_dict order
@@ -523,214 +523,7 @@ __global__ __launch_bounds__(256, 2) void k_layer_bwd_p(TrainParams p, TrainBwd 
     }
 }
 
-// ------------------------------------------------------------------------------------------ weight gradients, v2
-// One launch covers every layer (blockIdx.y) and every time chunk (blockIdx.x).  A workgroup (4 waves)
-// computes the WHOLE output block dW[M][N] of its layer for its chunk of rows: wave w owns m-tiles
-// {w, w+4, ...} x all n-tiles, operands staged once per 32 rows with 16-byte loads (no re-reads across
-// output tiles), partial result written to its slab.  dW = A^T B with
-//   A[row][m]  : plain array, or the sum of two arrays (grad wrt a layer output = own-row + scattered part)
-//   B[row][n]  : plain | relu(array) | product of two arrays (gate = sigma*tanh) | [x_cur | x_past | aux | 0]
-//                | one-hot of the row's sample class (k_wgrad3 only)
-struct Wg2 {
-    const float* A; const float* A2; size_t A_lstride; int lda, M;        // per-layer stride (floats)
-    int rowsA;                                                              // rows per batch item in A's array
-    int bmode; const float* B1; const float* B2; size_t B_lstride; int ldb, N, Nvalid;
-    int rowsB;
-    const float* hup; const int* tap; int C, Ap;
-    const int* xc;                                                          // bmode 4: B[t][q] = (xc[row] == q), one-hot of the sample class
-    int nb, nlayers;
-    float* slab; int gstage;
-    int row0A[TR_MAXL], row0B[TR_MAXL], R[TR_MAXL];                         // window per layer
-    int goff[TR_MAXL], gbias[TR_MAXL], tap_off[TR_MAXL], dil[TR_MAXL];
-    int ldc, ncol_groups;                                                   // post: N split into column groups (blockIdx.z)
-};
-
-struct Wg2L {            // per-workgroup scalars hoisted out of the kernel-argument arrays
-    const float* A; const float* A2; const float* B1; const float* B2; const float* hup; const int* tap;
-    int lda, ldb, M, Ng, Nvalid, rowsA, rowsB, row0A, row0B, C, Ap, dil, nb, ncol0, rend;
-    unsigned uR;
-};
-
-// tap rows of the stage starting at rs (pitch-dependent gather source rows), loaded one stage ahead of their use
-template <int NB>
-__device__ __forceinline__ void wg_taps(const Wg2L& q, int rs, int (&tp)[NB], bool b_act, int b_row0, int b_rstep) {
-#pragma unroll
-    for (int k = 0; k < NB; ++k) {
-        const int r = b_row0 + k * b_rstep, rr = rs + r;
-        int v = 0;
-        if (b_act && r < 32 && rr < q.rend) {
-            const unsigned b = q.nb > 1 ? (unsigned)rr / q.uR : 0u; const int i = rr - (int)(b * q.uR);
-            const int nloc = q.row0B + i;
-            v = q.tap ? q.tap[(size_t)b * q.rowsB + nloc] : nloc - q.dil;
-        }
-        tp[k] = v;
-    }
-}
-
-template <int BMODE, int NA, int NB>
-__device__ __forceinline__ void wg_fetch(const Wg2L& q, int rs, float4 (&ra)[NA], float4 (&ra2)[NA], float4 (&rb)[NB], float4 (&rb2)[NB], const int (&tpv)[NB],
-                                         bool a_act, int a_row0, int a_rstep, int a_col, bool b_act, int b_row0, int b_rstep, int b_col) {
-#pragma unroll
-    for (int k = 0; k < NA; ++k) {
-        const int r = a_row0 + k * a_rstep, rr = rs + r;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f), v2 = v;
-        if (a_act && r < 32 && rr < q.rend && a_col < q.M) {
-            const unsigned b = q.nb > 1 ? (unsigned)rr / q.uR : 0u; const int i = rr - (int)(b * q.uR);
-            const size_t o = ((size_t)b * q.rowsA + q.row0A + i) * q.lda + a_col;
-            v = *(const float4*)(q.A + o);
-            if (q.A2) v2 = *(const float4*)(q.A2 + o);
-        }
-        ra[k] = v; ra2[k] = v2;
-    }
-#pragma unroll
-    for (int k = 0; k < NB; ++k) {
-        const int r = b_row0 + k * b_rstep, rr = rs + r;
-        const int n = q.ncol0 + b_col;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f), v2 = make_float4(1.f, 1.f, 1.f, 1.f);
-        if (b_act && r < 32 && rr < q.rend && b_col < q.Ng && n < q.Nvalid) {
-            const unsigned b = q.nb > 1 ? (unsigned)rr / q.uR : 0u; const int i = rr - (int)(b * q.uR);
-            const int nloc = q.row0B + i;
-            const size_t row = (size_t)b * q.rowsB + nloc;
-            if (BMODE <= 1) v = *(const float4*)(q.B1 + row * q.ldb + n);
-            else if (BMODE == 2) { v = *(const float4*)(q.B1 + row * q.ldb + n); v2 = *(const float4*)(q.B2 + row * q.ldb + n); }
-            else {
-                if (n < q.C) v = *(const float4*)(q.B1 + row * q.C + n);
-                else if (n < 2 * q.C) v = *(const float4*)(q.B1 + ((size_t)b * q.rowsB + tpv[k]) * q.C + (n - q.C));
-                else v = *(const float4*)(q.hup + row * q.Ap + (n - 2 * q.C));
-            }
-        }
-        rb[k] = v; rb2[k] = v2;
-    }
-}
-
-template <int BMODE, int MPW, int NTMAX>
-__global__ __launch_bounds__(256) void k_wgrad2(Wg2 w, int nch) {
-    extern __shared__ float sm[];
-    constexpr int RS = 32;
-    constexpr int NA = 2 * MPW;              // staging passes of A: 32 rows / (256 / (Mp/4)) with Mp <= 64*MPW
-    constexpr int NB = (NTMAX + 1) / 2 + 1;  // staging passes of B: ceil(32 / floor(256 / (Np/4))), Np <= 16*NTMAX
-    const int y = blockIdx.y, ch = blockIdx.x, zg = blockIdx.z;
-    const int Mp = (w.M + 15) & ~15, Ng = w.N / w.ncol_groups, Np = (Ng + 15) & ~15;
-    const int ldA = tr_ldt(Mp), ldB = tr_ldt(Np);
-    float* As = sm; float* Bs = sm + RS * ldA;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int MT = Mp / 16, NT = Np / 16;
-    const int Rl = w.R[y];
-    const int64_t total = (int64_t)Rl * w.nb;
-    const int64_t per = ((total + nch - 1) / nch + RS - 1) / RS * RS;
-    const int rbeg = (int)(per * ch), rend = (int)(per * ch + per < total ? per * ch + per : total);
-    Wg2L q;
-    q.A = w.A + (size_t)y * w.A_lstride; q.A2 = w.A2 ? w.A2 + (size_t)y * w.A_lstride : nullptr;
-    q.B1 = w.B1 + (size_t)y * w.B_lstride; q.B2 = w.B2 ? w.B2 + (size_t)y * w.B_lstride : nullptr;
-    q.hup = w.hup; q.tap = (w.tap && w.tap_off[y] >= 0) ? w.tap + w.tap_off[y] : nullptr;
-    q.lda = w.lda; q.ldb = w.ldb; q.M = w.M; q.Ng = Ng; q.Nvalid = w.Nvalid; q.rowsA = w.rowsA; q.rowsB = w.rowsB;
-    q.row0A = w.row0A[y]; q.row0B = w.row0B[y]; q.C = w.C; q.Ap = w.Ap; q.dil = w.dil[y]; q.nb = w.nb; q.ncol0 = zg * Ng; q.rend = rend;
-    q.uR = (unsigned)(Rl > 0 ? Rl : 1);
-    const int gbias = zg == 0 ? w.gbias[y] : -1, goff = w.goff[y];
-    const int A4 = Mp / 4, B4 = Np / 4;
-    const int a_col = (tid % A4) * 4, a_row0 = tid / A4, a_rstep = 256 / A4;
-    const int b_rstep = 256 / B4 > 0 ? 256 / B4 : 1;
-    const int b_col = (tid % B4) * 4, b_row0 = tid / B4;
-    const bool a_act = tid < a_rstep * A4, b_act = tid < b_rstep * B4;
-    f32x4 acc[MPW][NTMAX];
-#pragma unroll
-    for (int a = 0; a < MPW; ++a)
-#pragma unroll
-        for (int b = 0; b < NTMAX; ++b) acc[a][b] = (f32x4){0, 0, 0, 0};
-    float csum = 0.f;
-    float4 ra[NA], ra2[NA], rb[NB], rb2[NB];
-    int tpv[NB];
-#pragma unroll
-    for (int k = 0; k < NB; ++k) tpv[k] = 0;
-    if (BMODE == 3 && rbeg < rend) wg_taps<NB>(q, rbeg, tpv, b_act, b_row0, b_rstep);
-    if (rbeg < rend) wg_fetch<BMODE, NA, NB>(q, rbeg, ra, ra2, rb, rb2, tpv, a_act, a_row0, a_rstep, a_col, b_act, b_row0, b_rstep, b_col);
-    if (BMODE == 3 && rbeg + RS < rend) wg_taps<NB>(q, rbeg + RS, tpv, b_act, b_row0, b_rstep);
-    const int g = lane >> 4, cl = lane & 15;
-    for (int rs = rbeg; rs < rend; rs += RS) {
-        // registers -> LDS
-#pragma unroll
-        for (int k = 0; k < NA; ++k) {
-            const int r = a_row0 + k * a_rstep;
-            if (a_act && r < RS) {
-                float4 v = ra[k];
-                v.x += ra2[k].x; v.y += ra2[k].y; v.z += ra2[k].z; v.w += ra2[k].w;
-                *(float4*)(As + (size_t)r * ldA + a_col) = v;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < NB; ++k) {
-            const int r = b_row0 + k * b_rstep;
-            if (b_act && r < RS) {
-                float4 v = rb[k];
-                if (BMODE == 1) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-                else if (BMODE == 2) { v.x *= rb2[k].x; v.y *= rb2[k].y; v.z *= rb2[k].z; v.w *= rb2[k].w; }
-                *(float4*)(Bs + (size_t)r * ldB + b_col) = v;
-            }
-        }
-        __syncthreads();
-        // next stage's rows fly while the matrix cores work on this one
-        if (rs + RS < rend) wg_fetch<BMODE, NA, NB>(q, rs + RS, ra, ra2, rb, rb2, tpv, a_act, a_row0, a_rstep, a_col, b_act, b_row0, b_rstep, b_col);
-        if (BMODE == 3 && rs + 2 * RS < rend) wg_taps<NB>(q, rs + 2 * RS, tpv, b_act, b_row0, b_rstep);   // gather rows of the stage after next
-        if (gbias >= 0 && tid < q.M) { float s = 0.f; for (int r = 0; r < RS; ++r) s += As[r * ldA + tid]; csum += s; }
-#pragma unroll
-        for (int ks = 0; ks < RS / 4; ++ks) {
-            float bfr[NTMAX];
-#pragma unroll
-            for (int nt = 0; nt < NTMAX; ++nt) bfr[nt] = nt < NT ? Bs[(4 * ks + g) * ldB + 16 * nt + cl] : 0.f;
-#pragma unroll
-            for (int mi = 0; mi < MPW; ++mi) {
-                const int mt = wave + 4 * mi;
-                if (mt < MT) {
-                    const float a = As[(4 * ks + g) * ldA + 16 * mt + cl];
-#pragma unroll
-                    for (int nt = 0; nt < NTMAX; ++nt)
-                        if (nt < NT) acc[mi][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bfr[nt], acc[mi][nt], 0, 0, 0);
-                }
-            }
-        }
-        __syncthreads();
-    }
-    float* out = w.slab + (size_t)ch * w.gstage;
-#pragma unroll
-    for (int mi = 0; mi < MPW; ++mi) {
-        const int mt = wave + 4 * mi;
-        if (mt >= MT) continue;
-#pragma unroll
-        for (int nt = 0; nt < NTMAX; ++nt) {
-            if (nt >= NT) continue;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int m = 16 * mt + 4 * (lane >> 4) + i, n = 16 * nt + (lane & 15);
-                if (m < q.M && n < Ng) out[goff + (size_t)m * w.ldc + q.ncol0 + n] = acc[mi][nt][i];
-            }
-        }
-    }
-    if (gbias >= 0 && tid < q.M) out[gbias + tid] = csum;
-}
-
-template <int BMODE, int MPW, int NTMAX>
-static int launch_wgrad2(const Wg2& w, int nch, hipStream_t stream) {
-    const int Mp = (w.M + 15) & ~15, Np = ((w.N / w.ncol_groups) + 15) & ~15;
-    if (Mp / 16 > 4 * MPW || Np / 16 > NTMAX) return -1;
-    const size_t lds = (size_t)32 * (tr_ldt(Mp) + tr_ldt(Np)) * sizeof(float);
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_wgrad2<BMODE, MPW, NTMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((k_wgrad2<BMODE, MPW, NTMAX>), dim3(nch, w.nlayers, w.ncol_groups), dim3(256), lds, stream, w, nch);
-    return 0;
-}
-template <int BMODE>
-static bool wgrad2_mode(const Wg2& w, int nch, hipStream_t stream) {
-    if (launch_wgrad2<BMODE, 1, 4>(w, nch, stream) == 0) return true;
-    if (launch_wgrad2<BMODE, 4, 4>(w, nch, stream) == 0) return true;
-    if (launch_wgrad2<BMODE, 2, 12>(w, nch, stream) == 0) return true;
-    if (launch_wgrad2<BMODE, 4, 8>(w, nch, stream) == 0) return true;       // 256 x 128 blocks (n_resch up to 128 with column groups)
-    return false;
-}
-// ------------------------------------------------------------------------------------------ weight gradients, v3
-// Same contraction and slab layout as k_wgrad2, for the geometries where the tile counts are known at compile time
-// (M = 64*MPW rows of dW -> every wave owns exactly MPW m-tiles, N per column group = 16*NT): no per-tile guards in
-// the matrix-core loop, no branches around the staging loads (out-of-range rows are clamped and zeroed, the three
-// sources of the [x_cur | x_past | aux] operand become one per-thread base/stride), bias column sums taken from the
-// staging registers instead of 32 LDS reads per stage.  k_wgrad2 stays as the generic fallback.
+// ------------------------------------------------------------------------------------------ upsampling kernel
 // upsampling kernel grad: dw[j] = sum_{a,f} dH[a, U f + j] h[a,f];  db = sum dH   (qpnet.py:134-158)
 // One workgroup per (frame, batch item): thread j < U owns sample U f + j of the frame, reads its dH row (Ap contiguous floats: the
 // workgroup's reads are one contiguous U*Ap*4-byte block) and dots it with the frame's feature column held in LDS; one global atomic per
@@ -780,308 +573,6 @@ __device__ __forceinline__ void up_bwd_body(const UpArgs& p, int fx, int b, int 
     if (tid == 0) { float a = 0.f; for (int k = 0; k < nthr / 64; ++k) a += red[k]; atomicAdd(&p.gflat[p.up_b], a * p.gscale); }
 }
 
-// (ch, y, zg) = (time chunk, layer, column group) of this workgroup: blockIdx of the one-contraction launches, decoded from a flat index in k_wgrad_tail
-template <int BMODE, int MPW, int NT, bool TWO_A>
-__device__ __forceinline__ void wgrad3_body(const Wg2& w, const int nch, const int ch, const int y, const int zg) {
-    extern __shared__ float sm[];
-    constexpr int RS = 32, Mp = 64 * MPW, Np = 16 * NT;
-    constexpr int ldA = ((Mp + 15) / 32) * 32 + 16, ldB = ((Np + 15) / 32) * 32 + 16;       // tr_ldt
-    constexpr int A4 = Mp / 4, ARS = 256 / A4, NA = RS / ARS;                               // A: every thread active, NA full passes
-    constexpr int B4 = Np / 4, BRS = 256 / B4, NB = (RS + BRS - 1) / BRS;                   // B: threads < BRS*B4 active
-    static_assert(256 % A4 == 0 && RS % ARS == 0, "A staging must tile the stage's rows exactly");
-    constexpr int BUF = RS * (ldA + ldB);                                                   // floats of one stage buffer
-    float* As = sm; float* Bs = sm + RS * ldA;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int Rl = w.R[y];
-    const int64_t total = (int64_t)Rl * w.nb;
-    const int64_t per = ((total + nch - 1) / nch + RS - 1) / RS * RS;
-    const int rbeg = (int)(per * ch), rend = (int)(per * ch + per < total ? per * ch + per : total);
-    const float* A = w.A + (size_t)y * w.A_lstride;
-    const float* A2 = TWO_A ? w.A2 + (size_t)y * w.A_lstride : nullptr;      // TWO_A: the A operand is the sum of two arrays (a template flag: the second
-                                                                               // staging set costs 32 registers the one-array launches need for a third workgroup per CU)
-    const float* B1 = BMODE == 4 ? nullptr : w.B1 + (size_t)y * w.B_lstride;
-    const float* B2 = w.B2 ? w.B2 + (size_t)y * w.B_lstride : nullptr;
-    const int* tap = BMODE == 3 ? w.tap + w.tap_off[y] : nullptr;      // BMODE 3: a tap table for every layer (the launcher checks)
-    const int row0A = w.row0A[y], row0B = w.row0B[y], ncol0 = zg * Np;
-    const unsigned uR = (unsigned)(Rl > 0 ? Rl : 1);
-    const bool multi = w.nb > 1;
-    const int gbias = zg == 0 ? w.gbias[y] : -1, goff = w.goff[y];
-    const int a_col = (tid % A4) * 4, a_row0 = tid / A4;
-    const int b_col = (tid % B4) * 4, b_row0 = tid / B4;
-    const int n = ncol0 + b_col;
-    const bool b_act = tid < BRS * B4;
-    const bool b_pad = n >= w.Nvalid;                           // zero padding columns of the operand (K padded to 16)
-    // B operand source of this thread's four columns
-    const float* bbase; int bstride; bool use_tap = false;
-    if (BMODE == 3) {
-        if (n < w.C) { bbase = B1 + n; bstride = w.C; }
-        else if (n < 2 * w.C) { bbase = B1 + (n - w.C); bstride = w.C; use_tap = true; }
-        else { bbase = w.hup + (b_pad ? 0 : n - 2 * w.C); bstride = w.Ap; }
-    } else if (BMODE == 4) { bbase = nullptr; bstride = 0; }
-    else { bbase = B1 + n; bstride = w.ldb; }
-    const ptrdiff_t b2off = (BMODE == 2) ? (B2 - B1) : 0;
-
-    f32x4 acc[MPW][NT];
-#pragma unroll
-    for (int a = 0; a < MPW; ++a)
-#pragma unroll
-        for (int b = 0; b < NT; ++b) acc[a][b] = (f32x4){0, 0, 0, 0};
-    float4 cs4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 ra[NA], ra2[NA], rb[NB], rb2[NB];
-    int tpv[NB];
-    int rbi[NB];                     // BMODE 4: sample class of the staged row (the one-hot is made when the stage goes to LDS)
-    unsigned okA = 0, okB = 0;       // bit k: staged row k is a real row.  The loaded registers are NOT touched before the stage goes to
-                                     // LDS: a select on a just-loaded value puts an s_waitcnt vmcnt in front of the matrix-core loop
-                                     // (measured with in-kernel stamps: 6-8 k cycles per stage in the skip 1x1 launch)
-
-    // Staging addresses.  A stage that lies inside one batch item and ends before rend -- all but the last one or two of a chunk -- takes
-    // the FAST form: one uniform base per operand and stage plus per-thread offsets fixed for the whole kernel.  The generic form below
-    // (row clamp, per-row batch split, 64-bit multiplies: ~650 instructions = 5.7 k cycles per stage in the dW1 launch, as long as its
-    // 176 MFMAs) only runs for the others.
-    const unsigned a_voff = (unsigned)a_row0 * (unsigned)w.lda + (unsigned)a_col, a_kstep = (unsigned)ARS * (unsigned)w.lda;
-    const unsigned b_voff = (unsigned)b_row0 * (unsigned)w.ldb + (unsigned)n, b_kstep = (unsigned)BRS * (unsigned)w.ldb;
-
-    // rows of a stage: r in [0,32); rows at or past rend are clamped to the last valid row and zeroed
-    auto rowsplit = [&](int rr, int& b, int& i) { if (multi) { b = (int)((unsigned)rr / uR); i = rr - b * (int)uR; } else { b = 0; i = rr; } };
-    auto stage_fast = [&](int rs, int& b0, int& i0) {       // uniform
-        rowsplit(rs, b0, i0);
-        return rs + RS <= rend && i0 + RS <= (int)uR;
-    };
-    // (every thread loads its row's tap entry, needed or not: a per-thread condition around the load becomes a branch with an
-    //  s_waitcnt behind each load, which also drains the operand loads issued just before -- the next stage's prefetch no longer
-    //  ran under the MFMAs)
-    auto taps = [&](int rs) {
-        int b0, i0;
-        if (stage_fast(rs, b0, i0)) {
-            const int* tst = tap + ((size_t)b0 * w.rowsB + row0B + i0);
-#pragma unroll
-            for (int k = 0; k < NB; ++k) { const int r = b_row0 + k * BRS; tpv[k] = tst[r < RS ? r : b_row0]; }
-            return;
-        }
-#pragma unroll
-        for (int k = 0; k < NB; ++k) {
-            const int r = b_row0 + k * BRS;
-            int rr = rs + r; rr = rr < rend ? rr : rend - 1;
-            int b, i; rowsplit(rr, b, i);
-            const int nloc = row0B + i;
-            tpv[k] = tap[(size_t)b * w.rowsB + nloc];
-        }
-    };
-    // Both forms only compute ADDRESSES (and the row masks) under the uniform branch; the loads themselves are issued once, behind it.
-    // [Loads in both arms made the merged values phi nodes: the copies at the join need the data, i.e. an s_waitcnt vmcnt(0) in front of
-    //  the matrix-core loop -- the whole memory latency exposed in every stage.]
-    auto fetch = [&](int rs) {
-        const float* pa[NA]; const float* pb[NB]; const int* pi[NB];
-        int b0, i0;
-        if (stage_fast(rs, b0, i0)) {
-            const float* Ast = A + ((size_t)b0 * w.rowsA + row0A + i0) * w.lda;
-#pragma unroll
-            for (int k = 0; k < NA; ++k) pa[k] = Ast + (k * a_kstep + a_voff);
-            okA = ~0u;
-            const size_t brow = (size_t)b0 * w.rowsB + row0B + i0;
-            const float* bsrc = BMODE == 3 ? bbase + (size_t)b0 * w.rowsB * bstride : B1 + brow * w.ldb;
-#pragma unroll
-            for (int k = 0; k < NB; ++k) {
-                const int r = b_row0 + k * BRS;
-                if (BMODE == 4) pi[k] = w.xc + brow + (r < RS ? r : b_row0);
-                else if (BMODE == 3) {
-                    const unsigned row = use_tap ? (unsigned)tpv[k] : (unsigned)(row0B + i0 + (r < RS ? r : b_row0));
-                    pb[k] = bsrc + __umul24(row, (unsigned)bstride);
-                } else pb[k] = bsrc + ((r < RS ? k * b_kstep : 0u) + b_voff);
-            }
-            okB = b_pad ? 0u : ~0u;
-        } else {
-            okA = 0; okB = 0;
-#pragma unroll
-            for (int k = 0; k < NA; ++k) {
-                const int r = a_row0 + k * ARS;
-                int rr = rs + r; const bool ok = rr < rend; rr = ok ? rr : rend - 1;
-                int b, i; rowsplit(rr, b, i);
-                pa[k] = A + (((size_t)b * w.rowsA + row0A + i) * w.lda + a_col);
-                okA |= ok ? 1u << k : 0u;
-            }
-#pragma unroll
-            for (int k = 0; k < NB; ++k) {
-                const int r = b_row0 + k * BRS;
-                int rr = rs + r; const bool ok = r < RS && rr < rend && !b_pad; rr = rr < rend ? rr : rend - 1;
-                int b, i; rowsplit(rr, b, i);
-                const size_t row = (size_t)b * w.rowsB + ((BMODE == 3 && use_tap) ? tpv[k] : row0B + i);
-                if (BMODE == 4) pi[k] = w.xc + row; else pb[k] = bbase + row * bstride;
-                okB |= ok ? 1u << k : 0u;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < NA; ++k) {
-            ra[k] = *(const float4*)pa[k];
-            if (TWO_A) ra2[k] = *(const float4*)(pa[k] + (A2 - A));
-        }
-        if (b_act) {
-#pragma unroll
-            for (int k = 0; k < NB; ++k) {
-                if (BMODE == 4) rbi[k] = *pi[k];
-                else {
-                    rb[k] = *(const float4*)pb[k];
-                    if (BMODE == 2) rb2[k] = *(const float4*)(pb[k] + b2off);
-                }
-            }
-        }
-    };
-    if (rbeg < rend) {
-        if (BMODE == 3) taps(rbeg);
-        fetch(rbeg);
-        if (BMODE == 3 && rbeg + RS < rend) taps(rbeg + RS);
-    }
-    const int g = lane >> 4, cl = lane & 15;
-    // staging registers -> LDS buffer `buf`
-    auto to_lds = [&](int buf) {
-        float* Ab = As + buf * BUF; float* Bb = Bs + buf * BUF;
-#pragma unroll
-        for (int k = 0; k < NA; ++k) {
-            float4 v = ra[k];
-            if (TWO_A) { v.x += ra2[k].x; v.y += ra2[k].y; v.z += ra2[k].z; v.w += ra2[k].w; }
-            { const bool ok = (okA >> k) & 1u; v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f; }     // (component-wise: a select between float4 objects makes the staging arrays addressable -> scratch)
-            cs4.x += v.x; cs4.y += v.y; cs4.z += v.z; cs4.w += v.w;
-            *(float4*)(Ab + (size_t)(a_row0 + k * ARS) * ldA + a_col) = v;
-        }
-        if (b_act) {
-#pragma unroll
-            for (int k = 0; k < NB; ++k) {
-                const int r = b_row0 + k * BRS;
-                if (r < RS) {
-                    float4 v;
-                    if (BMODE == 4) { const int dlt = rbi[k] - n; v = make_float4(dlt == 0 ? 1.f : 0.f, dlt == 1 ? 1.f : 0.f, dlt == 2 ? 1.f : 0.f, dlt == 3 ? 1.f : 0.f); }
-                    else v = rb[k];
-                    if (BMODE == 1) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-                    else if (BMODE == 2) { v.x *= rb2[k].x; v.y *= rb2[k].y; v.z *= rb2[k].z; v.w *= rb2[k].w; }
-                    { const bool ok = (okB >> k) & 1u; v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f; }
-                    *(float4*)(Bb + (size_t)r * ldB + b_col) = v;
-                }
-            }
-        }
-    };
-    auto ksteps = [&](int buf, int k0, int k1) {
-        const float* Ab = As + buf * BUF; const float* Bb = Bs + buf * BUF;
-#pragma unroll
-        for (int ks = k0; ks < k1; ++ks) {
-            float bfr[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) bfr[nt] = Bb[(4 * ks + g) * ldB + 16 * nt + cl];
-#pragma unroll
-            for (int mi = 0; mi < MPW; ++mi) {
-                const float a = Ab[(4 * ks + g) * ldA + 16 * (wave + 4 * mi) + cl];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[mi][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bfr[nt], acc[mi][nt], 0, 0, 0);
-            }
-        }
-    };
-    for (int rs = rbeg; rs < rend; rs += RS) {
-        to_lds(0);
-        __syncthreads();
-        // next stage's rows fly while the matrix cores work on this one
-        if (rs + RS < rend) {
-            fetch(rs + RS);
-            if (BMODE == 3 && rs + 2 * RS < rend) taps(rs + 2 * RS);       // gather rows of the stage after next
-        }
-        ksteps(0, 0, RS / 4);
-        __syncthreads();
-    }
-    float* out = w.slab + (size_t)ch * w.gstage;
-#pragma unroll
-    for (int mi = 0; mi < MPW; ++mi) {
-        const int mt = wave + 4 * mi;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int m = 16 * mt + 4 * (lane >> 4) + i, nn = 16 * nt + (lane & 15);
-                out[goff + (size_t)m * w.ldc + ncol0 + nn] = acc[mi][nt][i];
-            }
-        }
-    }
-    if (gbias >= 0) {          // bias grads: column sums of A, reduced over the ARS row groups of the staging layout
-        *(float4*)(sm + (size_t)a_row0 * Mp + a_col) = cs4;
-        __syncthreads();
-        if (tid < Mp) { float s = 0.f; for (int r = 0; r < ARS; ++r) s += sm[r * Mp + tid]; out[gbias + tid] = s; }
-    }
-}
-template <int BMODE, int MPW, int NT, bool TWO_A, int MINW = 1>
-__global__ __launch_bounds__(256, MINW) void k_wgrad3(Wg2 w, int nch) {          // MINW: waves per SIMD the register allocation must allow
-    wgrad3_body<BMODE, MPW, NT, TWO_A>(w, nch, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-
-#ifndef QPN_WGRAD_MINW
-#define QPN_WGRAD_MINW 2
-#endif
-template <int BMODE, int MPW, int NT, bool TWO_A>
-static void launch_wgrad3_k(const Wg2& w, int nch, size_t lds, hipStream_t stream) {
-    // the 256 x 64 one-array launches (post-net pair, skip 1x1) are 512 workgroups = two per CU: the allocation may use half a SIMD's registers
-    // (round 2 asked for a third of it -- three workgroups per CU; with the staging addresses hoisted that cap spills 80-150 B per lane)
-    constexpr int MINW = (MPW == 4 && NT == 4 && !TWO_A) ? QPN_WGRAD_MINW : 1;
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_wgrad3<BMODE, MPW, NT, TWO_A, MINW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((k_wgrad3<BMODE, MPW, NT, TWO_A, MINW>), dim3(nch, w.nlayers, w.ncol_groups), dim3(256), lds, stream, w, nch);
-}
-template <int BMODE, int MPW, int NT>
-static bool wgrad3_fits(const Wg2& w) {
-    const int Ng = w.N / w.ncol_groups;
-    if (w.bmode != BMODE) return false;
-    if (w.rowsB >= (1 << 24) || (int64_t)w.rowsB * (w.C > w.ldb ? w.C : w.ldb) >= (1ll << 32)) return false;      // 24 x 24-bit row x stride products of the fast staging path
-    if (w.M != 64 * MPW || Ng != 16 * NT || w.N % w.ncol_groups || (w.Nvalid != w.N && (w.ncol_groups != 1 || w.Nvalid % 4))) return false;
-    if (BMODE == 3 && (w.ldb != w.C || w.ncol_groups != 1 || (w.C % 4) || (w.Ap % 4) || !w.tap)) return false;
-    if (BMODE == 3) for (int l = 0; l < w.nlayers; ++l) if (w.tap_off[l] < 0) return false;      // the kernel loads taps unconditionally
-    return true;
-}
-template <int MPW, int NT> static constexpr size_t wgrad3_lds() { return (size_t)32 * (tr_ldt(64 * MPW) + tr_ldt(16 * NT)) * sizeof(float); }
-template <int BMODE, int MPW, int NT>
-static bool launch_wgrad3(const Wg2& w, int nch, hipStream_t stream) {
-    if (!wgrad3_fits<BMODE, MPW, NT>(w)) return false;
-    const size_t lds = wgrad3_lds<MPW, NT>();
-    if (w.A2) launch_wgrad3_k<BMODE, MPW, NT, true>(w, nch, lds, stream);
-    else launch_wgrad3_k<BMODE, MPW, NT, false>(w, nch, lds, stream);
-    return true;
-}
-static bool wgrad3_any(const Wg2& w, int nch, bool generic, hipStream_t stream) {
-    if (w.bmode == 4) return launch_wgrad3<4, 1, 8>(w, nch, stream) || launch_wgrad3<4, 1, 4>(w, nch, stream);      // causal table: C = 64, 128- or 64-class groups
-    if (generic) return false;
-    switch (w.bmode) {
-    case 3: return launch_wgrad3<3, 2, 11>(w, nch, stream) || launch_wgrad3<3, 2, 8>(w, nch, stream) || launch_wgrad3<3, 1, 7>(w, nch, stream);      // C = 64 (K = 176 / 128: aux at sample / frame rate), C = 32, n_aux 33..48
-    case 0: return launch_wgrad3<0, 1, 4>(w, nch, stream) || launch_wgrad3<0, 4, 4>(w, nch, stream);      // res / skip 1x1 at C = 64 (B = the gate product)
-    case 1: return launch_wgrad3<1, 4, 4>(w, nch, stream);                                                  // post-net (B rectified), 64-column groups
-    default: return false;
-    }
-}
-
-// smallest number of column groups g (N % g == 0, 4-column granularity kept) such that an M x N/g block fits a kernel's tile budget
-static int wgrad_col_groups(int M, int N) {
-    const int nt_max = M <= 64 ? 4 : M <= 128 ? 12 : 8;          // <1,4>, <2,12>, <4,8> / <4,4>
-    for (int g = 1; g <= N / 16; ++g)
-        if (N % g == 0 && (N / g) % 4 == 0 && (N / g + 15) / 16 <= nt_max) return g;
-    return 1;
-}
-
-static bool wgrad2_any(const Wg2& w, int nch, bool generic, hipStream_t stream) {
-    if (w.M > 256 && w.bmode != 4) {
-        // more output rows than a workgroup's tile budget (n_skipch / n_quantize > 256): blocks of 256 rows of dW, each a launch of its own -- the A operand's
-        // columns, the slab rows and the bias entries shift together
-        bool ok = true;
-        for (int m0 = 0; m0 < w.M && ok; m0 += 256) {
-            Wg2 sub = w;
-            sub.A = w.A + m0; if (w.A2) sub.A2 = w.A2 + m0;
-            sub.M = w.M - m0 < 256 ? w.M - m0 : 256;
-            for (int l = 0; l < w.nlayers; ++l) { sub.goff[l] = w.goff[l] + m0 * w.ldc; if (w.gbias[l] >= 0) sub.gbias[l] = w.gbias[l] + m0; }
-            sub.ncol_groups = wgrad_col_groups(sub.M, sub.N);
-            ok = wgrad2_any(sub, nch, generic, stream);
-        }
-        return ok;
-    }
-    if (wgrad3_any(w, nch, generic, stream)) return true;
-    switch (w.bmode) {
-    case 4: return false;                       // one-hot operand: k_wgrad3 only (the launcher checks the geometry first)
-    case 1: return wgrad2_mode<1>(w, nch, stream);
-    case 2: return wgrad2_mode<2>(w, nch, stream);
-    case 3: return wgrad2_mode<3>(w, nch, stream);
-    default: return wgrad2_mode<0>(w, nch, stream);
-    }
-}
 
 // ------------------------------------------------------------------------------------------ small backward kernels
 // Slabs -> flat gradient, walked in SLAB order: a wave reads 64 consecutive floats of each partial slab (the flat order is a
@@ -1345,7 +836,6 @@ int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k
     // QPN_STACK_QUEUE=0) keeps a launch per layer
     const bool stack_q = persist && k.stack_q_bwd && sq && sq->flags && p.qctl && qpn_stack_bwd_fits(p);
     const bool wr_summed = stack_q;
-    const size_t nDX = (size_t)B * N1 * C;
     // 16-row tiles (measured 11-15 % faster than 32 rows: twice the workgroups, a shorter last round)
     const size_t lds_post = (size_t)16 * (tr_lda(Q > S ? Q : S) + tr_lda(S)) * sizeof(float);
     const size_t lds_layer = (size_t)16 * (4 * tr_lda(C) + tr_lda(2 * C)) * sizeof(float);
@@ -1376,68 +866,21 @@ int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k
     const int nch = bw.nch;
     int nch_side_ = nch;      // time chunks (= partial slabs) of the skip / post-net contractions, which run on the side stream under the layer backward and are reduced by a launch of their own
     const bool gen = k.wgrad_generic;
-    Wg2 wbase; memset(&wbase, 0, sizeof(wbase));
-    wbase.slab = bw.slab; wbase.gstage = bw.gstage; wbase.nb = B; wbase.C = C; wbase.Ap = p.Ap; wbase.hup = p.HUP; wbase.tap = p.TAP; wbase.ncol_groups = 1;
+    // the five contraction records (train_wgrad_plan.h), from one view of the step; p.TH holds the gate product, as it is
+    const WgradView wv = tr_wgrad_view(p);
+    const WgradBufs wb = tr_wgrad_bufs(p, bw, p.TH);
+    // (wr_summed: the stack queue's tiles have replaced the own-row part of dXout by the sum of both parts -- store_dx in k_stack_bwd)
+    const WgradFlags wf = {wr_summed, k.post_pair, true, true};
     bool ok = true;
+    auto wgrad = [&](const Wg2& w, int chunks, hipStream_t st) { ok = ok && qpn_launch_wgrad(w, chunks, gen, st) == QPN_OK; };
     auto launch_skip_post = [&](hipStream_t st) {
-        Wg2 w = wbase;
-        {   // dWs_l = dS0^T g_l over the last BL rows; the shared skip-bias grad = colsum(dS0) (layer 0's block only)
-            w.nlayers = L;
-            w.A = bw.DS0; w.A2 = nullptr; w.A_lstride = 0; w.lda = S; w.M = S; w.rowsA = BL;
-            w.bmode = 0; w.B1 = p.TH; w.B2 = nullptr; w.B_lstride = nDX; w.ldb = C; w.N = C; w.Nvalid = C; w.rowsB = N1; w.ldc = C;      // (p.TH: the gate product, as it is)
-            w.ncol_groups = wgrad_col_groups(w.M, w.N);
-            for (int l = 0; l < L; ++l) { w.row0A[l] = 0; w.row0B[l] = N1 - BL; w.R[l] = BL; w.goff[l] = sl.g_ws[l]; w.gbias[l] = l == 0 ? sl.g_bs : -1; w.tap_off[l] = -1; }
-            ok = ok && wgrad2_any(w, nch_side_, gen, st);
-            qpn_prof_mark(PG_WGRAD_SKIP, st);
-        }
-        {   // post-net: dW2[q][s] = dlogits^T relu(Y0), dW1[o][s] = dY0^T relu(S0); N split into 64-column groups
-            w.nlayers = 1; w.A_lstride = w.B_lstride = 0; w.B2 = nullptr; w.bmode = 1; w.rowsA = w.rowsB = BL;
-            w.row0A[0] = w.row0B[0] = 0; w.R[0] = BL; w.tap_off[0] = -1;
-            // (S no multiple of 64: as few groups as fit a kernel's tile budget -- one group of all S columns fits none from S = 144 on, with Q or S rows > 128)
-            auto post_groups = [&](int M) { return S % 64 == 0 ? S / 64 : wgrad_col_groups(M, S); };
-            w.ncol_groups = post_groups(Q);
-            w.A = bw.dlogits; w.lda = Q; w.M = Q; w.B1 = p.Y0; w.ldb = S; w.N = S; w.Nvalid = S; w.ldc = S; w.goff[0] = sl.g_p2; w.gbias[0] = sl.g_bp2;
-            if (Q == S && k.post_pair) {
-                // both contractions have the same shape: ONE launch with the second as "layer 1" (strides = the distance between the arrays,
-                // modulo 2^64), 2 x 256 workgroups = two per CU, so one's staging runs under the other's MFMAs (alone, each launch put one
-                // workgroup on a CU: 35 % of every stage with the matrix cores idle, in-kernel stamps)
-                w.nlayers = 2;
-                w.A_lstride = (size_t)(bw.DY0 - bw.dlogits); w.B_lstride = (size_t)(p.S0 - p.Y0);
-                w.row0A[1] = w.row0B[1] = 0; w.R[1] = BL; w.tap_off[1] = -1; w.goff[1] = sl.g_p1; w.gbias[1] = sl.g_bp1;
-                ok = ok && wgrad2_any(w, nch_side_, gen, st);
-            } else {
-                ok = ok && wgrad2_any(w, nch_side_, gen, st);
-                w.A = bw.DY0; w.lda = S; w.M = S; w.B1 = p.S0; w.goff[0] = sl.g_p1; w.gbias[0] = sl.g_bp1; w.ncol_groups = post_groups(S);
-                ok = ok && wgrad2_any(w, nch_side_, gen, st);
-            }
-            qpn_prof_mark(PG_WGRAD_POST, st);
-        }
+        wgrad(wgrad_rec_skip(wv, sl, wb, wf), nch_side_, st);
+        qpn_prof_mark(PG_WGRAD_SKIP, st);
+        wgrad(wgrad_rec_post(wv, sl, wb, wf, 0), nch_side_, st);
+        if (!wgrad_post_paired(wv, wf)) wgrad(wgrad_rec_post(wv, sl, wb, wf, 1), nch_side_, st);
+        qpn_prof_mark(PG_WGRAD_POST, st);
     };
-    // ---- weight gradients that need the layer backward: dW1 (needs dZ_l), the residual 1x1 (needs dX_{l+1}), the causal table
-    auto build_w1 = [&]() {     // dW1_l = dZ_l^T [x_cur | x_past | aux],  bias1 grads = colsum(dZ_l)
-        Wg2 w = wbase;
-        w.A = bw.DZ; w.A2 = nullptr; w.A_lstride = (size_t)B * N1 * 2 * C; w.lda = 2 * C; w.M = 2 * C; w.rowsA = N1;
-        w.bmode = 3; w.B1 = p.X; w.B2 = nullptr; w.B_lstride = nDX; w.ldb = C; w.N = p.Ktp; w.Nvalid = p.hoist ? 2 * C : 2 * C + p.Ap; w.rowsB = N1;      // (aux hoist: no aux columns -- k_aux_tail)
-        w.nlayers = L; w.ldc = p.Ktp; w.ncol_groups = wgrad_col_groups(w.M, w.N);
-        for (int l = 0; l < L; ++l) {
-            const TrLayer& ly = p.layers[l];
-            w.row0A[l] = w.row0B[l] = ly.s_out; w.R[l] = N1 - ly.s_out; w.goff[l] = sl.g_w1[l]; w.gbias[l] = sl.g_b1[l];
-            w.tap_off[l] = ly.tap_off; w.dil[l] = ly.dilation;
-        }
-        return w;
-    };
-    auto build_wr = [&]() {     // dWr_l = dXout_l^T g_l (dXout_l = grad wrt X[l+1]); zero rows for the last layer
-        Wg2 w = wbase;
-        // (the stack queue's tiles have replaced the own-row part by the sum of both parts: store_dx in k_stack_bwd)
-        w.A = bw.DXA[0] + nDX; w.A2 = wr_summed ? nullptr : bw.DXB[0] + nDX; w.A_lstride = nDX; w.lda = C; w.M = C; w.rowsA = N1;
-        w.bmode = 0; w.B1 = p.TH; w.B2 = nullptr; w.B_lstride = nDX; w.ldb = C; w.N = C; w.Nvalid = C; w.rowsB = N1; w.ldc = C;      // (p.TH: the gate product, as it is)
-        w.nlayers = L; w.ncol_groups = wgrad_col_groups(w.M, w.N);
-        for (int l = 0; l < L; ++l) {
-            w.row0A[l] = w.row0B[l] = p.layers[l].s_out;
-            w.R[l] = l == L - 1 ? 0 : N1 - p.layers[l].s_out; w.goff[l] = sl.g_wr[l]; w.gbias[l] = sl.g_br[l]; w.tap_off[l] = -1; w.dil[l] = 0;
-        }
-        return w;
-    };
+    // ---- the weight gradients that need the layer backward -- dW1 (needs dZ_l), the residual 1x1 (needs dX_{l+1}), the causal table -- follow it below
     // the memory-bound reduction of the skip / post-net slabs (half of k_reduce_grad's 130 MB) runs on the side stream under the
     // matrix-bound layer backward instead of at the end of the step
     const bool early_reduce = overlap && bw.gdst && sl.g_early1 > sl.g_early0 && k.reduce_early;
@@ -1492,14 +935,6 @@ int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k
     }
     // the residual-1x1 weight gradient is a memory-bound 64 x 64 contraction: on the side stream next to the matrix-heavy dW1 launch
     // (measured 1028 -> 1052 steps/s; the causal table's contraction there as well: 1028 again, the side chain becomes the longer one)
-    auto build_causal = [&]() {      // causal conv table: dWc[tap][c][q] = (dX0)^T onehot(class of x[t-1+tap]); bias = colsum(dX0)
-        Wg2 w = wbase;
-        w.nlayers = 2; w.ncol_groups = Q / (Q % 64 == 0 ? 64 : 128);     /* 64-class groups: 512 workgroups, two per CU (29 -> 25 us) */ w.bmode = 4; w.xc = p.XC; w.B1 = w.B2 = nullptr; w.B_lstride = 0;
-        w.A = bw.DXA[0]; w.A2 = bw.DXB[0]; w.A_lstride = 0; w.lda = C; w.M = C; w.rowsA = N1;
-        w.N = Q; w.Nvalid = Q; w.rowsB = N1 + 1; w.ldb = 0; w.ldc = Q;
-        for (int tp = 0; tp < 2; ++tp) { w.row0A[tp] = 0; w.row0B[tp] = tp; w.R[tp] = N1; w.goff[tp] = sl.g_cw + tp * C * Q; w.gbias[tp] = tp == 0 ? sl.g_cb : -1; w.tap_off[tp] = -1; w.dil[tp] = 0; }
-        return w;
-    };
     // [One launch for everything that waits for the whole layer backward (dW1 + dWr + causal table + upsampling kernel as roles of one kernel)
     //  was tried: 1146 steps/s against 1205.  dW1 is a 247-register kernel (159 VGPRs + 88 accumulators): two of its workgroups fill a CU's
     //  register file, nothing runs beside them -- which is also why kernels launched next to it on the side stream start when it ends.]
@@ -1513,17 +948,17 @@ int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k
             if (bw.dh) qpn_launch_input_grad(p, bw, &ag, side);
             qpn_prof_mark(PG_GRAD_TAIL, side);
         }
-        if (wr_side) { ok = ok && wgrad2_any(build_wr(), nch, gen, side); qpn_prof_mark(PG_WGRAD_WR, side); }
+        if (wr_side) { wgrad(wgrad_rec_wr(wv, sl, wb, wf), nch, side); qpn_prof_mark(PG_WGRAD_WR, side); }
     }
     if (overlap) QPN_HIP(hipEventRecord(ev_join, side));
     qpn_prof_mark(PG_LAYER_BWD, stream);
-    ok = ok && wgrad2_any(build_w1(), nch, gen, stream);
+    wgrad(wgrad_rec_w1(wv, sl, wb, wf), nch, stream);
     qpn_prof_mark(PG_WGRAD, stream);
-    if (!wr_side) { ok = ok && wgrad2_any(build_wr(), nch, gen, stream); qpn_prof_mark(PG_WGRAD_WR, stream); }
+    if (!wr_side) { wgrad(wgrad_rec_wr(wv, sl, wb, wf), nch, stream); qpn_prof_mark(PG_WGRAD_WR, stream); }
     if (!overlap) launch_skip_post(stream);
-    if (sl.g_cw >= 0) ok = ok && wgrad2_any(build_causal(), nch, gen, stream);
+    if (sl.g_cw >= 0) wgrad(wgrad_rec_causal(wv, sl, wb), nch, stream);
     qpn_prof_mark(PG_WGRAD_CAUSAL, stream);
     if (overlap) { QPN_HIP(hipStreamWaitEvent(stream, ev_join, 0)); qpn_prof_mark(-1, stream); }      // joined BEFORE any early return: the caller's stream must own everything enqueued here
-    if (!ok) { qpn_set_error("weight-gradient tiles: unsupported geometry (n_resch <= 128 on this path; wider stacks take the GEMM path)"); return QPN_EINVAL; }
+    if (!ok) return QPN_EINVAL;      // (qpn_launch_wgrad has set the error text: a geometry no tile kernel takes)
     return qpn_launch_grad_tail(p, bw, &ag, stream, early_reduce, up_side);
 }

@@ -10,6 +10,7 @@
 #include "qpn_common.h"
 #include "train_plan.h"      // TR_MAXL, TR_EB_SLOTS, TrainSlabs, AuxGeom, TrainGemm, TrainKnobs: the host-only layout types, and the planner that fills them
 #include "adam_groups.h"     // QPN_ADAM_MAX_GROUPS, QPN_ADAM_FROZEN, AdamGroupTable: the Adam step's parameter groups (host-only too)
+#include "train_wgrad_plan.h"   // Wg2, WgradPick, the wgrad_rec_* record builders, TArgs: the weight-gradient contractions' host side (host-only as well)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -98,6 +99,22 @@ struct TrainBwd {            // backward-only buffers / maps (see train_bwd.hip)
     float* dh;                        // qpn_train_input_grad: [B][A][F] feature gradient of this backward, or nullptr (not armed: nothing extra is launched)
 };
 void qpn_launch_input_grad(const TrainParams& p, const TrainBwd& bw, const AuxGeom* ag, hipStream_t st);      // train_input_grad.hip
+
+// One weight-gradient contraction on the tile kernels (train_wgrad.hip): QPN_OK, or QPN_EINVAL with the error text set when no kernel instance fits the record
+int qpn_launch_wgrad(const Wg2& w, int nch, bool generic, hipStream_t stream);
+// what the record builders of train_wgrad_plan.h need of a step; gate: the array that holds the gate product
+static inline WgradView tr_wgrad_view(const TrainParams& p) {
+    WgradView v; memset(&v, 0, sizeof(v));
+    v.C = p.C; v.S = p.S; v.Q = p.Q; v.L = p.L; v.B = p.B; v.N1 = p.N1; v.BL = p.BL; v.Ap = p.Ap; v.Ktp = p.Ktp; v.hoist = p.hoist;
+    for (int l = 0; l < p.L; ++l) { const TrLayer& ly = p.layers[l]; v.s_out[l] = ly.s_out; v.tap_off[l] = ly.tap_off; v.dilation[l] = ly.dilation; v.adaptive[l] = ly.adaptive; }
+    return v;
+}
+static inline WgradBufs tr_wgrad_bufs(const TrainParams& p, const TrainBwd& bw, const float* gate) {
+    WgradBufs b;
+    b.DZ = bw.DZ; b.DXA = bw.DXA[0]; b.DXB = bw.DXB[0]; b.DS0 = bw.DS0; b.DY0 = bw.DY0; b.dlogits = bw.dlogits;
+    b.X = p.X; b.gate = gate; b.S0 = p.S0; b.Y0 = p.Y0; b.HUP = p.HUP; b.TAP = p.TAP; b.XC = p.XC; b.slab = bw.slab; b.gstage = bw.gstage;
+    return b;
+}
 
 
 // the (compact) kernel arguments of k_aux_proj / k_aux_tail (AuxGeom: train_plan.h)

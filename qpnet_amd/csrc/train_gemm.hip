@@ -271,18 +271,8 @@ __global__ __launch_bounds__(256) GEMM_WAVES void k_gemm_nn(GArgs g) {
 }
 
 // ------------------------------------------------------------------------------------------ time contraction (weight gradients)
-enum { BM_PLAIN = 0, BM_RELU = 1, BM_GATHER = 3 };
-struct TArgs {
-    int M, N;                        // valid rows / columns of dW
-    int nb, nsplit;
-    const float* a; const float* a2; long a_ls; int lda; int rowsA;      // A[t][m] (+ a2), per-layer stride, rows per batch item
-    const float* b1; long b_ls; int ldb; int rowsB;                      // B[t][n]
-    const float* hup; const int* tap; int C, Ap;                         // BM_GATHER: [x_cur | x_past | aux]
-    float* slab; long gstage; int ldc;
-    int row0A[TR_MAXL], row0B[TR_MAXL], R[TR_MAXL], goff[TR_MAXL], gbias[TR_MAXL], tap_off[TR_MAXL], dil[TR_MAXL];
-};
-
-// Staging as in k_wgrad3 (train_bwd.hip; in-kernel stamps there): a 16-row stage that lies inside one batch item and before the chunk's end
+// (TArgs, the BM_* operand modes and targs_of, which makes one from a contraction record: train_wgrad_plan.h)
+// Staging as in k_wgrad3 (train_wgrad.hip; in-kernel stamps there): a 16-row stage that lies inside one batch item and before the chunk's end
 // takes ONE uniform base per operand plus per-thread offsets; only ADDRESSES are computed under the uniform branch, the loads are issued once
 // behind it and the loaded registers are not touched (row masks, the two-array sum, ReLU) before the stage goes to LDS -- the first form selected
 // `row valid ? v : 0` right behind each load, i.e. five s_waitcnt vmcnt(0) and ~650 instructions of 64-bit row arithmetic in front of every
@@ -526,17 +516,6 @@ int qpn_launch_fwd_gemm(const TrainParams& p, const TrainGemm& w, hipStream_t st
 void qpn_launch_zero_dx(const TrainParams& p, const TrainBwd& bw, hipStream_t stream);
 int qpn_launch_grad_tail(const TrainParams& p, const TrainBwd& bw, const AuxGeom* ag, hipStream_t stream, bool early_done, bool up_done);
 
-// post-net weight gradients dW2 = dlogits^T relu(Y0), dW1 = dY0^T relu(S0) (+ bias column sums) into the `nch` partial slabs
-static void launch_post_wgrad_gemm(const TrainParams& p, const TrainBwd& bw, hipStream_t stream) {
-    TArgs a; memset(&a, 0, sizeof(a));
-    a.nb = p.B; a.nsplit = bw.nch; a.slab = bw.slab; a.gstage = bw.gstage; a.C = p.C; a.Ap = p.Ap;
-    a.M = p.Q; a.N = p.S; a.a = bw.dlogits; a.lda = p.Q; a.rowsA = p.BL; a.b1 = p.Y0; a.ldb = p.S; a.rowsB = p.BL; a.ldc = p.S;
-    a.R[0] = p.BL; a.goff[0] = bw.sl->g_p2; a.gbias[0] = bw.sl->g_bp2; a.tap_off[0] = -1;
-    launch_tn<BM_RELU>(a, 1, stream);
-    a.M = p.S; a.a = bw.DY0; a.lda = p.S; a.b1 = p.S0; a.goff[0] = bw.sl->g_p1; a.gbias[0] = bw.sl->g_bp1;
-    launch_tn<BM_RELU>(a, 1, stream);
-}
-
 int qpn_launch_bwd_gemm(const TrainParams& p, const TrainBwd& bw, const TrainGemm& w, hipStream_t stream) {
     const int C = p.C, S = p.S, Q = p.Q, L = p.L, B = p.B, N1 = p.N1, BL = p.BL;
     const size_t nDX = (size_t)B * N1 * C;
@@ -587,38 +566,17 @@ int qpn_launch_bwd_gemm(const TrainParams& p, const TrainBwd& bw, const TrainGem
         }
     }
     qpn_prof_mark(PG_LAYER_BWD, stream);
-    // ---- weight gradients: time contractions into `nch` partial slabs
-    TArgs t; memset(&t, 0, sizeof(t));
-    t.nb = B; t.nsplit = bw.nch; t.slab = bw.slab; t.gstage = bw.gstage; t.hup = p.HUP; t.tap = p.TAP; t.C = C; t.Ap = p.Ap;
-    {   // dW1_l = dZ_l^T [x_cur | x_past | aux]; bias1 grads = colsum(dZ_l)
-        TArgs a = t;
-        a.M = 2 * C; a.N = 2 * C + p.Ap; a.a = bw.DZ; a.a_ls = (long)B * N1 * 2 * C; a.lda = 2 * C; a.rowsA = N1;
-        a.b1 = p.X; a.b_ls = (long)nDX; a.ldb = C; a.rowsB = N1; a.ldc = p.Ktp;
-        for (int l = 0; l < L; ++l) {
-            const TrLayer& ly = p.layers[l];
-            a.row0A[l] = a.row0B[l] = ly.s_out; a.R[l] = N1 - ly.s_out; a.goff[l] = bw.sl->g_w1[l]; a.gbias[l] = bw.sl->g_b1[l];
-            a.tap_off[l] = ly.adaptive ? ly.tap_off : -1; a.dil[l] = ly.dilation;
-        }
-        launch_tn<BM_GATHER>(a, L, stream);
-    }
-    {   // dWr_l = dXout_l^T g_l
-        TArgs a = t;
-        a.M = C; a.N = C; a.a = bw.DXA[0] + nDX; a.a2 = bw.DXB[0] + nDX; a.a_ls = (long)nDX; a.lda = C; a.rowsA = N1;
-        a.b1 = w.G; a.b_ls = (long)nDX; a.ldb = C; a.rowsB = N1; a.ldc = C;
-        for (int l = 0; l < L; ++l) {
-            a.row0A[l] = a.row0B[l] = p.layers[l].s_out; a.R[l] = l == L - 1 ? 0 : N1 - p.layers[l].s_out;
-            a.goff[l] = bw.sl->g_wr[l]; a.gbias[l] = bw.sl->g_br[l]; a.tap_off[l] = -1;
-        }
-        launch_tn<BM_PLAIN>(a, L, stream);
-    }
-    {   // dWs_l = dS0^T g_l over the last BL rows; the shared skip-bias grad = colsum(dS0)
-        TArgs a = t;
-        a.M = S; a.N = C; a.a = bw.DS0; a.a_ls = 0; a.lda = S; a.rowsA = BL;
-        a.b1 = w.G; a.b_ls = (long)nDX; a.ldb = C; a.rowsB = N1; a.ldc = C;
-        for (int l = 0; l < L; ++l) { a.row0A[l] = 0; a.row0B[l] = N1 - BL; a.R[l] = BL; a.goff[l] = bw.sl->g_ws[l]; a.gbias[l] = l == 0 ? bw.sl->g_bs : -1; a.tap_off[l] = -1; }
-        launch_tn<BM_PLAIN>(a, L, stream);
-    }
-    launch_post_wgrad_gemm(p, bw, stream);
+    // ---- weight gradients: time contractions into `nch` partial slabs.  The records are the tile path's (train_wgrad_plan.h) with this path's flags: the
+    // gate product lives in TrainGemm::G, dXout comes in two parts, k_gemm_tn tiles N itself, the post-net contractions are two launches, and a fixed
+    // layer's x_past rows are row - dilation
+    const WgradView wv = tr_wgrad_view(p);
+    const WgradBufs wb = tr_wgrad_bufs(p, bw, w.G);
+    const WgradFlags wf = {false, false, false, false};
+    launch_tn<BM_GATHER>(targs_of(wgrad_rec_w1(wv, *bw.sl, wb, wf), bw.nch), L, stream);
+    launch_tn<BM_PLAIN>(targs_of(wgrad_rec_wr(wv, *bw.sl, wb, wf), bw.nch), L, stream);
+    launch_tn<BM_PLAIN>(targs_of(wgrad_rec_skip(wv, *bw.sl, wb, wf), bw.nch), L, stream);
+    launch_tn<BM_RELU>(targs_of(wgrad_rec_post(wv, *bw.sl, wb, wf, 0), bw.nch), 1, stream);
+    launch_tn<BM_RELU>(targs_of(wgrad_rec_post(wv, *bw.sl, wb, wf, 1), bw.nch), 1, stream);
     qpn_prof_mark(PG_WGRAD, stream);
     return qpn_launch_grad_tail(p, bw, nullptr, stream, false, false);
 }

@@ -223,7 +223,7 @@ inline TrainPlan train_plan(const Geom& g, const TrainKnobs& knobs, bool use_gem
     bias_grads(t.bias_p1, S, sl.g_bp1);
     for (int n = 0; n < Q; ++n) for (int k = 0; k < S; ++k) gs[tp_post2_src(g, k, n)] = sl.g_p2 + n * S + k;
     bias_grads(t.bias_p2, Q, sl.g_bp2);
-    // causal conv table: dW[c][q][tap] = sum_t dX0[t][c] * onehot(x[t-1+tap])[q] is one more time contraction (k_wgrad3 mode 4)
+    // causal conv table: dW[c][q][tap] = sum_t dX0[t][c] * onehot(x[t-1+tap])[q] is one more time contraction (k_wgrad3 mode 4, train_wgrad.hip; its record: wgrad_rec_causal)
     // when its tiles fit (C = 64, Q a multiple of 128); otherwise the LDS-histogram kernel owns it (gs stays -1)
     sl.g_cw = sl.g_cb = -1;
     if (C == 64 && Q % 128 == 0 && !use_gemm) {

@@ -32,13 +32,14 @@ BUDGET = {
     "k_layer_fwdILi1E": ("train_fwd.hip", 0, 5),          # five 16-row workgroups per CU must be co-resident
     "k_post_fwdILi1E": ("train_fwd.hip", 0, 5),
     "k_layer_bwdILi1E": ("train_bwd.hip", 0, 5),
-    "k_wgrad3ILi1ELi4ELi4ELb0ELi2EE": ("train_bwd.hip", 0, 2),      # post-net weight gradients (both in one launch: 512 workgroups, two per CU)
-    "k_wgrad3ILi0ELi4ELi4ELb0ELi2EE": ("train_bwd.hip", 0, 2),      # skip 1x1 (B = the gate product)
-    "k_wgrad3ILi3ELi2ELi11ELb0ELi1EE": ("train_bwd.hip", 0, 2),     # dW1: 159 VGPRs + 88 accumulators, two workgroups per CU
-    "k_wgrad3ILi3ELi2ELi8ELb0ELi1EE": ("train_bwd.hip", 0, 2),      # dW1 at K = 128 (aux 1x1 at frame rate)
+    "k_wgrad3ILi1ELi4ELi4ELb0ELi2EE": ("train_wgrad.hip", 0, 2),      # post-net weight gradients (both in one launch: 512 workgroups, two per CU)
+    "k_wgrad3ILi0ELi4ELi4ELb0ELi2EE": ("train_wgrad.hip", 0, 2),      # skip 1x1 (B = the gate product)
+    "k_wgrad3ILi3ELi2ELi11ELb0ELi1EE": ("train_wgrad.hip", 0, 2),     # dW1: 159 VGPRs + 88 accumulators, two workgroups per CU
+    "k_wgrad3ILi3ELi2ELi8ELb0ELi1EE": ("train_wgrad.hip", 0, 2),      # dW1 at K = 128 (aux 1x1 at frame rate)
     "k_aux_tail": ("train_bwd.hip", 0, 2),                             # 64 accumulator rows in registers at once, nothing in scratch
-    "k_wgrad3ILi0ELi1ELi4ELb0ELi1EE": ("train_bwd.hip", 0, 4),      # residual 1x1: one A array (dXout summed in place), one B array (the gate product); memory-bound: occupancy is what it lives on
-    "k_wgrad3ILi0ELi1ELi4ELb1ELi1EE": ("train_bwd.hip", 0, 4),      # ... with the two-part dXout of the per-layer backward launches
+    "k_wgrad3ILi0ELi1ELi4ELb0ELi1EE": ("train_wgrad.hip", 0, 4),      # residual 1x1: one A array (dXout summed in place), one B array (the gate product); memory-bound: occupancy is what it lives on
+    "k_wgrad3ILi0ELi1ELi4ELb1ELi1EE": ("train_wgrad.hip", 0, 4),      # ... with the two-part dXout of the per-layer backward launches
+    "k_wgrad2ILi3ELi4ELi8EE": ("train_wgrad.hip", 0, 1),            # the run-time-tiled kernel's widest instance (256 x 128 blocks of dW1): 223 VGPRs + 128 accumulators, one workgroup per CU
     "k_up_bwd": ("train_bwd.hip", 0, 2),                               # a row's 16 float4 words in registers at once, still nothing in scratch
     "k_adamILb": ("train_adam.hip", 0, 8),                             # all 8 instances of the optimiser step (clip x averaged weights x groups): memory-bound, full occupancy
     "k_grad_sumsq": ("train_adam.hip", 0, 8),                          # ... the norm's partial sums, without and with groups
