@@ -559,7 +559,7 @@ int qpn_train_profile_end(qpn_handle* h, float* h_ms, int n, void* stream);
 /* The draw of sampling decode on logits the caller provides: row r of the row-major (n_rows x Q) fp32 matrix d_logits is drawn with the
  * Philox counter (step0 + r, row) and key `seed` -- what a decode call with that seed picks at step step0 + r of batch row `row` when
  * these are its logits there -- into d_out[r].  One wave per row runs the device function the decode kernels' picks run (the default
- * draw for (1.0f, 0), the controlled one otherwise).  Q in {64,128,192,256} as for sampling decode; temperature / top_k as for
+ * draw for (1.0f, 0), the controlled one otherwise).  Q in {64,128,...,1024} (a multiple of 64) as for sampling decode; temperature / top_k as for
  * qpn_decode_sampling, checked (like every argument: n_rows >= 1, row >= 0, step0 >= 0, step0 + n_rows <= 2^31) before a device is
  * looked for.  For sampling from teacher-forced logits (qpn_train_forward, the logits output of qpn_decode).  Asynchronous on `stream`. */
 int qpn_sample_logits(const float* d_logits, int64_t n_rows, int Q, uint64_t seed, int row, int64_t step0, float temperature, int top_k,

@@ -166,7 +166,7 @@ struct Ctx {
 // where the one-CU kernels of the calls with per-row records keep the row's record (stage_row_draw, decode_dev.h): eight LDS words behind everything else the launch
 // uses, the dev stamps included (launch_one_cu sizes the launch's LDS to match)
 __device__ __forceinline__ int one_cu_rowd(const DecodeParams& p) { return p.o_stamp + (p.stamps ? 120 * QPN_NW : 0); }
-template <int ROW>
+template <int ROW, bool WIDE>
 __device__ __forceinline__ void run_slot(Ctx& c, int slot, int64_t t, float4 (&w)[4]) {
     const DecodeParams& p = *c.p; const UttView& u = *c.u;
     float* sm = SM; int* smi = SMI;
@@ -259,7 +259,7 @@ __device__ __forceinline__ void run_slot(Ctx& c, int slot, int64_t t, float4 (&w
         if (i >= 0 && u.logits) for (int k = lane; k < Q; k += 64) u.logits[(size_t)i * Q + k] = sm[p.o_lg + k];
         int next;
         if (i >= 0) {
-            if (p.mode != QPN_MODE_ARGMAX) bi = sample_pick<ROW>(p, (unsigned)u.row, one_cu_rowd(p), p.o_lg, Q, (unsigned)i, lane);
+            if (p.mode != QPN_MODE_ARGMAX) bi = sample_pick<ROW, WIDE>(p, (unsigned)u.row, one_cu_rowd(p), p.o_lg, Q, (unsigned)i, lane);
             next = bi;
             if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
             if (lane == 0) { u.out[i] = bi; if (live_put(p, u, (int)i, bi, c.creq)) smi[p.o_samp + 2] = 1; }      // stop on request: the workgroup leaves after the next step
@@ -281,19 +281,47 @@ __device__ __forceinline__ void run_slot(Ctx& c, int slot, int64_t t, float4 (&w
 
 #define QPN_KERNEL k_decode
 #define QPN_KERNEL_ROW false
+#define QPN_KERNEL_WIDE false
 #include "decode_slot_kernel.h"
 #undef QPN_KERNEL
 #undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
 #define QPN_KERNEL k_decode_r      // ... of the calls with per-row records
 #define QPN_KERNEL_ROW true
+#define QPN_KERNEL_WIDE false
 #include "decode_slot_kernel.h"
 #undef QPN_KERNEL
 #undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
 #define QPN_KERNEL k_decode_t      // ... of the calls with a draw track
 #define QPN_KERNEL_ROW 2
+#define QPN_KERNEL_WIDE false
 #include "decode_slot_kernel.h"
 #undef QPN_KERNEL
 #undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
+// ... and the three again for the sampled calls at n_quantize > 256: their picks run the wide draw (sample_pick<ROW, true>, decode_dev.h)
+#define QPN_KERNEL k_decode_w
+#define QPN_KERNEL_ROW false
+#define QPN_KERNEL_WIDE true
+#include "decode_slot_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
+#define QPN_KERNEL k_decode_wr
+#define QPN_KERNEL_ROW true
+#define QPN_KERNEL_WIDE true
+#include "decode_slot_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
+#define QPN_KERNEL k_decode_wt
+#define QPN_KERNEL_ROW 2
+#define QPN_KERNEL_WIDE true
+#include "decode_slot_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
 
 
 // ================================================================== specialised straight-line decode kernel
@@ -820,7 +848,8 @@ static int launch_one_cu(qpn_handle* h, DecodeParams p, const DecodeLaunch& l, h
                           : fast64 ? (resl ? k_decode_fast<64, 256, 256, 16, true> : k_decode_fast<64, 256, 256, 16, false>)
                           : fast32 ? (resl ? k_decode_fast<32, 32, 256, 16, true> : k_decode_fast<32, 32, 256, 16, false>) : nullptr;
     typedef void (*SlotKernel)(DecodeParams);
-    const SlotKernel interp = trackk ? k_decode_t : rowk ? k_decode_r : k_decode;
+    const bool wide = p.mode != QPN_MODE_ARGMAX && g.Q > 256;      // a sampled call at n_quantize > 256: the kernels whose pick is the wide draw (sample_pick<ROW, true>; never a straight-line kernel: those have Q = 256)
+    const SlotKernel interp = wide ? (trackk ? k_decode_wt : rowk ? k_decode_wr : k_decode_w) : trackk ? k_decode_t : rowk ? k_decode_r : k_decode;
     if (lds_bytes > 48 * 1024) QPN_HIP(hipFuncSetAttribute(fast ? (const void*)fast : (const void*)interp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     if (fast) hipLaunchKernelGGL(fast, dim3(n), dim3(QPN_NT), lds_bytes, stream, p, h->prog.fp);
     else hipLaunchKernelGGL(interp, dim3(n), dim3(QPN_NT), lds_bytes, stream, p);
@@ -958,7 +987,7 @@ extern "C" int qpn_decode_enqueue(qpn_handle* h, int B, int n_x, int64_t F, int6
     if (h->pending) { qpn_set_error("one decode in flight per handle: call qpn_decode_finish first"); return QPN_ESTATE; }
     if (B < 1 || n_x < 1 || F < 1 || !d_x || !d_h || !d_dfac || !h_n_samples || !d_out || maxd < 1) { qpn_set_error("bad decode arguments"); return QPN_EINVAL; }
     if (mode != QPN_MODE_ARGMAX && mode != QPN_MODE_SAMPLING) { qpn_set_error("mode must be QPN_MODE_ARGMAX or QPN_MODE_SAMPLING"); return QPN_EINVAL; }
-    if (mode == QPN_MODE_SAMPLING && (h->g.Q % 64 || h->g.Q > 256)) { qpn_set_error("sampling needs n_quantize in {64,128,192,256}"); return QPN_EINVAL; }
+    if (mode == QPN_MODE_SAMPLING && (h->g.Q < 64 || h->g.Q % 64 || h->g.Q > 1024)) { qpn_set_error("sampling needs n_quantize in {64,128,...,1024} (a multiple of 64)"); return QPN_EINVAL; }
     if (mode == QPN_MODE_SAMPLING && !h->samp_rows.empty() && (size_t)B != h->samp_rows.size()) {
         qpn_set_error("B = %d rows, but qpn_decode_row_sampling set n_rows = %zu records (one per batch row; n_rows = 0 switches them off)", B, h->samp_rows.size()); return QPN_EINVAL;
     }
@@ -1197,7 +1226,8 @@ __global__ __launch_bounds__(64) void k_sample_logits(const float* __restrict__ 
     for (int i = lane; i < Q; i += 64) SM[i] = src[i];
     __syncthreads();
     const unsigned step = step0 + blockIdx.x;
-    const int bi = (inv_temp != 1.0f || top_k != 0 || top_p != 1.0f || min_p != 0.0f)
+    const int bi = Q > 256 ? sample_wave_wide(0, Q, sample_uniform(seed, row, step), inv_temp, top_k, top_p, min_p, lane)      // (in place: the row's Q floats are all it needs)
+                   : (inv_temp != 1.0f || top_k != 0 || top_p != 1.0f || min_p != 0.0f)
                        ? sample_wave_ctl<true>(0, Q, sample_uniform(seed, row, step), inv_temp, top_k, top_p, min_p, lane)
                        : sample_wave(0, Q, seed, row, step, lane);
     if (lane == 0) out[blockIdx.x] = bi;
@@ -1209,7 +1239,7 @@ static int dev_ok() {
 }
 extern "C" int qpn_sample_logits_ex(const float* d_logits, int64_t n_rows, int Q, uint64_t seed, int row, int64_t step0, float temperature, int top_k,
                                     float top_p, float min_p, int64_t* d_out, void* stream) {
-    if (Q < 64 || Q % 64 || Q > 256) { qpn_set_error("sampling needs Q = n_quantize in {64,128,192,256}"); return QPN_EINVAL; }
+    if (Q < 64 || Q % 64 || Q > 1024) { qpn_set_error("sampling needs Q = n_quantize in {64,128,...,1024} (a multiple of 64)"); return QPN_EINVAL; }
     float inv; int k;
     int rc = sampling_controls(temperature, top_k, top_p, min_p, Q, &inv, &k); if (rc) return rc;
     if (!d_logits || !d_out || n_rows < 1 || row < 0 || step0 < 0 || step0 + n_rows > ((int64_t)1 << 31)) { qpn_set_error("bad arguments (n_rows >= 1, row >= 0, 0 <= step0, step0 + n_rows <= 2^31)"); return QPN_EINVAL; }

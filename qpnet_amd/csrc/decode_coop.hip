@@ -63,19 +63,47 @@ __device__ __forceinline__ void gather_vec(const u64* src, int n, unsigned tag, 
 
 #define QPN_KERNEL k_decode_coop
 #define QPN_KERNEL_ROW false
+#define QPN_KERNEL_WIDE false
 #include "decode_coop_kernel.h"
 #undef QPN_KERNEL
 #undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
 #define QPN_KERNEL k_decode_coop_r      // ... of the calls with per-row records
 #define QPN_KERNEL_ROW true
+#define QPN_KERNEL_WIDE false
 #include "decode_coop_kernel.h"
 #undef QPN_KERNEL
 #undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
 #define QPN_KERNEL k_decode_coop_t      // ... of the calls with a draw track
 #define QPN_KERNEL_ROW 2
+#define QPN_KERNEL_WIDE false
 #include "decode_coop_kernel.h"
 #undef QPN_KERNEL
 #undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
+// ... and the three again for the sampled calls at n_quantize > 256: their picks run the wide draw (sample_pick<ROW, true>, decode_dev.h)
+#define QPN_KERNEL k_decode_coop_w
+#define QPN_KERNEL_ROW false
+#define QPN_KERNEL_WIDE true
+#include "decode_coop_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
+#define QPN_KERNEL k_decode_coop_wr
+#define QPN_KERNEL_ROW true
+#define QPN_KERNEL_WIDE true
+#include "decode_coop_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
+#define QPN_KERNEL k_decode_coop_wt
+#define QPN_KERNEL_ROW 2
+#define QPN_KERNEL_WIDE true
+#include "decode_coop_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
 
 // ------------------------------------------------------------------------------------------ host side
 // l.rows utterances from l.first on (the kernel's b0), G workgroups each: the caller's launches hold no more than are resident together (one workgroup per CU)
@@ -102,7 +130,9 @@ int qpn_launch_decode_coop(qpn_handle* h, DecodeParams p, const DecodeLaunch& l,
     const size_t lds_bytes = (size_t)lds * sizeof(float);
     if (lds_bytes > 160 * 1024) { qpn_set_error("cooperative decode: %zu KiB of step state per workgroup exceed LDS (use more workgroups per utterance)", lds_bytes >> 10); return QPN_EINVAL; }
     typedef void (*CoopKernel)(DecodeParams, FastParams, CoopParams, int);
-    const CoopKernel kfn = p.mode == QPN_MODE_SAMPLING_TRACK ? k_decode_coop_t : p.mode == QPN_MODE_SAMPLING_ROW ? k_decode_coop_r : k_decode_coop;
+    const bool wide = p.mode != QPN_MODE_ARGMAX && Q > 256;      // a sampled call at n_quantize > 256: the kernels whose pick is the wide draw (sample_pick<ROW, true>)
+    const CoopKernel kfn = wide ? (p.mode == QPN_MODE_SAMPLING_TRACK ? k_decode_coop_wt : p.mode == QPN_MODE_SAMPLING_ROW ? k_decode_coop_wr : k_decode_coop_w)
+                         : p.mode == QPN_MODE_SAMPLING_TRACK ? k_decode_coop_t : p.mode == QPN_MODE_SAMPLING_ROW ? k_decode_coop_r : k_decode_coop;
     QPN_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     QPN_HIP(hipMemsetAsync(h->d_xch, 0, xwords * sizeof(unsigned long long), stream));      // tags, rings, abort flag
     hipLaunchKernelGGL(kfn, dim3(G, l.rows), dim3(COOP_NT), lds_bytes, stream, p, d.fp, c, l.first);

@@ -2,6 +2,7 @@
 // k_decode_coop_r, the kernel of the calls with per-row sampling records (QPN_KERNEL_ROW true).  Textual inclusion for the reason given in decode_coopb_kernel.h.
 __global__ __launch_bounds__(COOP_NT) void QPN_KERNEL(DecodeParams p, FastParams f, CoopParams c, int b0) {
     constexpr int ROW = QPN_KERNEL_ROW;      // (false, true, or 2: the kernel of the calls with a draw track -- sample_pick, decode_dev.h)
+    constexpr bool WIDE = QPN_KERNEL_WIDE;   // (true: the kernels of the sampled calls at n_quantize > 256 -- sample_pick, decode_dev.h)
     float* sm = SM; int* smi = SMI;
     const int gidx = blockIdx.x, b = b0 + blockIdx.y;
     const UttView u = make_view(p, p.utts[b]);
@@ -200,7 +201,7 @@ __global__ __launch_bounds__(COOP_NT) void QPN_KERNEL(DecodeParams p, FastParams
             if (i >= 0 && u.logits && gidx == 0) for (int k = lane; k < Q; k += 64) u.logits[(size_t)i * Q + k] = sm[o_lg + k];
             int next;
             if (i >= 0) {
-                if (p.mode != QPN_MODE_ARGMAX) bi = sample_pick<ROW>(p, (unsigned)u.row, o_rd, o_lg, Q, (unsigned)i, lane);
+                if (p.mode != QPN_MODE_ARGMAX) bi = sample_pick<ROW, WIDE>(p, (unsigned)u.row, o_rd, o_lg, Q, (unsigned)i, lane);
                 next = bi;
                 if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
                 if (lane == 0 && gidx == 0) {

@@ -195,19 +195,47 @@ __device__ __forceinline__ float close_elem(const float* P, int r, int n) {
 // Waves 4..7 EXCHANGE: tags and tap distances, layer 0's input, the aux terms, every publish and every gather.
 #define QPN_KERNEL k_decode_coopb
 #define QPN_KERNEL_ROW false
+#define QPN_KERNEL_WIDE false
 #include "decode_coopb_kernel.h"
 #undef QPN_KERNEL
 #undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
 #define QPN_KERNEL k_decode_coopb_r      // ... of the calls with per-row records
 #define QPN_KERNEL_ROW true
+#define QPN_KERNEL_WIDE false
 #include "decode_coopb_kernel.h"
 #undef QPN_KERNEL
 #undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
 #define QPN_KERNEL k_decode_coopb_t      // ... of the calls with a draw track
 #define QPN_KERNEL_ROW 2
+#define QPN_KERNEL_WIDE false
 #include "decode_coopb_kernel.h"
 #undef QPN_KERNEL
 #undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
+// ... and the three again for the sampled calls at n_quantize > 256: their picks run the wide draw (sample_pick<ROW, true>, decode_dev.h)
+#define QPN_KERNEL k_decode_coopb_w
+#define QPN_KERNEL_ROW false
+#define QPN_KERNEL_WIDE true
+#include "decode_coopb_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
+#define QPN_KERNEL k_decode_coopb_wr
+#define QPN_KERNEL_ROW true
+#define QPN_KERNEL_WIDE true
+#include "decode_coopb_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
+#define QPN_KERNEL k_decode_coopb_wt
+#define QPN_KERNEL_ROW 2
+#define QPN_KERNEL_WIDE true
+#include "decode_coopb_kernel.h"
+#undef QPN_KERNEL
+#undef QPN_KERNEL_ROW
+#undef QPN_KERNEL_WIDE
 
 // ------------------------------------------------------------------------------------------ host side
 // geometries this kernel takes: 8 channels per workgroup make the gate tile; S / G and Q / G rows fit their tiles; K = 256 or 512 chunks trees
@@ -256,7 +284,8 @@ int qpn_launch_decode_coopb(qpn_handle* h, DecodeParams p, const DecodeLaunch& l
     c.dev_nostream = getenv("QPN_COOPB_NOSTREAM") ? 1 : 0; c.dev_nocheck = getenv("QPN_COOPB_NOCHECK") ? 1 : 0;
 #endif
     typedef void (*CoopbKernel)(const DecodeParams, const CoopbParams);
-    const CoopbKernel kfn = trackk ? k_decode_coopb_t : rowk ? k_decode_coopb_r : k_decode_coopb;
+    const bool wide = p.mode != QPN_MODE_ARGMAX && Q > 256;      // a sampled call at n_quantize > 256: the kernels whose pick is the wide draw (sample_pick<ROW, true>)
+    const CoopbKernel kfn = wide ? (trackk ? k_decode_coopb_wt : rowk ? k_decode_coopb_wr : k_decode_coopb_w) : trackk ? k_decode_coopb_t : rowk ? k_decode_coopb_r : k_decode_coopb;
     QPN_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     QPN_HIP(hipMemsetAsync(h->d_xch, 0, xwords * sizeof(unsigned long long), stream));      // tags, rings, abort flag
 #ifdef QPN_TESTING

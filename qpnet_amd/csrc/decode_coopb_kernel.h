@@ -4,6 +4,7 @@
 // allocation) and default calls ran 0.65 % slower; included, k_decode_coopb is instruction for instruction the kernel it was before the second one existed.
 __global__ __launch_bounds__(CBB_NT) void QPN_KERNEL(const DecodeParams p, const CoopbParams c) {
     constexpr int ROW = QPN_KERNEL_ROW;      // (false, true, or 2: the kernel of the calls with a draw track -- sample_pick, decode_dev.h)
+    constexpr bool WIDE = QPN_KERNEL_WIDE;   // (true: the kernels of the sampled calls at n_quantize > 256 -- sample_pick, decode_dev.h)
     float* sm = SM; int* smi = SMI;
     const int w = blockIdx.x, grp = blockIdx.y;
     const int wblk = (int)(c.base4 + (long long)w * c.per_w);    // float4 offset of my fragments (relative to the buffer descriptor's base)
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(CBB_NT) void QPN_KERNEL(const DecodeParams p, const
             if (i >= 0 && u.logits && w == 0) for (int q = lane; q < Q; q += 64) u.logits[(size_t)i * Q + q] = sm[o_lg + k * Q + q];
             int next;
             if (i >= 0) {
-                if (p.mode != QPN_MODE_ARGMAX) bi = sample_pick<ROW>(p, (unsigned)u.row, o_rd + RDW * k, o_lg + k * Q, Q, (unsigned)i, lane);
+                if (p.mode != QPN_MODE_ARGMAX) bi = sample_pick<ROW, WIDE>(p, (unsigned)u.row, o_rd + RDW * k, o_lg + k * Q, Q, (unsigned)i, lane);
                 next = bi;
                 if (u.teacher) { const int64_t sv = u.teacher[i] % Q; next = (int)(sv < 0 ? sv + Q : sv); }
                 if (lane == 0 && w == 0) {

@@ -152,7 +152,7 @@ __device__ __forceinline__ void st_agent(float* p, float v) {
 // ---------------------------------------------------------------- sampling mode (reference qpnet.py:507-510)
 // softmax + categorical draw by inverse CDF with a counter-based generator (Philox4x32-10, counter = (step, row),
 // key = seed), in the fixed order of DESIGN.md §3 so that the CPU oracle reproduces every draw bit for bit.
-// (Parity with the reference's torch.Generator stream is statistical only.)  One wave, Q = 64 * per, per <= 4.
+// (Parity with the reference's torch.Generator stream is statistical only.)  One wave, Q = 64 * per: per <= 4 here, in registers; per = 5..16 in sample_wave_wide below, the same arithmetic on weights kept in LDS.
 __device__ __forceinline__ unsigned philox_first(unsigned c0, unsigned c1, unsigned k0, unsigned k1) {
     unsigned c2 = 0, c3 = 0;
 #pragma unroll
@@ -326,6 +326,99 @@ __device__ __forceinline__ int sample_wave_ctl(int o_lg, int Q, float u, float i
     const unsigned long long any = __builtin_amdgcn_ballot_w64(hi >= 0);
     return any ? __builtin_amdgcn_readlane(hi, 63 - __builtin_clzll(any)) : Q - 1;
 }
+// ---------------------------------------------------------------- the wide draw: Q = 64 * per with per in 5..16 (n_quantize 320..1024)
+// The same arithmetic as sample_wave_u / sample_wave_ctl / nucleus_cut, in the same order, for the rows whose lanes own more classes than the register
+// form above carries: `per` is a run-time count here and the lane's weights live in LDS -- IN PLACE of its logits.  Lane i reads and writes the slots per*i .. per*i+per-1
+// only, so no other lane's data is touched and no barrier is needed; every caller has copied the logits out (u.logits) before it picks, and every producer rewrites all Q
+// slots before the next pick.  No array is indexed at run time (that would be scratch memory): the draw holds a handful of registers whatever `per` is, and asks for
+// no LDS beyond the Q floats of the logits (decode_program's layout, the cooperative kernels' sizes and k_sample_logits' Q * 4 bytes are what they were).
+// A kept class always has a weight > 0 (qexp clamps its argument at -87: the smallest weight is about 2^-126, a normal float) and a class outside the kept set holds 0.0f,
+// so "kept" is the weight's bit pattern being non-zero and no second array of flags is needed.
+// The order-free passes (maximum, counts, forming the weights) visit a lane's slots rotated by rot = per * lane / 64: at per = 8 and 16 the 64 lanes then hit 64 different
+// LDS banks (straight, lane * per + j puts them on 8 or 4).  The ordered passes (lane sums left to right, the running sum of the pick) cannot.
+__device__ __forceinline__ int wide_rot(int j, int rot, int per) { const int r = j + rot; return r >= per ? r - per : r; }
+__device__ __forceinline__ float wide_lane_tree(float a) {      // nucleus_mass's balanced tree over the 64 lane sums
+    a = a + dpp_f<0xB1>(a); a = a + dpp_f<0x4E>(a); a = a + dpp_f<0x141>(a); a = a + dpp_f<0x140>(a);
+    return (rl_f(a, 0) + rl_f(a, 16)) + (rl_f(a, 32) + rl_f(a, 48));
+}
+// S(w) for the weight whose bit pattern is `cand`, over the weights at w[0 .. per-1] of every lane
+__device__ __forceinline__ float wide_mass(const float* w, int per, unsigned cand) {
+    const float e0 = w[0];
+    float a = __float_as_uint(e0) >= cand ? e0 : 0.0f;
+    for (int j = 1; j < per; ++j) { const float e = w[j]; a = a + (__float_as_uint(e) >= cand ? e : 0.0f); }
+    return wide_lane_tree(a);
+}
+// how many weights of the row reach `cand` (bit patterns; wave-uniform)
+__device__ __forceinline__ int wide_count(const float* w, int per, int rot, unsigned cand) {
+    int cnt = 0;
+    for (int j = 0; j < per; ++j) cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(__float_as_uint(w[wide_rot(j, rot, per)]) >= cand));
+    return cnt;
+}
+// invT == 1, k == 0, top_p == 1, min_p == 0 is the default draw (sample_wave_u's bits: every class kept, the fall-back pick Q - 1)
+__device__ __forceinline__ int sample_wave_wide(int o_lg, int Q, float u, float invT, int k, float top_p, float min_p, int lane) {
+    const int per = Q >> 6;
+    float* w = SM + o_lg + lane * per;
+    const int rot = (lane * per) >> 6;
+    float m = -INFINITY;
+    for (int j = 0; j < per; ++j) m = fmaxf(m, w[wide_rot(j, rot, per)]);
+    m = fmaxf(m, dpp_f<0xB1>(m)); m = fmaxf(m, dpp_f<0x4E>(m)); m = fmaxf(m, dpp_f<0x124>(m)); m = fmaxf(m, dpp_f<0x128>(m));
+    m = fmaxf(fmaxf(rl_f(m, 0), rl_f(m, 16)), fmaxf(rl_f(m, 32), rl_f(m, 48)));
+    unsigned thr = 0u;              // K = { key >= thr }: key 0 keeps every class
+    if (k > 0 && k < Q) {
+        for (int bit = 31; bit >= 0; --bit) {
+            const unsigned cand = thr | (1u << bit);
+            int cnt = 0;
+            for (int j = 0; j < per; ++j) cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(sample_key(w[wide_rot(j, rot, per)]) >= cand));
+            if (cnt >= k) thr = cand;
+            if (cnt == k) break;
+        }
+    }
+    for (int j = 0; j < per; ++j) {     // logits -> weights, with the min_p cut (min_p == 0 cuts nothing: every weight is >= 0)
+        const int s = wide_rot(j, rot, per);
+        const float l = w[s];
+        float e = sample_key(l) >= thr ? qexp((l - m) * invT) : 0.0f;
+        e = e >= min_p ? e : 0.0f;
+        w[s] = e;
+    }
+    if (top_p < 1.0f) {             // nucleus_cut's search, the weights read from LDS
+        const float target = top_p * wide_mass(w, per, 0u);
+        unsigned pthr = 0u;
+        int c_thr = wide_count(w, per, rot, 1u), c_rej = 0;
+        for (int bit = 30; bit >= 0 && c_thr - c_rej > 1; --bit) {
+            const unsigned cand = pthr | (1u << bit);
+            const int cnt = wide_count(w, per, rot, cand);
+            const bool stays = cnt == c_thr || (cnt != c_rej && wide_mass(w, per, cand) >= target);
+            if (stays) { pthr = cand; c_thr = cnt; } else c_rej = cnt;
+        }
+        for (int j = 0; j < per; ++j) { const int s = wide_rot(j, rot, per); const float e = w[s]; if (__float_as_uint(e) < pthr) w[s] = 0.0f; }
+    }
+    float a = w[0];
+    for (int j = 1; j < per; ++j) a = a + w[j];
+    float v = a;
+    { const float up = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, true)); if (lane >= 1) v = v + up; }
+    for (int d = 2; d < 64; d <<= 1) { const float up = __shfl_up(v, d); if (lane >= d) v = v + up; }
+    const float total = rl_f(v, 63);
+    float c = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, true));
+    if (lane == 0) c = 0.0f;
+    const float th = u * total;
+    int idx = 0x7fffffff, hi = -1;      // first kept class past the threshold / highest kept class, of this lane
+    for (int j = 0; j < per; ++j) {
+        const float e = w[j];
+        c = c + e;
+        if (__float_as_uint(e) != 0u) { hi = lane * per + j; if (idx == 0x7fffffff && c > th) idx = lane * per + j; }
+    }
+#define QPN_IMIN(CTRL) { const int o_ = __builtin_amdgcn_update_dpp(0x7fffffff, idx, CTRL, 0xf, 0xf, false); idx = o_ < idx ? o_ : idx; }
+    QPN_IMIN(0xB1) QPN_IMIN(0x4E) QPN_IMIN(0x124) QPN_IMIN(0x128)
+#undef QPN_IMIN
+    {
+        const int i0 = __builtin_amdgcn_readlane(idx, 0), i1 = __builtin_amdgcn_readlane(idx, 16), i2 = __builtin_amdgcn_readlane(idx, 32), i3 = __builtin_amdgcn_readlane(idx, 48);
+        const int a01 = i0 < i1 ? i0 : i1, a23 = i2 < i3 ? i2 : i3;
+        idx = a01 < a23 ? a01 : a23;
+    }
+    if (idx != 0x7fffffff) return idx;
+    const unsigned long long any = __builtin_amdgcn_ballot_w64(hi >= 0);
+    return any ? __builtin_amdgcn_readlane(hi, 63 - __builtin_clzll(any)) : Q - 1;
+}
 struct UttView {            // per-utterance pointers derived from kernel-argument bases (global address space)
     const float* pproj; const void* dfac; const int* known; const int64_t* teacher; int64_t* out; float* logits; float* ring;
     int n_pad, n0, n_samples, d_is_f32, row;
@@ -410,9 +503,25 @@ __device__ __forceinline__ FrameDraw frame_draw_lds(int o_rd, unsigned step) {
     o.top_p = __int_as_float(__builtin_amdgcn_readfirstlane(r[2])); o.min_p = __int_as_float(__builtin_amdgcn_readfirstlane(r[3]));
     return o;
 }
-template <int ROW>
+// WIDE: the kernels of the sampled calls at Q > 256 (k_decode_w*, k_decode_coop_w*, k_decode_coopb_w*: the same bodies included three more times).  The launchers test
+// Q > 256 once, on the host, where they choose the kernel; those kernels' picks run sample_wave_wide and nothing else.  Kernels of their own for the reason given above for
+// ROW: behind one more compare inside the existing kernels, even the LDS-walking draw cost them scratch memory (the interpreter 24 -> 76 bytes per lane, the batched
+// cooperative kernel 12 -> 28) and the per-utterance cooperative kernel six registers; with WIDE = false the source is what it was.  A call that set no control
+// carries the values that switch every control off (1.0f, 0, 1.0f, 0.0f), so the wide kernels read them whatever the mode.
+template <int ROW, bool WIDE = false>
 __device__ __forceinline__ int sample_pick(const DecodeParams& p, unsigned row, int o_rd, int o_lg, int Q, unsigned step, int lane) {
-    if constexpr (ROW == 2) {
+    if constexpr (WIDE) {
+        if constexpr (ROW == 2) {
+            const RowDraw r = row_draw_lds(o_rd);
+            const FrameDraw d = frame_draw_lds(o_rd, step);
+            return sample_wave_wide(o_lg, Q, sample_uniform(row_seed(r), r.stream, step), d.inv_temp, d.top_k, d.top_p, d.min_p, lane);
+        } else if constexpr (ROW == 1) {
+            const RowDraw r = row_draw_lds(o_rd);
+            return sample_wave_wide(o_lg, Q, sample_uniform(row_seed(r), r.stream, step), r.inv_temp, r.top_k, r.top_p, r.min_p, lane);
+        } else {
+            return sample_wave_wide(o_lg, Q, sample_uniform(p.seed, row, step), p.inv_temp, p.top_k, p.top_p, p.min_p, lane);
+        }
+    } else if constexpr (ROW == 2) {
         const RowDraw r = row_draw_lds(o_rd);
         const FrameDraw d = frame_draw_lds(o_rd, step);
         return sample_wave_ctl<true>(o_lg, Q, sample_uniform(row_seed(r), r.stream, step), d.inv_temp, d.top_k, d.top_p, d.min_p, lane);

@@ -2,6 +2,7 @@
 // calls with per-row sampling records (QPN_KERNEL_ROW true).  Textual inclusion for the reason given in decode_coopb_kernel.h.
 __global__ __launch_bounds__(QPN_NT) void QPN_KERNEL(DecodeParams p) {
     constexpr int ROW = QPN_KERNEL_ROW;      // (false, true, or 2: the kernel of the calls with a draw track -- sample_pick, decode_dev.h)
+    constexpr bool WIDE = QPN_KERNEL_WIDE;   // (true: the kernels of the sampled calls at n_quantize > 256 -- sample_pick, decode_dev.h)
     float* sm = SM;
     int* smi = SMI;
     const UttView u = make_view(p, p.utts[blockIdx.x]);
@@ -44,9 +45,9 @@ __global__ __launch_bounds__(QPN_NT) void QPN_KERNEL(DecodeParams p) {
     }
     for (int64_t t = 1; t + 1 < Ttot; ++t) {
         for (int slot = 0; slot < p.n_slots; slot += 3) {
-            run_slot<ROW>(c, slot, t, w0);
-            run_slot<ROW>(c, slot + 1, t, w1);
-            run_slot<ROW>(c, slot + 2, t, w2);
+            run_slot<ROW, WIDE>(c, slot, t, w0);
+            run_slot<ROW, WIDE>(c, slot + 1, t, w1);
+            run_slot<ROW, WIDE>(c, slot + 2, t, w2);
         }
         if (c.stop) break;      // stopped on request at the previous step's publish point (this step has drained: its pick published nothing)
     }
