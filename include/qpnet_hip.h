@@ -512,6 +512,33 @@ int qpn_train_step_acc(qpn_handle* h, float* d_flat, int B, int64_t T, int64_t F
                        int loss_mode, double* h_loss, int* h_valid, float max_grad_norm, double* h_grad_norm,
                        float* d_ema, float ema_decay, float* d_acc, int micro, int micro_count, void* stream);
 
+/* Per-tensor training statistics (no reference counterpart; the loop a user writes is 3 x n_tensors torch.norm launches on views of the flat buffers): for every
+ * tensor t = elements [h_tensor_end[t-1], h_tensor_end[t]) of the flat vectors (h_tensor_end[-1] = 0; state_dict order is the layout of d_flat), one record
+ *   grad_sumsq     sum of (g_i / den)^2 over the tensor's FINITE gradient elements, den = d_grad_denominator[0] (the summed row count of a data-parallel or accumulated
+ *                  gradient: what the Adam launch divides by; must be > 0) or 1 when NULL;   grad_absmax: max |g_i / den| over them;   grad_nonfinite: the NaN / inf among them
+ *   weight_sumsq   sum of w_i^2 over the finite weights;   weight_absmax: max |w_i| over them
+ *   update_sumsq   sum of u_i^2, u_i = m_i / (sqrtf(v_i) / bc2_sqrt + eps) in the fp32 operations of the Adam kernel, bc2_sqrt that of update number `step`
+ * computed by two launches that only READ: the Adam launch leaves d_grad as it is, and d_m, d_v after it determine what it subtracted from the weights,
+ * (lr / bc1) * u_i -- sqrt(update_sumsq) * lr / bc1 with the lr of the tensor's group is the norm of the latest update, nothing of which was stored (bc1 = 1 - beta1^step,
+ * formed in fp64 and rounded once to fp32, as the launch forms it).  After a skipped update m and v are those of the last applied one: so is the record.
+ * Sums are fp64 (an fp32 square is exact in it) in ONE fixed order without atomics, a function of the table alone: the same bits from run to run, at any alignment
+ * of the four bases (16-byte loads where a base allows, four loads otherwise) and on every data-parallel rank.
+ * d_grad may be NULL: the gradient fields are 0 (d_grad_denominator is not looked at).  d_m and d_v may both be NULL: update_sumsq is 0; step, beta1, beta2, eps are ignored.
+ * The work-item list of the table and the partial records live on the handle; a call whose table equals the one the handle holds uploads nothing.
+ * A synchronous diagnostic call: it drains `stream` and fills h_out[n_tensors]; QPN_ESTATE while that stream is capturing.  It neither reads nor writes the status word,
+ * the applied-update count or any other training state, and no launch of a training step differs for it.
+ * Errors, checked before the device is looked at (also on a handle created without a GPU), QPN_EINVAL naming the argument: a NULL d_flat, h_tensor_end or h_out;
+ * n_tensors < 1 or > 2^20; h_tensor_end[0] < 1, h_tensor_end not strictly ascending, or its last entry not n; only one of d_m / d_v; with moments step < 1, a beta outside
+ * [0, 1), an eps that is NaN, infinite or negative.  A valid call without a GPU returns QPN_ENODEV. */
+typedef struct qpn_tensor_stat {
+    double grad_sumsq, weight_sumsq, update_sumsq;
+    float grad_absmax, weight_absmax;
+    int64_t grad_nonfinite;
+} qpn_tensor_stat;
+int qpn_tensor_stats(qpn_handle* h, const float* d_flat, const float* d_grad, const float* d_m, const float* d_v,
+                     int64_t n, int step, float beta1, float beta2, float eps, const float* d_grad_denominator,
+                     int n_tensors, const int64_t* h_tensor_end, qpn_tensor_stat* h_out, void* stream);
+
 /* Per-launch-group device timings of the training calls issued between begin and end (HIP events on `stream`; used by bench.py for
  * the roofline).  h_ms[QPN_PG_*] receives milliseconds.  While a profile is being taken a step runs on ONE stream, and every heavy
  * kernel is a group of its own: LAYER_FWD / LAYER_BWD = the residual stack (one work-queue launch each at n_resch 64), WGRAD = the

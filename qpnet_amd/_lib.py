@@ -30,6 +30,11 @@ class QpnCorpusSeg(C.Structure):    # qpn_corpus_seg: one segment of a batch row
     _fields_ = [("sample0", C.c_int64), ("frame0", C.c_int64), ("factor0", C.c_int64), ("n_samples", C.c_int32), ("n_frames", C.c_int32)]
 
 
+class QpnTensorStat(C.Structure):   # qpn_tensor_stat: one tensor's record (qpn_tensor_stats); train.TENSOR_STAT_DTYPE is the same 40 bytes for numpy
+    _fields_ = [("grad_sumsq", C.c_double), ("weight_sumsq", C.c_double), ("update_sumsq", C.c_double), ("grad_absmax", C.c_float), ("weight_absmax", C.c_float),
+                ("grad_nonfinite", C.c_int64)]
+
+
 class QpnError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libqpnet_hip error %d: %s" % (code, msg))
@@ -100,6 +105,7 @@ SYMBOLS = [
                                 _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _i, C.POINTER(C.c_double), C.POINTER(C.c_int),
                                 C.c_float, C.POINTER(C.c_double), _vp, C.c_float, _vp, _i, _i, _vp]),
     ("qpn_train_applied_updates", _i, [_vp, C.POINTER(C.c_int64), _vp]),
+    ("qpn_tensor_stats", _i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, C.c_float, C.c_float, C.c_float, _vp, _i, C.POINTER(C.c_int64), C.POINTER(QpnTensorStat), _vp]),
     ("qpn_train_stack_stats", _i, [_vp, C.POINTER(C.c_uint), _i, _vp]),
     ("qpn_train_early_bucket", _i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp]),
     ("qpn_train_early_first", _i64, [_vp]),

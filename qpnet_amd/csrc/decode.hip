@@ -709,7 +709,7 @@ extern "C" int qpn_create(const qpn_config* cfg, qpn_handle** out) {
 extern "C" void qpn_destroy(qpn_handle* h) {      // (every member may still be null)
     if (!h) return;
     if (h->device >= 0) {
-        void* bufs[] = {h->d_map, h->d_wpk, h->d_tasks, h->d_qb, h->d_bd, h->d_status, h->d_bias_src, h->d_pproj, h->d_ring, h->d_known, h->d_utts, h->d_xch, h->d_adam_table, h->d_rows, h->d_track};
+        void* bufs[] = {h->d_map, h->d_wpk, h->d_tasks, h->d_qb, h->d_bd, h->d_status, h->d_bias_src, h->d_pproj, h->d_ring, h->d_known, h->d_utts, h->d_xch, h->d_adam_table, h->d_stats, h->d_rows, h->d_track};
         for (void* b : bufs) if (b) (void)hipFree(b);
         qpn_train_destroy(h->train);
         if (h->ev0) (void)hipEventDestroy(h->ev0);

@@ -3,6 +3,7 @@
 #include "qpn_common.h"
 #include "decode_plan.h"
 #include "adam_groups.h"
+#include "train_stats_plan.h"
 
 struct TrainState;
 void qpn_train_destroy(TrainState* t);
@@ -84,6 +85,9 @@ struct qpn_handle {      // every member has an initialiser: qpn_create sets onl
     float adam_lr[QPN_ADAM_MAX_GROUPS] = {}, adam_wd[QPN_ADAM_MAX_GROUPS] = {};
     AdamGroupTable adam_table;                 // the normalised table the device holds (adam_groups.h)
     char* d_adam_table = nullptr;              // [seg_end int64 | block pairs 2 x int32 | seg_group int32]
+    // per-tensor statistics (qpn_tensor_stats, train_stats.hip): the plan of the caller's tensor table and its device copy, for the same reason on the handle
+    StatsPlan stats_plan;                      // train_stats_plan.h
+    char* d_stats = nullptr;                   // [items | partial records, one per item | records, one per tensor | first_item int32]
 };
 // what the launch plan needs to know of the kernels' own limits (decode_pipe.hip, decode_coopb.hip)
 bool qpn_pipe_supported(const Geom& g);

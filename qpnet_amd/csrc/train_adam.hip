@@ -51,13 +51,6 @@ __device__ __forceinline__ bool adam_group_values(const AdamGroupsArg* G, int2 b
     for (int k = 0; k < QPN_ADAM_MAX_GROUPS; ++k) if (q == k) { lr = G->lr[k]; wd = G->wd[k]; }
     return true;
 }
-// sum of 256 doubles held one per thread, in ONE fixed order: xor butterfly inside each wave (both partners add the same two values, so every lane ends with the same bits), the four wave sums through LDS
-__device__ __forceinline__ double block_sum_f64(double x, double* red) {
-    for (int sft = 32; sft >= 1; sft >>= 1) x += __shfl_xor(x, sft);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // The three switches are compile-time: an instance with one off is the kernel as it was before that feature (its arguments are dead there).
 // The device-side status word (sticky until the host reads it: a tap / target out of range, an abandoned stack launch) flags results that must not

@@ -233,6 +233,15 @@ __device__ __forceinline__ void tr_queue_entry_bwd(const TrainParams& p, int pos
 
 int qpn_num_cus();                                   // compute units of the current device (cached per device)
 
+// sum of 256 doubles held one per thread, in ONE fixed order: xor butterfly inside each wave (both partners add the same two values, so every lane ends with the same bits), the four wave sums through LDS
+// (train_adam.hip's norm and train_stats.hip's per-tensor sums)
+__device__ __forceinline__ double block_sum_f64(double x, double* red) {
+    for (int sft = 32; sft >= 1; sft >>= 1) x += __shfl_xor(x, sft);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 #define TR_GN_BLOCKS 256                             // gradient-norm clipping: the sum of squares leaves k_grad_sumsq as at most this many fp64 partial sums (one per thread of a clipping k_adam block)
 
 // parameter groups of the Adam launch (qpn_adam_groups; adam_groups.h): the segment table lives in device memory, the groups' values travel with the launch

@@ -18,6 +18,7 @@ communication.
 With --n_gpus N > 1 and no torchrun environment the entry point re-launches itself as N ranks (before any GPU call).
 """
 import argparse
+import json
 import logging
 import os
 import queue
@@ -337,6 +338,8 @@ def _train_args(update):
     p.add_argument("--iters", default=3000 if update else 200000, type=int)
     p.add_argument("--checkpoint_interval", default=10000, type=int)
     p.add_argument("--intervals", default=100, type=int)
+    p.add_argument("--stats_interval", default=0, type=int, metavar="N", help="every N iterations rank 0 appends the per-tensor statistics of the latest update (gradient, weight and "
+                   "update norms: FusedTrainer.tensor_stats, a synchronous call) as one JSON line to <expdir>/tensor_stats.jsonl; 0: off")
     p.add_argument("--seed", default=1, type=int)
     p.add_argument("--resume", default=None, nargs="?", type=str)
     p.add_argument("--n_gpus", default=1, type=int)
@@ -374,6 +377,10 @@ def run_train(argv=None, update=False):
     if max_gb is not None and not (max_gb > 0.0 and np.isfinite(max_gb)):
         raise SystemExit("--device_corpus_max_gb must be finite and > 0, got %r" % (max_gb,))
     device_corpus = {"max_bytes": None if max_gb is None else int(max_gb * 1e9)} if device_corpus else None
+    # (... and the report's: --stats_interval changes what is written next to the model, not the model)
+    stats_interval = args.__dict__.pop("stats_interval")
+    if stats_interval < 0:
+        raise SystemExit("--stats_interval must be >= 0, got %r" % (stats_interval,))
     if not (0.0 <= label_smoothing < 1.0):
         raise SystemExit("--label_smoothing must lie in [0, 1), got %r" % (label_smoothing,))
     if not (unvoiced_weight >= 0.0 and np.isfinite(unvoiced_weight)):
@@ -476,7 +483,8 @@ def run_train(argv=None, update=False):
             if trainer.micro_step == 0:         # the window closed (or a status error abandoned it: the iteration ends with it)
                 break
         total += time.time() - start
-        if (i + 1) % args.intervals == 0 or (i + 1) % args.checkpoint_interval == 0 or i + 1 == args.iters:
+        stats_due = stats_interval > 0 and (i + 1) % stats_interval == 0
+        if (i + 1) % args.intervals == 0 or (i + 1) % args.checkpoint_interval == 0 or i + 1 == args.iters or stats_due:
             last = trainer.flush_loss() if lagged else None
             if last is not None:
                 note_loss(last)
@@ -489,6 +497,10 @@ def run_train(argv=None, update=False):
                 if not (clipping and _is_non_finite_norm(e)):
                     raise
                 logging.warning("(iter:%d) %s" % (i + 1, e))
+        if stats_due and rank == 0 and trainer.step_count > 0 and trainer.micro_step == 0:
+            # per-tensor statistics of the latest applied update (behind the checks above: what a flagged step left is reported as what it is), one JSON line
+            with open(os.path.join(args.expdir, "tensor_stats.jsonl"), "a", encoding="utf-8") as sf:
+                sf.write(json.dumps({"iter": i + 1, "tensors": trainer.tensor_stats()}) + "\n")
         if (i + 1) % args.intervals == 0:
             if clipping:
                 # (a step that raised for a non-finite norm took the loss it would have returned with it: the average is over the losses that arrived)

@@ -790,6 +790,50 @@ def _ema_from_state_dict(model, sd):
     return torch.cat([sd[k].detach().reshape(-1).to(dev, torch.float32) for k in ref]).contiguous()
 
 
+# ---------------------------------------------------------------- per-tensor statistics (qpn_tensor_stats) shared by FusedTrainer and FlatAdam
+TENSOR_STAT_FIELDS = ("grad_norm", "weight_norm", "update_norm", "update_ratio", "grad_absmax", "weight_absmax", "grad_nonfinite")
+
+
+def _tensor_lrs(n_tensors, positions, lrs):
+    """learning rate of every tensor (model.parameters() order) from the groups' values and positions[g], the tensors group g holds; 0.0: in no group (frozen)"""
+    out = [0.0] * n_tensors
+    for ps, lr in zip(positions, lrs):
+        for pos in ps:
+            out[pos] = lr
+    return out
+
+
+def _tensor_stats(who, model, w, g, den_ptr, m, v, step, betas, eps, tensor_lrs):
+    """One qpn_tensor_stats call over the flat buffers of `model` and its result as an ordered dict state_dict key -> {TENSOR_STAT_FIELDS}.  w, g, m, v: flat fp32
+    CUDA tensors (g may hold a trailer behind the gradient; den_ptr: the address of its denominator, or None); `step`: the number of the latest Adam launch;
+    tensor_lrs: the learning rate that launch used for every tensor.  update_norm = sqrt(update_sumsq) * (float32(lr) / bc1): the fp32 factor k_adam multiplies by."""
+    dev = w.device
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("qpnet_amd.%s.tensor_stats: a synchronous diagnostic call (it drains the stream and reads records back) cannot be captured into a graph" % who)
+    named = list(model.named_parameters())
+    ends, o = [], 0
+    for _, p in named:
+        o += p.numel()
+        ends.append(o)
+    if o != w.numel():
+        raise RuntimeError("qpnet_amd.%s.tensor_stats: the model's parameters hold %d elements, the flat vector %d" % (who, o, w.numel()))
+    nt = len(ends)
+    out = (_lib.QpnTensorStat * nt)()
+    L, hd = model._native(dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.qpn_tensor_stats(hd, w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), o, step, betas[0], betas[1], eps, den_ptr,
+                                      nt, (C.c_int64 * nt)(*ends), out, torch.cuda.current_stream(dev).cuda_stream))
+    bc1 = np.float32(1.0 - float(np.float32(betas[0])) ** step)      # qpn_launch_adam's: fp64, rounded once
+    res = collections.OrderedDict()
+    for (key, _), r, lr in zip(named, out, tensor_lrs):
+        wn = float(np.sqrt(r.weight_sumsq))
+        un = float(np.sqrt(r.update_sumsq)) * float(np.float32(lr) / bc1)
+        res[key] = {"grad_norm": float(np.sqrt(r.grad_sumsq)), "weight_norm": wn, "update_norm": un,
+                    "update_ratio": un / wn if wn > 0.0 else (0.0 if un == 0.0 else float("inf")),
+                    "grad_absmax": float(r.grad_absmax), "weight_absmax": float(r.weight_absmax), "grad_nonfinite": int(r.grad_nonfinite)}
+    return res
+
+
 # ---------------------------------------------------------------- Adam state in torch.optim.Adam's state_dict layout
 _ADAM_GROUP_DEFAULTS = dict(amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None)
 
@@ -1078,6 +1122,29 @@ class FlatAdam(torch.optim.Optimizer):
 
     def _hyper(self):
         return {k: self.param_groups[0][k] for k in ("lr", "betas", "eps", "weight_decay")}
+
+    def tensor_stats(self, weights="model"):
+        """FusedTrainer.tensor_stats for this optimizer's latest step(): the gradient is the parameters' `.grad` as they are now (the step left them alone),
+        the learning rates are the groups' current ones.  RuntimeError before the first step and on a capturing stream."""
+        if weights not in ("model", "ema"):
+            raise ValueError('tensor_stats: weights must be "model" or "ema", got %r' % (weights,))
+        if weights == "ema" and self.ema_decay <= 0.0:
+            raise RuntimeError('tensor_stats(weights="ema"): this optimizer keeps no averaged weights (ema_decay is off)')
+        model = self.model
+        flat = getattr(model, "_flat", None)
+        if self._steps < 1 or self._m is None or flat is None or not flat.is_cuda or self._m.device != flat.device:
+            raise RuntimeError("qpnet_amd.FlatAdam.tensor_stats before the first update: there is no Adam launch to describe")
+        params = model_params(model)
+        g = _flat_grad_of(params)
+        if g is None:
+            g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).float() for p in params])
+        grp = self.param_groups[0]
+        if self._groups is not None:
+            lrs = _tensor_lrs(len(params), self._groups.positions, [pg["lr"] for pg in self.param_groups])
+        else:
+            lrs = [grp["lr"]] * len(params)
+        w = _ema_home(self.ema, flat) if weights == "ema" else flat
+        return _tensor_stats("FlatAdam", model, w, g, None, self._m, self._v, self._steps, grp["betas"], grp["eps"], lrs)
 
     def ema_state_dict(self):
         """the averaged weights under the model's state_dict() keys ({} with averaging off); not part of state_dict(), which keeps torch.optim.Adam's layout."""
@@ -1578,6 +1645,41 @@ class FusedTrainer:
                 L, hd = self.model._native(flat.device)
                 self._rebase_step_count(L, hd, flat.device, torch.cuda.current_stream(flat.device).cuda_stream, 0)
             raise
+
+    def tensor_stats(self, weights="model"):
+        """Per-tensor statistics of the latest Adam launch of this trainer: an ordered dict state_dict key -> {"grad_norm", "weight_norm", "update_norm",
+        "update_ratio", "grad_absmax", "weight_absmax", "grad_nonfinite"}, in state_dict order (qpn_tensor_stats: two read-only launches over the buffers the step left).
+        grad_*: the gradient that launch consumed, divided as the launch divided it -- with accum_steps > 1 the accumulator over its summed row count (the row-weighted
+        mean gradient of the window), with world_size > 1 the exchanged buffer over its trailer -- before clipping; NaN / inf elements are counted in grad_nonfinite and
+        left out of norm and maximum.  weight_*: the weights after the update (weights="ema": the averaged weights).  update_norm: the norm of what the launch subtracted
+        from the tensor, rebuilt from m and v in the kernel's own fp32 expression and this tensor's group lr (float32(lr) * float32(lr_scale), over the bias correction);
+        0 for a frozen tensor.  update_ratio = update_norm / weight_norm.
+        A SYNCHRONOUS diagnostic call: it drains the current stream and reads the records back -- for a report every N steps, not for every step.  It changes nothing: weights,
+        moments, losses, the status word and the applied-update count are what they are without it.  After a step the device skipped (a flagged chunk, a non-finite
+        norm) m, v and, once the error has been raised, the step count are those of the last APPLIED update: the update fields describe that one, the gradient fields the
+        gradient of the skipped step (grad_nonfinite says which tensor held the NaN).  `lr` is read now: call it before changing it for the next step.
+        RuntimeError: before the first update, while an accumulation window is open (micro_step != 0: the accumulator holds part of a gradient) and on a capturing stream."""
+        if weights not in ("model", "ema"):
+            raise ValueError('tensor_stats: weights must be "model" or "ema", got %r' % (weights,))
+        if weights == "ema" and self.ema_decay <= 0.0:
+            raise RuntimeError('tensor_stats(weights="ema"): this trainer keeps no averaged weights (ema_decay is off)')
+        model = self.model
+        flat = getattr(model, "_flat", None)
+        if self.step_count < 1 or self.m is None or self.g is None or flat is None or not flat.is_cuda or self.m.device != flat.device:
+            raise RuntimeError("qpnet_amd.FusedTrainer.tensor_stats before the first update: there is no Adam launch to describe")
+        if self._micro != 0:
+            raise RuntimeError("qpnet_amd.FusedTrainer.tensor_stats while an accumulation window is open (micro_step = %d of %d): the accumulator holds part of a gradient"
+                               % (self._micro, self.accum_steps))
+        n = flat.numel()
+        gbuf = self.acc if self.accum_steps > 1 else self.g
+        den = gbuf.data_ptr() + 4 * n if (self.accum_steps > 1 or self.world > 1) else None
+        n_tensors = len(model_params(model))
+        if self._groups is not None:
+            lrs = _tensor_lrs(n_tensors, self._groups.positions, self._group_values()[0])
+        else:
+            lrs = [self.lr] * n_tensors
+        w = _ema_home(self.ema, flat) if weights == "ema" else flat
+        return _tensor_stats("FusedTrainer", model, w, gbuf, den, self.m, self.v, self.step_count, self.betas, self.eps, lrs)
 
     def forward_loss(self, x, h, t, d, blength, maxd=None, weights="model"):
         """forward + mean CE only (validation, reference qpnet_validate.py:409-430).  weights="ema": of the averaged weights (the forward reads the flat vector
