@@ -264,6 +264,12 @@ int qpn_train_input_grad(qpn_handle* h, float* d_dh, int64_t n);
  * compares before backward (reference: autograd keeps per-call activations, src/bin/qpnet_train.py:520-530). */
 int64_t qpn_train_generation(qpn_handle* h);
 
+/* What the handle's latest training calls launched, as text: "fwd[...] launches" of the latest forward and, behind " | ", "bwd[...] jobs" of its backward
+ * once that has run -- the layer path of each direction (generic / persist / stack), the fused forms, every launch with (grid; block; dynamic LDS bytes),
+ * the backward's jobs in order with their stream (main: / side:) and the fork / mid / join / wait / early event edges.  Diagnostics and tests; built when
+ * asked for (a step formats nothing), owned by the handle, valid until the next training call; "" before the first forward. */
+const char* qpn_train_last_plan(qpn_handle* h);
+
 /* Synchronise and report the device-side status of the last training call (QPN_ERANGE when a
  * pitch-dependent tap left its layer input: reference assert qpnet.py:294). */
 int qpn_train_status(qpn_handle* h, void* stream);

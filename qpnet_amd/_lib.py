@@ -70,6 +70,7 @@ SYMBOLS = [
     ("qpn_train_backward_ex", _i, [_vp, _vp, _vp, C.c_float, _i, _vp]),
     ("qpn_train_input_grad", _i, [_vp, _vp, _i64]),
     ("qpn_train_generation", _i64, [_vp]),
+    ("qpn_train_last_plan", C.c_char_p, [_vp]),
     ("qpn_train_status", _i, [_vp, _vp]),
     ("qpn_train_status_enqueue", _i, [_vp, _vp]),
     ("qpn_train_status_collect", _i, [_vp]),

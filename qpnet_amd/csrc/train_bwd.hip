@@ -769,196 +769,126 @@ void qpn_launch_zero_dx(const TrainParams& p, const TrainBwd& bw, hipStream_t st
     hipLaunchKernelGGL(k_zero_dx, dim3(64, p.L, p.B), dim3(256), 0, stream, p, bw);
 }
 
-// slabs -> flat gradient (writes every entry), then the histogram-style gradients on top (causal table when no
-// contraction owns it, upsampling kernel)
 // the skip / post-net part of the slab reduction, launched on the side stream right behind those weight gradients
 // tail: this launch also zeroes the entries no slab feeds and appends the trailer (then the final reduction must not: the upsampling
-// kernel's gradient is added onto those zeros in between, see qpn_launch_bwd)
-static void launch_reduce_early(const TrainBwd& bw, hipStream_t st, int tail, int nch_side) {
+// kernel's gradient is added onto those zeros in between)
+static void launch_reduce_early(const TrainBwd& bw, const TlpLaunch& l, hipStream_t st, int tail, int nch_side) {
     const TrainSlabs& sl = *bw.sl;
-    const int64_t n = (int64_t)(sl.g_early1 - sl.g_early0) + (tail ? bw.n_gzero + 4 : 0);
-    hipLaunchKernelGGL(k_reduce_grad_s, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, bw.slab, bw.gdst, bw.gdst_list, bw.gzero, bw.n_gzero,
+    hipLaunchKernelGGL(k_reduce_grad_s, dim3(l.gx), dim3(l.block), 0, st, bw.slab, bw.gdst, bw.gdst_list, bw.gzero, bw.n_gzero,
                        nch_side, bw.gstage, bw.n_params, bw.gflat, bw.gscale, bw.append_scale, sl.g_early0, sl.g_early1, 0, 0, tail, bw.status, 0);
 }
-static void launch_up_bwd(const TrainParams& p, const TrainBwd& bw, hipStream_t st) {
-    const UpArgs u = up_args(p, bw);
-    hipLaunchKernelGGL(k_up_bwd, dim3(u.nfr, p.B), dim3(128), 0, st, u);
-}
-
-// early_done: the [g_early0, g_early1) slab range has been reduced already; up_done: so have the zeroing / trailer and, on top of the zeros, the
-// upsampling kernel's gradient
-static void launch_aux_tail(const TrainParams& p, const TrainBwd& bw, const AuxGeom& ag, hipStream_t st) {
-    hipLaunchKernelGGL(k_aux_tail, dim3(p.L * p.A + p.U), dim3(128), 0, st, tr_aux_args(p, &bw, ag));
-}
-
-int qpn_launch_grad_tail(const TrainParams& p, const TrainBwd& bw, const AuxGeom* ag, hipStream_t stream, bool early_done, bool up_done) {
-    const int C = p.C, Q = p.Q, B = p.B, N1 = p.N1;
+// slabs -> flat gradient (writes every entry); the histogram-style gradients follow on top (causal table when no contraction owns it, upsampling kernel)
+static void launch_reduce(const TrainBwd& bw, const TrainTailPlan& t, hipStream_t st) {
     const TrainSlabs& sl = *bw.sl;
-    hipLaunchKernelGGL(k_reduce_grad_s, dim3((unsigned)(((int64_t)bw.gstage + (up_done ? 0 : bw.n_gzero + 4) + 255) / 256)), dim3(256), 0, stream, bw.slab, bw.gdst, bw.gdst_list, bw.gzero, bw.n_gzero,
-                       bw.nch, bw.gstage, bw.n_params, bw.gflat, bw.gscale, bw.append_scale, 0, bw.gstage, early_done ? sl.g_early0 : 0, early_done ? sl.g_early1 : 0, up_done ? 0 : 1, bw.status, bw.append_scale == 1 ? 1 : 0);
-    {
-        const int64_t total = (int64_t)B * N1;
-        const int nwg = 128, rpw = (int)((total + nwg - 1) / nwg);
-        if (sl.g_cw < 0) {
-            int CB = C < 64 ? C : 64;
-            while (CB > 1 && (size_t)2 * Q * CB * sizeof(float) > 128 * 1024) CB /= 2;
-            const size_t lds_c = (size_t)2 * Q * CB * sizeof(float);
-            if (lds_c > 160 * 1024) { qpn_set_error("causal-table gradient: n_quantize too large for the LDS histogram"); return QPN_EINVAL; }
-            if (lds_c > 48 * 1024) QPN_HIP(hipFuncSetAttribute((const void*)k_causal_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
-            hipLaunchKernelGGL(k_causal_bwd, dim3(nwg), dim3(256), lds_c, stream, p, bw, rpw, CB);
-        }
-        if (p.U > 0 && !up_done && !p.hoist) launch_up_bwd(p, bw, stream);
-        if (p.hoist && ag && !up_done) launch_aux_tail(p, bw, *ag, stream);      // (behind the reduction's zeroing: it adds onto the upsampling-bias entry; up_done: it ran on the side stream)
-        if (bw.dh && !up_done) qpn_launch_input_grad(p, bw, ag, stream);          // (armed only -- qpn_train_input_grad; up_done: it ran on the side stream too)
-    }
+    hipLaunchKernelGGL(k_reduce_grad_s, dim3(t.reduce.gx), dim3(t.reduce.block), 0, st, bw.slab, bw.gdst, bw.gdst_list, bw.gzero, bw.n_gzero,
+                       bw.nch, bw.gstage, bw.n_params, bw.gflat, bw.gscale, bw.append_scale, 0, bw.gstage, t.early_done ? sl.g_early0 : 0, t.early_done ? sl.g_early1 : 0, t.up_done ? 0 : 1, bw.status, bw.append_scale == 1 ? 1 : 0);
+}
+static int launch_causal_hist(const TrainParams& p, const TrainBwd& bw, const TrainTailPlan& t, hipStream_t st) {
+    if (t.causal.lds > TLP_LDS_OPTIN) QPN_HIP(hipFuncSetAttribute((const void*)k_causal_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.causal.lds));
+    hipLaunchKernelGGL(k_causal_bwd, dim3(t.causal.gx), dim3(t.causal.block), t.causal.lds, st, p, bw, t.rpw, t.CB);
+    return QPN_OK;
+}
+static void launch_up_bwd(const TrainParams& p, const TrainBwd& bw, const TlpLaunch& l, hipStream_t st) {
+    hipLaunchKernelGGL(k_up_bwd, dim3(l.gx, l.gy), dim3(l.block), 0, st, up_args(p, bw));
+}
+static void launch_aux_tail(const TrainParams& p, const TrainBwd& bw, const AuxGeom& ag, const TlpLaunch& l, hipStream_t st) {
+    hipLaunchKernelGGL(k_aux_tail, dim3(l.gx), dim3(l.block), 0, st, tr_aux_args(p, &bw, ag));
+}
+
+// The GEMM step's tail (train_gemm.hip keeps its own launchers): the final reduction with nothing done early, and what follows it.  The tile step's tail is
+// the last jobs of its plan (qpn_launch_bwd)
+int qpn_launch_grad_tail(const TrainParams& p, const TrainBwd& bw, const AuxGeom* ag, hipStream_t stream, bool early_done, bool up_done) {
+    const TrainTailIn in = {p.C, p.Q, p.U, p.L, p.A, p.B, p.N1, p.F, bw.gstage, bw.n_gzero, bw.sl->g_cw, p.hoist != 0};
+    const TrainTailPlan t = train_tail_plan(in, bw.dh != nullptr, early_done, up_done);
+    if (t.rc) return t.rc;
+    launch_reduce(bw, t, stream);
+    if (t.causal_hist) { const int rc = launch_causal_hist(p, bw, t, stream); if (rc) return rc; }
+    if (t.up_bwd) launch_up_bwd(p, bw, t.up, stream);
+    if (t.aux_tail && ag) launch_aux_tail(p, bw, *ag, t.aux, stream);
+    if (t.input_grad) qpn_launch_input_grad(p, bw, ag, stream);
     qpn_prof_mark(PG_GRAD_TAIL, stream);
     QPN_HIP(hipGetLastError());
     return QPN_OK;
 }
 
-bool qpn_stack_bwd_fits(const TrainParams& p);
-int qpn_launch_stack_bwd(const TrainParams& p, const TrainBwd& bw, const StackQ& q, const TrainKnobs& k, hipStream_t stream);
+int qpn_launch_stack_bwd(const TrainParams& p, const TrainBwd& bw, const StackQ& q, const TrainBwdPlan& pl, hipStream_t stream);
 
-void qpn_launch_post_fb(const TrainParams& p, const TrainBwd& bw, hipStream_t stream) {
-    constexpr int MTW = 5;
-    const size_t ldsw = (size_t)16 * MTW * (tr_lda(256) + 2 * tr_lda(64)) * sizeof(float);
-    (void)hipFuncSetAttribute((const void*)k_post_fb_w<MTW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-    hipLaunchKernelGGL((k_post_fb_w<MTW>), dim3((p.BL + 16 * MTW - 1) / (16 * MTW), p.B), dim3(512), ldsw, stream, p, bw, 1);
+void qpn_launch_post_fb(const TrainParams& p, const TrainBwd& bw, const TlpLaunch& l, hipStream_t stream) {
+    (void)hipFuncSetAttribute((const void*)k_post_fb_w<TLP_POST_MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds);
+    hipLaunchKernelGGL((k_post_fb_w<TLP_POST_MT>), dim3(l.gx, l.gy), dim3(l.block), l.lds, stream, p, bw, 1);
 }
 
-// post_done: the forward's launch sequence has run the post-net's backward (and the zeroing) already
-int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k, const AuxGeom& ag, const StackQ* sq, hipStream_t stream, bool post_done) {
-    const int C = p.C, S = p.S, Q = p.Q, L = p.L, B = p.B, N1 = p.N1, BL = p.BL;
-    const TrainSlabs& sl = *bw.sl;
-    const bool off32 = N1 < (1 << 24) && (int64_t)N1 * (p.LC > 2 * C ? p.LC : 2 * C) < (1ll << 32);       // k_layer_bwd_p's 32-bit element offsets (one batch item)
-    const bool persist = C == 64 && (p.Ktp == 176 || p.hoist) && p.Ap <= 64 && off32 && k.persist_bwd;
-    // the whole stack's backward as ONE persistent launch over a (layer, tile) work queue (train_stack.hip); QPN_STACK_QUEUE_BWD=0 (or
-    // QPN_STACK_QUEUE=0) keeps a launch per layer
-    const bool stack_q = persist && k.stack_q_bwd && sq && sq->flags && p.qctl && qpn_stack_bwd_fits(p);
-    const bool wr_summed = stack_q;
-    // 16-row tiles (measured 11-15 % faster than 32 rows: twice the workgroups, a shorter last round)
-    const size_t lds_post = (size_t)16 * (tr_lda(Q > S ? Q : S) + tr_lda(S)) * sizeof(float);
-    const size_t lds_layer = (size_t)16 * (4 * tr_lda(C) + tr_lda(2 * C)) * sizeof(float);
-    if (lds_post > 160 * 1024 || lds_layer > 160 * 1024) { qpn_set_error("backward tiles do not fit LDS"); return QPN_EINVAL; }
-    // grads wrt layer outputs: DXA/DXB[l] for l = 0..L (index l = grad wrt X[l]); zero (scatter targets / unwritten rows)
-    // only the rows a consumer reads but no producer writes (see k_zero_dx): 4 adaptive scatter targets instead of 2(L+1) full arrays
-    hipStream_t side = bw.side; hipEvent_t ev_fork = bw.ev_fork, ev_join = bw.ev_join;   // created with the handle's TrainState, on its device
-    const bool overlap = side && !qpn_prof_serial() && !k.serial;
-    const bool post_wide = S == 256 && Q == 256 && C == 64 && (p.LC == 256 || p.LC == 512) && k.post_wide;
-    const bool zero_in_post = post_wide && k.zero_in_post;
-    if (post_done) { }
-    else if (!zero_in_post) qpn_launch_zero_dx(p, bw, stream);
-    if (post_done) { }
-    else if (post_wide) {      // 80 rows per workgroup (k_post_bwd_w)
-        constexpr int MTW = 5;
-        const size_t ldsw = (size_t)16 * MTW * tr_lda(256) * sizeof(float);
-        QPN_HIP(hipFuncSetAttribute((const void*)k_post_bwd_w<MTW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw));
-        hipLaunchKernelGGL((k_post_bwd_w<MTW>), dim3((BL + 16 * MTW - 1) / (16 * MTW), B), dim3(512), ldsw, stream, p, bw, zero_in_post ? 1 : 0);
-    } else {
-        if (lds_post > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_post_bwd<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_post);
-        hipLaunchKernelGGL((k_post_bwd<1>), dim3((BL + 15) / 16, B), dim3(512), lds_post, stream, p, bw);
+// the persistent layer kernel of a plan: <8 | 11, last layer>
+typedef void (*LayerBwdP)(TrainParams, TrainBwd, int, int, int, float*);
+static LayerBwdP layer_bwd_p(int form, bool last) {
+    return form == 8 ? (last ? k_layer_bwd_p<8, true> : k_layer_bwd_p<8, false>) : (last ? k_layer_bwd_p<11, true> : k_layer_bwd_p<11, false>);
+}
+static int launch_layers_bwd(const TrainParams& p, const TrainBwd& bw, const TrainBwdPlan& pl, const StackQ& sq, hipStream_t stream) {
+    if (pl.path == TLP_STACK) return qpn_launch_stack_bwd(p, bw, sq, pl, stream);
+    for (int l = p.L - 1; l >= 0; --l) {
+        const TlpLaunch& y = pl.layer[l];
+        if (pl.path == TLP_PERSIST) {      // register-resident weights, 2 workgroups per CU over contiguous tile ranges (k_layer_bwd_p)
+            const LayerBwdP kf = layer_bwd_p(pl.form, l == p.L - 1);
+            (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)y.lds);
+            hipLaunchKernelGGL(kf, dim3(y.gx, y.gy), dim3(y.block), y.lds, stream, p, bw, l, pl.swz ? 2 : 0, p.qT[l], p.scratch_rows);
+        } else {
+            if (y.lds > TLP_LDS_OPTIN) (void)hipFuncSetAttribute((const void*)k_layer_bwd<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)y.lds);
+            hipLaunchKernelGGL((k_layer_bwd<1>), dim3(y.gx, y.gy), dim3(y.block), y.lds, stream, p, bw, l, l == p.L - 1 ? 1 : 0, pl.swz);
+        }
     }
-    qpn_prof_mark(PG_POST_BWD, stream);
-    // ---- the skip 1x1 and post-net weight gradients only need what k_post_bwd has just produced (dS0, dY0, dlogits) and
-    // saved activations: they run on a side stream UNDER the layer backward (the layer kernels are latency-bound but their
-    // workgroups still occupy every CU, so the overlap is partial).  Per-group profiling (bench roofline) and QPN_TRAIN_SERIAL=1
-    // keep everything on the one stream.
-    const int nch = bw.nch;
-    int nch_side_ = nch;      // time chunks (= partial slabs) of the skip / post-net contractions, which run on the side stream under the layer backward and are reduced by a launch of their own
-    const bool gen = k.wgrad_generic;
+    return QPN_OK;
+}
+
+// The backward of the tile step: the jobs of its plan (train_launch_plan.h), in order, each on the stream the plan names.  Why a job runs where it does: DESIGN 5.
+// sq: the backward queue (used by a TLP_STACK plan only)
+int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainBwdPlan& pl, const AuxGeom& ag, const StackQ& sq, hipStream_t stream) {
+    const TrainSlabs& sl = *bw.sl;
     // the five contraction records (train_wgrad_plan.h), from one view of the step; p.TH holds the gate product, as it is
     const WgradView wv = tr_wgrad_view(p);
     const WgradBufs wb = tr_wgrad_bufs(p, bw, p.TH);
-    // (wr_summed: the stack queue's tiles have replaced the own-row part of dXout by the sum of both parts -- store_dx in k_stack_bwd)
-    const WgradFlags wf = {wr_summed, k.post_pair, true, true};
+    const WgradFlags wf = {pl.wr_summed, pl.post_pair, true, true};
     bool ok = true;
-    auto wgrad = [&](const Wg2& w, int chunks, hipStream_t st) { ok = ok && qpn_launch_wgrad(w, chunks, gen, st) == QPN_OK; };
-    auto launch_skip_post = [&](hipStream_t st) {
-        wgrad(wgrad_rec_skip(wv, sl, wb, wf), nch_side_, st);
-        qpn_prof_mark(PG_WGRAD_SKIP, st);
-        wgrad(wgrad_rec_post(wv, sl, wb, wf, 0), nch_side_, st);
-        if (!wgrad_post_paired(wv, wf)) wgrad(wgrad_rec_post(wv, sl, wb, wf, 1), nch_side_, st);
-        qpn_prof_mark(PG_WGRAD_POST, st);
-    };
-    // ---- the weight gradients that need the layer backward -- dW1 (needs dZ_l), the residual 1x1 (needs dX_{l+1}), the causal table -- follow it below
-    // the memory-bound reduction of the skip / post-net slabs (half of k_reduce_grad's 130 MB) runs on the side stream under the
-    // matrix-bound layer backward instead of at the end of the step
-    const bool early_reduce = overlap && bw.gdst && sl.g_early1 > sl.g_early0 && k.reduce_early;
-    // with the early reduction doing the zeroing / trailer too, the upsampling kernel's gradient (atomics onto those zeros, needs dH of every
-    // layer) runs on the side stream next to dW1 instead of behind the final reduction
-    // (aux hoist: k_aux_tail takes k_up_bwd's place: it needs the layer backward's D / G / E and the zeroed upsampling-bias entry)
-    const bool up_side = early_reduce && p.U > 0 && k.up_side;
-    // (only with the early reduction: otherwise ONE launch reduces every block with one slab count)
-    if (early_reduce) {
-        // measured on the overlapped step: 64 -> 48 chunks makes each of these launches slower alone and the step faster
-        nch_side_ = k.wgrad_chunks_side > 0 && k.wgrad_chunks_side <= nch ? k.wgrad_chunks_side : (nch <= 48 ? nch : 48);
-    }
-    if (overlap) {
-        QPN_HIP(hipEventRecord(ev_fork, stream));
-        QPN_HIP(hipStreamWaitEvent(side, ev_fork, 0));
-        qpn_prof_mark(-1, side);
-        launch_skip_post(side);
-        if (early_reduce) { launch_reduce_early(bw, side, up_side ? 1 : 0, nch_side_); qpn_prof_mark(PG_GRAD_TAIL, side); }
-        // the post-net block of the flat gradient (and, with up_side, the zeroing and the row-count trailer behind it) is final from here on:
-        // a data-parallel caller exchanges that bucket while the layer backward still runs (qpn_train_early_bucket)
-        if (early_reduce && up_side && bw.ev_early && bw.early_recorded) { QPN_HIP(hipEventRecord(bw.ev_early, side)); *bw.early_recorded = 1; }
-    }
-    const int swz = k.xcd_swizzle ? 1 : 0;
-    if (p.hoist && !persist) { qpn_set_error("internal: the frame-rate aux term needs the register-resident layer kernels"); return QPN_EINVAL; }
-    if (stack_q) {
-        const int rcq = qpn_launch_stack_bwd(p, bw, *sq, k, stream);
-        if (rcq) return rcq;
-    }
-    for (int l = L - 1; l >= 0 && !stack_q; --l) {
-        const TrLayer& ly = p.layers[l];
-        const int rows = N1 - ly.s_out;
-        const int tiles = (rows + 15) / 16;
-        if (persist) {      // register-resident weights, 2 workgroups per CU over contiguous tile ranges (k_layer_bwd_p)
-            int G = qpn_num_cus() * 2; if (G > tiles) G = tiles;
-            if (G > 1024) G = 1024;                                // (scratch_rows holds a pair of rows for 1024 workgroups per batch item)
-            const size_t ldsp = (size_t)(8 * 16 * tr_lda(C) + 16 * tr_lda(2 * C) + 16 * tr_lda(p.Ktp) + 64) * sizeof(float);
-            const bool last = l == L - 1;
-            const void* kf = p.hoist ? (last ? (const void*)k_layer_bwd_p<8, true> : (const void*)k_layer_bwd_p<8, false>)
-                                     : (last ? (const void*)k_layer_bwd_p<11, true> : (const void*)k_layer_bwd_p<11, false>);
-            (void)hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-            if (p.hoist) {
-                if (last) hipLaunchKernelGGL((k_layer_bwd_p<8, true>), dim3(G, B), dim3(256), ldsp, stream, p, bw, l, swz ? 2 : 0, tiles, p.scratch_rows);
-                else hipLaunchKernelGGL((k_layer_bwd_p<8, false>), dim3(G, B), dim3(256), ldsp, stream, p, bw, l, swz ? 2 : 0, tiles, p.scratch_rows);
+    auto wgrad = [&](const Wg2& w, int chunks, hipStream_t st) { ok = ok && qpn_launch_wgrad(w, chunks, pl.wgrad_generic, st) == QPN_OK; };
+    for (int i = 0; i < pl.njobs; ++i) {
+        const TrainJob& j = pl.jobs[i];
+        const hipStream_t st = j.side ? bw.side : stream;
+        switch (j.kind) {
+        case TJ_MARK: break;
+        case TJ_ZERO: hipLaunchKernelGGL(k_zero_dx, dim3(pl.zero.gx, pl.zero.gy, pl.zero.gz), dim3(pl.zero.block), 0, st, p, bw); break;
+        case TJ_POST_BWD: {
+            const TlpLaunch& w = pl.post_l;
+            if (pl.post == TLP_POST_WIDE) {      // 80 rows per workgroup (k_post_bwd_w)
+                QPN_HIP(hipFuncSetAttribute((const void*)k_post_bwd_w<TLP_POST_MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.lds));
+                hipLaunchKernelGGL((k_post_bwd_w<TLP_POST_MT>), dim3(w.gx, w.gy), dim3(w.block), w.lds, st, p, bw, pl.zero_in_post ? 1 : 0);
             } else {
-                if (last) hipLaunchKernelGGL((k_layer_bwd_p<11, true>), dim3(G, B), dim3(256), ldsp, stream, p, bw, l, swz ? 2 : 0, tiles, p.scratch_rows);
-                else hipLaunchKernelGGL((k_layer_bwd_p<11, false>), dim3(G, B), dim3(256), ldsp, stream, p, bw, l, swz ? 2 : 0, tiles, p.scratch_rows);
+                if (w.lds > TLP_LDS_OPTIN) (void)hipFuncSetAttribute((const void*)k_post_bwd<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.lds);
+                hipLaunchKernelGGL((k_post_bwd<1>), dim3(w.gx, w.gy), dim3(w.block), w.lds, st, p, bw);
             }
-        } else {
-            if (lds_layer > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_layer_bwd<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_layer);
-            hipLaunchKernelGGL((k_layer_bwd<1>), dim3(tiles, B), dim3(256), lds_layer, stream, p, bw, l, l == L - 1 ? 1 : 0, swz);
+        } break;
+        case TJ_FORK: QPN_HIP(hipEventRecord(bw.ev_fork, stream)); QPN_HIP(hipStreamWaitEvent(bw.side, bw.ev_fork, 0)); break;
+        case TJ_SKIP: wgrad(wgrad_rec_skip(wv, sl, wb, wf), j.arg, st); break;
+        case TJ_POST: for (int part = 0; part < j.n; ++part) wgrad(wgrad_rec_post(wv, sl, wb, wf, part), j.arg, st); break;
+        case TJ_REDUCE_EARLY: launch_reduce_early(bw, pl.reduce_early, st, j.n, pl.nch_side); break;
+        // the post-net block of the flat gradient (and the zeroing and the row-count trailer behind it) is final from here on: a data-parallel caller
+        // exchanges that bucket while the layer backward still runs (qpn_train_early_bucket)
+        case TJ_EARLY_EVENT: QPN_HIP(hipEventRecord(bw.ev_early, st)); *bw.early_recorded = 1; break;
+        case TJ_LAYERS: { const int rc = launch_layers_bwd(p, bw, pl, sq, st); if (rc) return rc; } break;
+        case TJ_MID: QPN_HIP(hipEventRecord(bw.ev_mid, stream)); QPN_HIP(hipStreamWaitEvent(bw.side, bw.ev_mid, 0)); break;
+        case TJ_UP: launch_up_bwd(p, bw, pl.tail.up, st); break;
+        case TJ_AUX_TAIL: launch_aux_tail(p, bw, ag, pl.tail.aux, st); break;
+        case TJ_INPUT_GRAD: qpn_launch_input_grad(p, bw, &ag, st); break;
+        case TJ_W1: wgrad(wgrad_rec_w1(wv, sl, wb, wf), j.arg, st); break;
+        case TJ_WR: wgrad(wgrad_rec_wr(wv, sl, wb, wf), j.arg, st); break;
+        case TJ_CAUSAL: wgrad(wgrad_rec_causal(wv, sl, wb), j.arg, st); break;
+        case TJ_JOIN: QPN_HIP(hipEventRecord(bw.ev_join, bw.side)); break;
+        case TJ_WAIT: QPN_HIP(hipStreamWaitEvent(stream, bw.ev_join, 0)); break;
+        case TJ_REDUCE:
+            if (!ok) return QPN_EINVAL;      // (qpn_launch_wgrad has set the error text: a geometry no tile kernel takes; the side stream has been joined)
+            launch_reduce(bw, pl.tail, st); break;
+        case TJ_CAUSAL_HIST: { const int rc = launch_causal_hist(p, bw, pl.tail, st); if (rc) return rc; } break;
         }
+        if (j.mark > -2) qpn_prof_mark(j.mark, st);
     }
-    // the residual-1x1 weight gradient is a memory-bound 64 x 64 contraction: on the side stream next to the matrix-heavy dW1 launch
-    // (measured 1028 -> 1052 steps/s; the causal table's contraction there as well: 1028 again, the side chain becomes the longer one)
-    // [One launch for everything that waits for the whole layer backward (dW1 + dWr + causal table + upsampling kernel as roles of one kernel)
-    //  was tried: 1146 steps/s against 1205.  dW1 is a 247-register kernel (159 VGPRs + 88 accumulators): two of its workgroups fill a CU's
-    //  register file, nothing runs beside them -- which is also why kernels launched next to it on the side stream start when it ends.]
-    const bool wr_side = overlap && k.wr_side;
-    if (wr_side || up_side) {
-        QPN_HIP(hipEventRecord(bw.ev_mid, stream));
-        QPN_HIP(hipStreamWaitEvent(side, bw.ev_mid, 0));
-        qpn_prof_mark(-1, side);
-        if (up_side) {      // (behind the early reduction's zeroing, on the same stream; the feature gradient, when armed, next to it: it reads what the layer backward left, as they do)
-            if (p.hoist) launch_aux_tail(p, bw, ag, side); else launch_up_bwd(p, bw, side);
-            if (bw.dh) qpn_launch_input_grad(p, bw, &ag, side);
-            qpn_prof_mark(PG_GRAD_TAIL, side);
-        }
-        if (wr_side) { wgrad(wgrad_rec_wr(wv, sl, wb, wf), nch, side); qpn_prof_mark(PG_WGRAD_WR, side); }
-    }
-    if (overlap) QPN_HIP(hipEventRecord(ev_join, side));
-    qpn_prof_mark(PG_LAYER_BWD, stream);
-    wgrad(wgrad_rec_w1(wv, sl, wb, wf), nch, stream);
-    qpn_prof_mark(PG_WGRAD, stream);
-    if (!wr_side) { wgrad(wgrad_rec_wr(wv, sl, wb, wf), nch, stream); qpn_prof_mark(PG_WGRAD_WR, stream); }
-    if (!overlap) launch_skip_post(stream);
-    if (sl.g_cw >= 0) wgrad(wgrad_rec_causal(wv, sl, wb), nch, stream);
-    qpn_prof_mark(PG_WGRAD_CAUSAL, stream);
-    if (overlap) { QPN_HIP(hipStreamWaitEvent(stream, ev_join, 0)); qpn_prof_mark(-1, stream); }      // joined BEFORE any early return: the caller's stream must own everything enqueued here
-    if (!ok) return QPN_EINVAL;      // (qpn_launch_wgrad has set the error text: a geometry no tile kernel takes)
-    return qpn_launch_grad_tail(p, bw, &ag, stream, early_reduce, up_side);
+    QPN_HIP(hipGetLastError());
+    return QPN_OK;
 }

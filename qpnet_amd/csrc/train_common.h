@@ -11,12 +11,11 @@
 #include "train_plan.h"      // TR_MAXL, TR_EB_SLOTS, TrainSlabs, AuxGeom, TrainGemm, TrainKnobs: the host-only layout types, and the planner that fills them
 #include "adam_groups.h"     // QPN_ADAM_MAX_GROUPS, QPN_ADAM_FROZEN, AdamGroupTable: the Adam step's parameter groups (host-only too)
 #include "train_wgrad_plan.h"   // Wg2, WgradPick, the wgrad_rec_* record builders, TArgs: the weight-gradient contractions' host side (host-only as well)
+#include "train_launch_plan.h"  // tr_lda, X0_* / AUXP_FPB / SQ_NQ, the PG_* profile groups; TrainShape, TrainFwdPlan, TrainBwdPlan: what a step launches (host-only too)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// leading dimension for an LDS A-tile read "row = lane&15, k = lane>>4" with ds_read_b32:
-// ld == 2 (mod 32) makes the 32-lane groups conflict free (MI355X_MICROARCH.md §LDS).
-__host__ __device__ static inline int tr_lda(int K) { return ((K + 29) / 32) * 32 + 2; }
+// (tr_lda, the leading dimension of an LDS A tile: train_launch_plan.h -- ld == 2 (mod 32), MI355X_MICROARCH.md §LDS)
 // leading dimension for transposed reads "k-row = lane>>4, col = lane&15": ld == 16 (mod 32)
 __host__ __device__ static inline int tr_ldt(int N) { return ((N + 15) / 32) * 32 + 16; }
 
@@ -267,11 +266,7 @@ struct AdamCall {
 int qpn_launch_adam(const AdamCall& c, hipStream_t stream);
 int qpn_launch_grad_accum(float* acc, const float* g, int64_t cnt, int first, const int* status, int* h_status, double* h_loss, const double* d_loss, hipStream_t stream);
 
-// optional per-kernel-group timing (HIP events on the launch stream; bench.py roofline)
-// (one group per LAUNCH of the heavy kernels, so that bench.py can name the single longest kernel: PG_WGRAD = the gate contraction's weight
-//  gradient dW1, then the residual 1x1's, the skip 1x1's, the post-net pair's and the causal table's)
-enum { PG_PREP = 0, PG_LAYER_FWD, PG_POST_FWD, PG_CE, PG_POST_BWD, PG_WGRAD, PG_LAYER_BWD, PG_GRAD_TAIL, PG_ADAM, PG_ALLREDUCE,
-       PG_WGRAD_WR, PG_WGRAD_SKIP, PG_WGRAD_POST, PG_WGRAD_CAUSAL, PG_COUNT };
+// optional per-kernel-group timing (HIP events on the launch stream; bench.py roofline); the groups PG_*: train_launch_plan.h
 void qpn_prof_mark(int group, hipStream_t stream);
 bool qpn_prof_serial();                              // a SERIAL per-group timing is in progress (keeps the step on one stream; the overlapped mode does not)
 bool qpn_prof_active();                              // per-group timing in progress (keeps a step on one stream)   // attributes the work enqueued since the previous mark to `group`

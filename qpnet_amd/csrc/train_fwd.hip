@@ -25,7 +25,7 @@ __device__ __forceinline__ float tanhf_(float z) { return 2.0f * __builtin_amdgc
 // chunk's rows touch -- the auxiliary 1x1 (reference src/nets/qpnet.py:215-216, 663-664) applied BEFORE the rank-1 upsampling it commutes with
 // (qpnet.py:134-158): L x nfr x 2C x n_aux MACs per batch item instead of L x N1 x 2C x 48.  A role of k_train_prep's launch: one workgroup per
 // (AUXP_FPB frames, layer, batch item); thread = (gate row n, half of the frames).
-#define AUXP_FPB 8                                    // frames per workgroup
+// (AUXP_FPB = 8 frames per workgroup: train_launch_plan.h)
 template <bool BIAS>      // BIAS: this launch also adds the constant term to the packed gate bias (k_train_prep; k_step_prep's bias role has it)
 __device__ __forceinline__ void aux_proj_block(const TrainParams& p, const AuxGeom& ag, int fxb, int l, int b, float* sm) {
     // sm: Va_l [2C][A] (A odd: conflict-free column reads; even A: two-way), h tile [A][AUXP_FPB]
@@ -161,12 +161,8 @@ __global__ __launch_bounds__(256) void k_train_prep(TrainParams p, AuxGeom ag, i
 //               the 64 items behind the biases clear the loss accumulator
 //   weights   : fragment-ordered weight blocks, four elements per thread (one int4 of the map, four gathers in flight, one 16-byte store)
 //   items     : prep_items<false>: aux rows (no hoist), tap tables, WJ, queue tables / heads / abort word
-#ifndef X0_CS
-#define X0_CS 16          // channels of a table slice
-#define X0_ST 17          // row stride of the slice's table in LDS
-#endif
-#define X0_RPG 512        // rows of a table workgroup at most
-struct StepPrepPlan { int nx0, rpg, naux, nbias, nwt, nprep; };     // workgroups per role (items: per batch item); rpg: rows of a table workgroup
+// (X0_CS = 16 channels of a table slice, X0_ST = 17 its row stride in LDS, X0_RPG = 512 rows of a table workgroup at most, and StepPrepPlan -- the workgroups
+//  per role -- : train_launch_plan.h)
 
 __device__ __forceinline__ void x0_block(const TrainParams& p, const int blk, const int rpg, float* sm) {
     const int C = p.C, Q = p.Q, N1 = p.N1, tid = threadIdx.x;
@@ -800,108 +796,48 @@ __global__ __launch_bounds__(512) void k_post_fwd_w(TrainParams p) {
     post_fwd_w_tile<MT, false>(p, sm, mS, mY, bq);
 }
 
-// ------------------------------------------------------------------ host launchers (called from train_host.hip)
-void qpn_launch_prep(const TrainParams& p, const AuxGeom& ag, hipStream_t stream) {
-    const long items = (long)p.N1 * (p.C / 4 + (p.hoist ? 0 : p.Ap / 4) + p.L);
-    const int blocks = (int)((items + 255) / 256 < 4096 ? (items + 255) / 256 : 4096);
-    // aux hoist: the frame-rate projections PA are extra workgroups of this launch (they need k_refresh's packed biases: the launch before)
-    const int naux = p.hoist ? (p.nfr + 1 + AUXP_FPB - 1) / AUXP_FPB * p.L : 0;
-    const size_t lds = p.hoist ? (size_t)(2 * p.C * p.A + p.A * AUXP_FPB + 8) * sizeof(float) : 0;
-    hipLaunchKernelGGL(k_train_prep, dim3(blocks + naux, p.B), dim3(256), lds, stream, p, ag, blocks);
+// ------------------------------------------------------------------ host launchers (called from train_host.hip): they carry out a plan of train_launch_plan.h
+void qpn_launch_prep(const TrainParams& p, const AuxGeom& ag, hipStream_t stream) {      // (also the GEMM step's first launch)
+    int blocks = 0;
+    const TlpLaunch l = tlp_prep_launch(p.C, p.Ap, p.L, p.A, p.B, p.N1, p.hoist != 0, p.nfr, &blocks);
+    hipLaunchKernelGGL(k_train_prep, dim3(l.gx, l.gy), dim3(l.block), l.lds, stream, p, ag, blocks);
 }
 
-// the fused first launch (k_step_prep): whether this geometry takes it, and the launch.  Four workgroups of the launch per CU must stay resident
-// (its gather roles live on occupancy): 40 KB of dynamic LDS at most -- n_quantize up to 288 at 16 channels per table slice; larger tables keep
-// k_refresh + k_train_prep
-static size_t step_prep_lds_x0(const TrainParams& p, int rpg) { return ((size_t)2 * p.Q * X0_ST + 2 * (size_t)rpg) * sizeof(float); }
-static int step_prep_rpg(const TrainParams& p) {
-    const int64_t R = (int64_t)p.B * p.N1;
-    const int64_t rpg = (R + 127) / 128;                    // ~128 row groups: 128 x (C / 16) workgroups x 32 KB of L2 reads = 16 MB
-    return (int)(rpg < 16 ? 16 : rpg > X0_RPG ? X0_RPG : rpg);
-}
-bool qpn_step_prep_fits(const TrainParams& p) {
-    if (p.C % X0_CS || p.Q % 2 || p.causal_w % 4 || ((uintptr_t)p.flat & 15) || (p.hoist && p.A > 64)) return false;
-    return step_prep_lds_x0(p, X0_RPG) <= 40 * 1024;
-}
-void qpn_launch_step_prep(const TrainParams& p, const AuxGeom& ag, const RefreshArgs& rf, hipStream_t stream) {
-    StepPrepPlan pl;
-    pl.rpg = step_prep_rpg(p);
-    pl.nx0 = (int)(((int64_t)p.B * p.N1 + pl.rpg - 1) / pl.rpg) * (p.C / X0_CS);
-    pl.naux = p.hoist ? (p.nfr + 1 + AUXP_FPB - 1) / AUXP_FPB * p.L * p.B : 0;
-    pl.nbias = (rf.nb + 64 + 255) / 256;
-    pl.nwt = (int)((rf.nw + 1023) / 1024);
-    const long items = (long)p.N1 * ((p.hoist ? 0 : p.Ap / 4) + p.L);
-    pl.nprep = (int)((items + 255) / 256 < 4096 ? (items + 255) / 256 : 4096);
-    if (pl.nprep < 1) pl.nprep = 1;
-    size_t lds = step_prep_lds_x0(p, pl.rpg);
-    const size_t lds_aux = p.hoist ? (size_t)(2 * p.C * p.A + p.A * AUXP_FPB + 8) * sizeof(float) : 0;
-    if (lds_aux > lds) lds = lds_aux;
-    hipLaunchKernelGGL(k_step_prep, dim3((unsigned)(pl.nx0 + pl.naux + pl.nbias + pl.nwt + pl.nprep * p.B)), dim3(256), lds, stream, p, ag, rf, pl);
+int qpn_launch_stack_fwd(const TrainParams& p, const StackQ& q, const TrainFwdPlan& pl, hipStream_t stream);
+void qpn_launch_post_fb(const TrainParams& p, const TrainBwd& bw, const TlpLaunch& l, hipStream_t stream);      // train_bwd.hip: k_post_fb_w
+
+// the persistent layer kernel of a plan: <8 | 11, last layer>
+typedef void (*LayerFwdP)(TrainParams, int, int, int, float*);
+static LayerFwdP layer_fwd_p(int form, bool last) {
+    return form == 8 ? (last ? k_layer_fwd_p<8, true> : k_layer_fwd_p<8, false>) : (last ? k_layer_fwd_p<11, true> : k_layer_fwd_p<11, false>);
 }
 
-bool qpn_stack_fwd_fits(const TrainParams& p);
-int qpn_launch_stack_fwd(const TrainParams& p, const StackQ& q, const TrainKnobs& k, hipStream_t stream);
-
-void qpn_launch_post_fb(const TrainParams& p, const TrainBwd& bw, hipStream_t stream);      // train_bwd.hip: k_post_fb_w
-
-// fuse_post_bwd: the post-net's backward runs inside this launch sequence too (the caller has checked the geometry: the wide tiles, cross entropy fused)
-// rf != nullptr: the per-step refresh has NOT been launched: it runs as roles of the prep launch (k_step_prep; the caller has asked qpn_step_prep_fits)
-int qpn_launch_fwd(const TrainParams& p, const TrainKnobs& k, const AuxGeom& ag, const StackQ* sq, hipStream_t stream, const TrainBwd* fuse_post_bwd, const RefreshArgs* rf) {
-    const int C = p.C, S = p.S;
-    if (rf) qpn_launch_step_prep(p, ag, *rf, stream);
-    else qpn_launch_prep(p, ag, stream);
+// fuse_post_bwd: the buffers of the post-net's backward (pl.post == TLP_POST_FB: it runs inside this launch sequence);  rf: what the refresh gathers
+// (pl.fuse_prep: it has NOT been launched and runs as roles of the prep launch)
+int qpn_launch_fwd(const TrainParams& p, const TrainFwdPlan& pl, const AuxGeom& ag, const StackQ& sq, hipStream_t stream, const TrainBwd& fuse_post_bwd, const RefreshArgs& rf) {
+    if (pl.fuse_prep) hipLaunchKernelGGL(k_step_prep, dim3(pl.prep.gx), dim3(pl.prep.block), pl.prep.lds, stream, p, ag, rf, pl.roles);
+    else hipLaunchKernelGGL(k_train_prep, dim3(pl.prep.gx, pl.prep.gy), dim3(pl.prep.block), pl.prep.lds, stream, p, ag, pl.prep_blocks);
     qpn_prof_mark(PG_PREP, stream);
-    // 16-row tiles everywhere (twice the workgroups of 32-row tiles, all co-resident: measured 8-15 % faster for the layer and post-net kernels)
-    const size_t lds_layer = (size_t)16 * (tr_lda(p.Ktp) + tr_lda(C)) * sizeof(float);
-    const size_t lds_post = (size_t)16 * (tr_lda(S) + (tr_lda(S) > 2 * tr_lda(C) ? tr_lda(S) : 2 * tr_lda(C))) * sizeof(float);
-    if (lds_layer > 160 * 1024 || lds_post > 160 * 1024) {
-        qpn_set_error("training kernels: tiles do not fit the 160 KiB LDS for n_resch=%d n_skipch=%d (n_resch <= 128 supported)", C, S);
-        return QPN_EINVAL;
-    }
-    {
-        const int flags0 = k.xcd_swizzle ? 2 : 0;
-        // persistent register-resident form (n_resch 64, K = 176): 2 workgroups per CU; QPN_LAYER_PERSIST=0 keeps the tile-per-workgroup launches
-        const bool persist = C == 64 && (p.Ktp == 176 || p.hoist) && p.N1 < (1 << 24) && k.persist_fwd;      // (N1 < 2^24: 32-bit element offsets of one batch item)
-        if (p.hoist && !persist) { qpn_set_error("internal: the frame-rate aux term needs the register-resident layer kernels"); return QPN_EINVAL; }
-        // the whole stack as ONE persistent launch over a (layer, tile) work queue (train_stack.hip); QPN_STACK_QUEUE=0 keeps a launch per layer
-        const bool stack_q = persist && k.stack_q_fwd && sq && sq->flags && p.qctl && qpn_stack_fwd_fits(p);
-        if (stack_q) {
-            const int rcq = qpn_launch_stack_fwd(p, *sq, k, stream);
-            if (rcq) return rcq;
-        }
-        for (int l = 0; l < p.L && !stack_q; ++l) {
-            const int rows = p.N1 - p.layers[l].s_out;
-            const int tiles = (rows + 15) / 16;
-            if (persist) {
-                int G = qpn_num_cus() * 2; if (G > tiles) G = tiles;
-                if (G > 1024) G = 1024;                            // (scratch_rows holds a pair of rows for 1024 workgroups per batch item)
-                const size_t ldsp = (size_t)(32 * tr_lda(p.Ktp) + 4 * 16 * tr_lda(64)) * sizeof(float);
-                const bool last = l == p.L - 1;
-                if (p.hoist) {
-                    if (last) hipLaunchKernelGGL((k_layer_fwd_p<8, true>), dim3(G, p.B), dim3(256), ldsp, stream, p, l, flags0, tiles, p.scratch_rows);
-                    else hipLaunchKernelGGL((k_layer_fwd_p<8, false>), dim3(G, p.B), dim3(256), ldsp, stream, p, l, flags0, tiles, p.scratch_rows);
-                } else {
-                    if (last) hipLaunchKernelGGL((k_layer_fwd_p<11, true>), dim3(G, p.B), dim3(256), ldsp, stream, p, l, flags0, tiles, p.scratch_rows);
-                    else hipLaunchKernelGGL((k_layer_fwd_p<11, false>), dim3(G, p.B), dim3(256), ldsp, stream, p, l, flags0, tiles, p.scratch_rows);
-                }
-            } else {
-                if (lds_layer > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_layer_fwd<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_layer);
-                hipLaunchKernelGGL((k_layer_fwd<1>), dim3(tiles, p.B), dim3(256), lds_layer, stream, p, l, (l == p.L - 1 ? 1 : 0) | flags0);
-            }
+    if (pl.path == TLP_STACK) {
+        const int rcq = qpn_launch_stack_fwd(p, sq, pl, stream);
+        if (rcq) return rcq;
+    } else for (int l = 0; l < p.L; ++l) {
+        const TlpLaunch& y = pl.layer[l];
+        if (pl.path == TLP_PERSIST) hipLaunchKernelGGL(layer_fwd_p(pl.form, l == p.L - 1), dim3(y.gx, y.gy), dim3(y.block), y.lds, stream, p, l, pl.flags0, p.qT[l], p.scratch_rows);
+        else {
+            if (y.lds > TLP_LDS_OPTIN) (void)hipFuncSetAttribute((const void*)k_layer_fwd<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)y.lds);
+            hipLaunchKernelGGL((k_layer_fwd<1>), dim3(y.gx, y.gy), dim3(y.block), y.lds, stream, p, l, (l == p.L - 1 ? 1 : 0) | pl.flags0);
         }
     }
     qpn_prof_mark(PG_LAYER_FWD, stream);
-    // wide post-net tiles (S = Q = 256, n_resch 64): 16 * MT rows per workgroup, MT chosen so that the chunk is one round of workgroups
-    const bool post_wide = S == 256 && p.Q == 256 && C == 64 && k.post_wide;
-    if (post_wide && fuse_post_bwd) qpn_launch_post_fb(p, *fuse_post_bwd, stream);
-    else if (post_wide) {
-        constexpr int MTW = 5;
-        const size_t ldsw = (size_t)16 * MTW * (tr_lda(256) + 2 * tr_lda(64)) * sizeof(float);
-        QPN_HIP(hipFuncSetAttribute((const void*)k_post_fwd_w<MTW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw));
-        hipLaunchKernelGGL((k_post_fwd_w<MTW>), dim3((p.BL + 16 * MTW - 1) / (16 * MTW), p.B), dim3(512), ldsw, stream, p);
+    const TlpLaunch& w = pl.post_l;
+    if (pl.post == TLP_POST_FB) qpn_launch_post_fb(p, fuse_post_bwd, w, stream);
+    else if (pl.post == TLP_POST_WIDE) {
+        QPN_HIP(hipFuncSetAttribute((const void*)k_post_fwd_w<TLP_POST_MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.lds));
+        hipLaunchKernelGGL((k_post_fwd_w<TLP_POST_MT>), dim3(w.gx, w.gy), dim3(w.block), w.lds, stream, p);
     } else {
-        if (lds_post > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_post_fwd<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_post);
-        hipLaunchKernelGGL((k_post_fwd<1>), dim3((p.BL + 15) / 16, p.B), dim3(512), lds_post, stream, p);
+        if (w.lds > TLP_LDS_OPTIN) (void)hipFuncSetAttribute((const void*)k_post_fwd<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.lds);
+        hipLaunchKernelGGL((k_post_fwd<1>), dim3(w.gx, w.gy), dim3(w.block), w.lds, stream, p);
     }
     qpn_prof_mark(PG_POST_FWD, stream);
     QPN_HIP(hipGetLastError());

@@ -8,11 +8,9 @@
 #include <memory>
 #include <string.h>
 
-int qpn_launch_fwd(const TrainParams& p, const TrainKnobs& k, const AuxGeom& ag, const StackQ* sq, hipStream_t stream, const TrainBwd* fuse_post_bwd, const RefreshArgs* rf);
-bool qpn_step_prep_fits(const TrainParams& p);
-void qpn_stack_fill(TrainParams& p);
+int qpn_launch_fwd(const TrainParams& p, const TrainFwdPlan& pl, const AuxGeom& ag, const StackQ& sq, hipStream_t stream, const TrainBwd& fuse_post_bwd, const RefreshArgs& rf);
 static CeOpts ce_opts_of(const qpn_loss_opts& o, double* mass, double* d_mass);
-int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainKnobs& k, const AuxGeom& ag, const StackQ* sq, hipStream_t stream, bool post_done);
+int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainBwdPlan& pl, const AuxGeom& ag, const StackQ& sq, hipStream_t stream);
 int qpn_launch_fwd_gemm(const TrainParams& p, const TrainGemm& w, hipStream_t stream);
 int qpn_launch_bwd_gemm(const TrainParams& p, const TrainBwd& bw, const TrainGemm& w, hipStream_t stream);
 
@@ -23,12 +21,13 @@ static double loss_sum(const double* parts) { double sum = 0.0; for (int i = 0; 
 // Every member has a default: a state under construction is destroyable at any point (qpn_train_destroy frees what is there)
 struct TrainState {
     TrainLayout lay;                          // what train_plan decided (train_plan.h): the path, hoist, block / bias / slab offsets (bw.sl points at lay.slabs), early_first
-    int64_t n_map = 0;                        // entries of the uploaded gather map (fragment-ordered blocks, or the GEMM path's K-major ones): what the refresh gathers
     int* d_wmap = nullptr; float* d_wp = nullptr; int* d_bstart = nullptr; int* d_blist = nullptr; float* d_bp = nullptr;
-    int* d_gdst = nullptr; int* d_gdst_list = nullptr; int* d_gzero = nullptr; int n_gzero = 0;
+    int* d_gdst = nullptr; int* d_gdst_list = nullptr; int* d_gzero = nullptr;
     TrainParams tp = {};                      // template with block offsets filled in
     TrainBwd bw = {};
     TrainKnobs knobs = {};                    // launch-plan knobs, parsed once (qpn_train_knobs_parse)
+    TrainShape shape; TrainFwdPlan fplan; TrainBwdPlan bplan;      // what the latest forward / backward launched (train_launch_plan.h)
+    std::string plan_text;                    // qpn_train_last_plan: built when asked for
     AuxGeom ag = {};                          // aux hoist: per-layer offsets for k_aux_proj / k_aux_tail (s_out refreshed per forward)
     // workspaces (grow only)
     float* d_ws = nullptr; size_t ws_cap = 0; // one arena, carved per call (train_arena)
@@ -53,7 +52,6 @@ struct TrainState {
     hipEvent_t ev_early = nullptr; int early_recorded = 0;   // qpn_train_early_bucket: the flat-gradient tail (from lay.early_first) that is final before the layer backward ends
     int64_t bwd_generation = -1;                             // generation of the forward the last backward belonged to
     const float* post_bwd_dlogits = nullptr;                 // ... on this dL/dlogits buffer
-    bool post_bwd_done = false;                              // the last forward ran the post-net's backward too (k_post_fb_w: qpn_train_step)
     bool stack_disabled = false;                             // a stack-queue launch gave up once (status bit 4): this handle keeps to a launch per layer
     unsigned* d_sq = nullptr; size_t sq_pos_cap = 0, sq_per_dir = 0;         // stack work queues (train_stack.hip): [16 control words | forward flags | backward flags]
     StackQ sqf = {}, sqb = {};
@@ -202,7 +200,6 @@ static int train_init(qpn_handle* h) {
 
     int rc;
     const std::vector<int>& wmap = pl.use_gemm ? pl.h_gmap : pl.h_wmap;
-    t->n_map = (int64_t)wmap.size();
     if (pl.use_gemm) {
         rc = upload(&t->d_gmap, wmap); if (rc) return rc;
         QPN_HIP(hipMalloc(&t->d_gwp, wmap.size() * sizeof(float)));
@@ -217,7 +214,6 @@ static int train_init(qpn_handle* h) {
     rc = upload(&t->d_gdst, pl.gdst_start); if (rc) return rc;
     rc = upload(&t->d_gdst_list, pl.gdst_list); if (rc) return rc;
     rc = upload(&t->d_gzero, pl.gzero, 1); if (rc) return rc;
-    t->n_gzero = (int)pl.gzero.size();
     rc = upload(&t->d_ctmap, pl.h_ctmap); if (rc) return rc;
     QPN_HIP(hipMalloc(&t->d_ct, pl.h_ctmap.size() * sizeof(float)));
     QPN_HIP(hipMalloc(&t->d_status, 64));
@@ -306,29 +302,19 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
         if (cap_st != hipStreamCaptureStatusNone) { qpn_set_error("qpn_train_loss_opts: an armed forward cannot be captured (the arm is host state a replay would not renew)"); return QPN_ESTATE; }
         if (lo.norm == 1 && !t->d_mass) QPN_HIP(hipMalloc(&t->d_mass, 72 * sizeof(double)));
     }
-    const int64_t N0 = (int64_t)g.recA * maxd + g.recF + 1 + BL;           // qpnet.py:254-262
-    if (N0 > T || N0 - 1 > Td || N0 - 1 > (g.U > 0 ? F * g.U : F)) {
-        qpn_set_error("chunk too short: need receptive field (%lld) + batch_length (%d) = %lld samples, have x:%lld d:%lld h_up:%lld",
-                      (long long)(N0 - BL), BL, (long long)N0, (long long)T, (long long)Td, (long long)(g.U > 0 ? F * g.U : F));
-        return QPN_EINVAL;
+    // ---- the call's shape (train_launch_plan.h): rows, the layers' first valid rows and tap tables, the frames the rows touch, the queue positions -- or a refusal
+    {
+        const TrainShape shape = train_shape(g, t->lay, B, T, F, Td, BL, maxd);
+        if (shape.rc) return shape.rc;      // (the state still describes the previous forward)
+        t->shape = shape;
     }
-    if (T >= ((int64_t)1 << 31) || Td >= ((int64_t)1 << 31) || F * (g.U > 0 ? g.U : 1) >= ((int64_t)1 << 31) || (int64_t)B * N0 >= ((int64_t)1 << 31)) {
-        qpn_set_error("chunk too long: the training kernels index rows with 32 bits"); return QPN_EINVAL;
-    }
+    const TrainShape& sh = t->shape;
     TrainParams& p = t->tp;
-    p.B = B; p.T = (int)T; p.F = (int)F; p.Td = (int)Td; p.BL = BL; p.N0 = (int)N0; p.N1 = (int)N0 - 1; p.maxd = maxd;
+    p.B = B; p.T = sh.T; p.F = sh.F; p.Td = sh.Td; p.BL = BL; p.N0 = sh.N0; p.N1 = sh.N1; p.maxd = maxd; p.ffirst = sh.ffirst; p.nfr = sh.nfr;
     const int L = g.L, N1 = p.N1;
-    int s = 0, nA = 0;
-    for (int l = 0; l < L; ++l) {
-        TrLayer& ly = p.layers[l];
-        ly.s_in = s; s += ly.adaptive ? ly.dilation * maxd : ly.dilation; ly.s_out = s;
-        ly.tap_off = (nA++) * B * N1;          // every layer gets a tap table (fixed layers: n - dilation), so the kernels load taps unconditionally
-        t->ag.s_out[l] = ly.s_out;
-    }
-    if (t->lay.hoist) {
-        if (N1 >= (1 << 24)) { qpn_set_error("chunk too long for the register-resident layer kernels (%d rows; QPN_AUX_HOIST=0 QPN_LAYER_PERSIST=0 QPN_LAYER_BWD_PERSIST=0 selects the tile-per-workgroup kernels)", N1); return QPN_EINVAL; }
-        p.ffirst = (int)(((int64_t)F * g.U - N1) / g.U); p.nfr = (int)F - p.ffirst;
-    } else { p.ffirst = 0; p.nfr = 0; }
+    for (int l = 0; l < L; ++l) { TrLayer& ly = p.layers[l]; ly.s_in = sh.s_in[l]; ly.s_out = sh.s_out[l]; ly.tap_off = sh.tap_off[l]; t->ag.s_out[l] = sh.s_out[l]; p.qT[l] = sh.qT[l]; }
+    for (int l = 0; l <= TR_MAXL; ++l) p.qP[l] = sh.qP[l];
+    p.qtotal = sh.qtotal;
     // ---- carve the arena: ONE list (train_arena) gives its size and every buffer's place
     const TrainArena a = train_arena(t->lay, g, B, N1, BL, p.nfr);
     if (a.total > t->ws_cap) {
@@ -338,7 +324,7 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
         if (e != hipSuccess) { qpn_set_error("hipMalloc(%zu MiB) for the training workspace failed", a.total * 4 >> 20); return QPN_ENOMEM; }
         t->ws_cap = a.total;
     }
-    const size_t ntap = (size_t)std::max(nA, 1) * B * N1;
+    const size_t ntap = (size_t)std::max(L, 1) * B * N1;
     if (ntap > t->tap_cap) {
         if (t->d_tap) (void)hipFree(t->d_tap);
         t->d_tap = nullptr; t->tap_cap = 0;
@@ -359,7 +345,6 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
     {   // stack work queues (train_stack.hip): a flag word per (layer, batch item, 16-row tile) and direction, compared with a per-forward epoch
         // (zeroed only when (re)allocated), and the tile tables k_train_prep writes.  The regions keep their places for the life of an
         // allocation (sized for 1.5x the positions that forced it): a table word of an earlier step must never be read as a flag
-        qpn_stack_fill(p);
         if ((size_t)p.qtotal > t->sq_pos_cap) {
             if (t->d_sq) (void)hipFree(t->d_sq);
             t->d_sq = nullptr; t->sq_pos_cap = 0;
@@ -385,32 +370,36 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
         bq.flags = f.flags + t->sq_per_dir; bq.head = f.head + 8 * TR_QHEAD_STRIDE; bq.abort = f.abort; bq.stats = t->d_sq + 8; bq.epoch = epoch; bq.total = p.qtotal; bq.tab = p.qtab_b;
     }
     p.flat = d_flat; p.wp = (const float4*)t->d_wp; p.bp = t->d_bp; p.x = d_x; p.h = d_h; p.d = d_dfac; p.logits = d_logits;
-    // ---- refresh the fragment-ordered weights / packed biases from the current parameters: a launch of its own, or (tile path, causal table slices
-    //      that fit: qpn_step_prep_fits; QPN_PREP_FUSE=0 switches it off) roles of the prep launch -- then nothing is launched here
+    // ---- what this forward launches (train_launch_plan.h): the facts of the call, then the plan -- or a refusal, before anything is launched
+    TrainFwdFacts ff;
+    ff.cus = qpn_num_cus(); ff.queues_usable = p.qctl != nullptr; ff.flat_aligned16 = ((uintptr_t)d_flat & 15) == 0;
+    ff.targets = d_targets != nullptr; ff.want_logits = want_logits != 0; ff.dlogits = d_dlogits != nullptr; ff.fuse_bwd = fuse_bwd;
+    ff.soft_targets = d_teacher != nullptr; ff.loss_opts = lo_armed;
+    t->fwd_valid = false;
+    t->fplan = train_fwd_plan(g, t->lay, t->knobs, sh, ff);
+    const TrainFwdPlan& fp = t->fplan;
+    if (fp.rc) return fp.rc;
+    // ---- refresh the fragment-ordered weights / packed biases from the current parameters: a launch of its own, or (fp.fuse_prep: tile path, causal table
+    //      slices that fit; QPN_PREP_FUSE=0 switches it off) roles of the prep launch -- then nothing is launched here
     RefreshArgs rf;
-    bool fuse_prep;
     {
         const int* wmap = t->lay.use_gemm ? t->d_gmap : t->d_wmap;
         float* wout = t->lay.use_gemm ? t->d_gwp : t->d_wp;
-        const int64_t nw = t->n_map, nct = (int64_t)2 * g.Q * g.C;
-        const int64_t tot = nw + nct + t->lay.n_bias + 16 + 64;
+        const int64_t nw = t->lay.n_map, nct = (int64_t)2 * g.Q * g.C;
         rf.wmap = wmap; rf.wout = wout; rf.nw = nw; rf.bstart = t->d_bstart; rf.blist = t->d_blist; rf.nb = t->lay.n_bias; rf.loss = t->d_loss;
-        fuse_prep = t->knobs.prep_fuse && !t->lay.use_gemm && qpn_step_prep_fits(p);
-        if (!fuse_prep)
-            hipLaunchKernelGGL(k_refresh, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, d_flat, wmap, wout, nw, t->d_ctmap, t->d_ct, nct,
+        if (!fp.fuse_prep)
+            hipLaunchKernelGGL(k_refresh, dim3(fp.refresh.gx), dim3(fp.refresh.block), 0, stream, d_flat, wmap, wout, nw, t->d_ctmap, t->d_ct, nct,
                                t->d_bstart, t->d_blist, t->d_bp, t->lay.n_bias, t->d_status, t->d_loss);
         p.ct = t->d_ct;
     }
     qpn_prof_mark(PG_PREP, stream);
-    t->fwd_valid = false; t->loss_clear = true;
+    t->loss_clear = true;
     ++t->generation;
-    const bool fuse_ce = d_targets && !t->lay.use_gemm && g.Q <= g.S && g.Q % 256 == 0 && !t->knobs.ce_separate && !d_teacher && !lo_armed;      // (armed: QPN_CE_SEPARATE's route, k_ce_soft / k_ce_hard<NV, true> in the plain kernel's place)
+    const bool fuse_ce = fp.fuse_ce;
     p.ce_tgt = fuse_ce ? d_targets : nullptr; p.ce_stride = tgt_stride; p.ce_dlogits = d_dlogits; p.ce_loss = t->d_loss;
-    if (fuse_ce && !want_logits) p.logits = nullptr;
-    const bool fuse_post = fuse_bwd && fuse_ce && d_dlogits && t->knobs.post_fuse && t->knobs.post_wide && t->knobs.zero_in_post && g.S == 256 && g.Q == 256 && g.C == 64 && (p.LC == 256 || p.LC == 512);
-    t->post_bwd_done = false;
-    rc = t->lay.use_gemm ? qpn_launch_fwd_gemm(p, t->gm, stream) : qpn_launch_fwd(p, t->knobs, t->ag, &t->sqf, stream, fuse_post ? &t->bw : nullptr, fuse_prep ? &rf : nullptr);
-    if (!rc) { t->post_bwd_done = fuse_post; t->post_bwd_dlogits = d_dlogits; }
+    if (!fp.store_logits) p.logits = nullptr;
+    rc = t->lay.use_gemm ? qpn_launch_fwd_gemm(p, t->gm, stream) : qpn_launch_fwd(p, fp, t->ag, t->sqf, stream, t->bw, rf);
+    t->post_bwd_dlogits = d_dlogits;
     p.ce_tgt = nullptr; p.logits = d_logits;
     if (rc) return rc;
     t->fwd_valid = true;
@@ -753,17 +742,29 @@ extern "C" int qpn_train_backward_ex(qpn_handle* h, const float* d_dlogits, floa
         if (cap_st != hipStreamCaptureStatusNone) { qpn_set_error("qpn_train_input_grad: an armed backward cannot be captured (the arm is host state a replay would not renew)"); return QPN_ESTATE; }
         bw.dh = d_dh;
     }
-    bw.dlogits = d_dlogits; bw.gflat = d_flatgrad; bw.gdst = t->d_gdst; bw.gdst_list = t->d_gdst_list; bw.gzero = t->d_gzero; bw.n_gzero = t->n_gzero;
+    bw.dlogits = d_dlogits; bw.gflat = d_flatgrad; bw.gdst = t->d_gdst; bw.gdst_list = t->d_gdst_list; bw.gzero = t->d_gzero; bw.n_gzero = t->lay.n_gzero;
     bw.gscale = grad_scale; bw.append_scale = append_scale; bw.status = h->train->d_status;
     bw.side = t->side; bw.ev_fork = t->ev_fork; bw.ev_join = t->ev_join; bw.ev_mid = t->ev_mid;
     t->early_recorded = 0; bw.ev_early = t->ev_early; bw.early_recorded = (append_scale && t->lay.early_first >= 0) ? &t->early_recorded : nullptr;
-    // (the backward queue's heads and flags belong to ONE backward per forward: a repeated backward of the same forward runs a launch per layer)
-    const bool first_bwd = t->bwd_generation != t->generation;
+    // ---- what this backward launches (train_launch_plan.h).  The backward queue's heads and flags belong to ONE backward per forward: a repeated backward of
+    //      the same forward runs a launch per layer, and its own post-net backward
+    TrainBwdFacts bf;
+    bf.cus = qpn_num_cus(); bf.side_stream = t->side != nullptr; bf.prof_serial = qpn_prof_serial(); bf.gdst = t->d_gdst != nullptr; bf.append_scale = append_scale;
+    bf.feature_grad = bw.dh != nullptr; bf.first_bwd = t->bwd_generation != t->generation; bf.same_dlogits = d_dlogits == t->post_bwd_dlogits;
     t->bwd_generation = t->generation;
-    const bool post_done = t->post_bwd_done && first_bwd && d_dlogits == t->post_bwd_dlogits;      // (a repeated backward, or another dL/dlogits: the separate kernel)
-    t->post_bwd_done = false;
-    return t->lay.use_gemm ? qpn_launch_bwd_gemm(t->tp, bw, t->gm, (hipStream_t)stream_)
-                       : qpn_launch_bwd(t->tp, bw, t->knobs, t->ag, first_bwd ? &t->sqb : nullptr, (hipStream_t)stream_, post_done);
+    t->bplan = train_bwd_plan(h->g, t->lay, t->knobs, t->shape, t->fplan, bf);
+    if (t->bplan.rc) return t->bplan.rc;
+    return t->lay.use_gemm ? qpn_launch_bwd_gemm(t->tp, bw, t->gm, (hipStream_t)stream_) : qpn_launch_bwd(t->tp, bw, t->bplan, t->ag, t->sqb, (hipStream_t)stream_);
+}
+
+// The forward's and the backward's plan of the handle's latest training calls as one line of text each (train_launch_plan.h: plan_text), "fwd[...] ... | bwd[...] ...".
+// Formatted here, on request: a step formats nothing.  The handle owns the text; it is valid until the next training call
+extern "C" const char* qpn_train_last_plan(qpn_handle* h) {
+    if (!h || !h->train) return "";
+    TrainState* t = h->train;
+    t->plan_text = t->generation > 0 ? plan_text(h->g, t->lay, t->shape, t->fplan) : std::string();
+    if (t->bwd_generation == t->generation && t->generation > 0) t->plan_text += " | " + plan_text(h->g, t->lay, t->shape, t->bplan);
+    return t->plan_text.c_str();
 }
 
 extern "C" int qpn_train_early_bucket(qpn_handle* h, int64_t* first, int64_t* count, void* stream_) {

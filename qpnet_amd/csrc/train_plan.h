@@ -97,6 +97,8 @@ struct TrainLayout {
     TrainPlanLayer layers[TR_MAXL] = {};
     int ws_f4 = 0, p1_f4 = 0, p2_f4 = 0, wst_f4 = 0, p1t_f4 = 0, p2t_f4 = 0, bias_s = 0, bias_p1 = 0, bias_p2 = 0;
     int n_bias = 0;
+    int64_t n_map = 0;                         // entries of the uploaded gather map (fragment-ordered blocks, or the GEMM path's K-major ones): what the refresh gathers
+    int n_gzero = 0;                           // flat-grad entries no slab element feeds (TrainPlan::gzero)
     TrainSlabs slabs = {};                     // weight-grad staging space ("slab")
     int gstage = 0, nch = 0;                   // floats of one slab; time chunks (= partial slabs)
     int64_t early_first = -1;                  // first flat index of the tail that is final before the layer backward ends (the post-net blocks), or -1
@@ -250,6 +252,7 @@ inline TrainPlan train_plan(const Geom& g, const TrainKnobs& knobs, bool use_gem
     }
     t.h_ctmap.resize((size_t)2 * Q * C);
     for (int tp = 0; tp < 2; ++tp) for (int q = 0; q < Q; ++q) for (int c = 0; c < C; ++c) t.h_ctmap[((size_t)tp * Q + q) * C + c] = tp_idx(tp_causal_src(g, c, q, tp));
+    t.n_map = (int64_t)(use_gemm ? t.h_gmap.size() : t.h_wmap.size()); t.n_gzero = (int)t.gzero.size();
     return t;
 }
 

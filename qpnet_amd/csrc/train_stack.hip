@@ -38,7 +38,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #define SQ_OOB 0x80000000u                          // a buffer offset beyond every descriptor's range: the access is dropped
 #define SQ_SPIN_LIMIT (1u << 22)                    // polls of ~1-2 us: several seconds
 #define SQ_FLINE 1056u                              // words between the 128-byte lines of the flag array
-#define SQ_NQ 8                                     // sub-queues (head words 128 bytes apart)
+// (SQ_NQ = 8 sub-queues, head words 128 bytes apart: train_launch_plan.h)
 
 __device__ __forceinline__ unsigned sq_ld(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void sq_st(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -784,70 +784,34 @@ __global__ __launch_bounds__(256, 2) void k_stack_bwd(TrainParams p, TrainBwd bw
 // ------------------------------------------------------------------------------------------------ host side
 // tests/test_train_gpu.py::test_stack_queue_that_gives_up_... (a -DQPN_TESTING build, QPN_TEST_STACK_GIVES_UP=1): the published flags carry another
 // value than the consumers expect and the waits are short, so the first dependent tile runs out, raises the abort word and the launch drains
-static void sq_arm(StackQ& q, const TrainKnobs& k) {
-    q.epoch_pub = q.epoch; q.spin_limit = SQ_SPIN_LIMIT;
+static StackQ sq_arm(const StackQ& q0, unsigned nq, bool gives_up) {
+    StackQ q = q0;
+    q.nq = (int)nq; q.epoch_pub = q.epoch; q.spin_limit = SQ_SPIN_LIMIT;
 #ifdef QPN_TESTING
-    if (k.test_stack_gives_up) { q.epoch_pub = q.epoch ^ 0x55555555u; q.spin_limit = 2000u; }
+    if (gives_up) { q.epoch_pub = q.epoch ^ 0x55555555u; q.spin_limit = 2000u; }
 #else
-    (void)k;
+    (void)gives_up;
 #endif
-}
-bool qpn_stack_fwd_fits(const TrainParams& p) {
-    return p.C == 64 && (p.hoist ? p.Ktp == 128 : p.Ktp == 176) && p.L >= 1 && p.L <= TR_MAXL && p.B < 65536 && (int64_t)p.N1 * p.C * 4 <= (1ll << 30) &&
-           (int64_t)(p.L + 1) * p.B * p.N1 < (1ll << 31);
+    return q;
 }
 
-// positions of the queue: layer-major, batch item, tile (rows ascending); the table itself is written on the device by k_train_prep
-void qpn_stack_fill(TrainParams& p) {
-    int pos = 0;
-    for (int l = 0; l < p.L; ++l) {
-        p.qT[l] = (p.N1 - p.layers[l].s_out + 15) / 16;
-        p.qP[l] = pos; pos += p.B * p.qT[l];
-    }
-    for (int l = p.L; l <= TR_MAXL; ++l) p.qP[l] = pos;
-    p.qtotal = pos;
-}
-
+// the queue launches of a plan (train_launch_plan.h: grid, LDS bytes, sub-queues; the positions of the queue are TrainShape's, the table itself is written on the device by the prep launch)
 template <int KS>
-static int launch_stack_fwd_k(const TrainParams& p, const StackQ& q, const TrainKnobs& k, hipStream_t stream) {
-    constexpr int lda = ((16 * KS + 29) / 32) * 32 + 2, ldg = ((64 + 29) / 32) * 32 + 2;
-    const size_t lds = (size_t)(32 * lda + 4 * 16 * ldg) * sizeof(float) + 64;
-    int G = k.stack_wgs > 0 ? k.stack_wgs : qpn_num_cus() * 2;
-    if (G > q.total) G = q.total;
-    if (G > 1024) G = 1024;                                      // (scratch rows: one pair per workgroup)
-    QPN_HIP(hipFuncSetAttribute((const void*)k_stack_fwd<KS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    StackQ qq = q; qq.nq = G / 8 < 1 ? 1 : (G / 8 < SQ_NQ ? G / 8 : SQ_NQ);      // every sub-queue needs a puller (a workgroup's home: (blockIdx / 8) % nq)
-    sq_arm(qq, k);
-    hipLaunchKernelGGL((k_stack_fwd<KS>), dim3(G), dim3(256), lds, stream, p, qq);
+static int launch_stack_fwd_k(const TrainParams& p, const StackQ& q, const TrainFwdPlan& pl, hipStream_t stream) {
+    QPN_HIP(hipFuncSetAttribute((const void*)k_stack_fwd<KS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.stack.lds));
+    hipLaunchKernelGGL((k_stack_fwd<KS>), dim3(pl.stack.gx), dim3(pl.stack.block), pl.stack.lds, stream, p, sq_arm(q, pl.nq, pl.test_stack_gives_up));
     return QPN_OK;
 }
-int qpn_launch_stack_fwd(const TrainParams& p, const StackQ& q, const TrainKnobs& k, hipStream_t stream) {
-    return p.hoist ? launch_stack_fwd_k<8>(p, q, k, stream) : launch_stack_fwd_k<11>(p, q, k, stream);
-}
-
-bool qpn_stack_bwd_fits(const TrainParams& p) {
-    return qpn_stack_fwd_fits(p) && p.Ap <= 64 && (int64_t)p.B * p.BL * p.LC < (1ll << 31) && (int64_t)p.N1 * (p.LC > 2 * p.C ? p.LC : 2 * p.C) < (1ll << 32);
+int qpn_launch_stack_fwd(const TrainParams& p, const StackQ& q, const TrainFwdPlan& pl, hipStream_t stream) {
+    return pl.form == 8 ? launch_stack_fwd_k<8>(p, q, pl, stream) : launch_stack_fwd_k<11>(p, q, pl, stream);
 }
 
 template <int NTK>
-static int launch_stack_bwd_k(const TrainParams& p, const TrainBwd& bw, const StackQ& q, const TrainKnobs& k, hipStream_t stream) {
-    constexpr int ldx = ((64 + 29) / 32) * 32 + 2, ldz = ((128 + 29) / 32) * 32 + 2, ldo = ((16 * NTK + 29) / 32) * 32 + 2;
-    const size_t lds = (size_t)(8 * 16 * ldx + 16 * ldz + 16 * ldo) * sizeof(float) + 128 + 256;      // + control words, + the hoist form's G partials
-    // 1.5 workgroups per CU: the skip / post-net weight gradients run on the side stream while this launch is resident (qpn_launch_bwd), and a
-    // launch that fills every CU twice over leaves them no room -- measured on the overlapped step: 0.846 ms with 2 per CU, 0.776 with 1.5,
-    // 0.778 with 1, 0.790 for the eight per-layer launches
-    // (round 5, the K = 128 form: 1.25 per CU -- 320 -- measured 1411-1415 steps/s against 1375 at 384 and 1365 at 256; counts whose groups of eight
-    //  do not divide evenly over the eight sub-queues -- 304, 336, 352 -- are 3-4 % slower)
-    int G = k.stack_wgs_bwd > 0 ? k.stack_wgs_bwd : (NTK == 8 ? qpn_num_cus() * 5 / 4 / 64 * 64 : qpn_num_cus() * 3 / 2);
-    if (G < 8) G = qpn_num_cus();
-    if (G > q.total) G = q.total;
-    if (G > 1024) G = 1024;
-    QPN_HIP(hipFuncSetAttribute((const void*)k_stack_bwd<NTK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    StackQ qq = q; qq.nq = G / 8 < 1 ? 1 : (G / 8 < SQ_NQ ? G / 8 : SQ_NQ);
-    sq_arm(qq, k);
-    hipLaunchKernelGGL((k_stack_bwd<NTK>), dim3(G), dim3(256), lds, stream, p, bw, qq);
+static int launch_stack_bwd_k(const TrainParams& p, const TrainBwd& bw, const StackQ& q, const TrainBwdPlan& pl, hipStream_t stream) {
+    QPN_HIP(hipFuncSetAttribute((const void*)k_stack_bwd<NTK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.stack.lds));
+    hipLaunchKernelGGL((k_stack_bwd<NTK>), dim3(pl.stack.gx), dim3(pl.stack.block), pl.stack.lds, stream, p, bw, sq_arm(q, pl.nq, pl.test_stack_gives_up));
     return QPN_OK;
 }
-int qpn_launch_stack_bwd(const TrainParams& p, const TrainBwd& bw, const StackQ& q, const TrainKnobs& k, hipStream_t stream) {
-    return p.hoist ? launch_stack_bwd_k<8>(p, bw, q, k, stream) : launch_stack_bwd_k<11>(p, bw, q, k, stream);
+int qpn_launch_stack_bwd(const TrainParams& p, const TrainBwd& bw, const StackQ& q, const TrainBwdPlan& pl, hipStream_t stream) {
+    return pl.form == 8 ? launch_stack_bwd_k<8>(p, bw, q, pl, stream) : launch_stack_bwd_k<11>(p, bw, q, pl, stream);
 }

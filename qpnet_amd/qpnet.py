@@ -160,6 +160,13 @@ class QPNet(nn.Module):
             self._handle, self._handle_dev = hp, device
         return L, self._handle
 
+    @property
+    def last_train_plan(self):
+        """What the latest training forward (and its backward, once run) of this module launched, as text (qpn_train_last_plan); "" before the first one."""
+        if self._handle is None:
+            return ""
+        return _lib.lib().qpn_train_last_plan(self._handle).decode("utf-8", "replace")
+
     def _replicate_for_data_parallel(self):
         """torch.nn.DataParallel with more than one device (the reference wraps the model so, src/bin/qpnet_train.py:416-423, but forces one GPU:
         runQP.py:84-88) would call this once per replica.  The module's state -- the native handle, its workspace with the forward's activations, the

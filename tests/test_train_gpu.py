@@ -193,7 +193,9 @@ def test_backward_launch_arrangements_agree(knobs, cuda, monkeypatch):
     """Where the backward's launches run (side stream or not, early reduction, paired post-net contraction, zeroing inside k_post_bwd_w, the
     residual stack as one work-queue launch per direction or a launch per layer, the queues' grid sizes, the auxiliary 1x1 at frame or at
     sample rate ...) is a set of environment knobs, read once when a module's native training state is created: every arrangement yields the
-    default one's gradient up to the order of float atomics (and, for QPN_AUX_HOIST, of one fp32 reassociation)."""
+    default one's gradient up to the order of float atomics (and, for QPN_AUX_HOIST, of one fp32 reassociation).  The knob did select something:
+    the launch plan the library reports (qpn_train_last_plan) differs from the default's -- QPN_EVENT_FENCE changes event flags only -- and shows
+    what _PLAN_TOKENS says of the setting."""
     import torch
     from qpnet_amd.config import PAPER
     cfg = PAPER
@@ -207,14 +209,61 @@ def test_backward_launch_arrangements_agree(knobs, cuda, monkeypatch):
         logits = m(xt, ht, dt, bt)
         loss = torch.nn.CrossEntropyLoss()(logits.reshape(-1, cfg.n_quantize), tt[:, -BL:].reshape(-1))
         loss.backward()
-        return torch.cat([p.grad.reshape(-1) for p in m.parameters()]).cpu().numpy(), float(loss)
+        return torch.cat([p.grad.reshape(-1) for p in m.parameters()]).cpu().numpy(), float(loss), m.last_train_plan
 
-    g0, l0 = grad()
+    g0, l0, plan0 = grad()
     for k, v in knobs.items():
         monkeypatch.setenv(k, v)
-    g1, l1 = grad()
+    g1, l1, plan1 = grad()
     assert abs(l0 - l1) < 1e-6
     assert np.abs(g0 - g1).max() <= 1e-5 * np.abs(g0).max()
+    assert "fwd[path=stack hoist=1 " in plan0 and " | bwd[path=stack hoist=1 " in plan0 and " side:wr(64)" in plan0 and " early_reduce=1 up_side=1 " in plan0, plan0
+    assert (plan1 == plan0) == (set(knobs) == {"QPN_EVENT_FENCE"}), (plan0, plan1)
+    present, absent = _PLAN_TOKENS.get(",".join("%s=%s" % kv for kv in knobs.items()), ((), ()))
+    for token in present:
+        assert token in plan1, (token, plan1)
+    for token in absent:
+        assert token not in plan1, (token, plan1)
+
+
+# what qpn_train_last_plan must show (and must not show) under a knob setting of the test above
+_PLAN_TOKENS = {
+    "QPN_STACK_QUEUE=0": (("fwd[path=persist ", "bwd[path=persist ", "k_layer_fwd_p<8,1>(", "k_layer_bwd_p<8,1>("), ("k_stack_",)),
+    "QPN_STACK_QUEUE_BWD=0": (("fwd[path=stack ", "k_stack_fwd<8>(", "bwd[path=persist ", "k_layer_bwd_p<8,0>("), ("k_stack_bwd",)),
+    "QPN_LAYER_PERSIST=0,QPN_LAYER_BWD_PERSIST=0": (("fwd[path=generic hoist=0 ", "bwd[path=generic hoist=0 ", "k_layer_fwd<1>(", "k_layer_bwd<1>("), ("k_stack_", "_p<")),
+    "QPN_TRAIN_SERIAL=1": ((" overlap=0 ", " main:skip(", " main:wr("), (" side:", " fork", " mid", " join", " wait")),
+    "QPN_REDUCE_EARLY=0": ((" early_reduce=0 up_side=0 ", " tail=0,0]", " main:k_aux_tail("), (" side:k_reduce_grad_s", " side:k_aux_tail(")),
+    "QPN_WR_SIDE=0": ((" wr_side=0 ", " main:wr(64)"), (" side:wr(",)),
+    "QPN_STACK_WGS_BWD=512": ((" main:k_stack_bwd<8>(512,1,1;256;",), ()),
+    "QPN_STACK_WGS=96,QPN_STACK_WGS_BWD=40": ((" k_stack_fwd<8>(96,1,1;256;", " main:k_stack_bwd<8>(40,1,1;256;"), ()),
+    "QPN_WGRAD_CHUNKS_SIDE=64": ((" nch=64 nch_side=64 ", " side:skip(64)", " side:post(64)x1"), ()),
+    "QPN_WGRAD_CHUNKS=48,QPN_WGRAD_CHUNKS_SIDE=32": ((" nch=48 nch_side=32 ", " side:skip(32)", " main:w1(48)", " side:wr(48)"), ()),
+}
+
+
+def test_launch_plan_names_the_layer_path(cuda):
+    """qpn_train_last_plan after one small forward and backward: TINY (n_resch 32) and the (80, 48, 96) width class run the tile-per-workgroup layer kernels --
+    the latter with the two post-net contractions unpaired (n_skipch != n_quantize) --, the PAPER default the work-queue launch in both directions."""
+    import torch
+    from qpnet_amd.config import TINY, PAPER, QPNetConfig
+    wide = QPNetConfig(n_quantize=96, n_resch=80, n_skipch=48, dilationF_depth=2, dilationF_repeat=1, dilationA_depth=2, dilationA_repeat=1)
+    plans = {}
+    for name, cfg, B in (("tiny", TINY, 1), ("wide", wide, 2), ("paper", PAPER, 1)):
+        x, h, t, d, b = util.distinct_rows_batch(cfg, 300, 61, 2500, B) if B > 1 else synth.train_inputs(cfg, 300, 61, 2500)      # (a chunk of whole frames; the loss takes its last 17 samples)
+        b = np.full_like(b, 17)
+        m = util.build_model(cfg, synth.make_weights(cfg, 7), cuda).train()
+        assert m.last_train_plan == ""
+        xt, ht, dt, bt = _to(cuda, x, h, d, b)
+        logits = m(xt, ht, dt, bt)
+        assert logits.shape[:2] == (B, 17) and " | " not in m.last_train_plan
+        logits.sum().backward()
+        m.check_status()
+        plans[name] = m.last_train_plan
+    for name in ("tiny", "wide"):
+        assert "fwd[path=generic hoist=0 " in plans[name] and " k_layer_fwd<1>(" in plans[name] and " | bwd[path=generic hoist=0 " in plans[name] and " main:k_layer_bwd<1>(" in plans[name], plans[name]
+        assert "_p<" not in plans[name] and "k_stack_" not in plans[name], plans[name]
+    assert " side:post(48)x2" in plans["wide"], plans["wide"]
+    assert "fwd[path=stack hoist=1 " in plans["paper"] and " k_stack_fwd<8>(" in plans["paper"] and " | bwd[path=stack hoist=1 " in plans["paper"] and " main:k_stack_bwd<8>(" in plans["paper"], plans["paper"]
 
 
 def test_full_size_step_vs_oracle(cuda):
