@@ -2,8 +2,7 @@
 //   qpn_train_forward / qpn_train_backward  (QPNet.forward + autograd, reference qpnet.py:239-312)
 //   qpn_ce_loss                              (CrossEntropyLoss mean, reference qpnet_train.py:430,526-528)
 //   qpn_adam_step                            (torch.optim.Adam, reference qpnet_train.py:426-429,531)
-#include "train_common.h"
-#include "qpn_handle.h"
+#include "train_state.h"
 #include <algorithm>
 #include <memory>
 #include <string.h>
@@ -13,49 +12,6 @@ static CeOpts ce_opts_of(const qpn_loss_opts& o, double* mass, double* d_mass);
 int qpn_launch_bwd(const TrainParams& p, const TrainBwd& bw, const TrainBwdPlan& pl, const AuxGeom& ag, const StackQ& sq, hipStream_t stream);
 int qpn_launch_fwd_gemm(const TrainParams& p, const TrainGemm& w, hipStream_t stream);
 int qpn_launch_bwd_gemm(const TrainParams& p, const TrainBwd& bw, const TrainGemm& w, hipStream_t stream);
-
-// a pinned loss slot: the 64 partial sums, then the gradient norm of the same step (gradient-norm clipping)
-#define LOSS_SLOT 72
-static double loss_sum(const double* parts) { double sum = 0.0; for (int i = 0; i < 64; ++i) sum += parts[i]; return sum; }      // the loss of a step: its 64 partial sums, in order
-
-// Every member has a default: a state under construction is destroyable at any point (qpn_train_destroy frees what is there)
-struct TrainState {
-    TrainLayout lay;                          // what train_plan decided (train_plan.h): the path, hoist, block / bias / slab offsets (bw.sl points at lay.slabs), early_first
-    int* d_wmap = nullptr; float* d_wp = nullptr; int* d_bstart = nullptr; int* d_blist = nullptr; float* d_bp = nullptr;
-    int* d_gdst = nullptr; int* d_gdst_list = nullptr; int* d_gzero = nullptr;
-    TrainParams tp = {};                      // template with block offsets filled in
-    TrainBwd bw = {};
-    TrainKnobs knobs = {};                    // launch-plan knobs, parsed once (qpn_train_knobs_parse)
-    TrainShape shape; TrainFwdPlan fplan; TrainBwdPlan bplan;      // what the latest forward / backward launched (train_launch_plan.h)
-    std::string plan_text;                    // qpn_train_last_plan: built when asked for
-    AuxGeom ag = {};                          // aux hoist: per-layer offsets for k_aux_proj / k_aux_tail (s_out refreshed per forward)
-    // workspaces (grow only)
-    float* d_ws = nullptr; size_t ws_cap = 0; // one arena, carved per call (train_arena)
-    int* d_tap = nullptr; size_t tap_cap = 0;
-    double* d_loss3 = nullptr;                // qpn_distill_loss(h_loss3): 2 x 64 slots for the loss's two components, allocated by the first call that asks for them
-    double* d_mass = nullptr;                 // loss options: 64 slots for the effective sum of weights + [64] the word k_weight_mass writes, allocated by the first call that needs them
-    int* d_status = nullptr; double* d_loss = nullptr;   // d_status: 16 words -- [0] the sticky status word, [2..3] the count of Adam updates applied (k_adam)
-    hipStream_t last_stream = nullptr;        // the stream of the latest training call (where a collected status word is cleared)
-    int* h_status_pinned = nullptr; hipEvent_t ev_status[2] = {}; bool status_pending[2] = {}; int status_newest = 0;      // qpn_train_status_enqueue / _collect: the deferred check, two slots
-    double* h_loss_pinned = nullptr; hipEvent_t ev_loss[2] = {}; bool loss_pending[2] = {}; int loss_newest = 0;            // qpn_train_loss_enqueue / _collect: the loss read one step late, two slots of LOSS_SLOT doubles
-    // gradient-norm clipping (qpn_adam_step_clip): d_gnorm = TR_GN_BLOCKS partial sums of squares; the norm word a clipping k_adam leaves is d_loss[64] (one copy takes both out)
-    double* d_gnorm = nullptr; bool gnorm_last = false;      // gnorm_last: the latest Adam launch on this handle clipped (the norm word is that launch's)
-    bool gnorm_slot[2] = {};                  // loss slot i carries a norm
-    double gnorm_collected = 0.0; bool gnorm_collected_valid = false;      // the norm that came with the loss the last qpn_train_loss_collect returned
-    bool fwd_valid = false;
-    bool loss_clear = false;                  // the loss accumulator is zero (cleared by the forward's refresh kernel, consumed by one CE call)
-    int* d_ctmap = nullptr; float* d_ct = nullptr;           // causal conv table [tap][class][C] and its gather map
-    int* d_gmap = nullptr; float* d_gwp = nullptr;           // GEMM path (lay.use_gemm: n_resch > 128, or QPN_TRAIN_GEMM=1): the K-major weight blocks of train_gemm.hip and their map
-    TrainGemm gm = {};
-    int64_t generation = 0;                   // bumped by every qpn_train_forward: identifies whose activations the workspace holds
-    hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_mid = nullptr;   // side stream for the weight gradients that overlap the layer backward
-    hipEvent_t ev_early = nullptr; int early_recorded = 0;   // qpn_train_early_bucket: the flat-gradient tail (from lay.early_first) that is final before the layer backward ends
-    int64_t bwd_generation = -1;                             // generation of the forward the last backward belonged to
-    const float* post_bwd_dlogits = nullptr;                 // ... on this dL/dlogits buffer
-    bool stack_disabled = false;                             // a stack-queue launch gave up once (status bit 4): this handle keeps to a launch per layer
-    unsigned* d_sq = nullptr; size_t sq_pos_cap = 0, sq_per_dir = 0;         // stack work queues (train_stack.hip): [16 control words | forward flags | backward flags]
-    StackQ sqf = {}, sqb = {};
-};
 
 // The environment is read HERE, once per handle: the launch path of a step never calls getenv().
 static int env_int(const char* name, int dflt) { const char* e = getenv(name); return (e && *e) ? atoi(e) : dflt; }
@@ -218,16 +174,11 @@ static int train_init(qpn_handle* h) {
     QPN_HIP(hipMalloc(&t->d_ct, pl.h_ctmap.size() * sizeof(float)));
     QPN_HIP(hipMalloc(&t->d_status, 64));
     QPN_HIP(hipMemset(t->d_status, 0, 64));
-    QPN_HIP(hipHostMalloc((void**)&t->h_status_pinned, 64, hipHostMallocDefault));
-    QPN_HIP(hipHostMalloc((void**)&t->h_loss_pinned, 2 * LOSS_SLOT * sizeof(double), hipHostMallocDefault));
     QPN_HIP(hipMalloc(&t->d_gnorm, TR_GN_BLOCKS * sizeof(double)));
     QPN_HIP(hipMemset(t->d_gnorm, 0, TR_GN_BLOCKS * sizeof(double)));
     QPN_HIP(hipMalloc(&t->d_loss, LOSS_SLOT * sizeof(double)));
     QPN_HIP(hipMemset(t->d_loss, 0, LOSS_SLOT * sizeof(double)));
-    for (int i = 0; i < 2; ++i) {
-        QPN_HIP(hipEventCreateWithFlags(&t->ev_loss[i], hipEventDisableTiming));
-        QPN_HIP(hipEventCreateWithFlags(&t->ev_status[i], hipEventDisableTiming));
-    }
+    rc = t->report.init(); if (rc) return rc;
     QPN_HIP(hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking));          // on the handle's device (current at this call)
     // the fork / join events only order kernels of THIS device's streams: no system-scope fence (cache write-back for the host) at each record
     // (QPN_EVENT_FENCE=1 restores it)
@@ -244,22 +195,13 @@ void qpn_train_destroy(TrainState* t) {
     if (!t) return;
     void* bufs[] = {t->d_wmap, t->d_wp, t->d_bstart, t->d_blist, t->d_bp, t->d_gdst, t->d_gdst_list, t->d_gzero, t->d_ws, t->d_tap, t->d_status, t->d_loss, t->d_gmap, t->d_gwp, t->d_ctmap, t->d_ct, t->d_sq, t->d_gnorm, t->d_loss3, t->d_mass};
     for (void* b : bufs) if (b) (void)hipFree(b);
-    if (t->h_status_pinned) (void)hipHostFree(t->h_status_pinned);
-    if (t->h_loss_pinned) (void)hipHostFree(t->h_loss_pinned);
-    for (int i = 0; i < 2; ++i) if (t->ev_loss[i]) (void)hipEventDestroy(t->ev_loss[i]);
-    for (int i = 0; i < 2; ++i) if (t->ev_status[i]) (void)hipEventDestroy(t->ev_status[i]);
+    t->report.destroy();
     if (t->side) (void)hipStreamDestroy(t->side);
     if (t->ev_fork) (void)hipEventDestroy(t->ev_fork);
     if (t->ev_join) (void)hipEventDestroy(t->ev_join);
     if (t->ev_mid) (void)hipEventDestroy(t->ev_mid);
     if (t->ev_early) (void)hipEventDestroy(t->ev_early);
     delete t;
-}
-
-static int need_dev(qpn_handle* h) {
-    if (!h) { qpn_set_error("null handle"); return QPN_EINVAL; }
-    if (h->device < 0) { qpn_set_error("no HIP device: libqpnet_hip has no CPU fallback"); return QPN_ENODEV; }
-    return QPN_OK;
 }
 
 // targets == nullptr: plain forward.  Otherwise the mean cross entropy (and d_dlogits) is computed too: inside the post-net kernel
@@ -341,7 +283,7 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
     if (t->lay.use_gemm) t->gm.G = a.at(w, TA_G);
     p.PA = a.at(w, TA_PA); bw.DPA = a.at(w, TA_DPA); bw.EB = a.at(w, TA_EB); p.WJ = (float2*)a.at(w, TA_WJ); bw.GW = a.at(w, TA_GW);      // (null unless hoist)
     p.TAP = t->d_tap; p.status = t->d_status;
-    t->last_stream = stream;
+    t->report.call_on(stream);
     {   // stack work queues (train_stack.hip): a flag word per (layer, batch item, 16-row tile) and direction, compared with a per-forward epoch
         // (zeroed only when (re)allocated), and the tile tables k_train_prep writes.  The regions keep their places for the life of an
         // allocation (sized for 1.5x the positions that forced it): a table word of an earlier step must never be read as a flag
@@ -360,7 +302,7 @@ static int train_forward_impl(qpn_handle* h, const float* d_flat, int B, int64_t
         // While the stream is capturing the stack therefore runs as a launch per layer.
         hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(stream, &cap_st);
-        const bool no_queue = t->stack_disabled || cap_st != hipStreamCaptureStatusNone;
+        const bool no_queue = t->report.stack_given_up() || cap_st != hipStreamCaptureStatusNone;
         p.qctl = no_queue ? nullptr : t->d_sq;                   // (nullptr: no queue launches, no tables)
         p.qtab = no_queue ? nullptr : (int4*)(t->d_sq + TR_QHDR_WORDS + 2 * t->sq_per_dir);
         p.qtab_b = no_queue ? nullptr : p.qtab + 2 * (t->sq_pos_cap + 1);
@@ -424,137 +366,6 @@ extern "C" int qpn_train_forward_loss(qpn_handle* h, const float* d_flat, int B,
                                       float* d_logits, int want_logits, float* d_dlogits, void* stream_) {
     if (!d_targets) { qpn_set_error("bad train_forward_loss arguments: no targets"); return QPN_EINVAL; }
     return train_forward_impl(h, d_flat, B, T, F, Td, BL, maxd, d_x, d_h, d_dfac, d_logits, d_targets, tgt_stride, d_dlogits, want_logits & 1, stream_, (want_logits & QPN_FWD_BACKWARD_FOLLOWS) != 0);
-}
-
-extern "C" int qpn_train_loss(qpn_handle* h, double* h_loss, void* stream_) {
-    int rc = need_dev(h); if (rc) return rc;
-    if (!h->train || !h_loss) { qpn_set_error("qpn_train_loss needs a preceding qpn_train_forward_loss / qpn_ce_loss"); return QPN_ESTATE; }
-    hipStream_t stream = (hipStream_t)stream_;
-    double parts[64];
-    QPN_HIP(hipMemcpyAsync(parts, h->train->d_loss, sizeof(parts), hipMemcpyDeviceToHost, stream));
-    QPN_HIP(hipStreamSynchronize(stream));
-    *h_loss = loss_sum(parts);
-    return QPN_OK;
-}
-
-// The loss without draining the stream every step: _enqueue copies this step's 64 partial sums to a pinned slot behind the step's kernels (two
-// slots: the copy of two steps ago is long done when its slot is reused); _collect(newest = 0) returns the sum enqueued one call EARLIER -- complete
-// by the time the host has enqueued another step, so it does not wait in practice --, newest = 1 the last one (waits for it).  *h_valid = 0: no such copy.
-extern "C" int qpn_train_loss_enqueue(qpn_handle* h, void* stream_) {
-    int rc = need_dev(h); if (rc) return rc;
-    if (!h->train) { qpn_set_error("qpn_train_loss_enqueue needs a preceding qpn_train_forward_loss / qpn_ce_loss"); return QPN_ESTATE; }
-    TrainState* t = h->train;
-    const int slot = t->loss_newest ^ 1;
-    if (t->loss_pending[slot]) QPN_HIP(hipEventSynchronize(t->ev_loss[slot]));      // (an uncollected copy of two calls ago: dropped)
-    // (behind a clipping Adam launch the step's gradient norm, d_loss[64], leaves in the same copy)
-    QPN_HIP(hipMemcpyAsync(t->h_loss_pinned + LOSS_SLOT * slot, t->d_loss, (t->gnorm_last ? 65 : 64) * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream_));
-    t->gnorm_slot[slot] = t->gnorm_last;
-    QPN_HIP(hipEventRecord(t->ev_loss[slot], (hipStream_t)stream_));
-    t->loss_pending[slot] = true; t->loss_newest = slot;
-    return QPN_OK;
-}
-extern "C" int qpn_train_loss_collect(qpn_handle* h, int newest, double* h_loss, int* h_valid) {
-    int rc = need_dev(h); if (rc) return rc;
-    if (!h_loss || !h_valid) { qpn_set_error("bad loss_collect arguments"); return QPN_EINVAL; }
-    *h_valid = 0; *h_loss = 0.0;
-    if (!h->train) return QPN_OK;
-    TrainState* t = h->train;
-    const int slot = newest ? t->loss_newest : t->loss_newest ^ 1;
-    t->gnorm_collected_valid = false;
-    if (!t->loss_pending[slot]) return QPN_OK;
-    QPN_HIP(hipEventSynchronize(t->ev_loss[slot]));
-    t->loss_pending[slot] = false;
-    *h_loss = loss_sum(t->h_loss_pinned + LOSS_SLOT * slot); *h_valid = 1;
-    if (t->gnorm_slot[slot]) { t->gnorm_collected = t->h_loss_pinned[LOSS_SLOT * slot + 64]; t->gnorm_collected_valid = true; }
-    return QPN_OK;
-}
-
-static int status_to_rc(int st);
-extern "C" int qpn_train_status(qpn_handle* h, void* stream_) {
-    int rc = need_dev(h); if (rc) return rc;
-    if (!h->train) { qpn_set_error("no training call yet"); return QPN_ESTATE; }
-    QPN_HIP(hipStreamSynchronize((hipStream_t)stream_));
-    int st = 0;
-    QPN_HIP(hipMemcpy(&st, h->train->d_status, sizeof(int), hipMemcpyDeviceToHost));
-    if (st) QPN_HIP(hipMemsetAsync(h->train->d_status, 0, sizeof(int), (hipStream_t)stream_));          // sticky until read: reported once
-    h->train->last_stream = (hipStream_t)stream_;
-    if (st & 4) h->train->stack_disabled = true;
-    h->train->status_pending[0] = h->train->status_pending[1] = false;
-    return status_to_rc(st);
-}
-
-static int status_to_rc(int st) {
-    if (st & 1) { qpn_set_error("pitch-dependent tap outside the layer input (dilated factor > maxd or < 0; reference assert qpnet.py:294)"); return QPN_ERANGE; }
-    if (st & 4) { qpn_set_error("the one-launch residual stack gave up waiting for a peer workgroup: the flagged step's results are invalid (its Adam update, and that of the steps enqueued behind it until this report, were skipped on the device: parameters and moments are those of the last clean step); the handle runs a launch per layer from here on (QPN_STACK_QUEUE=0 selects that from the start)"); return QPN_ENODEV; }
-    if (st & 2) { qpn_set_error("target class outside [0, n_quantize) (reference assert qpnet_train.py:525)"); return QPN_ERANGE; }
-    if (st & 32) { qpn_set_error("a NaN or an infinity in the teacher logits of a distillation loss (qpn_distill_loss / qpn_train_distill): the step's Adam update, and that of the steps enqueued behind it until this report, were skipped on the device: parameters and moments are those of the last clean step"); return QPN_ERANGE; }
-    if (st & 64) { qpn_set_error("a NaN, infinite or negative value among the sample weights of a loss with options (qpn_ce_loss_opts / qpn_distill_loss_opts / qpn_train_loss_opts; it counted as 0): the step's Adam update, and that of the steps enqueued behind it until this report, were skipped on the device: parameters and moments are those of the last clean step"); return QPN_ERANGE; }
-    if (st & (1 << 16)) { qpn_set_error("non-finite gradient norm (an inf or NaN in the gradient): the step's Adam update, and that of the steps enqueued behind it until this report, were skipped on the device: parameters and moments are those of the last clean step"); return QPN_ERANGE; }
-    if (st & 8) { qpn_set_error("a peer rank flagged its chunk of this data-parallel step, or an earlier micro-step of this accumulation window was flagged (a tap or target out of range, or an abandoned stack launch there): every rank skipped the update, the replicas are unchanged"); return QPN_ERANGE; }
-    return QPN_OK;
-}
-
-// The same check without draining the stream: _enqueue copies the (sticky) status word to pinned memory behind the work enqueued so
-// far and returns; _collect waits for the copies only and reports them.  Two slots: _collect_lagged looks at every enqueued check
-// EXCEPT the newest -- a training loop that calls it at the start of step i + 1 never waits for step i (whose kernels the device still has
-// queued while the host enqueues the next step), and reports a bad chunk two steps late at most.
-static int status_collect_slot(TrainState* t, int slot) {
-    if (!t->status_pending[slot]) return QPN_OK;
-    QPN_HIP(hipEventSynchronize(t->ev_status[slot]));
-    t->status_pending[slot] = false;
-    const int st = t->h_status_pinned[slot];
-    if (st & 4) t->stack_disabled = true;
-    if (st) {
-        // sticky until read: reported once.  Cleared ON the stream the training calls run on, i.e. behind every step enqueued so far (their Adam kernels all see
-        // the word set and skip) and in front of the next one -- a null-stream memset is not ordered against a non-blocking stream and could land in the middle
-        // of a k_adam launch, whose blocks each read the word
-        QPN_HIP(hipMemsetAsync(t->d_status, 0, sizeof(int), t->last_stream));
-        const int other = slot ^ 1;                                   // ... also where the other slot copied the same sticky bits before this clear
-        if (t->status_pending[other]) {
-            QPN_HIP(hipEventSynchronize(t->ev_status[other]));
-            t->h_status_pinned[other] &= ~st;
-            if (!t->h_status_pinned[other]) t->status_pending[other] = false;
-        }
-    }
-    return status_to_rc(st);
-}
-extern "C" int qpn_train_status_enqueue(qpn_handle* h, void* stream_) {
-    int rc = need_dev(h); if (rc) return rc;
-    if (!h->train) { qpn_set_error("no training call yet"); return QPN_ESTATE; }
-    TrainState* t = h->train;
-    const int slot = t->status_newest ^ 1;
-    t->last_stream = (hipStream_t)stream_;
-    rc = status_collect_slot(t, slot); if (rc) return rc;            // (two enqueues old: long done)
-    QPN_HIP(hipMemcpyAsync(t->h_status_pinned + slot, t->d_status, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream_));
-    QPN_HIP(hipEventRecord(t->ev_status[slot], (hipStream_t)stream_));
-    t->status_pending[slot] = true; t->status_newest = slot;
-    return QPN_OK;
-}
-extern "C" int qpn_train_status_collect(qpn_handle* h) {
-    int rc = need_dev(h); if (rc) return rc;
-    if (!h->train) return QPN_OK;
-    TrainState* t = h->train;
-    rc = status_collect_slot(t, t->status_newest ^ 1); if (rc) return rc;
-    return status_collect_slot(t, t->status_newest);
-}
-// ... and without waiting at all: only the checks whose copies have already landed are looked at (hipEventQuery); *pending = checks still in flight
-extern "C" int qpn_train_status_poll(qpn_handle* h, int* pending) {
-    int rc = need_dev(h); if (rc) return rc;
-    if (pending) *pending = 0;
-    if (!h->train) return QPN_OK;
-    TrainState* t = h->train;
-    for (int k = 0; k < 2; ++k) {
-        const int slot = k == 0 ? t->status_newest ^ 1 : t->status_newest;      // older first
-        if (!t->status_pending[slot]) continue;
-        if (hipEventQuery(t->ev_status[slot]) != hipSuccess) { (void)hipGetLastError(); if (pending) ++*pending; continue; }
-        rc = status_collect_slot(t, slot); if (rc) return rc;
-    }
-    return QPN_OK;
-}
-extern "C" int qpn_train_status_collect_lagged(qpn_handle* h) {
-    int rc = need_dev(h); if (rc) return rc;
-    if (!h->train) return QPN_OK;
-    return status_collect_slot(h->train, h->train->status_newest ^ 1);
 }
 
 // alpha in (0, 1], temperature finite and > 0: the rules of both distillation entry points (checked without a device)
@@ -677,20 +488,6 @@ extern "C" int qpn_train_stack_stats(qpn_handle* h, unsigned* h_out, int n, void
     if (!h->train || !h->train->d_sq || !h_out || n < 1) { qpn_set_error("no stack-queue launch yet"); return QPN_ESTATE; }
     QPN_HIP(hipStreamSynchronize((hipStream_t)stream_));
     QPN_HIP(hipMemcpy(h_out, h->train->d_sq, sizeof(unsigned) * (size_t)(n < 1024 ? n : 1024), hipMemcpyDeviceToHost));      // (words 600.. : stamps of a -DQPN_STACK_STAMPS build)
-    return QPN_OK;
-}
-
-// Adam updates APPLIED on this handle so far (k_adam counts on the device: a launch that found the status word set -- its own rank's or, data-parallel, a peer's --
-// applies nothing).  Drains `stream`.  A caller that counts steps on the host (the bias correction's step number) re-bases its count on this after a status error.
-extern "C" int qpn_train_applied_updates(qpn_handle* h, int64_t* applied, void* stream_) {
-    int rc = need_dev(h); if (rc) return rc;
-    if (!applied) { qpn_set_error("bad applied_updates arguments"); return QPN_EINVAL; }
-    *applied = 0;
-    if (!h->train) return QPN_OK;
-    QPN_HIP(hipStreamSynchronize((hipStream_t)stream_));
-    unsigned long long v = 0;
-    QPN_HIP(hipMemcpy(&v, h->train->d_status + 2, sizeof(v), hipMemcpyDeviceToHost));
-    *applied = (int64_t)v;
     return QPN_OK;
 }
 
@@ -877,9 +674,9 @@ extern "C" int qpn_adam_step_avg(qpn_handle* h, float* d_flat, const float* d_gr
     const bool clip = max_grad_norm > 0.f;
     if (clip) { rc = train_init(h); if (rc) return rc; }                 // (the partial sums and the norm word live in the training state)
     TrainState* const t = h->train;
-    if (t) { t->last_stream = (hipStream_t)stream_; t->gnorm_last = clip; }
+    if (t) t->report.call_on((hipStream_t)stream_, clip ? StepEnd::AdamClipped : StepEnd::AdamPlain);
     const AdamCall c = {d_flat, d_grad, d_m, d_v, n, step, lr, beta1, beta2, eps, weight_decay, d_grad_denominator, t ? t->d_status : nullptr, nullptr, nullptr, nullptr,
-                        max_grad_norm, clip ? t->d_gnorm : nullptr, clip ? t->d_loss + 64 : nullptr, nullptr, d_ema, omd, grouped ? &ga : nullptr};
+                        max_grad_norm, clip ? t->d_gnorm : nullptr, clip ? t->d_loss + LOSS_NORM_AT : nullptr, nullptr, d_ema, omd, grouped ? &ga : nullptr};
     return qpn_launch_adam(c, (hipStream_t)stream_);
 }
 
@@ -892,29 +689,8 @@ extern "C" int qpn_grad_accumulate(qpn_handle* h, float* d_acc, const float* d_g
     if (d_acc == d_grad) { qpn_set_error("bad grad_accumulate arguments: d_acc is d_grad (the accumulator must be a buffer of its own)"); return QPN_EINVAL; }
     int rc = need_dev(h); if (rc) return rc;
     // (a step that ends here ran no Adam launch: the norm word is not this step's -- qpn_train_loss_enqueue / qpn_train_grad_norm report "did not clip")
-    if (h->train) { h->train->last_stream = (hipStream_t)stream_; h->train->gnorm_last = false; }
+    if (h->train) h->train->report.call_on((hipStream_t)stream_, StepEnd::NoAdam);
     return qpn_launch_grad_accum(d_acc, d_grad, cnt, first, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream_);
-}
-
-// The norm the latest Adam launch on this handle clipped by (drains `stream`); *h_valid = 0 when that launch did not clip, or there was none
-extern "C" int qpn_train_grad_norm(qpn_handle* h, double* h_norm, int* h_valid, void* stream_) {
-    int rc = need_dev(h); if (rc) return rc;
-    if (!h_norm || !h_valid) { qpn_set_error("bad grad_norm arguments"); return QPN_EINVAL; }
-    *h_norm = 0.0; *h_valid = 0;
-    if (!h->train || !h->train->gnorm_last) return QPN_OK;
-    QPN_HIP(hipStreamSynchronize((hipStream_t)stream_));
-    QPN_HIP(hipMemcpy(h_norm, h->train->d_loss + 64, sizeof(double), hipMemcpyDeviceToHost));
-    *h_valid = 1;
-    return QPN_OK;
-}
-// ... and without a wait of its own: the norm of the step whose loss the last qpn_train_loss_collect returned (it left the device in that loss's copy)
-extern "C" int qpn_train_grad_norm_lagged(qpn_handle* h, double* h_norm, int* h_valid) {
-    int rc = need_dev(h); if (rc) return rc;
-    if (!h_norm || !h_valid) { qpn_set_error("bad grad_norm arguments"); return QPN_EINVAL; }
-    *h_norm = 0.0; *h_valid = 0;
-    if (!h->train || !h->train->gnorm_collected_valid) return QPN_OK;
-    *h_norm = h->train->gnorm_collected; *h_valid = 1;
-    return QPN_OK;
 }
 
 // One optimisation step behind ONE call -- what a training loop's body is (reference src/bin/qpnet_train.py:517-531: forward, CrossEntropyLoss, backward,
@@ -952,10 +728,8 @@ static int train_step_body(qpn_handle* h, const TrainStepArgs& a) {
     rc = need_dev(h); if (rc) return rc;
     AdamGroupsArg ga; bool grouped = false;
     if (closing) { rc = adam_groups_arg(h, a.n, &ga, &grouped); if (rc) return rc; }      // (before anything is enqueued: a table for another n fails the whole step)
-    // a flagged word found here is cleared on THIS call's stream, in front of the step the caller runs on it next: the stream of the call before may be another
-    // one, busy with work of the caller's own, and a clear queued behind that work lands after the next step's Adam launch has read the word
     const hipStream_t stream = (hipStream_t)a.stream;
-    if (h->train) h->train->last_stream = stream;
+    if (h->train) h->train->report.call_on(stream);                      // (a flagged word found here is cleared on THIS call's stream: train_report.h)
     rc = qpn_train_status_collect_lagged(h); if (rc) return rc;          // the check of the step before the previous one (never waits for queued work)
     if (!a.d_targets || !a.d_dlogits) { qpn_set_error("qpn_train_forward_loss needs targets and a dlogits buffer"); return QPN_EINVAL; }
     if (accum && (!a.d_grad || a.n < 1)) { qpn_set_error("bad train_step arguments: d_grad / n"); return QPN_EINVAL; }
@@ -969,38 +743,29 @@ static int train_step_body(qpn_handle* h, const TrainStepArgs& a) {
     if (loss_mode == 2) {
         if (accum) { rc = qpn_launch_grad_accum(a.d_acc, a.d_grad, a.n + 4, a.micro == 0, nullptr, nullptr, nullptr, nullptr, stream); if (rc) return rc; }
         if (closing) { rc = qpn_adam_step_avg(h, a.d_flat, g_adam, a.d_m, a.d_v, a.n, a.step, a.lr, a.beta1, a.beta2, a.eps, a.weight_decay, den, a.max_grad_norm, a.d_ema, a.ema_decay, a.stream); if (rc) return rc; }
-        else { t->last_stream = stream; t->gnorm_last = false; }                                       // (no Adam launch: this micro-step has no norm)
+        else t->report.call_on(stream, StepEnd::NoAdam);                                              // (this micro-step has no norm)
         rc = qpn_train_loss(h, a.h_loss, a.stream); if (rc) return rc;
         *a.h_valid = 1;
         if (clip && a.h_grad_norm) { int nv = 0; rc = qpn_train_grad_norm(h, a.h_grad_norm, &nv, a.stream); if (rc) return rc; }      // (the stream has just been drained)
         return qpn_train_status(h, a.stream);
     }
-    // modes 0 / 1: the Adam kernel -- the step's last -- writes the status word (and the loss partials) into the pinned slots itself: what
-    // qpn_train_status_enqueue / qpn_train_loss_enqueue do with a copy each, without the two copy-engine launches behind the step
+    // modes 0 / 1: the step's last kernel writes the status word (and the loss partials, and the norm) into the pinned report slots itself (train_state.h)
     if (!a.d_flat || !a.d_grad || !a.d_m || !a.d_v || a.n < 1 || a.step < 1) { qpn_set_error("bad adam_step arguments"); return QPN_EINVAL; }
-    const int sslot = t->status_newest ^ 1;
-    rc = status_collect_slot(t, sslot); if (rc) return rc;               // (two enqueues old: long done)
-    const int lslot = t->loss_newest ^ 1;
-    if (loss_mode == 1 && t->loss_pending[lslot]) QPN_HIP(hipEventSynchronize(t->ev_loss[lslot]));      // (an uncollected copy of two calls ago: dropped)
-    double* const hl = loss_mode == 1 ? t->h_loss_pinned + LOSS_SLOT * lslot : nullptr;
-    t->gnorm_last = clip;
-    t->last_stream = stream;
+    ReportSlots rs;
+    rc = qpn_report_open(t, loss_mode == 1, clip ? StepEnd::AdamClipped : closing ? StepEnd::AdamPlain : StepEnd::NoAdam, stream, &rs); if (rc) return rc;
     // (the micro-steps in front of the closing one end in the accumulate kernel: it carries the reports; in the closing one the Adam launch does, as ever)
-    if (accum) { rc = qpn_launch_grad_accum(a.d_acc, a.d_grad, a.n + 4, a.micro == 0, closing ? nullptr : t->d_status, t->h_status_pinned + sslot,
-                                            hl, (!closing && loss_mode == 1) ? t->d_loss : nullptr, stream); if (rc) return rc; }
+    if (accum) { rc = qpn_launch_grad_accum(a.d_acc, a.d_grad, a.n + 4, a.micro == 0, closing ? nullptr : t->d_status, rs.h_status,
+                                            rs.h_loss, (!closing && loss_mode == 1) ? t->d_loss : nullptr, stream); if (rc) return rc; }
     if (closing) {
         const AdamCall c = {a.d_flat, g_adam, a.d_m, a.d_v, a.n, a.step, a.lr, a.beta1, a.beta2, a.eps, a.weight_decay, den, t->d_status,
-                            t->h_status_pinned + sslot, hl, loss_mode == 1 ? t->d_loss : nullptr,
-                            a.max_grad_norm, t->d_gnorm, t->d_loss + 64, hl ? hl + 64 : nullptr, a.d_ema, omd, grouped ? &ga : nullptr};
+                            rs.h_status, rs.h_loss, loss_mode == 1 ? t->d_loss : nullptr,
+                            a.max_grad_norm, t->d_gnorm, t->d_loss + LOSS_NORM_AT, rs.h_norm, a.d_ema, omd, grouped ? &ga : nullptr};
         rc = qpn_launch_adam(c, stream); if (rc) return rc;
     }
-    QPN_HIP(hipEventRecord(t->ev_status[sslot], stream));
-    t->status_pending[sslot] = true; t->status_newest = sslot;
+    rc = qpn_report_close(t, rs, stream); if (rc) return rc;
     if (loss_mode == 1) {
-        QPN_HIP(hipEventRecord(t->ev_loss[lslot], stream));
-        t->loss_pending[lslot] = true; t->loss_newest = lslot; t->gnorm_slot[lslot] = clip;
         rc = qpn_train_loss_collect(h, 0, a.h_loss, a.h_valid); if (rc) return rc;
-        if (a.h_grad_norm && t->gnorm_collected_valid) *a.h_grad_norm = t->gnorm_collected;
+        if (a.h_grad_norm) { int nv = 0; rc = qpn_train_grad_norm_lagged(h, a.h_grad_norm, &nv); if (rc) return rc; }      // (the norm that left the device in that loss's slot)
     }
     return QPN_OK;
 }

@@ -353,6 +353,43 @@ def test_grad_norm_is_delivered_with_its_loss_in_every_loss_mode(cuda, clip_leve
     assert tr.step_count == 2
 
 
+def _chunk2(cuda, k):      # B = 2, one short chunk (seeds whose two rows share a batch length)
+    return _to(cuda, *synth.train_inputs(TINY, 400, (91, 100)[k], 30000, batch_size=2))
+
+
+def _two_lagged_steps(cuda, c, second_by_calls):
+    """one handle, clipping on: a one-call step in lagged mode, then one more -- one call again, or made call by call over the C ABI (FusedTrainer._step_calls) --, then
+    flush_loss(): -> what the second step and the flush returned, [(loss, norm), (loss, norm)]"""
+    from qpnet_amd.train import FusedTrainer
+    m = util.build_model(TINY, synth.make_weights(TINY, WSEED), cuda).train()
+    tr = FusedTrainer(m, lr=1e-3, max_grad_norm=c)
+    assert tr.step(*_chunk2(cuda, 0), want_loss="lagged") is None and tr.last_grad_norm is None
+    if second_by_calls:      # (the path a data-parallel or capturing trainer takes: the same arguments, one C-ABI call per piece)
+        tr._step_call = lambda L, hd, dev, flat, stream, x, h, t, d, B, T, BL, maxd, want_loss, loss: \
+            tr._step_calls(L, hd, dev, flat, stream, x, h, t, d, B, T, BL, maxd, want_loss, False, False, loss)
+    l1 = tr.step(*_chunk2(cuda, 1), want_loss="lagged")
+    n1 = tr.last_grad_norm
+    l2 = tr.flush_loss(); n2 = tr.last_grad_norm
+    assert tr.flush_loss() is None and tr.last_grad_norm is None
+    tr.check_status()
+    assert tr.step_count == 2
+    return [(l1, n1), (l2, n2)]
+
+
+def test_one_call_step_and_call_by_call_step_share_the_report_slots(cuda, clip_level):
+    """The one-call step's last kernel and the copies of qpn_train_loss_enqueue / qpn_train_status_enqueue write ONE pair of pinned slots (train_report.h): a lagged
+    one-call step followed by a lagged step made call by call returns the first step's loss and norm at the second step and the second's at flush_loss(), the values
+    two one-call steps return (losses atol 1e-6, norms rtol 1e-5: the bounds of test_grad_norm_is_delivered_with_its_loss_in_every_loss_mode, float-atomics order)."""
+    c = clip_level
+    ref = _two_lagged_steps(cuda, c, False)
+    got = _two_lagged_steps(cuda, c, True)
+    print("one call + one call", ref, "one call + call by call", got)
+    assert all(v is not None for pair in ref + got for v in pair)
+    np.testing.assert_allclose([p[0] for p in got], [p[0] for p in ref], rtol=0, atol=1e-6)
+    np.testing.assert_allclose([p[1] for p in got], [p[1] for p in ref], rtol=1e-5, atol=0)
+    assert abs(ref[0][0] - ref[1][0]) > 1e-5 and abs(ref[0][1] - ref[1][1]) > 1e-4 * ref[0][1]      # (the two steps' values lie ten bounds apart: a pair delivered a step off, or a loss with the other step's norm, would show)
+
+
 def test_world2_with_the_identity_exchange_clips_like_world1(cuda):
     """No process group: world_size=2 holds n_r g_r | n_r and divides by n_r on the device, so the clipped step must reproduce world_size=1's (the norm is that of the AVERAGED
     gradient).  The per-step weight re-sync and the bounds are test_world2_without_exchange_equals_world1's; the norms agree to rtol 1e-6 (the denominator's division)."""

@@ -915,6 +915,43 @@ def test_fused_step_normalises_inputs_and_flags_bad_targets(cuda):
     assert e.value.code == -4
 
 
+def test_status_poll_reports_a_flagged_step_once(cuda):
+    """qpn_train_status_poll: three FusedTrainer.step(want_loss=False) calls, the first with an out-of-range target.  The third call's own deferred check would
+    fetch the first step's report (it is the check of the step before the previous one), so the poll goes in front of it: with the stream synchronised, both reports have
+    landed -- the poll returns QPN_ERANGE once, with the target message, clears the word and takes the same sticky bit out of the second step's report (pending ends at 0);
+    a second poll and check_status() are clean.  Neither the flagged step nor the one enqueued behind it changed a parameter (bit-equal); the third is applied."""
+    import ctypes as C
+    import torch
+    from qpnet_amd.config import TINY
+    from qpnet_amd.train import FusedTrainer
+    from qpnet_amd import _lib
+    cfg = TINY
+    x, h, t, d, b = synth.train_inputs(cfg, 400, 91, 30000, batch_size=2)
+    m = util.build_model(cfg, synth.make_weights(cfg, 23), cuda).train()
+    xt, ht, tt, dt, bt = _to(cuda, x, h, t, d, b)
+    bad = tt.clone(); bad[0, -5] = cfg.n_quantize + 3
+    tr = FusedTrainer(m, lr=1e-3)
+    L, hd = m._native(cuda)
+    w0 = m.flat_parameters().clone()
+    assert tr.step(xt, ht, bad, dt, bt, want_loss=False) is None
+    assert tr.step(xt, ht, tt, dt, bt, want_loss=False) is None
+    torch.cuda.current_stream(cuda).synchronize()
+    pending = C.c_int(-1)
+    with torch.cuda.device(cuda):
+        rc = L.qpn_train_status_poll(hd, C.byref(pending))
+        msg = L.qpn_last_error().decode()
+        assert rc == -4 and "target class" in msg, (rc, msg)
+        assert pending.value == 0
+        assert L.qpn_train_status_poll(hd, C.byref(pending)) == 0 and pending.value == 0
+    tr.check_status()
+    assert torch.equal(m.flat_parameters(), w0)
+    assert tr.step(xt, ht, tt, dt, bt, want_loss=False) is None
+    tr.check_status()
+    with torch.cuda.device(cuda):
+        assert L.qpn_train_status_poll(hd, C.byref(pending)) == 0 and pending.value == 0
+    assert not torch.equal(m.flat_parameters(), w0)
+
+
 def _same_after_adam(w, w_ref, lr, steps):
     """Adam moves an element by ~lr per step whatever its gradient's size, so where a gradient is at fp32-noise level two
     summation orders (float atomics, torch's kernels) may disagree on a fraction of a step: almost all elements agree to
